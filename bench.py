@@ -1,19 +1,24 @@
 #!/usr/bin/env python3
 """bench.py -- PT-iterations/s of the 3D Stokes pseudo-transient loop (SolVi3D, 512^3 per GPU, fp64): the driver's contract line.
 
-    python bench.py --gpus N --steps K --warmup W [--n 512] [--extras]
+    python bench.py --gpus N --steps K --warmup W [--n 512] [--dump-outputs DIR] [--full] [--extras]
 
 One "step" = one PT iteration (velocity sweep + boundary conditions + stress sweep [+ halo exchange]) over one n^3 block per GPU, inputs resident in HBM
 (the boundary hands device pointers: there is no PCIe-inclusive variant of this path).  N > 1: weak scaling, one process per GPU, IGG-style block
 decomposition, RCCL halo exchange inside the native library; torch.distributed (gloo) only carries the RCCL unique id, the barriers and the max-reduce.
 
-stdout carries exactly ONE line: strict JSON (no NaN tokens), under 4 KB -- metric, value, ms_per_step, config, state_ok, roofline, cpu_baseline.  Everything
-else (per-leg records, device clocks, the other configs with --extras) goes to bench_details.json (`details` in the line names it) and, abridged, to stderr.
+stdout carries exactly ONE line: strict JSON (no NaN tokens), under 4 KB -- metric, value, ms_per_step, config, roofline [, state_ok, steady_state, cpu_baseline
+with --full].  Everything else (per-leg records, device clocks, the other configs with --extras) goes to bench_details.json (`details` in the line names it) and,
+abridged, to stderr.
+
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs DIR: the state the last timed step left, P, tau(6), V(3), as DIR/<name>.npy,
+float64, large arrays as a fixed seeded sample, see dump_outputs) and prints the line: `value` and `ms_per_step` come from the K timed steps alone, and the roofline
+of the line from the launch times those same steps recorded.  Every leg below the headline runs only with --full (--extras implies it).
 
 Launching.  `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (the parent makes no GPU call); started by
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` it finds WORLD_SIZE set and runs as one rank.
 
-What is timed (N = 1), in this order, all on the library's DEFAULT options except where said:
+What is timed (N = 1), in this order, all on the library's DEFAULT options except where said (all but the headline: --full only):
   headline        W warm-up + K timed iterations of jrx_stokes3d_iterate_timed on arrays of the library's array constructor with option "field_placement" = 1
                   (--placement pool: every array ONE physical chunk picked at random from a pool spanning most of the free memory, mapped once, never moved;
                   --placement hipmalloc: torch's arrays).  dt = Inf (SolVi3D.jl:96), so the library runs the viscous-limit form of k_fused3d, priced at the
@@ -102,6 +107,33 @@ def build_block(jr, h, n, dev, update_halo=None):
     ητ = jr.fzeros((n, n, n), dev)
     jr.compute_maxloc_(ητ, st.viscosity.η, handle=h)
     return (st, pt, geo, bcs, ρg, K, G, ητ, dt)
+
+
+DUMP_SAMPLE = 1 << 19       # entries per dumped array at most: ten arrays of 4 MiB (float64) stay under 64 MB
+DUMP_SEED = 20251015
+
+
+def state_outputs(st):
+    """what a caller of the timed path receives: the state the last iteration left in the caller's arrays, by name"""
+    return {"P": st.P, "tau_xx": st.τ.xx, "tau_yy": st.τ.yy, "tau_zz": st.τ.zz, "tau_yz": st.τ.yz, "tau_xz": st.τ.xz, "tau_xy": st.τ.xy,
+            "Vx": st.V.Vx, "Vy": st.V.Vy, "Vz": st.V.Vz}
+
+
+def dump_outputs(st, out_dir):
+    """--dump-outputs: every array of state_outputs(st) as out_dir/<name>.npy, float64.  An array of more than DUMP_SAMPLE entries is written as the entries at
+    DUMP_SAMPLE flat (C-order) indices of its shape, drawn (sorted, with repeats) from a generator seeded by DUMP_SEED and the array's place in the list: the same
+    entries in every run and every build"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for i, (name, t) in enumerate(state_outputs(st).items()):
+        if t.numel() <= DUMP_SAMPLE:
+            a = t.detach().to("cpu", torch.float64).numpy()
+        else:
+            flat = np.sort(np.random.default_rng([DUMP_SEED, i]).integers(0, t.numel(), DUMP_SAMPLE))
+            idx = tuple(torch.from_numpy(k.astype(np.int64)).to(t.device) for k in np.unravel_index(flat, tuple(t.shape)))
+            a = t.detach()[idx].to("cpu", torch.float64).numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def timed_batch(run, warm, steps, after_warm=None):
@@ -206,19 +238,22 @@ def run_single(args, json_fd) -> int:
         pci = f"{pp.pci_bus_id:02x}:{pp.pci_device_id:02x}.0"
     except Exception:       # noqa: BLE001
         pci = None
-    dstate = X.DeviceState(pci)
+    dstate = X.DeviceState(pci) if args.full else None
     f0 = [None]
 
     def after_warm():
         if args.warmup > 0:
             pa.trim()                      # the library's second state set exists now (first driver call): the pool's unused chunks go back to the driver
-        dstate.start()
+        if dstate:
+            dstate.start()
         f0[0] = counters(h)
     el, (tot_ms, sa_ms, sb_ms, sf_ms, sk_ms, kcells) = timed_batch(run, args.warmup, args.steps, after_warm)
-    dev_state = dstate.stop()
+    dev_state = dstate.stop() if dstate else None
     pa.trim()
+    if args.dump_outputs:
+        dump_outputs(blk[0], args.dump_outputs)
     pr = pricing(h, dt, nof_ran(h, f0[0])) if f0[0] else pricing(h, dt, 0)
-    sums_a = X.state_checksums(blk[0]) if not args.no_state_check else None
+    sums_a = X.state_checksums(blk[0]) if args.full and not args.no_state_check else None
     pool_stats = None
     if pool:
         s6 = (C.c_int64 * 6)()
@@ -251,12 +286,12 @@ def run_single(args, json_fd) -> int:
     full["roofline"]["launch_ms_per_rank"] = [sk_ms if fused else None]
 
     # ---- steady state: a short requested batch (the driver times 20 steps = 0.1 s) also holds the per-call operand pass; 100 steps of the same loop beside it
-    if args.steps < 50 and not args.no_steady_state:
+    if args.full and args.steps < 50 and not args.no_steady_state:
         sel, sres = timed_batch(run, 0, 100)
         full["steady_state"] = {"steps": 100, "value": 100 / sel, "ms_per_step": sel / 100 * 1e3, "kernel_avg_launch_ms": sres[4] if sres[4] > 0 else None}
 
     # ---- the general form of the same kernel (any dt, every operand and body-force array loaded): SURVEY 8d's 360 B/cell, same arrays, same batch length
-    if fused and pr["form"].startswith("viscous_limit") and not args.no_general_kernel and not self_halo:
+    if args.full and fused and pr["form"].startswith("viscous_limit") and not args.no_general_kernel and not self_halo:
         try:
             h.set_option("viscous_limit", 0)
             h.set_option("zero_forces", 0)
@@ -305,7 +340,7 @@ def run_single(args, json_fd) -> int:
 
     if args.extras and not self_halo:
         full["other_configs"] = X.other_configs(jr, h)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         grid.finalize_global_grid()
         full["cpu_baseline"] = cpu_baseline_record(args, n)
     emit(json_fd, full, args.details)
@@ -355,6 +390,8 @@ def run_multi(args, world, rank, local_rank, json_fd) -> int:
     tot_ms, sa_ms, sb_ms, sf_ms, sk_ms, kcells = R.run(args.steps)
     R.sync()
     el = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and not args.dry_transports:
+        dump_outputs(R.blk[0], args.dump_outputs)
     if not args.dry_transports:
         pr = pricing(R.h, R.blk[8], nof_ran(R.h, f0))
     ctl.barrier()
@@ -362,7 +399,7 @@ def run_multi(args, world, rank, local_rank, json_fd) -> int:
     per_rank = ctl.gather({"rank": rank, "k_fused3d_ms": sk_ms, "arrays": getattr(R, "placement", None)})
     el, tot_ms, sa_ms, sb_ms, sf_ms, sk_ms, kcells = ctl.max([el, tot_ms, sa_ms, sb_ms, sf_ms, sk_ms, kcells])
     steady = None
-    if args.steps < 50 and not args.no_steady_state:
+    if args.full and args.steps < 50 and not args.no_steady_state:
         ctl.barrier()
         t1 = time.perf_counter()
         sres = R.run(100)

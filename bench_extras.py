@@ -206,7 +206,12 @@ def parse_args(argv=None):
     ap.add_argument("--placement", choices=["pool", "hipmalloc"], default="pool",
                     help="where the arrays of the headline come from: pool = the library's array constructor with option field_placement = 1 (every array ONE physical chunk picked at random "
                          "from a pool that spans most of the free memory, mapped once at a fresh virtual range: csrc/fieldpool.hip); hipmalloc = torch's arrays (plain hipMalloc)")
-    ap.add_argument("--extras", action="store_true", help="also run the legs of bench_extras.py (other configs, coupled blocks, solve path; N > 1: transports and decompositions) and write them to --details")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: steady state, general form, state_ok, device clocks, cpu_baseline (a plain run only sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the state the last step left (P, the six stresses, the three velocities) as DIR/<name>.npy, float64; "
+                         "an array of more than 2^19 entries as a fixed, seeded sample of 2^19 of them (bench.dump_outputs)")
+    ap.add_argument("--extras", action="store_true", help="also run the legs of bench_extras.py (other configs, coupled blocks, solve path; N > 1: transports and decompositions) and write them to --details; implies --full")
     ap.add_argument("--details", default=str(ROOT / "bench_details.json"), help="where the full record goes (the stdout line stays compact)")
     ap.add_argument("--no-state-check", action="store_true", help="skip the state_ok leg (the same batch on hipMalloc arrays, checksums compared)")
     ap.add_argument("--no-steady-state", action="store_true", help="skip the extra 100-step batch that follows a requested batch of fewer than 50 steps")
@@ -233,7 +238,9 @@ def parse_args(argv=None):
     ap.add_argument("--ipc-helper", action="store_true", help="internal: one of the two parked rank processes of the multi_rank_path leg (see start_ipc_helpers)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="test hook: the ranks only report their launch environment (no GPU is touched, the device-count check is skipped)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    args.full = args.full or args.extras
+    return args
 
 
 def visible_gpus() -> int:

@@ -5,7 +5,7 @@ out=gpurun_out/$tag; mkdir -p $out
 for i in $(seq 1 $pairs); do
   for v in base opt; do
     extra=""; [ $v = opt ] && extra="--option $opt"
-    python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-state-check $extra --details $out/d_${v}$i.json > $out/b_${v}$i.json 2> $out/b_${v}$i.err
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-state-check $extra --details $out/d_${v}$i.json > $out/b_${v}$i.json 2> $out/b_${v}$i.err
     python - $out/b_${v}$i.json "$v $extra" <<'P'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d["roofline"]

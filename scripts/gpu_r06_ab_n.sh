@@ -5,7 +5,7 @@ out=gpurun_out/$tag; mkdir -p $out
 for i in $(seq 1 $pairs); do
   for v in base "$@"; do
     extra=""; [ "$v" != base ] && extra="--option $v"
-    python bench.py --gpus 1 --n $n --steps 40 --warmup 5 --no-cpu-baseline --no-state-check --no-general-kernel $extra --details $out/d.json > $out/b.json 2> $out/b.err
+    python bench.py --gpus 1 --n $n --steps 40 --warmup 5 --full --no-cpu-baseline --no-state-check --no-general-kernel $extra --details $out/d.json > $out/b.json 2> $out/b.err
     python - $out/b.json "n $n $v" <<'P'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d["roofline"]

@@ -8,13 +8,13 @@ cd $GRAFT_REPO_ROOT
 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc $?" >> $OUT/pytest.log; tail -3 $OUT/pytest.log | cut -c1-200
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
 for i in 1 2; do
-  ( time python bench.py --gpus 1 --steps 20 --warmup 5 --details $OUT/bench${i}_details.json ) > $OUT/bench$i.json 2> $OUT/bench$i.err
+  ( time python bench.py --gpus 1 --steps 20 --warmup 5 --full --details $OUT/bench${i}_details.json ) > $OUT/bench$i.json 2> $OUT/bench$i.err
   wc -c $OUT/bench$i.json
 done
 cd /tmp; export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $GRAFT_REPO_ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --details $OUT/profiled_details.json > $OUT/bench_profiled_run.json 2> $OUT/stats.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $OLDPWD/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --details $OUT/profiled_details.json > $OUT/bench_profiled_run.json 2> $OUT/stats.err
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/$C -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-steady-state --no-state-check --steps 20 --warmup 2 --details $OUT/$C.details.json > $OUT/$C.json 2> $OUT/$C.err
+  timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/$C -- python3 $OLDPWD/bench.py --full --no-cpu-baseline --no-steady-state --no-state-check --steps 20 --warmup 2 --details $OUT/$C.details.json > $OUT/$C.json 2> $OUT/$C.err
 done
 cd $GRAFT_REPO_ROOT
 python3 scripts/pmc_traffic.py $OUT $OUT/pmc_bench_traffic.txt --json $OUT/pmc_traffic.json --source profiles/${tag}_pmc_bench_traffic.txt | cut -c1-250

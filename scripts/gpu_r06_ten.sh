@@ -3,7 +3,7 @@
 tag=${1:-r06ten}; n=${2:-10}
 out=gpurun_out/$tag; mkdir -p $out
 for i in $(seq 1 $n); do
-  python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --details $out/d$i.json > $out/b$i.json 2> $out/b$i.err
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --details $out/d$i.json > $out/b$i.json 2> $out/b$i.err
   python - $out/b$i.json <<'P'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d["roofline"]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn the rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py --no-extras --no-cpu-baseline --no-steady-state --steps 20 --warmup 2` (one counter per pass,
+"""Turn the rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py --full --no-extras --no-cpu-baseline --no-steady-state --steps 20 --warmup 2` (one counter per pass,
 as MI355X_MICROARCH.md prescribes) into (i) a readable table and (ii) profiles/pmc_traffic.json, the file bench.py takes `roofline.traffic` from.  The JSON carries the
 sha256 of csrc/stokes3d_kernels.hpp and the git commit of the tree the passes ran on, so that bench.py can tell when the figures are stale.
 
@@ -27,7 +27,7 @@ def main():
             for r in csv.DictReader(open(f)):
                 res[r["Kernel_Name"].replace("(anonymous namespace)::", "")][r["Counter_Name"]].append(float(r["Counter_Value"]))
     n = 512.0 ** 3
-    lines = ["# python3 bench.py --no-extras --no-cpu-baseline --no-steady-state --steps 20 --warmup 2 under rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (one pass each); FETCH_SIZE doubled",
+    lines = ["# python3 bench.py --full --no-extras --no-cpu-baseline --no-steady-state --steps 20 --warmup 2 under rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (one pass each); FETCH_SIZE doubled",
              "# (gfx950: 128-B read requests tallied at 64 B, MI355X_MICROARCH.md 'HBM'); rocprofv3 reports KiB; passes = bytes / (8 B x 512^3)",
              "# k_fused3d<..., TAG, VISC, HIF, VFOLD, NBR, NOF>: VISC true = viscous-limit form (dt = Inf), false = general form (the general_kernel leg); HIF true = high-face layers inside;",
              "# NOF (last argument) 2 = the three zero body-force arrays of SolVi3D are not loaded (the headline), 0 = they are (the with_body_forces leg)"]

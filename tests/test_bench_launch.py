@@ -61,7 +61,7 @@ def _dry_transports(extra_args=(), env_extra=None, torchrun=False, timeout=180, 
     env = dict(os.environ, **(env_extra or {}))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    bench_args = ["--gpus", str(world), "--dry-transports", "--steps", "4", "--warmup", "1", "--leg-steps", "4", *(["--extras"] if extras else []), *(["--details", str(details)] if details else []), *extra_args]
+    bench_args = ["--gpus", str(world), "--dry-transports", "--steps", "4", "--warmup", "1", "--leg-steps", "4", *(["--full", "--extras"] if extras else []), *(["--details", str(details)] if details else []), *extra_args]
     if torchrun:        # how the driver starts N > 1
         import socket
         with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
@@ -100,6 +100,7 @@ def test_default_two_rank_line_is_compact_and_strict(tmp_path):
     assert out["details"] == "d.json"
     full = json.loads((tmp_path / "d.json").read_text())
     assert set(full["transports"]) == {"rccl"} and "alt_decomposition" not in full
+    assert full["steady_state"] is None and "steady_state" not in out          # a plain run times the requested steps and nothing else
 
 
 def test_eight_rank_line_reports_the_2x2x2_rccl_job(tmp_path):
@@ -233,3 +234,40 @@ def test_the_contract_line_is_a_fixed_selection_under_4_kb():
     out = _strict(line)
     assert out["roofline"]["avg_launch_ms"] is None and out["roofline"]["general_form"]["frac"] == 0.82 and "other_configs" not in out and "kernel" not in out["roofline"]
     assert out["cpu_baseline"]["cores"] == 16 and out["state_ok"] is True and out["value"] == 200.123
+
+
+def test_plain_run_is_the_headline_alone_and_full_adds_the_legs():
+    """--full is off by default and turns on every leg beside the headline; --extras implies it; --dump-outputs names a directory"""
+    sys.path.insert(0, str(ROOT))
+    import bench_extras as X
+    a = X.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    assert X.parse_args(["--full"]).full is True and X.parse_args(["--extras"]).full is True
+    assert X.parse_args(["--dump-outputs", "out"]).dump_outputs == "out"
+
+
+def test_dump_outputs_writes_the_same_sample_every_time(tmp_path):
+    """--dump-outputs: the ten state arrays as <name>.npy in float64, whole when small, else the entries at DUMP_SAMPLE seeded flat indices of the logical shape
+    (whatever the strides), identical from call to call and under 64 MB for the 512^3 block"""
+    sys.path.insert(0, str(ROOT))
+    from types import SimpleNamespace as NS
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(3)
+    big = torch.rand(75, 80, 90, dtype=torch.float64, generator=g).permute(2, 1, 0)          # 540000 > DUMP_SAMPLE entries, column-major strides
+    assert big.numel() > bench.DUMP_SAMPLE and not big.is_contiguous()
+    small = [torch.rand(4, 5, 6 + k, dtype=torch.float64, generator=g) for k in range(9)]
+    st = NS(P=big, τ=NS(xx=small[0], yy=small[1], zz=small[2], yz=small[3], xz=small[4], xy=small[5]), V=NS(Vx=small[6], Vy=small[7], Vz=small[8]))
+    bench.dump_outputs(st, tmp_path / "a")
+    bench.dump_outputs(st, tmp_path / "b")
+    names = list(bench.state_outputs(st))
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(n + ".npy" for n in names) and len(names) == 10
+    for n in names:
+        x = np.load(tmp_path / "a" / f"{n}.npy")
+        assert x.dtype == np.float64 and np.array_equal(x, np.load(tmp_path / "b" / f"{n}.npy"))
+    p = np.load(tmp_path / "a" / "P.npy")
+    flat = np.sort(np.random.default_rng([bench.DUMP_SEED, 0]).integers(0, big.numel(), bench.DUMP_SAMPLE))
+    assert p.shape == (bench.DUMP_SAMPLE,) and np.array_equal(p, big.numpy().reshape(-1)[flat])
+    assert np.array_equal(np.load(tmp_path / "a" / "Vz.npy"), small[8].numpy())
+    assert 10 * bench.DUMP_SAMPLE * 8 <= 64e6
