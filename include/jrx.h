@@ -125,7 +125,8 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   (profiles/r05_placement_search.txt section 13, profiles/r06_ten_processes.txt).
  * Read-only counters (jrx_get_option): "stat_fused3d", "stat_fused2d", "stat_thermal_fused", "stat_vep3_fused" = launches of the fused
  *   kernels since jrx_create, "stat_fused3d_visc" = those of "stat_fused3d" that ran the viscous-limit form, "stat_fused3d_inkernel" = those that finished the faces with a neighbour themselves ("fused_overlap" = 3), "stat_visc_checks" /
- *   "stat_visc_fallbacks" = operand checks run / failed (general kernels used), "stat_operand_cache_hits" = driver calls that reused the operand verdict, "stat_graph_replays" = hipGraphLaunch calls -- so that a caller
+ *   "stat_visc_fallbacks" = operand checks run / failed (general kernels used), "stat_operand_cache_hits" = driver calls that reused the operand verdict, "stat_graph_replays" = hipGraphLaunch calls,
+ *   "stat_weno_calls" / "stat_weno_fused" = jrx_weno5_advection2d calls / those that ran the fused three-launch form -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
 /* the caller has written to an operand array (tau_o, P0, Q, K, G, eta, rho g) since the last driver call: a cached verdict of the operand pass ("operand_cache") is dropped */
@@ -652,6 +653,27 @@ jrx_status jrx_compute_viscosity_single(jrx_handle *h, double *eta, const jrx_rh
  * n = {nx, ny, nz}; ndim 2 or 3. */
 jrx_status jrx_compute_shear_heating(jrx_handle *h, double *shear_heating, const double *const *tau, const double *const *tau_o, const double *const *eps,
                                      const double *phase_c, const jrx_rheology *rh, const double *chi, double dt, const int64_t n[3], int32_t ndim);
+
+/* ------------------------------------------------------------------ WENO-5 advection (2D)
+ * WENO_advection!(u, (vx, vy), weno, di, dt) -- src/advection/weno5.jl:195-230 (fluxes :10-151, weno_rhs :154-168, weno_f! :170-175; constants
+ * src/types/constructors/weno.jl:7-24; AMDGPU methods src/ext/AMDGPU/2D.jl:84-88,470-472): SSP-RK3, u <- 1/3 u + 2/3 ut - 2/3 dt r(ut) with
+ * ut = 3/4 u + 1/4 u1 - 1/4 dt r(u1), u1 = u - dt r(u).  method 1 = JS (Val(1)), 2 = Z (Val(2)); dx, dy the uniform spacings (_di = inv.(di)).
+ * udim = size(u), vxdim / vydim = size(vx) / size(vy), wdim = the common size of weno.ut, fL, fR, fB, fT.
+ * Semantics kept from the reference:
+ *  - the loop box and the clamping of every stencil index come from size(u) = (nx, ny); every array is indexed with ITS OWN extents (column-major), which
+ *    may be larger than u's: Benchmark2D_WENO5.jl:77,182 builds weno for ni .+ 1 and advects a field of ni, with velocities Vx_c, Vy_c larger still.  Only the
+ *    (nx, ny) box of ut, fL..fT is written; the velocities are point reads vx[i, j], vy[i, j];
+ *  - weno_rhs clamps iS, iN, jW, jE: on the first and last vertex of a direction the flux difference of that direction is exactly 0;
+ *  - after the call weno.ut holds the stage-2 field.
+ * Two kernel forms, bit-identical in u and ut (tuning key "weno_fused", include/jrx_tuning.h): the default runs one launch per RK stage with the fluxes in
+ * registers, and then fL holds the stage-1 field and fR, fB, fT are not touched -- after such a call fL..fT do NOT hold fluxes (nothing outside weno5.jl
+ * reads them); "weno_fused" = 0 runs the reference's six launches and leaves the fluxes of the stage-2 field in fL..fT.  2D only: the reference's 3D
+ * forwards (src/ext/AMDGPU/3D.jl:71-75,493-495) feed a 3D array into this 2D indexing.  No halo exchange (the reference has none; callers update_halo!).
+ * JRX_ERR_ARG without a launch: method not 1 or 2, nx or ny < 1, any of vx, vy, ut, fL..fT smaller than u along a dimension, two arrays overlapping (vx, vy
+ * excepted).  JRX_ERR_UNSUPPORTED: an array of 2^31 or more entries (32-bit offsets).  Counters "stat_weno_calls", "stat_weno_fused" (jrx_get_option). */
+jrx_status jrx_weno5_advection2d(jrx_handle *h, double *u, const int64_t udim[2], const double *vx, const int64_t vxdim[2], const double *vy,
+                                 const int64_t vydim[2], double *ut, double *fL, double *fR, double *fB, double *fT, const int64_t wdim[2], double dx, double dy,
+                                 double dt, int32_t method);
 
 /* ------------------------------------------------------------------ timing hooks for bench.py */
 /* Runs `iters` PT iterations of the 3D loop body back to back (no norm checks) and reports device times

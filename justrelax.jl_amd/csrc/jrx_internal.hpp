@@ -104,6 +104,9 @@ struct jrx_handle {
                                              // Measured 256^3 311.6 / 311.4 / 312.2 it/s forked vs 312.7 / 313.2 / 312.2 in order (profiles/r04_vep3d_fork.txt): nothing to gain, off
     bool vep3_map = true, vep3_xcd = true;   // 3D VEP edge kernel thread mapping / XCD slab order (A/B)
     bool scratch_sets = true;            // the fused pipelines may allocate their library-owned second state set (0: never -- un-fused paths)
+    bool weno_fused = true;              // tuning: WENO_advection! as three fused launches (0: the reference's six, flux arrays in memory; bit-identical)
+    int weno_rows = 0;                   // tuning: rows a wave of the fused WENO kernel marches (0: by the grid, 64 .. 8)
+    int64_t stat_weno_calls = 0, stat_weno_fused = 0;   // jrx_weno5_advection2d calls / those that ran the fused form
     // ---- read-only counters (jrx_get_option "stat_*"): launches of the fused kernels since jrx_create, so that tests and the bench can
     //      prove which kernel path ran
     int64_t stat_fused3d_inkernel = 0;   // launches of k_fused3d that finished the neighbour faces themselves (fused_overlap = 3)
