@@ -126,7 +126,8 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  * Read-only counters (jrx_get_option): "stat_fused3d", "stat_fused2d", "stat_thermal_fused", "stat_vep3_fused" = launches of the fused
  *   kernels since jrx_create, "stat_fused3d_visc" = those of "stat_fused3d" that ran the viscous-limit form, "stat_fused3d_inkernel" = those that finished the faces with a neighbour themselves ("fused_overlap" = 3), "stat_visc_checks" /
  *   "stat_visc_fallbacks" = operand checks run / failed (general kernels used), "stat_operand_cache_hits" = driver calls that reused the operand verdict, "stat_graph_replays" = hipGraphLaunch calls,
- *   "stat_weno_calls" / "stat_weno_fused" = jrx_weno5_advection2d calls / those that ran the fused three-launch form -- so that a caller
+ *   "stat_weno_calls" / "stat_weno_fused" = jrx_weno5_advection2d calls / those that ran the fused three-launch form,
+ *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
 /* the caller has written to an operand array (tau_o, P0, Q, K, G, eta, rho g) since the last driver call: a cached verdict of the operand pass ("operand_cache") is dropped */
@@ -674,6 +675,27 @@ jrx_status jrx_compute_shear_heating(jrx_handle *h, double *shear_heating, const
 jrx_status jrx_weno5_advection2d(jrx_handle *h, double *u, const int64_t udim[2], const double *vx, const int64_t vxdim[2], const double *vy,
                                  const int64_t vydim[2], double *ut, double *fL, double *fR, double *fB, double *fT, const int64_t wdim[2], double dx, double dy,
                                  double dt, int32_t method);
+
+/* ------------------------------------------------------------------ principal stresses
+ * compute_principal_stresses!(stokes, σ) -- src/stokes/PrincipalStresses.jl:1-63 (hessenberg_eigen_3x3 :67-97), PrincipalStress
+ * src/types/constructors/stokes.jl:121-147, AMDGPU methods src/ext/AMDGPU/2D.jl:182-197, 3D.jl:187-202.  Inputs are @stress_center(stokes.τ)
+ * (src/Utils.jl:346-355), (nx, ny[, nz]) = size(stokes.P); outputs s1, s2[, s3] are (2, nx, ny) / (3, nx, ny, nz) arrays, column-major with the component
+ * index fastest (σ.σ1[i, I...]).  One launch, synchronous.
+ *  - 2D: the reference's closed form KEPT AS WRITTEN (PrincipalStresses.jl:20-36), so that one script gives the same numbers on every backend:
+ *    a = (xx + yy)/2, b = sqrt((xx - yy)^2/2 + xy^2) -- /2 where the eigenvalues need /4, so diag(1, -1) gives +-sqrt(2) --, s1 = (a + b)(cos t, sin t),
+ *    s2 = (a - b)(-sin t, cos t) with t = atan(2 xy / (xx - yy))/2, the one-argument atan: where xx < yy, s1 lies along the minor axis; where xx = yy and
+ *    xy = 0 the vectors are NaN (0/0).  The (2, 1, 1) placeholder σ.σ3 is not passed and never written.
+ *  - 3D: a DELIBERATE DEVIATION: the exact eigendecomposition instead of hessenberg_eigen_3x3, whose QR steps shifted by H[3,3] with an absolute tolerance
+ *    of 1e-10 and at most 50 iterations cannot split +-s of a simple shear (it returns (0, 0, 0) there) and never meet the tolerance at Pa-scale stresses.
+ *    Where the reference converges the two agree (its own case xx, yy, zz = 1, 2, 3, xy, xz, yz = .5, .25, .75 gives 3.48702452, 1.721857, 0.79111848).
+ *    s_j = lambda_j e_j with lambda_1 >= lambda_2 >= lambda_3 (signed, as reverse(sortperm(σ))), e_j a unit eigenvector whose largest-magnitude component
+ *    is positive (the lowest index on ties); a zero tensor gives zeros; a NaN / Inf cell gives non-finite output for that cell only.  Cyclic Jacobi in
+ *    fp64 registers, a fixed cap on the sweeps.
+ * JRX_ERR_ARG without a launch: a NULL pointer, an extent < 1, overlapping outputs or an output overlapping an input.  JRX_ERR_UNSUPPORTED: 2^39 or more
+ * cells.  Counter "stat_principal_calls" (jrx_get_option) counts the calls that launched. */
+jrx_status jrx_principal_stresses2d(jrx_handle *h, double *s1, double *s2, const double *xx, const double *yy, const double *xy_c, int64_t nx, int64_t ny);
+jrx_status jrx_principal_stresses3d(jrx_handle *h, double *s1, double *s2, double *s3, const double *xx, const double *yy, const double *zz,
+                                    const double *yz_c, const double *xz_c, const double *xy_c, int64_t nx, int64_t ny, int64_t nz);
 
 /* ------------------------------------------------------------------ timing hooks for bench.py */
 /* Runs `iters` PT iterations of the 3D loop body back to back (no norm checks) and reports device times

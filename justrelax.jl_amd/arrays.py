@@ -248,6 +248,28 @@ class StokesArrays:
         return t
 
 
+class PrincipalStress(SimpleNamespace):
+    """PrincipalStress(backend, ni) -- src/types/constructors/stokes.jl:121-147 (the AMDGPU methods src/ext/AMDGPU/2D.jl:182-184, 3D.jl:187-189): σ1, σ2,
+    σ3 of shape (ndim, ni...), component index fastest; in 2D σ3 is the (2, 1, 1) placeholder the reference allocates (never written).  ni must be two or
+    three integers (the reference's NTuple{N, Integer} method: anything else is a MethodError there)."""
+
+    def __init__(self, backend_tag, ni):
+        if not isinstance(ni, (tuple, list)) or len(ni) not in (2, 3) or not all(isinstance(n, (int, np.integer)) and not isinstance(n, bool) for n in ni):
+            raise TypeError(f"PrincipalStress: ni must be a tuple of two or three integers, got {ni!r}")
+        super().__init__()
+        ni = tuple(int(n) for n in ni)
+        dev = device_of(backend_tag)
+        nd = len(ni)
+        self.σ1 = fzeros((nd,) + ni, dev)
+        self.σ2 = fzeros((nd,) + ni, dev)
+        self.σ3 = fzeros((2, 1, 1) if nd == 2 else (nd,) + ni, dev)
+
+    # ASCII aliases
+    sigma1 = property(lambda s: s.σ1)
+    sigma2 = property(lambda s: s.σ2)
+    sigma3 = property(lambda s: s.σ3)
+
+
 class PTStokesCoeffs:
     """src/types/stokes.jl:203-229"""
 

@@ -107,6 +107,7 @@ struct jrx_handle {
     bool weno_fused = true;              // tuning: WENO_advection! as three fused launches (0: the reference's six, flux arrays in memory; bit-identical)
     int weno_rows = 0;                   // tuning: rows a wave of the fused WENO kernel marches (0: by the grid, 64 .. 8)
     int64_t stat_weno_calls = 0, stat_weno_fused = 0;   // jrx_weno5_advection2d calls / those that ran the fused form
+    int64_t stat_principal_calls = 0;    // jrx_principal_stresses2d / 3d calls that launched
     // ---- read-only counters (jrx_get_option "stat_*"): launches of the fused kernels since jrx_create, so that tests and the bench can
     //      prove which kernel path ran
     int64_t stat_fused3d_inkernel = 0;   // launches of k_fused3d that finished the neighbour faces themselves (fused_overlap = 3)

@@ -1,7 +1,7 @@
 """Grid operators a time step runs either side of solve! / heatdiffusion_PT! -- the methods the reference's AMDGPU extension forwards to its
 generic kernels (src/ext/AMDGPU/2D.jl:301-352, 3D.jl:311-362): velocity2vertex!, velocity2center!, vertex2center!, center2vertex! (3D),
-center2vertex_harm!, compute_ρg!, compute_shear_heating!.  Julia's `f!` is spelled `f_`.  Every function forwards to one C-ABI entry point of
-include/jrx.h (csrc/gridops.hip); nothing is computed in Python.
+center2vertex_harm!, compute_ρg!, compute_shear_heating!, and compute_principal_stresses[!] (src/ext/AMDGPU/2D.jl:182-197, 3D.jl:187-202).  Julia's `f!` is spelled `f_`.  Every function forwards to one C-ABI entry point of
+include/jrx.h (csrc/gridops.hip, csrc/principal.hip); nothing is computed in Python.
 """
 from __future__ import annotations
 
@@ -183,3 +183,30 @@ def compute_shear_heating_(thermal, stokes, *rest, handle=None):
     pc = pr.center if pr is not None else None
     _h(sh, handle).call("jrx_compute_shear_heating", *_p(sh), arr(stokes.τ, cen), arr(stokes.τ_o, cen), arr(stokes.ε, stag), *_p(pc), C.byref(rh), chi,
                         C.c_double(float(dt)), n, C.c_int32(nd))
+
+
+def compute_principal_stresses_(stokes, σ, *, handle=None):
+    """compute_principal_stresses!(stokes, σ) -- stokes/PrincipalStresses.jl:8-12 (AMDGPU methods src/ext/AMDGPU/2D.jl:193-197, 3D.jl:198-202): the
+    principal stresses of @stress_center(stokes.τ) into σ.σ1, σ.σ2 (and σ.σ3 in 3D) over size(stokes.P).  2D keeps the reference's closed form as written;
+    3D is the exact eigendecomposition, λ1 ≥ λ2 ≥ λ3 (include/jrx.h)."""
+    ni = tuple(stokes.P.shape)
+    nd = len(ni)
+    want = ((nd,) + ni, (nd,) + ni, (2, 1, 1) if nd == 2 else (nd,) + ni)
+    got = tuple(tuple(getattr(σ, k).shape) for k in ("σ1", "σ2", "σ3"))
+    if got[0][:1] != (nd,) or len(got[0]) != nd + 1:
+        raise ValueError(f"compute_principal_stresses!: a {len(got[0]) - 1}D PrincipalStress for {nd}D StokesArrays")
+    if got != want:
+        raise ValueError(f"compute_principal_stresses!: σ1, σ2, σ3 must be {want} for size(stokes.P) = {ni}, got {got}")
+    τ = stokes.τ
+    if nd == 2:
+        _h(σ.σ1, handle).call("jrx_principal_stresses2d", *_p(σ.σ1, σ.σ2, τ.xx, τ.yy, τ.xy_c), *_i64(*ni))
+    else:
+        _h(σ.σ1, handle).call("jrx_principal_stresses3d", *_p(σ.σ1, σ.σ2, σ.σ3, τ.xx, τ.yy, τ.zz, τ.yz_c, τ.xz_c, τ.xy_c), *_i64(*ni))
+
+
+def compute_principal_stresses(backend, stokes, *, handle=None):
+    """compute_principal_stresses(backend, stokes) -- PrincipalStresses.jl:1-6: a new PrincipalStress(backend, size(stokes.P)), filled"""
+    from .arrays import PrincipalStress
+    σ = PrincipalStress(backend, tuple(stokes.P.shape))
+    compute_principal_stresses_(stokes, σ, handle=handle)
+    return σ
