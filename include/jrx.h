@@ -126,6 +126,8 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  * Read-only counters (jrx_get_option): "stat_fused3d", "stat_fused2d", "stat_thermal_fused", "stat_vep3_fused" = launches of the fused
  *   kernels since jrx_create, "stat_fused3d_visc" = those of "stat_fused3d" that ran the viscous-limit form, "stat_fused3d_inkernel" = those that finished the faces with a neighbour themselves ("fused_overlap" = 3), "stat_visc_checks" /
  *   "stat_visc_fallbacks" = operand checks run / failed (general kernels used), "stat_operand_cache_hits" = driver calls that reused the operand verdict, "stat_graph_replays" = hipGraphLaunch calls,
+ *   "stat_sweeps3d" = launches of the 3D z-marching stress and velocity sweeps (k_stress3d_zb, k_velocity3d_zb),
+ *   "stat_fused2d_b" = those of "stat_fused2d" that ran the batch form k_fused2d_b (32-bit byte offsets: only below 2^29 nodes, see "fused2d_batch" in jrx_tuning.h),
  *   "stat_weno_calls" / "stat_weno_fused" = jrx_weno5_advection2d calls / those that ran the fused three-launch form,
  *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */

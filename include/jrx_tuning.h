@@ -42,6 +42,8 @@
  *                                 with batched loads and, with "thermal_fused_ph", the one-launch iteration); 0 = run-time loops, two kernels per iteration (A/B)
  *   "fused2d_batch" (1)           2D visco-elastic loop, one-launch iteration: 1 = the form that requests every operand up front (k_fused2d_b; dt = Inf: its viscous-limit instantiation,
  *                                 which does not load τ_o, P0, K, G, Q, behind the operand check of "viscous_limit"); 0 = the control-flow form (A/B)
+ *                                 It addresses with 32-bit byte offsets and runs only where (nx + 2)(ny + 2) < 2^29; larger blocks take the control-flow form.  The read-only
+ *                                 counter "stat_fused2d_b" (jrx_get_option) counts its launches
  *   "fused2d_max_nodes" (1200000)  ... on grids of up to this many nodes (larger: the two-kernel iteration)
  *   "vep3_prec_tile" (2)          thread map of the fused 3D VEP pre / centre kernel: 1 = 64 x 4 tiles of node columns, 0 = 256 consecutive nodes of the flattened plane, 2 = tiles from 16,384 node columns per plane
  *   "thermal_fused_ph" (1)        3D heat diffusion, phase-ratio form (phase count 1..4): 1 = unobserved iterations as one launch (flux + update + BCs + next PT coefficients; θr_dτ ping-pongs), 0 = two kernels

@@ -112,6 +112,8 @@ struct jrx_handle {
     //      prove which kernel path ran
     int64_t stat_fused3d_inkernel = 0;   // launches of k_fused3d that finished the neighbour faces themselves (fused_overlap = 3)
     int64_t stat_fused3d_visc = 0, stat_visc_checks = 0, stat_visc_fallbacks = 0, stat_fused3d_nof1 = 0, stat_fused3d_nof2 = 0;     // launches of the viscous-limit form of k_fused3d; operand checks run / failed
+    int64_t stat_sweeps3d = 0;               // launches of the 3D z-marching sweeps (k_stress3d_zb, k_velocity3d_zb; 32-bit byte offsets)
+    int64_t stat_fused2d_b = 0;              // ... of them the batch form k_fused2d_b (32-bit byte offsets)
     int64_t stat_fused3d = 0, stat_fused2d = 0, stat_thermal_fused = 0, stat_vep3_fused = 0, stat_graph_replays = 0;
     bool chain_profile = false;          // tuning switch: jrx_stokes3d_iterate_timed also times the stages of a multi-rank fused step (jrx_tuning_chain_profile)
     double chain_us[8] = {};

@@ -732,6 +732,7 @@ jrx_status jrx_stokes2d_solve(jrx_handle *h, const jrx_stokes2d_fields *f, const
                             JRX_HIP(h, hipGraphLaunch(gexec[par], s));
                             iter += GIT; frun -= GIT;
                             h->stat_fused2d += GIT;
+                            if (batch2) h->stat_fused2d_b += GIT;
                         }
                         continue;
                     }
@@ -751,6 +752,7 @@ jrx_status jrx_stokes2d_solve(jrx_handle *h, const jrx_stokes2d_fields *f, const
             const Out6_2d dst = cur_is_user ? setS : setU;
             launch_fused2d(s, a, dst);
             h->stat_fused2d++;
+            if (batch2) h->stat_fused2d_b++;
             JRX_LAUNCH_CHECK(h);
             cur.P = dst.P; cur.txx = dst.txx; cur.tyy = dst.tyy; cur.txy = dst.txy; cur.Vx = dst.Vx; cur.Vy = dst.Vy;
             cur_is_user = !cur_is_user;

@@ -222,6 +222,7 @@ jrx_status launch_stress_zb(jrx_handle *h, hipStream_t s, const SweepArgs &a, bo
         hipLaunchKernelGGL((k_stress3d_zb<false, TX, TY, KZ, 4, false, 8, true, true>), dim3(tm.ntiles), dim3(TX * TY), 0, s, a, tm);
     else hipLaunchKernelGGL((k_stress3d_zb<false, TX, TY, KZ, 4, false, 8, true>), dim3(tm.ntiles), dim3(TX * TY), 0, s, a, tm);
     JRX_LAUNCH_CHECK(h);
+    h->stat_sweeps3d++;
     return JRX_OK;
 }
 
@@ -235,6 +236,7 @@ jrx_status launch_velocity_zb(jrx_handle *h, hipStream_t s, const SweepArgs &a, 
     else if (diag) hipLaunchKernelGGL((k_velocity3d_zb<true, TX, TY, KZ, 4, 8, true>), dim3(tm.ntiles), dim3(TX * TY), 0, s, a, tm);
     else hipLaunchKernelGGL((k_velocity3d_zb<false, TX, TY, KZ, 4, 8, true>), dim3(tm.ntiles), dim3(TX * TY), 0, s, a, tm);
     JRX_LAUNCH_CHECK(h);
+    h->stat_sweeps3d++;
     return JRX_OK;
 }
 

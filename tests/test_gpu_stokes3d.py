@@ -403,7 +403,7 @@ def test_body_forces_that_are_zero_are_not_loaded_and_the_bits_stay(env, ni, bcs
 
 
 @pytest.mark.parametrize("name,where,val", [("P0", "first", np.nan), ("P0", "last", np.inf), ("toxy", "last", np.nan), ("toyz", "first", np.inf), ("G", "last", 0.0), ("eta", "last", np.inf),
-                                            ("fz", "last", 1e-300), ("fx", "first", -0.0)])
+                                            ("fz", "last", 1e-300), ("fx", "first", -0.0)])      # = OPERAND_POISONS below (kept literal: the test ids stay)
 def test_operand_pass_sees_the_first_and_the_last_entry_of_every_array(env, name, where, val):
     """round 6: the operand pass streams every array on its own in 16-byte pairs; the entries outside the pairs -- the last one of an array of odd length (65 x 9 x 9 = 5,265
     cells, 66 x 9 x 10 nodes ...) -- and the very first one are looked at all the same: a poisoned one sends the call to the general kernels, a body-force entry that is not
@@ -435,6 +435,125 @@ def test_operand_pass_sees_the_first_and_the_last_entry_of_every_array(env, name
         assert d[1] == 0 and d[4] == 0 and d[3] == (d[2] if name == "fz" else 0), d        # fz not zero: the x, y loads are still dropped (NOF = 1); fx not +0.0: every load stays
     else:
         assert d[1] == 1 and d[3] == d[4] == 0, d                                               # the check failed: general kernels
+
+
+def _offset_view(t, off):
+    """a Fortran view of t's values that starts `off` bytes into a larger allocation (base[1:1 + n] for 8 B); the entries around it are NaN"""
+    import torch
+    n = t.numel()
+    base = torch.full((n + 2,), float("nan"), dtype=torch.float64, device=t.device)
+    v = base[off // 8: off // 8 + n].view(*reversed(t.shape)).permute(*range(t.dim() - 1, -1, -1))
+    v.copy_(t)
+    return v
+
+
+def _run_operand_pass(env, s, offset, keys):
+    """one solve with every operand array (P0, Q, τ_o, η, K, G, ρg) an offset view; returns (counter deltas, error or None, downloaded state)"""
+    jr = env["jr"]
+    from justrelax_jl_amd import _lib
+    h = _lib.default_handle()
+    try:
+        h.set_option("kernel_variant", 3)
+        stokes, ρg, K, G = env["up"](s, jr.AMDGPUBackend)
+        if offset:
+            stokes.P0, stokes.Q = _offset_view(stokes.P0, offset), _offset_view(stokes.Q, offset)
+            for c in ("xx", "yy", "zz", "yz", "xz", "xy"):
+                setattr(stokes.τ_o, c, _offset_view(getattr(stokes.τ_o, c), offset))
+            stokes.viscosity.η = _offset_view(stokes.viscosity.η, offset)
+            K, G = _offset_view(K, offset), _offset_view(G, offset)
+            ρg = tuple(_offset_view(t, offset) for t in ρg)
+            assert all(t.data_ptr() % 16 == offset % 16 for t in (stokes.P0, stokes.Q, stokes.τ_o.xy, stokes.viscosity.η, K, G, ρg[2]))
+        h.fields_dirty()
+        c0 = [h.get_option(k) for k in keys]
+        err = None
+        try:
+            jr.solve_(stokes, s.pt, s.grid, s.flow_bcs, ρg, K, G, s.dt, None, kwargs=s.kwargs)
+        except _lib.JrxError as e:
+            err = str(e)
+        d = [b - a for a, b in zip(c0, [h.get_option(k) for k in keys])]
+    finally:
+        h.set_option("kernel_variant", 0)
+    return d, err, env["down"](stokes)
+
+
+def _same_bits(a, b, nan_run=False):
+    """every bit outside the racily written ghost edges of V (checks.interior_mask3d); U = V dt (±Inf, NaN where V = 0 when dt = Inf) and the fields of a run
+    that went NaN compare as numbers, NaN = NaN"""
+    from justrelax_jl_amd import checks
+    for k in a:
+        m = checks.interior_mask3d(k, a[k].shape)
+        x, y = np.ascontiguousarray(a[k][m]), np.ascontiguousarray(b[k][m])
+        if nan_run or k[0] == "U":
+            assert np.array_equal(x, y, equal_nan=True), k
+        else:
+            assert np.array_equal(x.view(np.uint64), y.view(np.uint64)), k
+
+
+OPERAND_KEYS = ("stat_visc_checks", "stat_visc_fallbacks", "stat_fused3d", "stat_fused3d_nof1", "stat_fused3d_nof2")
+
+
+OPERAND_POISONS = [("P0", "first", np.nan), ("P0", "last", np.inf), ("toxy", "last", np.nan), ("toyz", "first", np.inf), ("G", "last", 0.0), ("eta", "last", np.inf),
+                   ("fz", "last", 1e-300), ("fx", "first", -0.0)]          # test_operand_pass_sees_the_first_and_the_last_entry_of_every_array
+# every poison at every 16-byte phase and parity of the length, and three more (the entry after the first pair, no poison) -- except the eight cases the
+# test above runs already (aligned arrays of 65 x 9 x 9 cells)
+OPERAND_PHASES = [(name, where, val, ni, offset) for offset in (0, 8) for ni in ((65, 9, 9), (66, 9, 9))
+                  for name, where, val in OPERAND_POISONS + [("Q", "pair", np.nan), ("K", "pair", 0.0), ("fy", "pair", 1e-300), ("none", "", 0.0)]
+                  if not (offset == 0 and ni == (65, 9, 9) and (name, where, val) in OPERAND_POISONS)]
+
+
+@pytest.mark.parametrize("name,where,val,ni,offset", OPERAND_PHASES)
+def test_operand_pass_sees_every_entry_of_arrays_at_any_16_byte_phase(env, name, where, val, ni, offset):
+    """the operand pass of the viscous-limit guard streams each array in 16-byte pairs, with one entry of its own in front when the array starts 8 bytes
+    off a 16-byte boundary (any allocator may hand such an array in) and one behind when the rest is odd: every operand array as a view one double
+    into a larger allocation (or not), odd (65 x 9 x 9) and even (66 x 9 x 9) cell counts, a poisoned first, last or first-after-the-first-pair entry.
+    The verdicts are those of test_operand_pass_sees_the_first_and_the_last_entry_of_every_array, and the run equals the one on aligned copies bit for bit."""
+    jr = env["jr"]
+    s = jr.miniapps.random_fields3d(ni, bcs="free_slip", dt=np.inf, iterMax=9, nout=4)
+    s.pt.ϵ_rel = s.pt.ϵ_abs = 1e-30
+    for c in "xyz":
+        s.arrays["f" + c][...] = 0.0
+    if name != "none":
+        flat = s.arrays[name].reshape(-1, order="F")
+        assert flat.base is s.arrays[name] or flat.base is s.arrays[name].base
+        flat[{"first": 0, "last": -1, "pair": 2 + offset // 8}[where]] = val
+    d, err, out = _run_operand_pass(env, s, offset, OPERAND_KEYS)
+    if err is not None:
+        assert "NaN" in err
+    assert d[0] == 1 and d[2] > 0
+    if name in ("fx", "fy", "fz"):
+        assert d[1] == 0 and d[4] == 0 and d[3] == (d[2] if name == "fz" else 0), d
+    elif name == "none":
+        assert d[1] == 0 and d[3] == 0 and d[4] == d[2], d
+    else:
+        assert d[1] == 1 and d[3] == d[4] == 0, d
+    if offset:
+        d0, err0, out0 = _run_operand_pass(env, s, 0, OPERAND_KEYS)
+        assert d0 == d and (err0 is None) == (err is None)
+        _same_bits(out, out0, nan_run=err is not None)
+
+
+@pytest.mark.parametrize("offset", [0, 8])
+@pytest.mark.parametrize("ni", [(65, 9, 9), (66, 9, 9)])
+@pytest.mark.parametrize("name,where", [("fz", "first"), ("fz", "last"), ("fx", "pair"), ("fy", "last"), ("none", "")])
+def test_force_pass_sees_every_entry_of_arrays_at_any_16_byte_phase(env, name, where, ni, offset):
+    """finite dt: the body-force pass (k_forces_zero) picks the loads of the general form from the bits of ρg, with the arrays as views one double into
+    a larger allocation (or not): ρg_z not +0.0 keeps its load only (NOF = 1), ρg_x / ρg_y not +0.0 keeps every load, all +0.0 drops them (NOF = 2)"""
+    jr = env["jr"]
+    s = jr.miniapps.random_fields3d(ni, bcs="free_slip", dt=0.25, iterMax=9, nout=4)
+    s.pt.ϵ_rel = s.pt.ϵ_abs = 1e-30
+    for c in "xyz":
+        s.arrays["f" + c][...] = 0.0
+    if name != "none":
+        s.arrays[name].reshape(-1, order="F")[{"first": 0, "last": -1, "pair": 2 + offset // 8}[where]] = -0.0 if where == "pair" else 1e-300
+    d, err, out = _run_operand_pass(env, s, offset, OPERAND_KEYS)
+    assert err is None
+    assert d[0] == d[1] == 0 and d[2] > 0, d
+    want = {"fz": [d[2], 0], "fx": [0, 0], "fy": [0, 0], "none": [0, d[2]]}[name]
+    assert d[3:] == want, (d, want)
+    if offset:
+        d0, _, out0 = _run_operand_pass(env, s, 0, OPERAND_KEYS)
+        assert d0 == d
+        _same_bits(out, out0)
 
 
 @pytest.mark.parametrize("poison", ["toxx=nan", "toyz=inf", "P0=inf", "Q=nan", "K=0", "G=nan", "none"])
