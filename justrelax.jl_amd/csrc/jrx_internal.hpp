@@ -241,3 +241,9 @@ jrx_status jrx3d_bcs(jrx_handle *h, hipStream_t s, double *Vx, double *Vy, doubl
 // all free-slip / no-slip faces in one launch: equal to jrx3d_bcs on every entry a Stokes stencil reads once jrx3d_bcs has run on the same arrays
 jrx_status jrx3d_bcs_faces(jrx_handle *h, hipStream_t s, double *Vx, double *Vy, double *Vz, int nx, int ny, int nz, uint32_t fs, uint32_t ns);
 jrx_status jrx3d_sumsq(jrx_handle *h, hipStream_t s, const jrx_stokes3d_fields *f, const jrx_stokes3d_params *p);
+
+// stokes2d.hip: host pieces of the 2D visco-elastic path that the 2D VEP drivers (stokes2d_vep.hip) reuse.  Asynchronous on `s`.
+// bcs = flow_bcs! on (Vx, Vy); sumsq leaves Σx² of Rx, Ry (interior slices) and RP in h->d_sums; spacing_ok: the six inverse-spacing arrays come together or not at all
+jrx_status jrx2d_bcs(jrx_handle *h, hipStream_t s, double *Vx, double *Vy, int nx, int ny, uint32_t fs, uint32_t ns, uint32_t pe);
+jrx_status jrx2d_sumsq(jrx_handle *h, hipStream_t s, const jrx_stokes2d_fields *f, const jrx_stokes2d_params *p);
+bool jrx2d_spacing_ok(const double *const sp[6]);

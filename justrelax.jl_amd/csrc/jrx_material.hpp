@@ -1,4 +1,5 @@
-// jrx_material.hpp -- per-phase material laws of the rheology table (jrx_rheology): density, strain softening, creep viscosity.
+// jrx_material.hpp -- per-phase material laws of the rheology table (jrx_rheology): density, strain softening, creep viscosity, and the
+// plasticity helpers of rheology/StressUpdate.jl that the 2D and 3D visco-elasto-plastic drivers share (one copy: stokes2d_vep.hip, stokes3d_vep.hip).
 // The reference delegates these to GeoParams.jl (compute_density, softening_C / softening_ϕ, compute_viscosity_τII; call sites
 // rheology/BuoyancyForces.jl:37-60, rheology/StressUpdate.jl:305-381, rheology/Viscosity.jl:142-167); the forms are stated in include/jrx.h.
 #pragma once
@@ -107,4 +108,91 @@ __host__ __device__ static inline bool mat_viscosity_reads_invariant(const jrx_r
     for (int q = 0; q < rh->nphase; q++)
         if (rh->visc_kind[q] == 2) return true;
     return false;
+}
+
+// ---- plasticity (rheology/StressUpdate.jl), as update_stresses_center_vertex_ps! 2D and 3D use it
+
+// second invariant of a deviatoric tensor: (xx, yy, xy) in 2D, (xx, yy, zz, yz, xz, xy) in 3D
+__device__ __forceinline__ double sinv2(double xx, double yy, double xy) { return sqrt(0.5 * (xx * xx + yy * yy) + xy * xy); }
+__device__ __forceinline__ double sinv3(const double t[6])
+{
+    return sqrt(0.5 * (t[0] * t[0] + t[1] * t[1] + t[2] * t[2]) + t[3] * t[3] + t[4] * t[4] + t[5] * t[5]);
+}
+// fn_ratio, src/phases/phases.jl:6-15
+// UNROLL: `#pragma unroll` on the phase loop.  The 3D kernels have it, the 2D ones do not, and each side keeps what it was tuned with: with the pragma the 2D kernels
+// that take the phase count at run time grow by 12 - 30 % in instructions (k_vep_vertex 5,893 -> 6,900 lines of ISA, k_phase_avg 890 -> 1,170)
+template <bool UNROLL = false>
+__device__ __forceinline__ double ratio_avg(const double *val, const double *r, int n)
+{
+    double x = 0.0;
+    if (UNROLL) {
+#pragma unroll
+        for (int q = 0; q < n; q++) x += (r[q] == 0.0) ? 0.0 : val[q] * r[q];
+    } else {
+        for (int q = 0; q < n; q++) x += (r[q] == 0.0) ? 0.0 : val[q] * r[q];
+    }
+    return x;
+}
+// NP > 0: the number of phases as a compile-time constant (the phase loops unroll and the caller hands the ratios in registers, loaded in one batch), else rh.nphase
+template <int NP = 0>
+__device__ __forceinline__ void plastic_params(const jrx_rheology &rh, const double *r, bool &is_pl, double &eta_reg)
+{   // plastic_params_phase, rheology/StressUpdate.jl:152-176
+    is_pl = false; eta_reg = 0.0;
+    const int np = NP > 0 ? NP : rh.nphase;
+#pragma unroll
+    for (int q = 0; q < np; q++)
+        if (rh.is_pl[q]) { is_pl = true; eta_reg += rh.eta_vp[q] * r[q]; }
+}
+// SOFT: some phase has a softening law (compiled out otherwise: the erfc / sincos paths cost the 3D edge kernel its second wave per SIMD)
+template <bool SOFT, int NP = 0>
+__device__ __forceinline__ double yield_F(const jrx_rheology &rh, const double *r, double P, double tII, double EII)
+{   // compute_yieldfunction_phase, StressUpdate.jl:399-410 (2D), :435-452 (3D) ; DP: F = τII - cosϕ(EII) C(EII) - sinϕ(EII) P (softening at the EII keyword)
+    double F = 0.0;
+    const int np = NP > 0 ? NP : rh.nphase;
+#pragma unroll
+    for (int q = 0; q < np; q++) {
+        if (r[q] == 0.0) continue;
+        double Fq = tII;
+        if (rh.is_pl[q]) {
+            if (SOFT) {
+                double sp, cp;
+                mat_friction(rh, q, EII, sp, cp);
+                Fq = tII - cp * mat_cohesion(rh, q, EII) - sp * P;
+            } else Fq = tII - rh.cosphi[q] * rh.C[q] - rh.sinphi[q] * P;
+        }
+        F += r[q] * Fq;
+    }
+    return F;
+}
+// NN normal components followed by NC - NN shear components: 2, 3 in 2D and 3, 6 in 3D
+template <int NN, int NC, int NP = 0>
+__device__ __forceinline__ void plastic_grad(const jrx_rheology &rh, const double *r, const double t[NC], double dQdt[NC], double &dQdP, double &dFdP)
+{   // compute_plastic_gradients_phase, StressUpdate.jl:476-495 (2D), :463-550 (3D; shear slots halved once, :466-472) ; ∂Q/∂τ = τ/(2 τII), ∂Q/∂P = -sinψ, ∂F/∂P = -sinϕ
+    static_assert((NN == 2 && NC == 3) || (NN == 3 && NC == 6), "2D or 3D tensor");
+#pragma unroll
+    for (int q = 0; q < NC; q++) dQdt[q] = 0.0;
+    dQdP = 0.0; dFdP = 0.0;
+    double tII;
+    if constexpr (NC == 3) tII = sinv2(t[0], t[1], t[2]);
+    else tII = sinv3(t);
+    const int np = NP > 0 ? NP : rh.nphase;
+    // ∂Q/∂τ of a Drucker-Prager phase does not depend on the phase: one division per component instead of one per component and phase (the same quotient, so the same bits)
+    bool any_pl = false;
+#pragma unroll
+    for (int q = 0; q < np; q++) any_pl |= rh.is_pl[q] != 0;
+    double g[NC] = {};
+    if (any_pl) {
+#pragma unroll
+        for (int s = 0; s < NN; s++) g[s] = 0.5 * t[s] / tII;
+#pragma unroll
+        for (int s = NN; s < NC; s++) g[s] = 0.5 * (t[s] / tII);
+    }
+#pragma unroll
+    for (int q = 0; q < np; q++) {
+        if (r[q] == 0.0 || !rh.is_pl[q]) continue;
+#pragma unroll
+        for (int s = 0; s < NC; s++) dQdt[s] = fma(r[q], g[s], dQdt[s]);
+        dQdP = fma(r[q], -rh.sinpsi[q], dQdP);
+        dFdP = fma(r[q], -rh.sinphi[q], dFdP);
+    }
 }

@@ -6,7 +6,7 @@
 // (update_viscosity_τII!), rheology/StressUpdate.jl:146-176,435-550 (plastic parameters, yield function, gradients),
 // stress_rotation_particles.jl:31-50 (vorticity), Interpolations.jl:314-323 (shear2center!),
 // StressKernels.jl:394-431 (accumulate_tensor!, accumulate_vol!), as test/test_shearband3D_MPI.jl drives them.
-// Rheology table as in the 2D driver (stokes2d.hip): per-phase LinearViscous η, ConstantElasticity (G, Kb),
+// Rheology table as in the 2D driver (stokes2d_vep.hip): per-phase LinearViscous η, ConstantElasticity (G, Kb),
 // DruckerPrager_regularised (C, ϕ, ψ, η_vp); constant densities (ρg given).
 //
 // Per PT iteration: k_vep3_pre (∇V, θ, RP, ε(6)) -> k_vep3_visc -> 3 edge kernels (yz, xz, xy; new edge stresses to
@@ -62,78 +62,6 @@ struct Vep3Args {
     if (j >= (n2_) || k >= (n3_)) return;
 #define GRID_IJK4(n1_, n2_, n3_) dim3((unsigned)(((i64)(n1_) * (n2_) + 63) / 64), (unsigned)(((n3_) + 3) / 4))
 
-__device__ __forceinline__ int clampi3(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ double sinv3(const double t[6])
-{
-    return sqrt(0.5 * (t[0] * t[0] + t[1] * t[1] + t[2] * t[2]) + t[3] * t[3] + t[4] * t[4] + t[5] * t[5]);
-}
-__device__ __forceinline__ double ratio_avg3(const double *val, const double *r, int n)
-{   // fn_ratio, src/phases/phases.jl:6-15
-    double x = 0.0;
-#pragma unroll
-    for (int q = 0; q < n; q++) x += (r[q] == 0.0) ? 0.0 : val[q] * r[q];
-    return x;
-}
-// NP > 0: the number of phases as a compile-time constant (the phase loops unroll), else rh.nphase
-template <int NP = 0>
-__device__ __forceinline__ void plastic_params3(const jrx_rheology &rh, const double *r, bool &is_pl, double &eta_reg)
-{   // plastic_params_phase, rheology/StressUpdate.jl:152-176
-    is_pl = false; eta_reg = 0.0;
-    const int np = NP > 0 ? NP : rh.nphase;
-#pragma unroll
-    for (int q = 0; q < np; q++)
-        if (rh.is_pl[q]) { is_pl = true; eta_reg += rh.eta_vp[q] * r[q]; }
-}
-// SOFT: some phase has a softening law (compiled out otherwise: the erfc / sincos paths cost the edge kernel its second wave per SIMD)
-template <bool SOFT, int NP = 0>
-__device__ __forceinline__ double yield_F3(const jrx_rheology &rh, const double *r, double P, double tII, double EII)
-{   // compute_yieldfunction_phase, StressUpdate.jl:435-452 ; DP: F = τII - cosϕ(EII) C(EII) - sinϕ(EII) P (softening at the EII keyword)
-    double F = 0.0;
-    const int np = NP > 0 ? NP : rh.nphase;
-#pragma unroll
-    for (int q = 0; q < np; q++) {
-        if (r[q] == 0.0) continue;
-        double Fq = tII;
-        if (rh.is_pl[q]) {
-            if (SOFT) {
-                double sp, cp;
-                mat_friction(rh, q, EII, sp, cp);
-                Fq = tII - cp * mat_cohesion(rh, q, EII) - sp * P;
-            } else Fq = tII - rh.cosphi[q] * rh.C[q] - rh.sinphi[q] * P;
-        }
-        F += r[q] * Fq;
-    }
-    return F;
-}
-template <int NP = 0>
-__device__ __forceinline__ void plastic_grad3(const jrx_rheology &rh, const double *r, const double t[6], double dQdt[6], double &dQdP, double &dFdP)
-{   // compute_plastic_gradients_phase, StressUpdate.jl:463-550 (shear slots halved once, :466-472)
-#pragma unroll
-    for (int q = 0; q < 6; q++) dQdt[q] = 0.0;
-    dQdP = 0.0; dFdP = 0.0;
-    const double tII = sinv3(t);
-    const int np = NP > 0 ? NP : rh.nphase;
-    // ∂Q/∂τ of a Drucker-Prager phase does not depend on the phase: one division per component instead of one per component and phase (the same quotient, so the same bits)
-    bool any_pl = false;
-#pragma unroll
-    for (int q = 0; q < np; q++) any_pl |= rh.is_pl[q] != 0;
-    double g[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (any_pl) {
-#pragma unroll
-        for (int s = 0; s < 3; s++) g[s] = 0.5 * t[s] / tII;
-#pragma unroll
-        for (int s = 3; s < 6; s++) g[s] = 0.5 * (t[s] / tII);
-    }
-#pragma unroll
-    for (int q = 0; q < np; q++) {
-        if (r[q] == 0.0 || !rh.is_pl[q]) continue;
-#pragma unroll
-        for (int s = 0; s < 6; s++) dQdt[s] = fma(r[q], g[s], dQdt[s]);
-        dQdP = fma(r[q], -rh.sinpsi[q], dQdP);
-        dFdP = fma(r[q], -rh.sinphi[q], dFdP);
-    }
-}
-
 // store of an output array that no thread of this launch reads back: non-temporal when a.nt (the lines do not displace the operands the neighbouring
 // blocks are about to re-read from L2; tuning switch "vep3_nt")
 #define VST(a_, ptr_, val_) do { double *q_ = &(ptr_); const double v_ = (val_); if ((a_).nt) __builtin_nontemporal_store(v_, q_); else *q_ = v_; } while (0)
@@ -167,10 +95,10 @@ __global__ __launch_bounds__(256) void k_vep3_pre(const Vep3Args a)
 #define VY(i_, j_, k_) Vy[(i_) + (i64)(nx + 2) * ((j_) + (i64)(ny + 1) * (k_))]
 #define VZ(i_, j_, k_) Vz[(i_) + (i64)(nx + 2) * ((j_) + (i64)(ny + 2) * (k_))]
     const bool cellcol = i < nx && j < ny;
-    const int il = clampi3(i - 1, 0, nx - 1), ic = clampi3(i, 0, nx - 1), ir = clampi3(i + 1, 0, nx - 1);
-    const int jl = clampi3(j - 1, 0, ny - 1), jc = clampi3(j, 0, ny - 1), jr = clampi3(j + 1, 0, ny - 1);
+    const int il = clampi(i - 1, 0, nx - 1), ic = clampi(i, 0, nx - 1), ir = clampi(i + 1, 0, nx - 1);
+    const int jl = clampi(j - 1, 0, ny - 1), jc = clampi(j, 0, ny - 1), jr = clampi(j + 1, 0, ny - 1);
     auto plane_max = [&](int kk) {          // clamped 3 x 3 maximum of η in plane clamp(kk), the comparison order of k_maxloc within the plane
-        const i64 pk = (i64)nx * ny * clampi3(kk, 0, nz - 1);
+        const i64 pk = (i64)nx * ny * clampi(kk, 0, nz - 1);
         double m = -INFINITY;
         const int js[3] = {jl, jc, jr}, is[3] = {il, ic, ir};
 #pragma unroll
@@ -277,8 +205,8 @@ __global__ __launch_bounds__(256) void k_vep3_phase_avg(double *__restrict__ Kc,
     if (c >= (i64)a.nx * a.ny * a.nz) return;
     if (eta_lin) eta_lin[c] = vep3_eta_linear(a, c);
     const double *r = a.f.phase_c + (i64)a.rh.nphase * c;
-    Kc[c] = ratio_avg3(a.rh.Kb, r, a.rh.nphase);
-    Gc[c] = ratio_avg3(a.rh.G, r, a.rh.nphase);
+    Kc[c] = ratio_avg<true>(a.rh.Kb, r, a.rh.nphase);
+    Gc[c] = ratio_avg<true>(a.rh.G, r, a.rh.nphase);
     if (rho) {
         const int k = (int)(c / ((i64)a.nx * a.ny)), j = (int)((c - (i64)k * a.nx * a.ny) / a.nx), i = (int)(c - (i64)k * a.nx * a.ny - (i64)j * a.nx);
         const double T = !a.f.T ? 0.0 : (a.tg ? a.f.T[i + (i64)(a.nx + 2) * (j + (i64)(a.ny + 2) * k)] : a.f.T[c]);
@@ -316,9 +244,9 @@ __device__ __forceinline__ EdgeMat edge_mat(const Vep3Args &a, const double *rv)
 {
     EdgeMat m;
     const int np = NP > 0 ? NP : a.rh.nphase;
-    plastic_params3<NP>(a.rh, rv, m.is_pl, m.eta_reg);
-    m._Gdt = 1.0 / (ratio_avg3(a.rh.G, rv, np) * a.dt);
-    m.Kv = ratio_avg3(a.rh.Kb, rv, np);
+    plastic_params<NP>(a.rh, rv, m.is_pl, m.eta_reg);
+    m._Gdt = 1.0 / (ratio_avg<true>(a.rh.G, rv, np) * a.dt);
+    m.Kv = ratio_avg<true>(a.rh.Kb, rv, np);
     return m;
 }
 // PRE: lam_pre is λv of the node, fetched by the caller ahead of the return mapping
@@ -329,9 +257,9 @@ __device__ __forceinline__ void vep3_edge_plastic(const Vep3Args &a, i64 v, cons
     double *const eplsh[3] = {a.f.eplyz, a.f.eplxz, a.f.eplxy};
     const double tIIv = sinv3(tt);
     double dQdt[6], dQdP, dFdP;
-    plastic_grad3<NP>(a.rh, rv, tt, dQdt, dQdP, dFdP);
+    plastic_grad<3, 6, NP>(a.rh, rv, tt, dQdt, dQdP, dFdP);
     const double vol = isinf(m.Kv) ? 0.0 : m.Kv * a.dt * dFdP * dQdP;
-    const double F = yield_F3<SOFT, NP>(a.rh, rv, Pv, tIIv, SOFT ? EIIv : 0.0);
+    const double F = yield_F<SOFT, NP>(a.rh, rv, Pv, tIIv, SOFT ? EIIv : 0.0);
     constexpr int own = 3 + T;
     if (m.is_pl && tIIv != 0.0 && F > 0) {
         const double l = (1.0 - a.rel) * (PRE ? lam_pre : a.lamv[T][v]) + a.rel * (fmax(F, 0.0) / (etav * dtr + m.eta_reg + vol));
@@ -474,9 +402,9 @@ __global__ __launch_bounds__(256) void k_vep3_edges(const Vep3Args a, const int 
         if (j >= ny + 1) return;
     }
     const int nz = a.nz;
-    const int ci[3] = {clampi3(i - 1, 0, nx - 1), clampi3(i, 0, nx - 1), clampi3(i + 1, 0, nx - 1)};
-    const int cj[3] = {clampi3(j - 1, 0, ny - 1), clampi3(j, 0, ny - 1), clampi3(j + 1, 0, ny - 1)};
-    const int ck[3] = {clampi3(k - 1, 0, nz - 1), clampi3(k, 0, nz - 1), clampi3(k + 1, 0, nz - 1)};
+    const int ci[3] = {clampi(i - 1, 0, nx - 1), clampi(i, 0, nx - 1), clampi(i + 1, 0, nx - 1)};
+    const int cj[3] = {clampi(j - 1, 0, ny - 1), clampi(j, 0, ny - 1), clampi(j + 1, 0, ny - 1)};
+    const int ck[3] = {clampi(k - 1, 0, nz - 1), clampi(k, 0, nz - 1), clampi(k + 1, 0, nz - 1)};
     CenAvg C;
     vep3_gather_centres<SOFT>(a, ci, cj, ck, C);
     vep3_edge_body<0, SOFT, NP>(a, i, j, k, ci, cj, ck, C);
@@ -519,8 +447,8 @@ __device__ __forceinline__ void vep3_edges_z_tile(const Vep3Args &a, const int s
     const int i = seg * 62 - 1 + lane;
     const bool useful = lane >= 1 && lane <= 62 && i <= nx && i < ilim;
     const int kb = zchunk * KZ, ke = min(kb + KZ, nz + 1);
-    const int ic = clampi3(i, 0, nx - 1), ir = clampi3(i, 0, nx);
-    const int cj0 = clampi3(j - 1, 0, ny - 1), cj1 = clampi3(j, 0, ny - 1), cj2 = clampi3(j + 1, 0, ny - 1);
+    const int ic = clampi(i, 0, nx - 1), ir = clampi(i, 0, nx);
+    const int cj0 = clampi(j - 1, 0, ny - 1), cj1 = clampi(j, 0, ny - 1), cj2 = clampi(j + 1, 0, ny - 1);
     const bool lo_i = i >= 1, hi_i = i < nx - 1;
     // value at clamp(i - 1) / clamp(i + 1): the neighbouring lane's, or the own one on the domain's faces and at the ends of the wave -- the clamp goes into the permute address
     // (as a select behind __shfl_up / __shfl_down it was two v_cndmask per double: 56 of the ~430 VALU instructions of a plane step)
@@ -615,12 +543,12 @@ __device__ __forceinline__ void vep3_edges_z_tile(const Vep3Args &a, const int s
         }
     };
     {
-        const u32 kc = (u32)clampi3(kb - 1, 0, nz - 1);
-        if constexpr (LDSC) { publish(kc, (u32)clampi3(kb, 0, nz - 1), kc, 0); __syncthreads(); }
+        const u32 kc = (u32)clampi(kb - 1, 0, nz - 1);
+        if constexpr (LDSC) { publish(kc, (u32)clampi(kb, 0, nz - 1), kc, 0); __syncthreads(); }
         if constexpr (PROD == 2) {      // the publishing wave: one publication and one barrier per plane, in step with the family waves
 #pragma unroll 1
             for (int k = kb; k < ke; k++) {
-                const u32 k1 = (u32)clampi3(k, 0, nz - 1), k2 = (u32)clampi3(k + 1, 0, nz - 1);
+                const u32 k1 = (u32)clampi(k, 0, nz - 1), k2 = (u32)clampi(k + 1, 0, nz - 1);
                 const int bsel = (k - kb + 1) & 1;
                 publish(k1, k2, k1, bsel, k);
                 __syncthreads();
@@ -641,7 +569,7 @@ __device__ __forceinline__ void vep3_edges_z_tile(const Vep3Args &a, const int s
             pyz[s] = v0 + v1;
             pxz[s] = u1 + v1;
         }
-        const u32 k1 = (u32)clampi3(kb, 0, nz - 1);
+        const u32 k1 = (u32)clampi(kb, 0, nz - 1);
         if constexpr (LDSS) read_shear(0);
         else {
 #pragma unroll
@@ -654,7 +582,7 @@ __device__ __forceinline__ void vep3_edges_z_tile(const Vep3Args &a, const int s
     }
 #pragma unroll 1
     for (int k = kb; k < ke; k++) {
-        const u32 k1 = (u32)clampi3(k, 0, nz - 1), k2 = (u32)clampi3(k + 1, 0, nz - 1);
+        const u32 k1 = (u32)clampi(k, 0, nz - 1), k2 = (u32)clampi(k + 1, 0, nz - 1);
         const bool act2 = useful && k < nz;
         const i64 vi[3] = {i + (i64)nx * (j + (i64)(ny + 1) * k), i + (i64)(nx + 1) * (j + (i64)ny * k), i + (i64)(nx + 1) * (j + (i64)(ny + 1) * k)};
         double rvl[PROD == 1 ? NP : 1];          // PROD == 1: the own family's phase ratios, from the publishing wave's slots (read behind the barrier below)
@@ -846,10 +774,10 @@ __global__ __launch_bounds__(256) void k_vep3_centre(const Vep3Args a)
         for (int q = 0; q < NP; q++) rcv[q] = a.f.phase_c[(i64)NP * c + q];
     }
     const double *rc = NP > 0 ? rcv : a.f.phase_c + (i64)np * c;
-    const double _Gdt = 1.0 / (ratio_avg3(a.rh.G, rc, np) * a.dt);
+    const double _Gdt = 1.0 / (ratio_avg<true>(a.rh.G, rc, np) * a.dt);
     bool is_pl; double eta_reg;
-    plastic_params3<NP>(a.rh, rc, is_pl, eta_reg);
-    const double K = ratio_avg3(a.rh.Kb, rc, np);
+    plastic_params<NP>(a.rh, rc, is_pl, eta_reg);
+    const double K = ratio_avg<true>(a.rh.Kb, rc, np);
     const double e = a.f.eta[c];
     const double dtr = 1.0 / (a.theta_dtau + e * _Gdt + 1.0);
     double eij[6] = {a.f.exx[c], a.f.eyy[c], a.f.ezz[c], 0, 0, 0};
@@ -876,10 +804,10 @@ __global__ __launch_bounds__(256) void k_vep3_centre(const Vep3Args a)
         tII = sinv3(q6);
     }
     double dQdt[6], dQdP, dFdP;
-    plastic_grad3<NP>(a.rh, rc, tt, dQdt, dQdP, dFdP);
+    plastic_grad<3, 6, NP>(a.rh, rc, tt, dQdt, dQdP, dFdP);
     const double vol = isinf(K) ? 0.0 : K * a.dt * dFdP * dQdP;
     const double Pr = a.theta[c];
-    const double F = yield_F3<SOFT, NP>(a.rh, rc, Pr, tII, SOFT ? a.f.EII_pl[c] : 0.0);
+    const double F = yield_F<SOFT, NP>(a.rh, rc, Pr, tII, SOFT ? a.f.EII_pl[c] : 0.0);
     double l = a.lam[c];
     if (is_pl && tII != 0.0 && F > 0) {
         l = (1.0 - a.rel) * l + a.rel * (fmax(F, 0.0) / (e * dtr + eta_reg + vol));
@@ -969,10 +897,10 @@ __global__ __launch_bounds__(256, 3) void k_vep3_prec(const Vep3Args a, double *
     const double *const Y01 = Vy + qY, *const Y11 = Vy + rY + qY, *const Y02 = Vy + 2 * qY, *const Y12 = Vy + rY + 2 * qY, *const Y00 = Vy, *const Y10 = Vy + rY;
     const double *const Z00 = Vz, *const Z10 = Vz + rZ, *const Z20 = Vz + 2 * rZ, *const Z01 = Vz + qZ, *const Z11 = Vz + rZ + qZ, *const Z21 = Vz + 2 * rZ + qZ;
     // clamped 3 x 3 window of η: three row offsets, the x displacements 0 on the faces
-    const u32 er[3] = {8u * (u32)(i + nx * clampi3(j - 1, 0, ny - 1)), 8u * (u32)(i + nx * j), 8u * (u32)(i + nx * clampi3(j + 1, 0, ny - 1))};
+    const u32 er[3] = {8u * (u32)(i + nx * clampi(j - 1, 0, ny - 1)), 8u * (u32)(i + nx * j), 8u * (u32)(i + nx * clampi(j + 1, 0, ny - 1))};
     const u32 dxl = i > 0 ? 8u : 0u, dxr = i < nx - 1 ? 8u : 0u;
     auto plane_max = [&](int kk) {          // clamped 3 x 3 maximum of η in plane clamp(kk), the comparison order of k_maxloc within the plane
-        const double *const ep = a.f.eta + (i64)nx * ny * clampi3(kk, 0, nz - 1);
+        const double *const ep = a.f.eta + (i64)nx * ny * clampi(kk, 0, nz - 1);
         double m = -INFINITY;
 #pragma unroll
         for (int q = 0; q < 3; q++) {
@@ -1007,7 +935,7 @@ __global__ __launch_bounds__(256, 3) void k_vep3_prec(const Vep3Args a, double *
         const double Kc_ = LB(a.Kc, oc), Gc_ = LB(a.Gc, oc), P = LB(a.theta, oc), P0 = LB(a.f.P0, oc), Q_ = LB(a.f.Q, oc);
         double w9[9], et_in = 0.0;
         if (ML) {
-            const double *const ep = a.f.eta + (i64)nx * ny * clampi3(k + 1, 0, nz - 1);
+            const double *const ep = a.f.eta + (i64)nx * ny * clampi(k + 1, 0, nz - 1);
 #pragma unroll
             for (int q = 0; q < 3; q++) { w9[3 * q] = LB(ep, er[q] - dxl); w9[3 * q + 1] = LB(ep, er[q]); w9[3 * q + 2] = LB(ep, er[q] + dxr); }
         } else et_in = LB(a.etatau, oc);
@@ -1082,10 +1010,10 @@ __global__ __launch_bounds__(256, 3) void k_vep3_prec(const Vep3Args a, double *
         SW(eta_out, oc) = e;
         // ---- update_stresses_center_vertex_ps!, centres (k_vep3_centre)
         const double *rc = NP > 0 ? rcv : a.f.phase_c + (i64)np * c;
-        const double _Gdt = 1.0 / (ratio_avg3(a.rh.G, rc, np) * a.dt);
+        const double _Gdt = 1.0 / (ratio_avg<true>(a.rh.G, rc, np) * a.dt);
         bool is_pl; double eta_reg;
-        plastic_params3<NP>(a.rh, rc, is_pl, eta_reg);
-        const double K = ratio_avg3(a.rh.Kb, rc, np);
+        plastic_params<NP>(a.rh, rc, is_pl, eta_reg);
+        const double K = ratio_avg<true>(a.rh.Kb, rc, np);
         const double dtr = 1.0 / (a.theta_dtau + e * _Gdt + 1.0);
         double d[6], tt[6];
 #pragma unroll
@@ -1101,9 +1029,9 @@ __global__ __launch_bounds__(256, 3) void k_vep3_prec(const Vep3Args a, double *
             tII = sinv3(q6);
         }
         double dQdt[6], dQdP, dFdP;
-        plastic_grad3<NP>(a.rh, rc, tt, dQdt, dQdP, dFdP);
+        plastic_grad<3, 6, NP>(a.rh, rc, tt, dQdt, dQdP, dFdP);
         const double vol = isinf(K) ? 0.0 : K * a.dt * dFdP * dQdP;
-        const double F = yield_F3<SOFT, NP>(a.rh, rc, Pr, tII, EII_);
+        const double F = yield_F<SOFT, NP>(a.rh, rc, Pr, tII, EII_);
         double l = l_old;
         if (is_pl && tII != 0.0 && F > 0) {
             l = (1.0 - a.rel) * l + a.rel * (fmax(F, 0.0) / (e * dtr + eta_reg + vol));
