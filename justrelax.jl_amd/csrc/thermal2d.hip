@@ -516,7 +516,7 @@ jrx_status heat2d(jrx_handle *h, const jrx_thermal2d_fields *t, const jrx_therma
                     while (run >= GIT) {
                         JRX_HIP(h, hipGraphLaunch(gexec[par], s));
                         iter += GIT; run -= GIT;
-                        h->stat_thermal_fused += GIT;
+                        h->stat_thermal_fused += GIT; h->stat_graph_replays++;
                     }
                     continue;
                 }
@@ -546,6 +546,7 @@ jrx_status heat2d(jrx_handle *h, const jrx_thermal2d_fields *t, const jrx_therma
                     while (run >= GIT) {
                         JRX_HIP(h, hipGraphLaunch(gexec[0], s));
                         iter += GIT; run -= GIT;
+                        h->stat_graph_replays++;
                     }
                     continue;
                 }
