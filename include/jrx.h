@@ -409,6 +409,43 @@ jrx_status jrx_vep2d_compute_viscosity(jrx_handle *h, const jrx_vep2d_fields *f,
  * @stress_center (vertices: τ.xy alone, the PT solvers leave τ.xx_v, τ.yy_v zero) instead of the strain rate's; identical for the other creep laws */
 jrx_status jrx_vep2d_compute_viscosity_tauII(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_rheology *rh, const jrx_vep2d_params *p, double nu);
 
+/* ------------------------------------------------------------------ 2D variational Stokes (free surface through a rock-ratio mask)
+ * solve_VariationalStokes!(stokes, pt_stokes, grid, flow_bcs, ρg, phase_ratios, ϕ::RockRatio, rheology, args, dt, igg; air_phase, kwargs)
+ * -- src/variational_stokes/Stokes2D.jl:24-314: the multiphase visco-elasto-plastic driver above with the rock ratio ϕ on ∇V, the strain
+ * rates, the stress update and the velocity update (variational_stokes/VelocityKernels.jl:6-59,332-401, StressKernels.jl:2-170,
+ * MiniKernels.jl, mask.jl:168-254), residual norms over the valid nodes only, and the air_phase correction of the viscosity
+ * (rheology/Viscosity.jl:403-405,638-650).  Built: 2D, one block, uniform spacing, strain-rate form.  Status JRX_ERR_ARG, with a text that
+ * names it, for: p->inv_spacing non-NULL, p->strain_increment, a handle with a communicator, a DruckerPragerCap phase (the table has no such law: a caller
+ * that meets one marks the phase with is_pl = 2, and any is_pl other than 0 or 1 is refused), and -- beyond the reference, where correct_phase_ratio would index
+ * out of range -- an air_phase outside 0..nphase (the solve and jrx_vep2d_compute_viscosity_air; jrx_update_rock_ratio accepts any value, as compute_rock_ratio does).
+ * ϕ (variational_stokes/mask.jl:1-42): center (nx, ny), vertex (nx+1, ny+1), Vx (nx+1, ny), Vy (nx, ny+1) -- no ghost nodes. */
+typedef struct jrx_rock_ratio2d {
+    const double *center, *vertex, *Vx, *Vy;
+} jrx_rock_ratio2d;
+/* compute_rock_ratio / update_rock_ratio_cv! / _update_rock_ratio! (variational_stokes/mask.jl:112-157) for one member of ϕ, any dimension:
+ * dst[t] = 1 - phase[air_phase - 1 + nphase * t] (CellArray layout, phase index fastest; air_phase is 1-based), zeroed when <= 1e-5; 1.0 when
+ * air_phase is outside 1..nphase; clamp != 0: clamped to [0, 1] (the velocity and shear members; center and vertex are not clamped). */
+jrx_status jrx_update_rock_ratio(jrx_handle *h, double *dst, const double *phase, int32_t nphase, int32_t air_phase, int64_t count, int32_t clamp);
+/* _solve_VS! (variational_stokes/Stokes2D.jl:24-314).  air_phase: 1-based index of the air phase, 0 = none.  The norms are taken over
+ * Rx[ϕ.Vx[2:end-1, :] .> 0], Ry[ϕ.Vy[:, 2:end-1] .> 0], RP[ϕ.center .> 0] and divided by the unmasked counts (:59-61,255-259). */
+jrx_status jrx_stokes2d_vs_solve(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_rock_ratio2d *phi, const jrx_rheology *rh,
+                                 const jrx_vep2d_params *p, int32_t air_phase, jrx_solve_result *res);
+/* masked compute_∇V! + compute_strain_rate! alone (variational_stokes/VelocityKernels.jl:6-59): writes ∇V, ε.xx, ε.yy, ε.xy; zero at invalid nodes -- for parity tests */
+jrx_status jrx_vs2d_strain_rates(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_rock_ratio2d *phi, const jrx_vep2d_params *p);
+/* masked update_stresses_center_vertex! 2D alone (variational_stokes/StressKernels.jl:2-170; θ, λ, λv are caller arrays of extents ni, ni, ni.+1).
+ * At an invalid centre τ (xx, yy, xy_c), ε_pl (xx, yy, and xy at the centre's own index), Pr_c = f->P, η_vep and ε_vol_pl are zeroed and τ.II is
+ * left; at an invalid vertex only τ.xy is zeroed -- for parity tests */
+jrx_status jrx_vs2d_update_stresses(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_rock_ratio2d *phi, const double *theta, double *lambda,
+                                    double *lambda_v, const jrx_rheology *rh, const jrx_vep2d_params *p);
+/* masked compute_V! with dt alone (variational_stokes/VelocityKernels.jl:332-401): V, Rx, Ry; etatau is ητ (ni); the free-surface term takes
+ * dt * free_surface = p->free_surface ? p->dt : 0 -- for parity tests */
+jrx_status jrx_vs2d_compute_V(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_rock_ratio2d *phi, const double *etatau, const jrx_vep2d_params *p);
+/* compute_viscosity! (tauII = 0) / update_viscosity_τII! (tauII != 0) with the air_phase keyword (rheology/Viscosity.jl:382-418): the ratios of a
+ * node go through correct_phase_ratio (:638-650) first -- all zero where the air ratio ≈ 1, else the air entry dropped and the rest
+ * renormalised.  air_phase = 0: the arithmetic of jrx_vep2d_compute_viscosity / _tauII. */
+jrx_status jrx_vep2d_compute_viscosity_air(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_rheology *rh, const jrx_vep2d_params *p, double nu,
+                                           int32_t air_phase, int32_t tauII);
+
 /* ------------------------------------------------------------------ 3D multiphase visco-elasto-plastic Stokes
  * solve!(stokes, pt_stokes, grid, flow_bcs, ρg, phase_ratios, rheology, args, dt, igg; kwargs) for 3D grids --
  * src/stokes/Stokes3D.jl:447-668 with update_stresses_center_vertex_ps! 3D (src/stokes/StressKernels.jl:604-989), as

@@ -98,6 +98,7 @@ VEP_NAMES = ["P", "P0", "divV", "Q", "Vx", "Vy", "Ux", "Uy", "exx", "eyy", "exy"
              "dexy_c", "dexy", "txx", "tyy", "txy", "txy_c", "tII", "toxx", "toyy", "toxy", "toxy_c", "eta", "eta_v", "eta_vep",
              "EII_pl", "evol_pl", "EVol_pl", "fx", "fy", "RP", "Rx", "Ry", "omega_xy", "phase_c", "phase_v", "T", "dexx", "deyy", "divU"]
 VEP2DFields = _ptr_struct("VEP2DFields", VEP_NAMES)
+RockRatio2D = _ptr_struct("RockRatio2D", ["center", "vertex", "Vx", "Vy"])      # jrx_rock_ratio2d
 MAXPHASE = 8
 
 

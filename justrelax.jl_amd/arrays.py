@@ -270,6 +270,40 @@ class PrincipalStress(SimpleNamespace):
     sigma3 = property(lambda s: s.σ3)
 
 
+class RockRatio:
+    """RockRatio(backend, ni) / RockRatio(backend, nx, ny[, nz]) -- src/variational_stokes/mask.jl:1-42: the rock fraction ϕ (1 - air) at the centres (ni),
+    the vertices (ni .+ 1) and the velocity nodes Vx, Vy[, Vz] without ghost nodes, zero-initialised.  In 2D Vz, yz, xz, xy are the (1, 1) placeholders the
+    reference allocates; in 3D they are the real arrays at the velocity / shear-stress locations.  Non-integer sizes raise (test/test_types.jl:306-307)."""
+
+    def __init__(self, backend_tag, *ni):
+        if len(ni) == 1 and isinstance(ni[0], (tuple, list)):
+            ni = tuple(ni[0])
+        if len(ni) not in (2, 3) or not all(isinstance(n, (int, np.integer)) and not isinstance(n, bool) for n in ni):
+            raise TypeError(f"RockRatio: the sizes must be two or three integers, got {ni!r}")
+        ni = tuple(int(n) for n in ni)
+        dev = device_of(backend_tag)
+        self._ni = ni
+        self.center = fzeros(ni, dev)
+        self.vertex = fzeros(tuple(n + 1 for n in ni), dev)
+        for d, name in enumerate(("Vx", "Vy", "Vz")[: len(ni)]):
+            setattr(self, name, fzeros(tuple(n + (1 if e == d else 0) for e, n in enumerate(ni)), dev))
+        if len(ni) == 3:
+            ts = _tensor_shapes(ni)
+            self.yz, self.xz, self.xy = (fzeros(ts[k], dev) for k in ("yz", "xz", "xy"))
+        else:
+            self.Vz = self.yz = self.xz = self.xy = fzeros((1, 1), dev)
+
+
+def size_c(x): return tuple(x.center.shape)
+def size_v(x): return tuple(x.vertex.shape)
+def size_vx(x): return tuple(x.Vx.shape)
+def size_vy(x): return tuple(x.Vy.shape)
+def size_vz(x): return tuple(x.Vz.shape)
+def size_yz(x): return tuple(x.yz.shape)
+def size_xz(x): return tuple(x.xz.shape)
+def size_xy(x): return tuple(x.xy.shape)
+
+
 class PTStokesCoeffs:
     """src/types/stokes.jl:203-229"""
 

@@ -173,6 +173,54 @@ def shearband2d(n=32, *, iterMax=50_000, nout=100, xvi=None) -> Setup:
                  extra=dict(li=li, di=di, phases=phases, εbg=εbg, G0=G0, η0=η0))
 
 
+def shearband2d_variational(n=32, air_rows=0, *, iterMax=50_000, nout=100) -> Setup:
+    """ShearBand2D_variational -- miniapps/benchmarks/stokes2D/shear_band/ShearBand2D_variational.jl: the shear band of `shearband2d` solved with
+    solve_VariationalStokes!.  air_rows = 0 is the script's own set-up: two rock phases, air_phase = 0, so that update_rock_ratio! gives ϕ ≡ 1.
+    air_rows > 0 adds a third phase on top -- low constant viscosity, no plasticity, a small density against the rock's (g = 1) -- with air_phase = 3: it fills
+    the top `air_rows` rows of cells, and the row of cells below them partially, so that centres, vertices and both velocity locations carry fractional ratios
+    (a ramp in y over one and a half cells, modulated in x); the rock ratios are scaled by what the air leaves.  arrays["phase_vx"], ["phase_vy"] are the ratios at
+    the velocity nodes without ghost nodes, (nx+1, ny) and (nx, ny+1).  A finite viscosity_cutoff is set then: correct_phase_ratio gives pure air an all-zero ratio
+    vector, whose phase viscosity is Inf before the cutoff."""
+    s = shearband2d(n, iterMax=iterMax, nout=nout)
+    nx, ny = s.ni
+    grid, a = s.grid, s.arrays
+    (xc, yc), (xv, yv) = grid.xci, grid.xvi
+    dy = s.extra["di"][1]
+    nph = 3 if air_rows > 0 else 2
+    if not 0 <= air_rows < ny - 2:
+        raise ValueError("air_rows must leave rock rows below the partially filled one")
+    y0 = yv[ny - air_rows - 1] if air_rows > 0 else None      # bottom of the partially filled row of cells
+
+    def air(x, y):
+        X, Y = np.meshgrid(x, y, indexing="ij")
+        if air_rows <= 0:
+            return np.zeros(X.shape)
+        R = np.clip((Y - (y0 - 0.25 * dy)) / (1.5 * dy), 0.0, 1.0)
+        return np.where(R >= 1.0, 1.0, np.clip(R * (0.6 + 0.8 * X), 0.0, 1.0))
+    radius, ox, oy = 0.1, 0.5, 0.5
+    for name, (xs, ys) in (("phase_c", (xc, yc)), ("phase_v", (xv, yv)), ("phase_vx", (xv, yc)), ("phase_vy", (xc, yv))):
+        X, Y = np.meshgrid(xs, ys, indexing="ij")
+        outside = ((X - ox) ** 2 + (Y - oy) ** 2) > radius ** 2
+        A = air(xs, ys)
+        r = np.zeros((nph,) + X.shape, order="F")
+        r[0] = np.where(outside, 1.0, 0.0) * (1.0 - A)
+        r[1] = np.where(outside, 0.0, 1.0) * (1.0 - A)
+        if nph == 3:
+            r[2] = A
+        a[name] = r
+    phases = [dict(ph) for ph in s.extra["phases"]]
+    kwargs = dict(s.kwargs, air_phase=0)
+    if nph == 3:
+        for ph in phases:
+            ph["density"] = dict(kind="constant", rho0=1.0)
+        phases[0]["g"] = 1.0
+        phases.append(dict(eta=1.0e-2, G=phases[0]["G"], Kb=phases[0]["Kb"], density=dict(kind="constant", rho0=1.0e-3)))
+        kwargs.update(air_phase=3, viscosity_cutoff=(1.0e-2, 1.0e2))
+    s.extra["phases"] = phases
+    s.kwargs = kwargs
+    return s
+
+
 def shearheating2d(n=32, *, iterMax=75_000, nout=1000) -> Setup:
     """Shearheating2D -- test/test_shearheating2D.jl:66-232 without the particles (phase ratios from 8 x 8 sample points per cell / vertex area): 70 x 40 km box,
     dislocation-creep matrix and inclusion of Duretz et al. 2014 (Shearheating_rheology.jl:6-7; no elastic or plastic element), disc of radius 3 km at 40 km depth,

@@ -537,22 +537,26 @@ def _ghosted_T_flag(stokes, T):
     return 1
 
 
-def compute_viscosity_τII_(stokes, *rest, relaxation=1.0, handle=None):
-    """compute_viscosity_τII!(stokes, phase_ratios, args, rheology, cutoff; relaxation) / update_viscosity_τII! (rheology/Viscosity.jl:67-106,198-216)"""
-    return compute_viscosity_(stokes, *rest, relaxation=relaxation, handle=handle, fn="τII")
+def compute_viscosity_τII_(stokes, *rest, relaxation=1.0, handle=None, air_phase=0):
+    """compute_viscosity_τII!(stokes, phase_ratios, args, rheology, cutoff; relaxation, air_phase) / update_viscosity_τII! (rheology/Viscosity.jl:67-106,198-216)"""
+    return compute_viscosity_(stokes, *rest, relaxation=relaxation, handle=handle, fn="τII", air_phase=air_phase)
 
 
-def compute_viscosity_(stokes, *rest, relaxation=1.0, handle=None, fn="εII", AII=None):
+def compute_viscosity_(stokes, *rest, relaxation=1.0, handle=None, fn="εII", AII=None, air_phase=0):
     """compute_viscosity!(stokes, phase_ratios, args, rheology, cutoff; relaxation) for the table rheology (rheology/Viscosity.jl:203-216), or -- without
     phase ratios -- compute_viscosity!(stokes, args, rheology::MaterialParams, cutoff; relaxation) (Viscosity.jl:118-167; args.T is thermal.T, read at I .+ 1).
     fn: "εII" (compute_viscosity!) or "τII" (compute_viscosity_τII! / update_viscosity_τII!): the invariant a power-law creep is evaluated at.
-    AII (single-material form): the invariant array of compute_viscosity_εII! / _τII!(η, ν, AII, args, rheology, cutoff) (Viscosity.jl:169-196)"""
+    AII (single-material form): the invariant array of compute_viscosity_εII! / _τII!(η, ν, AII, args, rheology, cutoff) (Viscosity.jl:169-196)
+    air_phase (phase-ratio form, 2D): 1-based index of the air phase whose ratio correct_phase_ratio removes before the phase average (Viscosity.jl:403-405,638-650);
+    0 (default) keeps the path without it"""
     if fn not in ("εII", "τII"):
         raise ValueError("fn must be 'εII' or 'τII'")
     _require_gpu(stokes)
     h = handle or _lib.default_handle(stokes.P.device.index)
     from .arrays import PhaseRatios
     if not rest or not (isinstance(rest[0], PhaseRatios) or hasattr(rest[0], "center")):
+        if air_phase:
+            raise NotImplementedError("air_phase needs phase ratios: compute_viscosity!(stokes, phase_ratios, args, rheology, cutoff; air_phase)")
         args, rheology = rest[0], rest[1]
         cutoff = rest[2] if len(rest) > 2 else (-float("inf"), float("inf"))
         if isinstance(rheology, (list, tuple)):
@@ -573,6 +577,8 @@ def compute_viscosity_(stokes, *rest, relaxation=1.0, handle=None, fn="εII", AI
     sfx = "_tauII" if fn == "τII" else ""
     pt = SimpleNamespace(r=0.0, θ_dτ=1.0, ηdτ=1.0, ϵ_rel=0.0, ϵ_abs=0.0)
     if len(stokes._ni) == 3:
+        if air_phase:
+            raise NotImplementedError("the air_phase correction of the viscosity is built in 2D only")
         fake = SimpleNamespace(_di=dict(center=(1.0, 1.0, 1.0)))
         p = vep_params3d(stokes, pt, fake, None, 1.0, viscosity_cutoff=cutoff)
         f = vep_fields3d(stokes, (stokes.P, stokes.P, stokes.P), phase_ratios, args)
@@ -586,6 +592,10 @@ def compute_viscosity_(stokes, *rest, relaxation=1.0, handle=None, fn="εII", AI
     p.T_ghosted = _ghosted_T_flag(stokes, _args_T(args))
     rh = rheology_table(rheology)
     torch.cuda.current_stream(stokes.P.device).synchronize()
+    if air_phase:
+        h.call("jrx_vep2d_compute_viscosity_air", C.byref(f), C.byref(rh), C.byref(p), C.c_double(float(relaxation)), C.c_int32(int(air_phase)),
+               C.c_int32(int(fn == "τII")))
+        return
     h.call("jrx_vep2d_compute_viscosity" + sfx, C.byref(f), C.byref(rh), C.byref(p), C.c_double(float(relaxation)))
 
 
