@@ -129,7 +129,7 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   "stat_sweeps3d" = launches of the 3D z-marching stress and velocity sweeps (k_stress3d_zb, k_velocity3d_zb),
  *   "stat_fused2d_b" = those of "stat_fused2d" that ran the batch form k_fused2d_b (32-bit byte offsets: only below 2^29 nodes, see "fused2d_batch" in jrx_tuning.h),
  *   "stat_weno_calls" / "stat_weno_fused" = jrx_weno5_advection2d calls / those that ran the fused three-launch form,
- *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched -- so that a caller
+ *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* entry points -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
 /* the caller has written to an operand array (tau_o, P0, Q, K, G, eta, rho g) since the last driver call: a cached verdict of the operand pass ("operand_cache") is dropped */
@@ -746,6 +746,68 @@ jrx_status jrx_principal_stresses3d(jrx_handle *h, double *s1, double *s2, doubl
  *   whose stresses the launch timed in [4] updates (its units; 0 when nothing was fused). */
 jrx_status jrx_stokes3d_iterate_timed(jrx_handle *h, const jrx_stokes3d_fields *f, const double *etatau,
                                       const jrx_stokes3d_params *p, int64_t iters, double times_ms[6]);
+
+/* ------------------------------------------------------------------ 2D DYREL: self-tuned dynamic relaxation inside Powell-Hestenes pressure iterations
+ * solve_DYREL!(stokes, ρg, dyrel, flow_bcs, phase_ratios, rheology, args, grid, dt, igg; kwargs...) -- src/DYREL/solver.jl:44-294 (_solve_DYREL!), with
+ * DYREL / DYREL! (src/DYREL/types.jl:24-59, constructors.jl:13-57,137-190), the table rheology of jrx_rheology (every visc_kind, ConstantElasticity, an optional
+ * DruckerPrager_regularised with the softening laws, the density laws for compute_ρg! / update_ρg!) and both values of linear_viscosity.
+ * Built: 2D, one block, uniform spacing, velocity boundary conditions (free slip / no slip), the plain pressure residual -∇V - (P - P0)/ηb + Q/dt.
+ * Status JRX_ERR_ARG before anything is launched, with a text that names the cause, for: a handle with a communicator; p->inv_spacing non-NULL; a RockRatio
+ * (phi non-NULL: the ϕ methods of constructors.jl:192,259, stress_kernels.jl:320-431, velocity_kernels_VS.jl); an is_pl other than 0 or 1; the thermal and
+ * melt-fraction forms of _RP_cell (pressure_kernels.jl:54-127: d->dT or d->melt_fraction non-NULL); periodic faces; 2^31 or more entries in an array.
+ * Of jrx_vep2d_params these entry points read nx, ny, nxg, nyg, _dx, _dy (= inv(dx), inv(dy): Gershgorin.jl:47-48 inverts the same spacing), dt, free_slip,
+ * no_slip, periodic, T_ghosted and inv_spacing; the solver's keywords are jrx_dyrel2d_params.  Counter "stat_dyrel_launches" (jrx_get_option): kernels launched
+ * by these entry points.
+ * jrx_dyrel2d_fields: the arrays of the DYREL struct a 2D solve uses (types.jl:24-59 less the 3D members Dz, λmaxVz, dVzdτ, dτVz, dVz, βVz, cVz, αVz, Rz0):
+ * γ_eff, ηb, P_num (ni); Dx, λmaxVx, dVxdτ, dτVx, dVx, βVx, cVx, αVx, Rx0 (nx-1, ny) and their y members (nx, ny-1); then the StokesArrays members that
+ * jrx_vep2d_fields does not carry: τ.xx_v, τ.yy_v, τ_o.xx_v, τ_o.yy_v, λv (ni .+ 1), λ, ΔPψ (ni); then args.ΔT and args.melt_fraction, which must be NULL. */
+typedef struct jrx_dyrel2d_fields {
+    double *gamma_eff, *etab, *P_num;
+    double *Dx, *Dy, *lmaxVx, *lmaxVy, *dVxdtau, *dVydtau, *dtauVx, *dtauVy, *dVx, *dVy, *betaVx, *betaVy, *cVx, *cVy, *alphaVx, *alphaVy, *Rx0, *Ry0;
+    double *txx_v, *tyy_v, *toxx_v, *toyy_v, *lambda, *lambda_v, *dPpsi;
+    const double *dT, *melt_fraction;
+} jrx_dyrel2d_fields;
+/* the keywords of _solve_DYREL! (solver.jl:55-66; defaults: viscosity_cutoff = (-Inf, Inf), viscosity_relaxation = 1e-2, λ_relaxation_DR = λ_relaxation_PH = 1,
+ * iterMax = total_iterMax = 50e3, nout = 100, rel_drop = 1e-2, b_width = (4, 4, 0) [not read: one block], verbose_PH = verbose_DR = true, linear_viscosity = false)
+ * and the scalars of the DYREL struct and of DYREL! (CFL = 0.99, ϵ = 1e-6, ϵ_vel = 1e-6, c_fact = 0.5, γfact = 20) */
+typedef struct jrx_dyrel2d_params {
+    double cutoff_lo, cutoff_hi, viscosity_relaxation, lambda_relaxation_DR, lambda_relaxation_PH;
+    int64_t iterMax, total_iterMax, nout;
+    double rel_drop;
+    int32_t b_width[3], verbose_PH, verbose_DR, linear_viscosity;
+    double CFL, eps, eps_vel, c_fact, gamma_fact;
+} jrx_dyrel2d_params;
+/* the named tuple _solve_DYREL! returns (solver.jl:292): err_evo_it / V / P / tot, caller buffers of cap entries (nchecks of them written), plus the counts */
+typedef struct jrx_dyrel2d_result {
+    int64_t iter, itPH, nchecks, cap;              /* inner iterations; Powell-Hestenes iterations; residual checks recorded; capacity of the buffers */
+    double *err_evo_it, *err_evo_V, *err_evo_P, *err_evo_tot;
+    double time_s;
+} jrx_dyrel2d_result;
+/* DYREL!(dyrel, stokes, rheology, phase_ratios, di, dt; CFL, γfact) -- constructors.jl:178-190: compute_bulk_viscosity_and_penalty!, the Gershgorin estimate, update_dτV_α_β! */
+jrx_status jrx_dyrel2d_init(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rock_ratio2d *phi, const jrx_rheology *rh,
+                            const jrx_vep2d_params *p, const jrx_dyrel2d_params *dp);
+/* _solve_DYREL! (solver.jl:44-294) with the epilogue :269-290 (P += ΔPψ, ∇V, vorticity, shear2center!, accumulate_tensor!, accumulate_vol!, τ_o = τ with xx_v, yy_v).
+ * At entry P0 = P and ε_pl (xx, yy, xy_c), λ, λv are zeroed, as the reference does.  An inner iteration is three launches; the host reads the device sums once per
+ * Powell-Hestenes iteration and once per nout inner iterations.  JRX_ERR_NAN for the reference's error("NaN detected ...") / error("Kaboom! ..."). */
+jrx_status jrx_dyrel2d_solve(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rock_ratio2d *phi, const jrx_rheology *rh,
+                             const jrx_vep2d_params *p, const jrx_dyrel2d_params *dp, jrx_dyrel2d_result *res);
+/* the kernels alone, for parity tests.  compute_∇V_strain_rate_RP! (velocity_kernels.jl:154-240): ε.xx, ε.yy, ε.xy (do_strain_rate != 0) and R.RP; ∇V is not stored */
+jrx_status jrx_dyrel2d_strain_rate_RP(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_vep2d_params *p, int32_t do_strain_rate);
+/* compute_stress_viscosity_DRYEL! (stress_kernels.jl:100-307): τ (xx, yy, xy_c; xx_v, yy_v, xy), ε_pl, ε_vol_pl, τII, η_vep, λ, λv, ΔPψ, θc = γ_eff RP + ΔPψ in
+ * d->P_num and, unless dp->linear_viscosity, η and ηv; of dp it reads viscosity_relaxation, the cutoff and linear_viscosity */
+jrx_status jrx_dyrel2d_stress_viscosity(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rheology *rh, const jrx_vep2d_params *p,
+                                        const jrx_dyrel2d_params *dp, double lambda_relaxation);
+/* compute_PH_residual_V! (velocity_kernels.jl:326-349): R.Rx, R.Ry from τ, P, ΔPψ, ρg */
+jrx_status jrx_dyrel2d_PH_residual(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_vep2d_params *p);
+/* compute_DR_residual_update_V! (velocity_kernels.jl:660-727): R / D, dVdτ <- α dVdτ + R, V += dVdτ β dτ; the ghosts are left to flow_bcs! */
+jrx_status jrx_dyrel2d_DR_residual_update_V(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_vep2d_params *p);
+/* Gershgorin_Stokes2D_SchurComplement! (Gershgorin.jl:1-155): Dx, Dy, λmaxVx, λmaxVy */
+jrx_status jrx_dyrel2d_gershgorin(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rheology *rh, const jrx_vep2d_params *p);
+/* update_dτV_α_β! (Gershgorin.jl:216-247; from_lambda_max != 0) or update_α_β! (:171-198; dτV as it is, CFL not read) */
+jrx_status jrx_dyrel2d_update_dtauV_alpha_beta(jrx_handle *h, const jrx_dyrel2d_fields *d, const jrx_vep2d_params *p, double CFL, int32_t from_lambda_max);
+/* compute_bulk_viscosity_and_penalty! (constructors.jl:230-254): ηb, γ_eff; the mean of the finite η is reduced on the device */
+jrx_status jrx_dyrel2d_bulk_viscosity_and_penalty(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rheology *rh,
+                                                  const jrx_vep2d_params *p, double gamma_fact);
 
 #ifdef __cplusplus
 }

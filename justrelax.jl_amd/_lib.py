@@ -100,6 +100,9 @@ VEP_NAMES = ["P", "P0", "divV", "Q", "Vx", "Vy", "Ux", "Uy", "exx", "eyy", "exy"
 VEP2DFields = _ptr_struct("VEP2DFields", VEP_NAMES)
 RockRatio2D = _ptr_struct("RockRatio2D", ["center", "vertex", "Vx", "Vy"])      # jrx_rock_ratio2d
 MAXPHASE = 8
+DYREL_NAMES = ["gamma_eff", "etab", "P_num", "Dx", "Dy", "lmaxVx", "lmaxVy", "dVxdtau", "dVydtau", "dtauVx", "dtauVy", "dVx", "dVy", "betaVx", "betaVy",
+               "cVx", "cVy", "alphaVx", "alphaVy", "Rx0", "Ry0", "txx_v", "tyy_v", "toxx_v", "toyy_v", "lambda", "lambda_v", "dPpsi", "dT", "melt_fraction"]
+DYREL2DFields = _ptr_struct("DYREL2DFields", DYREL_NAMES)      # jrx_dyrel2d_fields
 
 
 class Rheology(C.Structure):
@@ -143,6 +146,18 @@ class VEP3DParams(C.Structure):
                 ("free_slip", C.c_uint32), ("no_slip", C.c_uint32), ("periodic", C.c_uint32),
                 ("lambda_relaxation", C.c_double), ("viscosity_relaxation", C.c_double), ("cutoff_lo", C.c_double), ("cutoff_hi", C.c_double),
                 ("verbose", C.c_int32), ("displacement_bcs", C.c_int32), ("T_ghosted", C.c_int32), ("b_width", C.c_int32 * 3)]
+
+
+class DYREL2DParams(C.Structure):      # jrx_dyrel2d_params
+    _fields_ = [("cutoff_lo", C.c_double), ("cutoff_hi", C.c_double), ("viscosity_relaxation", C.c_double), ("lambda_relaxation_DR", C.c_double),
+                ("lambda_relaxation_PH", C.c_double), ("iterMax", C.c_int64), ("total_iterMax", C.c_int64), ("nout", C.c_int64), ("rel_drop", C.c_double),
+                ("b_width", C.c_int32 * 3), ("verbose_PH", C.c_int32), ("verbose_DR", C.c_int32), ("linear_viscosity", C.c_int32),
+                ("CFL", C.c_double), ("eps", C.c_double), ("eps_vel", C.c_double), ("c_fact", C.c_double), ("gamma_fact", C.c_double)]
+
+
+class DYREL2DResult(C.Structure):      # jrx_dyrel2d_result
+    _fields_ = [("iter", C.c_int64), ("itPH", C.c_int64), ("nchecks", C.c_int64), ("cap", C.c_int64),
+                ("err_evo_it", _dp), ("err_evo_V", _dp), ("err_evo_P", _dp), ("err_evo_tot", _dp), ("time_s", C.c_double)]
 
 
 class SolveResult(C.Structure):

@@ -1,0 +1,821 @@
+// dyrel2d.hip -- 2D DYREL (self-tuned dynamic relaxation inside Powell-Hestenes pressure iterations) for gfx950: kernels, per-kernel entry points, driver.
+//
+// Reference being replaced (PTsolvers/JustRelax.jl): src/DYREL/solver.jl:44-294 (_solve_DYREL!), :359-365 (compute_λminV!), constructors.jl:178-190 (DYREL!),
+// :230-254 (compute_bulk_viscosity_and_penalty!), pressure_kernels.jl:112 (_compute_RP!, the plain form of _RP_cell :118-121), velocity_kernels.jl:154-240
+// (compute_∇V_strain_rate_RP!), :326-349 (compute_PH_residual_V!), :625-658 (compute_dV!, update_cV!), :660-727 (damped_update_V, compute_DR_residual_update_V!),
+// stress_kernels.jl:100-307 (compute_stress_viscosity_DRYEL!, compute_local_stress, _compute_local_stress), Gershgorin.jl:1-155 (Gershgorin_Stokes2D_SchurComplement!),
+// :171-247 (update_α_β!, update_dτV_α_β!).
+//
+// One inner iteration is three launches, as the reference fuses it: k_dy_strain_rp -> k_dy_stress -> k_dy_update.
+// Hazards of the stress kernel (the reference's ordering is stress, halo, viscosity): every array it writes -- τ (xx, yy, xy_c, xx_v, yy_v, xy), ε_pl, ε_vol_pl,
+// τII, η_vep, λ, λv, ΔPψ, θc, η, ηv -- is read by the same launch at the thread's own index only (η[I], ηv[I], λ[I], λv[I]); what it reads at neighbours (ε.xx, ε.yy,
+// ε.xy, P, EII_pl, and P / T for the viscosity arguments) it never writes.  The viscosity refresh reads the in-register stress of the own node.  So η needs no
+// second set here (k_vs_pre does: compute_maxloc! reads the neighbours' η).  The Gershgorin estimate, which does read η and ηv at neighbours, is its own launch.
+//
+// The per-phase laws (cohesion and friction softening, creep viscosity, the phase average of the viscosity, fn_ratio) are jrx_material.hpp's.  Its phase-weighted
+// plasticity helpers (plastic_params, yield_F, plastic_grad) average the PARAMETERS over the phases of a node; DYREL's compute_local_stress evaluates the whole
+// return mapping per phase and averages the RESULTS, so those three do not apply: the yield function and the flow direction of one phase are formed here from
+// the same per-phase laws.  32-bit element offsets (the extents are checked against 2^31).  fma only in update_α_β (the reference's @muladd).
+// Not built: 3D, more than one rank, non-uniform spacing, a RockRatio, the thermal / melt-fraction forms of _RP_cell.
+#include <initializer_list>
+#include "jrx_internal.hpp"
+#include "jrx_kernels.hpp"
+#include "jrx_material.hpp"
+#include "stokes2d_kernels.hpp"
+
+namespace {
+
+struct DyArgs {
+    jrx_vep2d_fields f;
+    jrx_dyrel2d_fields d;
+    jrx_rheology rh;
+    double _dx, _dy, dt, rel, nu, cut_lo, cut_hi;
+    int nx, ny;
+    unsigned fs, ns;
+    bool tg;
+};
+
+#define C2(A, i_, j_) (A)[(i_) + nx * (j_)]
+#define V2(A, i_, j_) (A)[(i_) + (nx + 1) * (j_)]
+
+// compute_∇V_strain_rate_RP! (velocity_kernels.jl:180-240): one thread per vertex index (i, j) of (nx+1, ny+1); ∇V stays in a register
+template <bool STRAIN>
+__global__ __launch_bounds__(256) void k_dy_strain_rp(double *__restrict__ exx, double *__restrict__ eyy, double *__restrict__ exy, const double *__restrict__ Vx,
+                                                      const double *__restrict__ Vy, double *__restrict__ RP, const double *__restrict__ P,
+                                                      const double *__restrict__ P0, const double *__restrict__ Q, const double *__restrict__ etab,
+                                                      const double _dx, const double _dy, const double dt, const int nx, const int ny)
+{
+    const int t = xcd_slab_block() * blockDim.x + threadIdx.x;
+    const int j = t / (nx + 1), i = t - j * (nx + 1);
+    if (j > ny) return;
+#define VX(i_, j_) Vx[(i_) + (nx + 1) * (j_)]
+#define VY(i_, j_) Vy[(i_) + (nx + 2) * (j_)]
+    const double vx_n = VX(i, j + 1), vy_e = VY(i + 1, j);
+    if (STRAIN) {
+        const double dVx_dy = (vx_n - VX(i, j)) * _dy, dVy_dx = (vy_e - VY(i, j)) * _dx;
+        exy[t] = 0.5 * (dVx_dy + dVy_dx);
+    }
+    if (i < nx && j < ny) {
+        const int c = i + nx * j;
+        const double dVx_dx = (VX(i + 1, j + 1) - vx_n) * _dx, dVy_dy = (VY(i + 1, j + 1) - vy_e) * _dy;
+        const double div = dVx_dx + dVy_dy;
+        if (STRAIN) {
+            const double div_third = div * (1.0 / 3.0);
+            exx[c] = dVx_dx - div_third;
+            eyy[c] = dVy_dy - div_third;
+        }
+        RP[c] = -div - (P[c] - P0[c]) / etab[c] + (Q[c] / dt);      // _compute_RP!, pressure_kernels.jl:112
+    }
+#undef VX
+#undef VY
+}
+
+// the 11 values compute_local_stress returns: τ (xx, yy, xy), ε_pl (xx, yy, xy), τII, λ, ΔPψ, η_vep, ε_vol_pl
+struct DyLocal { double v[11]; };
+
+// compute_local_stress (stress_kernels.jl:224-247) with _compute_local_stress (:249-307) per phase: ratio .* result, summed in phase order
+template <bool SOFT>
+__device__ __forceinline__ DyLocal dy_local_stress(const jrx_rheology &rh, const double *__restrict__ r, const double e0, const double e1, const double e2,
+                                                   const double to0, const double to1, const double to2, const double eta, const double P, const double lam,
+                                                   const double rel, const double dt, const double EII)
+{
+    DyLocal acc;
+#pragma unroll
+    for (int s = 0; s < 11; s++) acc.v[s] = 0.0;
+    const double eII_in = sinv2(e0, e1, e2);
+    for (int q = 0; q < rh.nphase; q++) {
+        const double rq = r[q];
+        double o[11];
+#pragma unroll
+        for (int s = 0; s < 11; s++) o[s] = 0.0;      // empty_stress_solution / the early return
+        if (rq != 0.0) {
+            const double G = rh.G[q], Kb = rh.Kb[q];
+            const bool ispl = rh.is_pl[q] != 0;
+            const double eta_reg = ispl ? rh.eta_vp[q] : 0.0;
+            const double eta_ve = isinf(G) ? 1.0 / (1.0 / eta + 1.0 / (G * dt)) : (eta * G * dt) / (eta + G * dt);
+            const double inv_2Gdt = 1.0 / (2 * G * dt);
+            const double f0 = e0 + to0 * inv_2Gdt, f1 = e1 + to1 * inv_2Gdt, f2 = e2 + to2 * inv_2Gdt;
+            if (sinv2(f0, f1, f2) == 0.0) o[9] = eta;
+            else {
+                double t0 = 2 * eta_ve * f0, t1 = 2 * eta_ve * f1, t2 = 2 * eta_ve * f2;
+                double tII = sinv2(t0, t1, t2);
+                double F = tII, g0 = 0.0, g1 = 0.0, g2 = 0.0, dQdP = 0.0, dFdP = 0.0;
+                if (ispl) {      // Drucker-Prager: F = τII - cosϕ(EII) C(EII) - sinϕ(EII) P; ∂Q/∂τ = τ / (2 τII), shear slot halved once; ∂Q/∂P = -sinψ; ∂F/∂P = -sinϕ
+                    double sp = rh.sinphi[q], cp = rh.cosphi[q], C = rh.C[q];
+                    if (SOFT) { mat_friction(rh, q, EII, sp, cp); C = mat_cohesion(rh, q, EII); }
+                    F = tII - cp * C - sp * P;
+                    g0 = 0.5 * t0 / tII; g1 = 0.5 * t1 / tII; g2 = 0.5 * (t2 / tII);
+                    dQdP = -rh.sinpsi[q]; dFdP = -rh.sinphi[q];
+                }
+                double l = 0.0, evol = 0.0;
+                if (ispl && F >= 0) {
+                    const double bulk = isinf(Kb) ? 0.0 : Kb * dt * dFdP * dQdP;
+                    const double lnew = F / (eta_ve + eta_reg + bulk);
+                    l = rel * lnew + (1 - rel) * lam;
+                    evol = -l * dQdP;
+                }
+                double p0 = 0.0, p1 = 0.0, p2 = 0.0, dP = 0.0;
+                if (l > 0) {
+                    p0 = l * g0; p1 = l * g1; p2 = l * g2;
+                    t0 = t0 - 2.0 * eta_ve * p0; t1 = t1 - 2.0 * eta_ve * p1; t2 = t2 - 2.0 * eta_ve * p2;
+                    tII = sinv2(t0, t1, t2);
+                    dP = dQdP == 0.0 ? 0.0 : -l * dQdP * Kb * dt;
+                }
+                o[0] = t0; o[1] = t1; o[2] = t2; o[3] = p0; o[4] = p1; o[5] = p2; o[6] = tII; o[7] = l; o[8] = dP;
+                o[9] = tII * 0.5 * (1.0 / eII_in);
+                o[10] = evol;
+            }
+#pragma unroll
+            for (int s = 0; s < 11; s++) o[s] = rq * o[s];
+        }
+#pragma unroll
+        for (int s = 0; s < 11; s++) acc.v[s] = q == 0 ? o[s] : acc.v[s] + o[s];
+    }
+    return acc;
+}
+
+// _update_τII_viscosity (stress_kernels.jl:129-135): the creep viscosity at the invariant of the fresh stress, continuation_linear with the old value, cutoff
+__device__ __forceinline__ double dy_visc(const DyArgs &a, const double *r, const double txx, const double tyy, const double txy, const double T, const double P,
+                                          const double eta_old)
+{
+    const double tII = mat_visc_invariant2(txx, tyy, txy);
+    const double e = mat_phase_viscosity(a.rh, r, tII, T, P, true);
+    const double x = (1 - a.nu) * eta_old + a.nu * e;
+    return fmin(fmax(x, a.cut_lo), a.cut_hi);
+}
+
+// compute_stress_viscosity_DRYEL! (stress_kernels.jl:137-222): one thread per vertex index; the vertex half, then the centre half of the cell with the same index
+template <bool SOFT, bool LIN>
+__global__ __launch_bounds__(256) void k_dy_stress(const DyArgs a)
+{
+    const int nx = a.nx, ny = a.ny, np = a.rh.nphase;
+    const int t = xcd_slab_block() * blockDim.x + threadIdx.x;
+    const int j = t / (nx + 1), i = t - j * (nx + 1);
+    if (j > ny) return;
+    const double *__restrict__ P = a.f.P, *__restrict__ exx = a.f.exx, *__restrict__ eyy = a.f.eyy, *__restrict__ exy = a.f.exy, *__restrict__ EIIa = a.f.EII_pl;
+    const bool vfields = mat_viscosity_reads_fields(&a.rh);
+    {   // vertex (i, j): clamped_indices / av_clamped (StressKernels.jl:1304-1315)
+        const int i0 = clampi(i - 1, 0, nx - 1), ic = clampi(i, 0, nx - 1), j0 = clampi(j - 1, 0, ny - 1), jc = clampi(j, 0, ny - 1);
+#define AVC(A) (0.25 * (C2(A, i0, j0) + C2(A, ic, jc) + C2(A, i0, jc) + C2(A, ic, j0)))
+        const double e0 = AVC(exx), e1 = AVC(eyy), Pv = AVC(P), EIIv = AVC(EIIa);
+#undef AVC
+        const double etav = a.f.eta_v[t];
+        const double *rv = a.f.phase_v + np * t;
+        const DyLocal o = dy_local_stress<SOFT>(a.rh, rv, e0, e1, exy[t], a.d.toxx_v[t], a.d.toyy_v[t], a.f.toxy[t], etav, Pv, a.d.lambda_v[t], a.rel, a.dt, EIIv);
+        a.d.txx_v[t] = o.v[0]; a.d.tyy_v[t] = o.v[1]; a.f.txy[t] = o.v[2];
+        a.f.eplxy[t] = o.v[5];
+        a.d.lambda_v[t] = o.v[7];
+        if (!LIN) {
+            double T = 0.0;      // local_viscosity_args_vertex (Viscosity.jl:526-548): T and P averaged over the clamped cells around the vertex
+            if (vfields && a.f.T) {
+                if (a.tg) { const double *q = a.f.T + i + (nx + 2) * j; T = 0.25 * (q[0] + q[1] + q[nx + 2] + q[nx + 3]); }
+                else T = 0.25 * (C2(a.f.T, i0, j0) + C2(a.f.T, ic, j0) + C2(a.f.T, i0, jc) + C2(a.f.T, ic, jc));
+            }
+            const double Pa = vfields ? 0.25 * (C2(P, i0, j0) + C2(P, ic, j0) + C2(P, i0, jc) + C2(P, ic, jc)) : 0.0;
+            a.f.eta_v[t] = dy_visc(a, rv, o.v[0], o.v[1], o.v[2], T, Pa, etav);
+        }
+    }
+    if (i < nx && j < ny) {      // centre (i, j)
+        const int c = i + nx * j;
+        const double e2 = (V2(exy, i, j) + V2(exy, i + 1, j) + V2(exy, i, j + 1) + V2(exy, i + 1, j + 1)) / 4;      // sum(_gather(ε.xy)) / 4
+        const double eta = a.f.eta[c], Pc = P[c];
+        const double *rc = a.f.phase_c + np * c;
+        const DyLocal o = dy_local_stress<SOFT>(a.rh, rc, exx[c], eyy[c], e2, a.f.toxx[c], a.f.toyy[c], a.f.toxy_c[c], eta, Pc, a.d.lambda[c], a.rel, a.dt, EIIa[c]);
+        a.f.txx[c] = o.v[0]; a.f.tyy[c] = o.v[1]; a.f.txy_c[c] = o.v[2];
+        a.f.eplxx[c] = o.v[3]; a.f.eplyy[c] = o.v[4];
+        a.f.evol_pl[c] = o.v[10];
+        a.f.tII[c] = o.v[6];
+        a.f.eta_vep[c] = o.v[9];
+        a.d.lambda[c] = o.v[7];
+        a.d.dPpsi[c] = o.v[8];
+        a.d.P_num[c] = a.d.gamma_eff[c] * a.f.RP[c] + o.v[8];      // θc = γ_eff RP + ΔPψ
+        if (!LIN) {
+            const double T = (vfields && a.f.T) ? (a.tg ? a.f.T[(i + 1) + (nx + 2) * (j + 1)] : a.f.T[c]) : 0.0;      // local_viscosity_args: T[I .+ 1]
+            a.f.eta[c] = dy_visc(a, rc, o.v[0], o.v[1], o.v[2], T, Pc, eta);
+        }
+    }
+}
+
+// the momentum residuals d_xa(τxx) + d_yi(τxy) - d_xa(P) - d_xa(θ) - av_xa(ρgx) and the y analogue (MiniKernels.jl:37-72), θ = ΔPψ (PH) or θc (DR)
+struct DyMom { const double *P, *th, *txx, *tyy, *txy, *fx, *fy; double _dx, _dy; int nx, ny; };
+__device__ __forceinline__ double dy_Rx(const DyMom &m, const int i, const int j)
+{
+    const int nx = m.nx, c = i + nx * j;
+    return (-m.txx[c] + m.txx[c + 1]) * m._dx + (-V2(m.txy, i + 1, j) + V2(m.txy, i + 1, j + 1)) * m._dy - (-m.P[c] + m.P[c + 1]) * m._dx -
+           (-m.th[c] + m.th[c + 1]) * m._dx - (m.fx[c] + m.fx[c + 1]) * 0.5;
+}
+__device__ __forceinline__ double dy_Ry(const DyMom &m, const int i, const int j)
+{
+    const int nx = m.nx, c = i + nx * j;
+    return (-m.tyy[c] + m.tyy[c + nx]) * m._dy + (-V2(m.txy, i, j + 1) + V2(m.txy, i + 1, j + 1)) * m._dx - (-m.P[c] + m.P[c + nx]) * m._dy -
+           (-m.th[c] + m.th[c + nx]) * m._dy - (m.fy[c] + m.fy[c + nx]) * 0.5;
+}
+
+// compute_PH_residual_V! (velocity_kernels.jl:326-349)
+__global__ __launch_bounds__(256) void k_dy_ph_residual(const DyMom m, double *__restrict__ Rx, double *__restrict__ Ry)
+{
+    const int nx = m.nx;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = t / nx, i = t - j * nx;
+    if (j >= m.ny) return;
+    if (i < nx - 1) Rx[i + (nx - 1) * j] = dy_Rx(m, i, j);
+    if (j < m.ny - 1) Ry[t] = dy_Ry(m, i, j);
+}
+
+// compute_DR_residual_update_V! (velocity_kernels.jl:671-727).  BCF: the thread that moves a velocity node next to a free-slip / no-slip face refreshes that
+// node's ghost copy, as velocity2d_cell does (stokes2d_kernels.hpp): all flow_bcs! changes once it has been applied in full one time
+struct DyUpd { double *Rx, *Ry, *Vx, *Vy, *dVxdtau, *dVydtau; const double *Dx, *Dy, *ax, *ay, *bx, *by, *tx, *ty; unsigned fs, ns; };
+template <bool BCF>
+__global__ __launch_bounds__(256) void k_dy_update(const DyMom m, const DyUpd u)
+{
+    const int nx = m.nx, ny = m.ny;
+    const int t = xcd_slab_block() * blockDim.x + threadIdx.x;
+    const int j = t / nx, i = t - j * nx;
+    if (j >= ny) return;
+    if (i < nx - 1) {
+        const int k = i + (nx - 1) * j, q = (i + 1) + (nx + 1) * (j + 1);
+        const double R = dy_Rx(m, i, j) / u.Dx[k];
+        u.Rx[k] = R;
+        const double dnew = u.ax[k] * u.dVxdtau[k] + R;      // damped_update_V :660-663
+        u.dVxdtau[k] = dnew;
+        const double v = u.Vx[q] + dnew * u.bx[k] * u.tx[k];
+        u.Vx[q] = v;
+        if (BCF) {
+            if (j == 0) { if (u.fs & JRX_FACE_BOT) u.Vx[q - (nx + 1)] = v; else if (u.ns & JRX_FACE_BOT) u.Vx[q - (nx + 1)] = -v; }
+            if (j == ny - 1) { if (u.fs & JRX_FACE_TOP) u.Vx[q + (nx + 1)] = v; else if (u.ns & JRX_FACE_TOP) u.Vx[q + (nx + 1)] = -v; }
+        }
+    }
+    if (j < ny - 1) {
+        const int q = (i + 1) + (nx + 2) * (j + 1);
+        const double R = dy_Ry(m, i, j) / u.Dy[t];
+        u.Ry[t] = R;
+        const double dnew = u.ay[t] * u.dVydtau[t] + R;
+        u.dVydtau[t] = dnew;
+        const double v = u.Vy[q] + dnew * u.by[t] * u.ty[t];
+        u.Vy[q] = v;
+        if (BCF) {
+            if (i == 0) { if (u.fs & JRX_FACE_LEFT) u.Vy[q - 1] = v; else if (u.ns & JRX_FACE_LEFT) u.Vy[q - 1] = -v; }
+            if (i == nx - 1) { if (u.fs & JRX_FACE_RIGHT) u.Vy[q + 1] = v; else if (u.ns & JRX_FACE_RIGHT) u.Vy[q + 1] = -v; }
+        }
+    }
+}
+
+// _Gershgorin_Stokes2D_SchurComplement! (Gershgorin.jl:21-155), uniform spacing: _dx = inv(dx), _dy = inv(dy)
+__global__ __launch_bounds__(256) void k_dy_gershgorin(const DyArgs a)
+{
+    const int nx = a.nx, ny = a.ny, np = a.rh.nphase;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = t / nx, i = t - j * nx;
+    if (j >= ny) return;
+    const double *__restrict__ eta = a.f.eta, *__restrict__ etav = a.f.eta_v, *__restrict__ gam = a.d.gamma_eff;
+    const double dt = a.dt, _dx = a._dx, _dy = a._dy;
+    const double _dx2 = _dx * _dx, _dy2 = _dy * _dy, _dxdy = _dx * _dy, c43 = 4.0 / 3.0, c23 = 2.0 / 3.0;
+#define GV(i_, j_) ratio_avg(a.rh.G, a.f.phase_v + np * ((i_) + (nx + 1) * (j_)), np)
+#define GC(i_, j_) ratio_avg(a.rh.G, a.f.phase_c + np * ((i_) + nx * (j_)), np)
+#define VE(e_, G_) (1 / (1 / (e_) + 1 / ((G_) * dt)))
+    const double Gne = GV(i + 1, j + 1), Gc = GC(i, j);
+    const double e_c = eta[t], g_c = gam[t], e_ne = V2(etav, i + 1, j + 1);
+    if (i < nx - 1) {
+        const double gE = gam[t + 1], gW = g_c;
+        const double eN = VE(e_ne, Gne), eS = VE(V2(etav, i + 1, j), GV(i + 1, j)), eW = VE(e_c, Gc), eE = VE(eta[t + 1], GC(i + 1, j));
+        const double eN_dy = eN * _dy, eS_dy = eS * _dy, eE_dx = eE * _dx, eW_dx = eW * _dx, gE_dx = gE * _dx, gW_dx = gW * _dx;
+        const double D = (eN_dy + eS_dy) * _dy + (gE_dx + gW_dx + c43 * (eE_dx + eW_dx)) * _dx;
+        const double Cxx = fabs(eN * _dy2) + fabs(eS * _dy2) + fabs((gE + c43 * eE) * _dx2) + fabs((gW + c43 * eW) * _dx2) + fabs(D);
+        const double Cxy = fabs((gE - c23 * eE + eN) * _dxdy) + fabs((gE - c23 * eE + eS) * _dxdy) + fabs((gW + eN - c23 * eW) * _dxdy) +
+                           fabs((gW + eS - c23 * eW) * _dxdy);
+        const int k = i + (nx - 1) * j;
+        a.d.Dx[k] = D;
+        a.d.lmaxVx[k] = (1 / D) * (Cxx + Cxy);
+    }
+    if (j < ny - 1) {
+        const double gN = gam[t + nx], gS = g_c;
+        const double eN = VE(eta[t + nx], GC(i, j + 1)), eS = VE(e_c, Gc), eW = VE(V2(etav, i, j + 1), GV(i, j + 1)), eE = VE(e_ne, Gne);
+        const double eE_dx = eE * _dx, eW_dx = eW * _dx, eN_dy = eN * _dy, eS_dy = eS * _dy, gN_dy = gN * _dy, gS_dy = gS * _dy;
+        const double D = (gN_dy + gS_dy + c43 * (eN_dy + eS_dy)) * _dy + (eE_dx + eW_dx) * _dx;
+        const double Cyy = fabs(eE * _dx2) + fabs(eW * _dx2) + fabs((gN + c43 * eN) * _dy2) + fabs((gS + c43 * eS) * _dy2) + fabs(D);
+        const double Cyx = fabs((gN + eE - c23 * eN) * _dxdy) + fabs((gN - c23 * eN + eW) * _dxdy) + fabs((gS + eE - c23 * eS) * _dxdy) +
+                           fabs((gS - c23 * eS + eW) * _dxdy);
+        a.d.Dy[t] = D;
+        a.d.lmaxVy[t] = (1 / D) * (Cyx + Cyy);
+    }
+#undef GV
+#undef GC
+#undef VE
+}
+
+// _update_dτV_α_β! (Gershgorin.jl:229-247; DTAU) / _update_α_β! (:182-198): the reference's @muladd is the two fma here
+template <bool DTAU>
+__global__ __launch_bounds__(256) void k_dy_dtau(const jrx_dyrel2d_fields d, const double CFL, const int nxn, const int nyn)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        if (t >= (c ? nyn : nxn)) continue;
+        double *dtau = c ? d.dtauVy : d.dtauVx, *beta = c ? d.betaVy : d.betaVx, *alpha = c ? d.alphaVy : d.alphaVx;
+        const double *cV = c ? d.cVy : d.cVx, *lmax = c ? d.lmaxVy : d.lmaxVx;
+        double x = dtau[t];
+        if (DTAU) { x = 2 / sqrt(lmax[t]) * CFL; dtau[t] = x; }
+        const double cv = cV[t], den = fma(cv, x, 2.0);
+        beta[t] = 2 * x / den;
+        alpha[t] = fma(-cv, x, 2.0) / den;
+    }
+}
+
+// compute_bulk_viscosity_and_penalty! (constructors.jl:237-254); eta_mean = mean(η[.!isinf.(η)]) is sums[0] / sums[1] of k_dy_eta_sum
+__global__ __launch_bounds__(256) void k_dy_bulk(const DyArgs a, const double *__restrict__ sums, const double gamma_fact)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.nx * a.ny) return;
+    const double eta_mean = sums[0] / sums[1];
+    const double Kbdt = ratio_avg(a.rh.Kb, a.f.phase_c + a.rh.nphase * t, a.rh.nphase) * a.dt;
+    a.d.etab[t] = Kbdt;
+    const double e = a.f.eta[t];
+    const double g_num = gamma_fact * (isinf(e) ? eta_mean : e);
+    const double g_phy = isinf(Kbdt) ? g_num : Kbdt;
+    a.d.gamma_eff[t] = g_phy * g_num / (g_phy + g_num);
+}
+
+// fixed-order two-stage sums: wave shuffle -> the four waves of a block -> one partial row of 8 per block -> k_dy_sum_final in one block
+__device__ __forceinline__ void dy_block_store(const double s[8], const int ns, double *__restrict__ partials)
+{
+    __shared__ double sm[8][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c = 0; c < ns; c++) {
+        const double w = wave_sum(s[c]);
+        if (lane == 0) sm[c][wave] = w;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 8) {
+        const int c = threadIdx.x;
+        partials[blockIdx.x * 8 + c] = c < ns ? (sm[c][0] + sm[c][1]) + (sm[c][2] + sm[c][3]) : 0.0;
+    }
+}
+__global__ __launch_bounds__(256) void k_dy_sum_final(const double *__restrict__ partials, const int nblocks, double *__restrict__ out)
+{
+    __shared__ double sm[8][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < nblocks; b += blockDim.x) s += partials[b * 8 + c];
+        s = wave_sum(s);
+        if (lane == 0) sm[c][wave] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        const int c = threadIdx.x;
+        out[c] = (sm[c][0] + sm[c][1]) + (sm[c][2] + sm[c][3]);
+    }
+}
+// Σ η and the count over the finite entries
+__global__ __launch_bounds__(256) void k_dy_eta_sum(const double *__restrict__ eta, const int n, double *__restrict__ partials)
+{
+    double s[8] = {};
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
+        const double e = eta[t];
+        if (!isinf(e)) { s[0] += e; s[1] += 1.0; }
+    }
+    dy_block_store(s, 2, partials);
+}
+// the Powell-Hestenes norms (solver.jl:151-152): Σ Rx², Σ Ry², Σ RP² over the whole arrays
+__global__ __launch_bounds__(256) void k_dy_ph_sums(const double *__restrict__ Rx, const double *__restrict__ Ry, const double *__restrict__ RP, const int nx,
+                                                    const int ny, double *__restrict__ partials)
+{
+    double s[8] = {};
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < nx * ny; t += gridDim.x * blockDim.x) {
+        if (t < (nx - 1) * ny) { const double v = Rx[t]; s[0] += v * v; }
+        if (t < nx * (ny - 1)) { const double v = Ry[t]; s[1] += v * v; }
+        const double v = RP[t];
+        s[2] += v * v;
+    }
+    dy_block_store(s, 3, partials);
+}
+// the residual check of the inner loop (solver.jl:231,251, :359-365): compute_dV!, then Σ (D R)² per component, Σ dV (R - R0) and Σ dV² per component
+__global__ __launch_bounds__(256) void k_dy_check_sums(const jrx_dyrel2d_fields d, const double *__restrict__ Rx, const double *__restrict__ Ry, const int nxn,
+                                                       const int nyn, double *__restrict__ partials)
+{
+    double s[8] = {};
+    const int n = nxn > nyn ? nxn : nyn;
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
+        if (t < nxn) {
+            const double R = Rx[t], DR = d.Dx[t] * R, dV = d.dVxdtau[t] * d.betaVx[t] * d.dtauVx[t];
+            d.dVx[t] = dV;
+            s[0] += DR * DR; s[2] += dV * (R - d.Rx0[t]); s[4] += dV * dV;
+        }
+        if (t < nyn) {
+            const double R = Ry[t], DR = d.Dy[t] * R, dV = d.dVydtau[t] * d.betaVy[t] * d.dtauVy[t];
+            d.dVy[t] = dV;
+            s[1] += DR * DR; s[3] += dV * (R - d.Ry0[t]); s[5] += dV * dV;
+        }
+    }
+    dy_block_store(s, 6, partials);
+}
+// update_cV! (velocity_kernels.jl:642-654)
+__global__ __launch_bounds__(256) void k_dy_fill2(double *__restrict__ a0, const int n0, double *__restrict__ a1, const int n1, const double v)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n0) a0[t] = v;
+    if (t < n1) a1[t] = v;
+}
+// @. P += γ_eff * RP (solver.jl:264)
+__global__ __launch_bounds__(256) void k_dy_add_P(double *__restrict__ P, const double *__restrict__ gam, const double *__restrict__ RP, const int n)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n) P[t] = P[t] + gam[t] * RP[t];
+}
+// the epilogue (solver.jl:269-286): P += ΔPψ, compute_∇V!, compute_vorticity!, shear2center! of ε, ε_pl, Δε, accumulate_tensor!, accumulate_vol!
+__global__ __launch_bounds__(256) void k_dy_epilogue(const DyArgs a)
+{
+    const int nx = a.nx, ny = a.ny;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = t / (nx + 1), i = t - j * (nx + 1);
+    if (j > ny) return;
+    const double *__restrict__ Vx = a.f.Vx, *__restrict__ Vy = a.f.Vy;
+    if (a.f.omega_xy)
+        a.f.omega_xy[t] = 0.5 * ((-Vy[i + (nx + 2) * j] + Vy[(i + 1) + (nx + 2) * j]) * a._dx - (-Vx[i + (nx + 1) * j] + Vx[i + (nx + 1) * (j + 1)]) * a._dy);
+    if (i < nx && j < ny) {
+        const int c = i + nx * j;
+        a.f.P[c] = a.f.P[c] + a.d.dPpsi[c];
+        a.f.divV[c] = (-Vx[i + (nx + 1) * (j + 1)] + Vx[(i + 1) + (nx + 1) * (j + 1)]) * a._dx + (-Vy[(i + 1) + (nx + 2) * j] + Vy[(i + 1) + (nx + 2) * (j + 1)]) * a._dy;
+#define S2C(V) (0.25 * (V2(V, i, j) + V2(V, i + 1, j) + V2(V, i, j + 1) + V2(V, i + 1, j + 1)))
+        if (a.f.exy_c) a.f.exy_c[c] = S2C(a.f.exy);
+        if (a.f.eplxy_c) a.f.eplxy_c[c] = S2C(a.f.eplxy);
+        if (a.f.dexy_c && a.f.dexy) a.f.dexy_c[c] = S2C(a.f.dexy);
+#undef S2C
+        const double p = V2(a.f.eplxy, i, j), q = V2(a.f.eplxy, i + 1, j), r = V2(a.f.eplxy, i, j + 1), s = V2(a.f.eplxy, i + 1, j + 1);
+        const double xx = a.f.eplxx[c], yy = a.f.eplyy[c];
+        a.f.EII_pl[c] += sqrt(0.5 * (xx * xx + yy * yy) + 0.25 * (p * p + q * q + r * r + s * s)) * a.dt;
+        a.f.EVol_pl[c] += a.dt * a.f.evol_pl[c];
+    }
+}
+#undef C2
+#undef V2
+
+// what every DYREL entry point refuses (status JRX_ERR_ARG, each named), before anything is launched
+jrx_status dy_check(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rock_ratio2d *phi, const jrx_rheology *rh,
+                    const jrx_vep2d_params *p)
+{
+    if (!h) return JRX_ERR_ARG;
+    if (!f || !d || !p) return jrx_fail(h, JRX_ERR_ARG, "DYREL: null argument");
+    JRX_TRY(jrx_check_device(h));
+    if (jrx_comm_active(h)) return jrx_fail(h, JRX_ERR_ARG, "DYREL: a communicator of more than one rank is not built (single block only)");
+    for (int q = 0; q < 6; q++)
+        if (p->inv_spacing[q]) return jrx_fail(h, JRX_ERR_ARG, "DYREL: a non-uniform Geometry (inv_spacing) is not built");
+    if (phi) return jrx_fail(h, JRX_ERR_ARG, "DYREL: the variational form with a RockRatio is not built");
+    if (d->dT) return jrx_fail(h, JRX_ERR_ARG, "DYREL: the thermal form of the pressure residual (args.ΔT) is not built");
+    if (d->melt_fraction) return jrx_fail(h, JRX_ERR_ARG, "DYREL: the melt-fraction form of the pressure residual (args.melt_fraction) is not built");
+    if (p->periodic) return jrx_fail(h, JRX_ERR_ARG, "DYREL: periodic velocity boundary conditions are not built");
+    if (p->nx < 3 || p->ny < 3) return jrx_fail(h, JRX_ERR_ARG, "DYREL: needs at least 3 cells per dimension");
+    if (rh) {
+        if (rh->nphase < 1 || rh->nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "nphase must be in 1..%d", JRX_MAXPHASE);
+        for (int q = 0; q < rh->nphase; q++)
+            if (rh->is_pl[q] != 0 && rh->is_pl[q] != 1) return jrx_fail(h, JRX_ERR_ARG, "DYREL: is_pl = %d of phase %d is not built (0 or 1: none, DruckerPrager_regularised)", (int)rh->is_pl[q], q);
+    }
+    if ((p->nx + 2) * (p->ny + 2) * (int64_t)(rh ? rh->nphase : 1) >= (int64_t)1 << 31)
+        return jrx_fail(h, JRX_ERR_ARG, "DYREL: an array of 2^31 or more entries exceeds the 32-bit offsets of its kernels");
+    return JRX_OK;
+}
+
+DyArgs dy_make(const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rheology *rh, const jrx_vep2d_params *p)
+{
+    DyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.f = *f; a.d = *d;
+    if (rh) a.rh = *rh;
+    a._dx = p->_dx; a._dy = p->_dy; a.dt = p->dt;
+    a.nx = (int)p->nx; a.ny = (int)p->ny;
+    a.fs = p->free_slip; a.ns = p->no_slip;
+    a.tg = p->T_ghosted != 0;
+    a.rel = 1.0; a.nu = 1.0e-2; a.cut_lo = -INFINITY; a.cut_hi = INFINITY;
+    return a;
+}
+DyMom dy_mom(const DyArgs &a, const double *th)
+{
+    return DyMom{a.f.P, th, a.f.txx, a.f.tyy, a.f.txy, a.f.fx, a.f.fy, a._dx, a._dy, a.nx, a.ny};
+}
+DyUpd dy_upd(const DyArgs &a)
+{
+    const jrx_dyrel2d_fields &d = a.d;
+    return DyUpd{a.f.Rx, a.f.Ry, a.f.Vx, a.f.Vy, d.dVxdtau, d.dVydtau, d.Dx, d.Dy, d.alphaVx, d.alphaVy, d.betaVx, d.betaVy, d.dtauVx, d.dtauVy, a.fs, a.ns};
+}
+bool dy_has(std::initializer_list<const void *> req)
+{
+    for (const void *q : req)
+        if (!q) return false;
+    return true;
+}
+#define DY_REQ(h, what, ...) \
+    if (!dy_has({__VA_ARGS__})) return jrx_fail(h, JRX_ERR_ARG, "%s: a required field pointer is NULL", what)
+#define DY_LAUNCH(h) \
+    do { (h)->stat_dyrel_launches++; JRX_LAUNCH_CHECK(h); } while (0)
+
+inline unsigned dy_gv(const DyArgs &a) { return (unsigned)(((a.nx + 1) * (a.ny + 1) + 255) / 256); }
+inline unsigned dy_gc(const DyArgs &a) { return (unsigned)((a.nx * a.ny + 255) / 256); }
+inline int dy_nblk(const DyArgs &a) { const unsigned g = (dy_gc(a) + 7) / 8; return (int)(g < 1 ? 1 : (g > 1024 ? 1024 : g)); }      // partial rows of 8: half of kMaxRedBlocks rows of 4
+
+jrx_status dy_strain_rp(jrx_handle *h, hipStream_t s, const DyArgs &a, bool strain)
+{
+    if (strain) hipLaunchKernelGGL(k_dy_strain_rp<true>, dim3(dy_gv(a)), dim3(256), 0, s, a.f.exx, a.f.eyy, a.f.exy, (const double *)a.f.Vx, (const double *)a.f.Vy,
+                                   a.f.RP, (const double *)a.f.P, (const double *)a.f.P0, (const double *)a.f.Q, (const double *)a.d.etab, a._dx, a._dy, a.dt, a.nx, a.ny);
+    else hipLaunchKernelGGL(k_dy_strain_rp<false>, dim3(dy_gv(a)), dim3(256), 0, s, a.f.exx, a.f.eyy, a.f.exy, (const double *)a.f.Vx, (const double *)a.f.Vy,
+                            a.f.RP, (const double *)a.f.P, (const double *)a.f.P0, (const double *)a.f.Q, (const double *)a.d.etab, a._dx, a._dy, a.dt, a.nx, a.ny);
+    DY_LAUNCH(h);
+    return JRX_OK;
+}
+jrx_status dy_stress(jrx_handle *h, hipStream_t s, const DyArgs &a, bool lin)
+{
+    const bool soft = mat_has_softening(&a.rh);
+    if (soft) {
+        if (lin) hipLaunchKernelGGL((k_dy_stress<true, true>), dim3(dy_gv(a)), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_dy_stress<true, false>), dim3(dy_gv(a)), dim3(256), 0, s, a);
+    } else {
+        if (lin) hipLaunchKernelGGL((k_dy_stress<false, true>), dim3(dy_gv(a)), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_dy_stress<false, false>), dim3(dy_gv(a)), dim3(256), 0, s, a);
+    }
+    DY_LAUNCH(h);
+    return JRX_OK;
+}
+jrx_status dy_gershgorin(jrx_handle *h, hipStream_t s, const DyArgs &a)
+{
+    hipLaunchKernelGGL(k_dy_gershgorin, dim3(dy_gc(a)), dim3(256), 0, s, a);
+    DY_LAUNCH(h);
+    return JRX_OK;
+}
+jrx_status dy_dtau(jrx_handle *h, hipStream_t s, const DyArgs &a, double CFL, bool from_lmax)
+{
+    const int nxn = (a.nx - 1) * a.ny, nyn = a.nx * (a.ny - 1);
+    const unsigned g = (unsigned)(((nxn > nyn ? nxn : nyn) + 255) / 256);
+    if (from_lmax) hipLaunchKernelGGL(k_dy_dtau<true>, dim3(g), dim3(256), 0, s, a.d, CFL, nxn, nyn);
+    else hipLaunchKernelGGL(k_dy_dtau<false>, dim3(g), dim3(256), 0, s, a.d, CFL, nxn, nyn);
+    DY_LAUNCH(h);
+    return JRX_OK;
+}
+jrx_status dy_bulk(jrx_handle *h, hipStream_t s, const DyArgs &a, double gamma_fact)
+{
+    const int nb = dy_nblk(a);
+    hipLaunchKernelGGL(k_dy_eta_sum, dim3(nb), dim3(256), 0, s, (const double *)a.f.eta, a.nx * a.ny, h->d_partials);
+    DY_LAUNCH(h);
+    hipLaunchKernelGGL(k_dy_sum_final, dim3(1), dim3(256), 0, s, (const double *)h->d_partials, nb, h->d_sums);
+    DY_LAUNCH(h);
+    hipLaunchKernelGGL(k_dy_bulk, dim3(dy_gc(a)), dim3(256), 0, s, a, (const double *)h->d_sums, gamma_fact);
+    DY_LAUNCH(h);
+    return JRX_OK;
+}
+// DYREL! (constructors.jl:178-190)
+jrx_status dy_init(jrx_handle *h, hipStream_t s, const DyArgs &a, double CFL, double gamma_fact)
+{
+    JRX_TRY(dy_bulk(h, s, a, gamma_fact));
+    JRX_TRY(dy_gershgorin(h, s, a));
+    return dy_dtau(h, s, a, CFL, true);
+}
+// the sums of one reduction kernel, read on the host: the one synchronisation of a check
+jrx_status dy_read_sums(jrx_handle *h, hipStream_t s, int nb, int count)
+{
+    hipLaunchKernelGGL(k_dy_sum_final, dim3(1), dim3(256), 0, s, (const double *)h->d_partials, nb, h->d_sums);
+    DY_LAUNCH(h);
+    JRX_HIP(h, hipMemcpyAsync(h->h_sums, h->d_sums, count * sizeof(double), hipMemcpyDeviceToHost, s));
+    JRX_HIP(h, hipStreamSynchronize(s));
+    return JRX_OK;
+}
+
+#define DY_FIELDS_STRESS(f, d)                                                                                                                                   \
+    (f)->P, (f)->exx, (f)->eyy, (f)->exy, (f)->eplxx, (f)->eplyy, (f)->eplxy, (f)->txx, (f)->tyy, (f)->txy, (f)->txy_c, (f)->tII, (f)->toxx, (f)->toyy, (f)->toxy,  \
+        (f)->toxy_c, (f)->eta, (f)->eta_v, (f)->eta_vep, (f)->EII_pl, (f)->evol_pl, (f)->RP, (f)->phase_c, (f)->phase_v, (d)->txx_v, (d)->tyy_v, (d)->toxx_v,       \
+        (d)->toyy_v, (d)->lambda, (d)->lambda_v, (d)->dPpsi, (d)->P_num, (d)->gamma_eff
+#define DY_FIELDS_MOM(f) (f)->P, (f)->txx, (f)->tyy, (f)->txy, (f)->fx, (f)->fy, (f)->Rx, (f)->Ry
+#define DY_FIELDS_DAMP(d)                                                                                                                                      \
+    (d)->Dx, (d)->Dy, (d)->lmaxVx, (d)->lmaxVy, (d)->dVxdtau, (d)->dVydtau, (d)->dtauVx, (d)->dtauVy, (d)->dVx, (d)->dVy, (d)->betaVx, (d)->betaVy, (d)->cVx,      \
+        (d)->cVy, (d)->alphaVx, (d)->alphaVy, (d)->Rx0, (d)->Ry0
+
+}   // namespace
+
+extern "C" {
+
+jrx_status jrx_dyrel2d_strain_rate_RP(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_vep2d_params *p, int32_t do_strain_rate)
+{
+    JRX_TRY(dy_check(h, f, d, nullptr, nullptr, p));
+    DY_REQ(h, "compute_∇V_strain_rate_RP!", f->exx, f->eyy, f->exy, f->Vx, f->Vy, f->RP, f->P, f->P0, f->Q, d->etab);
+    const DyArgs a = dy_make(f, d, nullptr, p);
+    JRX_TRY(dy_strain_rp(h, h->stream, a, do_strain_rate != 0));
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_dyrel2d_stress_viscosity(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rheology *rh, const jrx_vep2d_params *p,
+                                        const jrx_dyrel2d_params *dp, double lambda_relaxation)
+{
+    JRX_TRY(dy_check(h, f, d, nullptr, rh, p));
+    if (!rh || !dp) return jrx_fail(h, JRX_ERR_ARG, "DYREL: null argument");
+    DY_REQ(h, "compute_stress_viscosity_DRYEL!", DY_FIELDS_STRESS(f, d));
+    DyArgs a = dy_make(f, d, rh, p);
+    a.rel = lambda_relaxation; a.nu = dp->viscosity_relaxation; a.cut_lo = dp->cutoff_lo; a.cut_hi = dp->cutoff_hi;
+    JRX_TRY(dy_stress(h, h->stream, a, dp->linear_viscosity != 0));
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_dyrel2d_PH_residual(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_vep2d_params *p)
+{
+    JRX_TRY(dy_check(h, f, d, nullptr, nullptr, p));
+    DY_REQ(h, "compute_PH_residual_V!", DY_FIELDS_MOM(f), d->dPpsi);
+    const DyArgs a = dy_make(f, d, nullptr, p);
+    hipLaunchKernelGGL(k_dy_ph_residual, dim3(dy_gc(a)), dim3(256), 0, h->stream, dy_mom(a, d->dPpsi), f->Rx, f->Ry);
+    DY_LAUNCH(h);
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_dyrel2d_DR_residual_update_V(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_vep2d_params *p)
+{
+    JRX_TRY(dy_check(h, f, d, nullptr, nullptr, p));
+    DY_REQ(h, "compute_DR_residual_update_V!", DY_FIELDS_MOM(f), f->Vx, f->Vy, d->P_num, d->Dx, d->Dy, d->dVxdtau, d->dVydtau, d->alphaVx, d->alphaVy, d->betaVx,
+           d->betaVy, d->dtauVx, d->dtauVy);
+    const DyArgs a = dy_make(f, d, nullptr, p);
+    hipLaunchKernelGGL(k_dy_update<false>, dim3(dy_gc(a)), dim3(256), 0, h->stream, dy_mom(a, d->P_num), dy_upd(a));
+    DY_LAUNCH(h);
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_dyrel2d_gershgorin(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rheology *rh, const jrx_vep2d_params *p)
+{
+    JRX_TRY(dy_check(h, f, d, nullptr, rh, p));
+    if (!rh) return jrx_fail(h, JRX_ERR_ARG, "DYREL: null argument");
+    DY_REQ(h, "Gershgorin_Stokes2D_SchurComplement!", f->eta, f->eta_v, f->phase_c, f->phase_v, d->gamma_eff, d->Dx, d->Dy, d->lmaxVx, d->lmaxVy);
+    const DyArgs a = dy_make(f, d, rh, p);
+    JRX_TRY(dy_gershgorin(h, h->stream, a));
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_dyrel2d_update_dtauV_alpha_beta(jrx_handle *h, const jrx_dyrel2d_fields *d, const jrx_vep2d_params *p, double CFL, int32_t from_lambda_max)
+{
+    jrx_vep2d_fields none;
+    memset(&none, 0, sizeof(none));
+    JRX_TRY(dy_check(h, &none, d, nullptr, nullptr, p));
+    DY_REQ(h, "update_dτV_α_β!", d->dtauVx, d->dtauVy, d->betaVx, d->betaVy, d->alphaVx, d->alphaVy, d->cVx, d->cVy, d->lmaxVx, d->lmaxVy);
+    const DyArgs a = dy_make(&none, d, nullptr, p);
+    JRX_TRY(dy_dtau(h, h->stream, a, CFL, from_lambda_max != 0));
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_dyrel2d_bulk_viscosity_and_penalty(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rheology *rh,
+                                                  const jrx_vep2d_params *p, double gamma_fact)
+{
+    JRX_TRY(dy_check(h, f, d, nullptr, rh, p));
+    if (!rh) return jrx_fail(h, JRX_ERR_ARG, "DYREL: null argument");
+    DY_REQ(h, "compute_bulk_viscosity_and_penalty!", f->eta, f->phase_c, d->etab, d->gamma_eff);
+    const DyArgs a = dy_make(f, d, rh, p);
+    JRX_TRY(dy_bulk(h, h->stream, a, gamma_fact));
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_dyrel2d_init(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rock_ratio2d *phi, const jrx_rheology *rh,
+                            const jrx_vep2d_params *p, const jrx_dyrel2d_params *dp)
+{
+    JRX_TRY(dy_check(h, f, d, phi, rh, p));
+    if (!rh || !dp) return jrx_fail(h, JRX_ERR_ARG, "DYREL: null argument");
+    DY_REQ(h, "DYREL!", f->eta, f->eta_v, f->phase_c, f->phase_v, d->gamma_eff, d->etab, DY_FIELDS_DAMP(d));
+    const DyArgs a = dy_make(f, d, rh, p);
+    JRX_TRY(dy_init(h, h->stream, a, dp->CFL, dp->gamma_fact));
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_dyrel2d_solve(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rock_ratio2d *phi, const jrx_rheology *rh,
+                             const jrx_vep2d_params *p, const jrx_dyrel2d_params *dp, jrx_dyrel2d_result *res)
+{
+    JRX_TRY(dy_check(h, f, d, phi, rh, p));
+    if (!rh || !dp || !res) return jrx_fail(h, JRX_ERR_ARG, "DYREL: null argument");
+    if (dp->nout < 1) return jrx_fail(h, JRX_ERR_ARG, "nout must be >= 1");
+    DY_REQ(h, "solve_DYREL!", DY_FIELDS_STRESS(f, d), DY_FIELDS_MOM(f), DY_FIELDS_DAMP(d), f->P0, f->divV, f->Q, f->Vx, f->Vy, f->eplxy_c, f->EVol_pl, d->etab);
+    if (mat_viscosity_reads_invariant(rh) && !f->exy_c) return jrx_fail(h, JRX_ERR_ARG, "a power-law creep needs ε.xy_c for compute_viscosity!");
+    hipStream_t s = h->stream;
+    DyArgs a = dy_make(f, d, rh, p);
+    a.nu = dp->viscosity_relaxation; a.cut_lo = dp->cutoff_lo; a.cut_hi = dp->cutoff_hi;
+    const int nx = a.nx, ny = a.ny;
+    const size_t n = (size_t)nx * ny, nv = (size_t)(nx + 1) * (ny + 1), nxn = (size_t)(nx - 1) * ny, nyn = (size_t)nx * (ny - 1);
+    const bool lin = dp->linear_viscosity != 0;
+    const int nb = dy_nblk(a);
+    const double EPS = 2.220446049250313e-16;
+
+    // solver.jl:86-95: P0 <- P, @tensor_center(ε_pl) = 0, λ = λv = 0
+    JRX_HIP(h, hipMemcpyAsync(f->P0, f->P, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    JRX_HIP(h, hipMemsetAsync(f->eplxx, 0, n * sizeof(double), s));
+    JRX_HIP(h, hipMemsetAsync(f->eplyy, 0, n * sizeof(double), s));
+    JRX_HIP(h, hipMemsetAsync(f->eplxy_c, 0, n * sizeof(double), s));
+    JRX_HIP(h, hipMemsetAsync(d->lambda, 0, n * sizeof(double), s));
+    JRX_HIP(h, hipMemsetAsync(d->lambda_v, 0, nv * sizeof(double), s));
+    JRX_HIP(h, hipEventRecord(h->ev[6], s));
+    {   // :117-119: compute_viscosity! (relaxation 1, the strain-rate invariant), compute_ρg!(ρg[end], ...), DYREL!
+        jrx_vep2d_params pv = *p;
+        pv.cutoff_lo = dp->cutoff_lo; pv.cutoff_hi = dp->cutoff_hi;
+        JRX_TRY(jrx_vep2d_compute_viscosity(h, f, rh, &pv, 1.0));
+    }
+    const int64_t nn[3] = {nx, ny, 1}, tdim[3] = {a.tg ? nx + 2 : nx, a.tg ? ny + 2 : ny, 1};
+    if (rh->has_density) JRX_TRY(jrx_compute_rhog(h, f->fy, rh, f->phase_c, f->T, f->P, nn, tdim, 2));
+    JRX_TRY(dy_init(h, s, a, dp->CFL, dp->gamma_fact));
+    const bool rho_loop = rh->has_density && !mat_density_is_constant(rh);
+
+    double err = 2 * dp->eps, err_min = INFINITY, errV0[2] = {1.0, 1.0}, errPt0 = 1.0, errV00 = 1.0, errPt = 1.0, rel_drop = dp->rel_drop;
+    int64_t iter = 0, cont = 0, itPH_done = 0;
+    bool bcs_applied = false;
+    jrx_status bad = JRX_OK;
+    for (int64_t itPH = 1; itPH <= 1000; itPH++) {
+        itPH_done = itPH;
+        if (rho_loop) JRX_TRY(jrx_compute_rhog(h, f->fy, rh, f->phase_c, f->T, f->P, nn, tdim, 2));      // update_ρg! :124
+        JRX_TRY(dy_strain_rp(h, s, a, true));
+        a.rel = dp->lambda_relaxation_PH;
+        JRX_TRY(dy_stress(h, s, a, lin));
+        hipLaunchKernelGGL(k_dy_ph_residual, dim3(dy_gc(a)), dim3(256), 0, s, dy_mom(a, d->dPpsi), f->Rx, f->Ry);
+        DY_LAUNCH(h);
+        hipLaunchKernelGGL(k_dy_ph_sums, dim3(nb), dim3(256), 0, s, (const double *)f->Rx, (const double *)f->Ry, (const double *)f->RP, nx, ny, h->d_partials);
+        DY_LAUNCH(h);
+        JRX_TRY(dy_read_sums(h, s, nb, 3));      // the host read of this Powell-Hestenes iteration
+        const double errV[2] = {sqrt(h->h_sums[0]) / sqrt((double)((p->nxg - 2) * (p->nyg - 1))), sqrt(h->h_sums[1]) / sqrt((double)((p->nxg - 1) * (p->nyg - 2)))};
+        errPt = sqrt(h->h_sums[2]) / sqrt((double)(p->nxg * p->nyg));
+        if (itPH == 1) { errV0[0] = errV[0] + EPS; errV0[1] = errV[1] + EPS; errPt0 = errPt + EPS; }
+        if (itPH == 2) errPt0 = errPt + EPS;
+        const double e0 = fmin(errV[0] / errV0[0], errV[0]), e1 = fmin(errV[1] / errV0[1], errV[1]), e2 = fmin(errPt / errPt0, errPt);
+        err = fmax(e0, fmax(e1, e2));
+        if (std::isnan(e0) || std::isnan(e1) || std::isnan(e2)) err = NAN;
+        if (dp->verbose_PH)
+            printf("itPH = %02lld iter = %06lld iter/nx = %03lld, err = %1.3e - norm[R1=%1.3e %1.3e, R2=%1.3e %1.3e, Rp=%1.3e %1.3e] \n", (long long)itPH, (long long)iter,
+                   (long long)(iter / nx), err, errV[0], errV[0] / errV0[0], errV[1], errV[1] / errV0[1], errPt, errPt / errPt0);
+        if (std::isnan(err)) { bad = jrx_fail(h, JRX_ERR_NAN, "NaN detected in outer loop"); break; }
+        if (err > 1.0e10) { bad = jrx_fail(h, JRX_ERR_NAN, "Kaboom! Error > 1e10 in outer loop"); break; }
+        if (err < dp->eps) break;
+        if (err > err_min * 1.05) rel_drop = fmax(rel_drop * 0.1, 1.0e-3);
+        if (err_min > err) err_min = err;
+        const double eps_vel = err * rel_drop;
+        int64_t itPT = 0;
+        a.rel = dp->lambda_relaxation_DR;
+        while (err > eps_vel && itPT <= dp->iterMax) {
+            itPT++; iter++;
+            const bool check = iter % dp->nout == 0;
+            if (check) {      // pseudo-old residuals :191
+                hipLaunchKernelGGL(k_copy6, dim3(256), dim3(256), 0, s, d->Rx0, (const double *)f->Rx, (i64)nxn, d->Ry0, (const double *)f->Ry, (i64)nyn,
+                                   (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr,
+                                   (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0);
+                DY_LAUNCH(h);
+            }
+            JRX_TRY(dy_strain_rp(h, s, a, true));
+            JRX_TRY(dy_stress(h, s, a, lin));
+            // flow_bcs! in full the first time; afterwards the update kernel refreshes the ghosts of the nodes it moves
+            if (bcs_applied) hipLaunchKernelGGL(k_dy_update<true>, dim3(dy_gc(a)), dim3(256), 0, s, dy_mom(a, d->P_num), dy_upd(a));
+            else hipLaunchKernelGGL(k_dy_update<false>, dim3(dy_gc(a)), dim3(256), 0, s, dy_mom(a, d->P_num), dy_upd(a));
+            DY_LAUNCH(h);
+            if (!bcs_applied) { JRX_TRY(jrx2d_bcs(h, s, f->Vx, f->Vy, nx, ny, p->free_slip, p->no_slip, 0)); bcs_applied = true; }
+            if (check) {
+                hipLaunchKernelGGL(k_dy_check_sums, dim3(nb), dim3(256), 0, s, a.d, (const double *)f->Rx, (const double *)f->Ry, (int)nxn, (int)nyn, h->d_partials);
+                DY_LAUNCH(h);
+                JRX_TRY(dy_read_sums(h, s, nb, 6));      // the host read of these nout iterations
+                const double *S = h->h_sums;
+                const double eV0 = sqrt(S[0]) / sqrt((double)((p->nxg - 2) * (p->nyg - 1))), eV1 = sqrt(S[1]) / sqrt((double)((p->nxg - 1) * (p->nyg - 2)));
+                if (iter == dp->nout) errV00 = fmax(eV0, eV1) + EPS;
+                err = fmax(eV0 / errV00, eV1 / errV00);
+                if (std::isnan(eV0) || std::isnan(eV1)) err = NAN;
+                if (cont < res->cap) {
+                    if (res->err_evo_tot) res->err_evo_tot[cont] = err;
+                    if (res->err_evo_V) res->err_evo_V[cont] = err;
+                    if (res->err_evo_P) res->err_evo_P[cont] = errPt / errPt0;
+                    if (res->err_evo_it) res->err_evo_it[cont] = (double)iter;
+                }
+                cont++;
+                if (std::isnan(err)) { bad = jrx_fail(h, JRX_ERR_NAN, "NaN detected in inner loop"); break; }
+                if (dp->verbose_DR) printf("it = %lld, iter = %lld, err = %1.3e \n", (long long)itPT, (long long)iter, err);
+                const double lmin = fabs(S[2] + S[3]) / (S[4] + S[5]);      // compute_λminV! :359-365
+                const double cV = 2 * sqrt(lmin) * dp->c_fact;
+                hipLaunchKernelGGL(k_dy_fill2, dim3((unsigned)(((nxn > nyn ? nxn : nyn) + 255) / 256)), dim3(256), 0, s, d->cVx, (int)nxn, d->cVy, (int)nyn, cV);
+                DY_LAUNCH(h);
+                JRX_TRY(dy_gershgorin(h, s, a));
+                JRX_TRY(dy_dtau(h, s, a, dp->CFL, true));
+            }
+        }
+        if (bad != JRX_OK) break;
+        JRX_TRY(dy_strain_rp(h, s, a, false));      // update pressure :263-264
+        hipLaunchKernelGGL(k_dy_add_P, dim3(dy_gc(a)), dim3(256), 0, s, f->P, (const double *)d->gamma_eff, (const double *)f->RP, (int)n);
+        DY_LAUNCH(h);
+        if (iter > dp->total_iterMax) break;
+    }
+    JRX_HIP(h, hipEventRecord(h->ev[7], s));
+    if (bad == JRX_OK) {      // epilogue :269-290
+        hipLaunchKernelGGL(k_dy_epilogue, dim3(dy_gv(a)), dim3(256), 0, s, a);
+        DY_LAUNCH(h);
+        hipLaunchKernelGGL(k_copy6, dim3(256), dim3(256), 0, s, f->toxx, (const double *)f->txx, (i64)n, f->toyy, (const double *)f->tyy, (i64)n, f->toxy,
+                           (const double *)f->txy, (i64)nv, f->toxy_c, (const double *)f->txy_c, (i64)n, d->toxx_v, (const double *)d->txx_v, (i64)nv, d->toyy_v,
+                           (const double *)d->tyy_v, (i64)nv);
+        DY_LAUNCH(h);
+    }
+    JRX_HIP(h, hipStreamSynchronize(s));
+    float ms = 0.f;
+    JRX_HIP(h, hipEventElapsedTime(&ms, h->ev[6], h->ev[7]));
+    res->iter = iter; res->itPH = itPH_done;
+    res->nchecks = cont < res->cap ? cont : res->cap;
+    res->time_s = ms * 1e-3;
+    return bad;
+}
+
+}   // extern "C"

@@ -120,6 +120,7 @@ int find_opt(jrx_handle *h, const char *key, bool tuning, OptRef *out)
         {"stat_vep3_fused", 2, &h->stat_vep3_fused}, {"stat_graph_replays", 2, &h->stat_graph_replays},
         {"stat_fused3d_visc", 2, &h->stat_fused3d_visc}, {"stat_fused3d_inkernel", 2, &h->stat_fused3d_inkernel}, {"stat_visc_checks", 2, &h->stat_visc_checks}, {"stat_visc_fallbacks", 2, &h->stat_visc_fallbacks}, {"stat_fused3d_nof1", 2, &h->stat_fused3d_nof1}, {"stat_fused3d_nof2", 2, &h->stat_fused3d_nof2},
         {"stat_weno_calls", 2, &h->stat_weno_calls}, {"stat_weno_fused", 2, &h->stat_weno_fused}, {"stat_principal_calls", 2, &h->stat_principal_calls},
+        {"stat_dyrel_launches", 2, &h->stat_dyrel_launches},
     };
     const OptRef tun[] = {
         {"fused_split", 0, &h->fused_split}, {"fused_tile", 1, &h->fused_tile}, {"fused_ylds", 0, &h->fused_ylds}, {"fused_hiface", 0, &h->fused_hiface}, {"visc_fold", 0, &h->visc_fold}, {"zero_forces", 0, &h->zero_forces}, {"scratch_stagger", 1, &h->scratch_stagger}, {"scratch_contiguous", 0, &h->scratch_contiguous}, {"end_flips", 0, &h->end_flips}, {"comm_bcs_lazy", 0, &h->comm_bcs_lazy}, {"fused_first_pct", 1, &h->fused_first_pct},

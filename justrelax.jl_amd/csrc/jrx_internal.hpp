@@ -108,6 +108,7 @@ struct jrx_handle {
     int weno_rows = 0;                   // tuning: rows a wave of the fused WENO kernel marches (0: by the grid, 64 .. 8)
     int64_t stat_weno_calls = 0, stat_weno_fused = 0;   // jrx_weno5_advection2d calls / those that ran the fused form
     int64_t stat_principal_calls = 0;    // jrx_principal_stresses2d / 3d calls that launched
+    int64_t stat_dyrel_launches = 0;     // kernels launched by the jrx_dyrel2d_* entry points (dyrel2d.hip)
     // ---- read-only counters (jrx_get_option "stat_*"): launches of the fused kernels since jrx_create, so that tests and the bench can
     //      prove which kernel path ran
     int64_t stat_fused3d_inkernel = 0;   // launches of k_fused3d that finished the neighbour faces themselves (fused_overlap = 3)
