@@ -129,6 +129,7 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   "stat_sweeps3d" = launches of the 3D z-marching stress and velocity sweeps (k_stress3d_zb, k_velocity3d_zb),
  *   "stat_fused2d_b" = those of "stat_fused2d" that ran the batch form k_fused2d_b (32-bit byte offsets: only below 2^29 nodes, see "fused2d_batch" in jrx_tuning.h),
  *   "stat_weno_calls" / "stat_weno_fused" = jrx_weno5_advection2d calls / those that ran the fused three-launch form,
+ *   "stat_weno3d_calls" / "stat_weno3d_fused" = the same for jrx_weno5_advection3d (the 2D pair counts 2D calls only),
  *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* entry points -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
@@ -707,13 +708,36 @@ jrx_status jrx_compute_shear_heating(jrx_handle *h, double *shear_heating, const
  *  - after the call weno.ut holds the stage-2 field.
  * Two kernel forms, bit-identical in u and ut (tuning key "weno_fused", include/jrx_tuning.h): the default runs one launch per RK stage with the fluxes in
  * registers, and then fL holds the stage-1 field and fR, fB, fT are not touched -- after such a call fL..fT do NOT hold fluxes (nothing outside weno5.jl
- * reads them); "weno_fused" = 0 runs the reference's six launches and leaves the fluxes of the stage-2 field in fL..fT.  2D only: the reference's 3D
- * forwards (src/ext/AMDGPU/3D.jl:71-75,493-495) feed a 3D array into this 2D indexing.  No halo exchange (the reference has none; callers update_halo!).
+ * reads them); "weno_fused" = 0 runs the reference's six launches and leaves the fluxes of the stage-2 field in fL..fT.  3D fields: jrx_weno5_advection3d
+ * below (the reference's 3D forwards, src/ext/AMDGPU/3D.jl:71-75,493-495, feed a 3D array into this 2D indexing).  No halo exchange (the reference has none; callers update_halo!).
  * JRX_ERR_ARG without a launch: method not 1 or 2, nx or ny < 1, any of vx, vy, ut, fL..fT smaller than u along a dimension, two arrays overlapping (vx, vy
  * excepted).  JRX_ERR_UNSUPPORTED: an array of 2^31 or more entries (32-bit offsets).  Counters "stat_weno_calls", "stat_weno_fused" (jrx_get_option). */
 jrx_status jrx_weno5_advection2d(jrx_handle *h, double *u, const int64_t udim[2], const double *vx, const int64_t vxdim[2], const double *vy,
                                  const int64_t vydim[2], double *ut, double *fL, double *fR, double *fB, double *fT, const int64_t wdim[2], double dx, double dy,
                                  double dt, int32_t method);
+
+/* ------------------------------------------------------------------ WENO-5 advection (3D)
+ * WENO_advection!(u, (vx, vy, vz), weno, di, dt) on a 3D vertex field: jrx_weno5_advection2d one dimension up.  The reference defines the scheme one direction
+ * at a time (src/advection/weno5.jl:10-168) but its 3D methods (src/ext/AMDGPU/3D.jl:71-75,493-495) feed a 3D array into the 2D indexing, so the 3D form is
+ * written out here: the same clamped five-point reconstruction along z, two more terms in weno_rhs, the same SSP-RK3.  method, dt as in 2D; dx, dy, dz the
+ * uniform spacings.  udim = size(u), vxdim / vydim / vzdim = size(vx) / size(vy) / size(vz), wdim = the common size of weno.ut and the six flux arrays.
+ *  - the loop box and the clamping of every stencil index come from size(u) = (nx, ny, nz); every array is indexed with ITS OWN extents (column-major), which
+ *    may be larger than u's.  Only the (nx, ny, nz) box of ut and the flux arrays is written; the velocities are point reads vx[i, j, k], vy[i, j, k], vz[i, j, k];
+ *  - fB / fT are the upwind / downwind fluxes along x and fL / fR those along y, as in the reference; fD / fU are the upwind / downwind fluxes along z (from
+ *    u[i, j, k-2..k+2]) -- these two names are this project's, the reference's struct has no such fields;
+ *  - weno_rhs = the reference's four terms followed by max(vz,0) (fD[i,j,k] - fD[i,j,kD]) _dz + min(vz,0) (fU[i,j,kU] - fU[i,j,k]) _dz with kD = clamp(k-1),
+ *    kU = clamp(k+1): on the first and last vertex of a direction the flux difference of that direction is exactly 0 (the reference's quirk, kept).  The device
+ *    evaluates the z terms first (innermost), then the y and x chain of the 2D kernels: for a field constant along z the result has the 2D entry point's bits;
+ *  - after the call weno.ut holds the stage-2 field.
+ * Two kernel forms, bit-identical in u and ut (tuning key "weno_fused"): the default runs one launch per RK stage with the fluxes in registers and LDS; then fL
+ * holds the stage-1 field and fR, fB, fT, fD, fU are not touched and may be NULL.  "weno_fused" = 0 runs six launches and leaves the six fluxes of the stage-2
+ * field; all six flux arrays must then be non-NULL.  No halo exchange, as in 2D.
+ * JRX_ERR_ARG without a launch: method not 1 or 2, an extent of u < 1, any of vx, vy, vz, ut and the flux arrays smaller than u along a dimension, two arrays
+ * overlapping (the velocities among themselves excepted), a NULL flux array with "weno_fused" = 0.  JRX_ERR_UNSUPPORTED: an array of 2^31 or more entries
+ * (32-bit offsets).  Counters "stat_weno3d_calls", "stat_weno3d_fused" (jrx_get_option); the 2D counters count 2D calls only. */
+jrx_status jrx_weno5_advection3d(jrx_handle *h, double *u, const int64_t udim[3], const double *vx, const int64_t vxdim[3], const double *vy,
+                                 const int64_t vydim[3], const double *vz, const int64_t vzdim[3], double *ut, double *fL, double *fR, double *fB, double *fT,
+                                 double *fD, double *fU, const int64_t wdim[3], double dx, double dy, double dz, double dt, int32_t method);
 
 /* ------------------------------------------------------------------ principal stresses
  * compute_principal_stresses!(stokes, σ) -- src/stokes/PrincipalStresses.jl:1-63 (hessenberg_eigen_3x3 :67-97), PrincipalStress

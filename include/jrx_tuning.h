@@ -69,9 +69,10 @@
  *   "field_pool_pct" (70)         "field_placement" = 1 with chunks of >= 128 MiB: the first allocation of a chunk size creates chunks for this share of the free memory (less 6 GiB), and every
  *                                 array takes random chunks of that pool -- chunks from all over the device's memory are what makes a placement good (profiles/r05_placement_search.txt,
  *                                 section 13); jrx_field_trim releases what nobody took; 0 = no pool (chunks are created as needed)
- *   "weno_fused" (1)             jrx_weno5_advection2d: one launch per RK stage, fluxes in registers (fL holds the stage-1 field afterwards); 0 = the reference's six launches with the
- *                                 fluxes in fL, fR, fB, fT (bit-identical u and ut)
- *   "weno_rows" (0)              fused WENO kernel: rows a wave marches (0 = by the grid: 64, halved down to 8 while the launch has fewer than 4,096 waves)
+ *   "weno_fused" (1)             jrx_weno5_advection2d / 3d: one launch per RK stage, fluxes in registers (fL holds the stage-1 field afterwards); 0 = the reference's six launches with the
+ *                                 fluxes in fL, fR, fB, fT (3D: and fD, fU; bit-identical u and ut)
+ *   "weno_rows" (0)              fused WENO kernel: rows a wave marches (0 = by the grid: 64, halved down to 8 while the launch has fewer than 4,096 waves); 3D: planes a
+ *                                 block of 8 waves marches (0 = 64, halved down to 8 while the launch has fewer than 1,024 blocks)
  *   "general_hif" (0)            3D fused kernel, general form (any dt), 64 x 4 tile: the stress nodes on the high faces i = nx, j = ny, k = nz are updated inside the kernel (one launch per
  *                                 unobserved iteration) and, with neighbours, the kernel's boundary tiles read the received planes ("fused_overlap" = 3: no flow_bcs! launch, no fix-up):
  *                                 4 / 3 = the instantiation built for four (128 VGPRs + 28 dwords of scratch: 10.99 ms at 512^3) / three (155 VGPRs: 7.95 ms) waves per SIMD; 0 = boundary-layer launch (7.47 + 0.11 ms)

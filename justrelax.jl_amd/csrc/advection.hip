@@ -1,4 +1,4 @@
-// advection.hip -- WENO-5 advection of a 2D vertex field (WENO_advection!), for gfx950.
+// advection.hip -- WENO-5 advection of a 2D or 3D vertex field (WENO_advection!), for gfx950.
 //
 // Reference being replaced (PTsolvers/JustRelax.jl): src/advection/weno5.jl:10-16 (betas), :23-55 (alphas, Val(1) JS / Val(2) Z), :59-71 (candidate
 // stencils), :84-107 (weights and flux), :120-151 (clamped stencils), :154-168 (weno_rhs), :170-175 (weno_f!), :195-230 (WENO_advection!: SSP-RK3 as six
@@ -14,6 +14,14 @@
 //     own vertex).  No stage writes the array whose neighbours it reads.
 // Upwind and downwind flux of a direction share the betas and inv(β + ϵ) (same operations on the same operands: the bits do not change).
 // fma() stands where the reference has muladd / @muladd; the library builds with -ffp-contract=off, so nothing else is contracted.
+// 3D (jrx_weno5_advection3d): the scheme is defined one direction at a time, so its 3D form is the same clamped five-point reconstruction along z (fD upwind,
+// fU downwind: this project's names), two more terms in weno_rhs and the same SSP-RK3 -- the reference's own 3D methods (src/ext/AMDGPU/3D.jl:71-75,493-495)
+// feed a 3D array into the 2D indexing of weno5.jl.  Again two forms from the same __device__ functions:
+//   per-kernel: k_weno_flux3d writes the six fluxes, k_weno_step3d<S> reads them; six launches.
+//   fused: one launch per RK stage.  A block is 64 columns x 8 rows of vertices (62 x 6 outputs, one flux column / row either side) and marches in z over a
+//     chunk of planes: every thread keeps the five-plane z window of its vertex in registers with the z fluxes one plane ahead (the 2D kernel's y march), takes
+//     the x stencil and the x-neighbour fluxes from the neighbouring lanes, and the y stencil and the y-neighbour fluxes of the current plane from LDS (two
+//     block barriers per plane).  The first and last wave of a block are the y halo: they evaluate only the y fluxes of their row.
 // Addressing: 32-bit element offsets (every array below 2^31 entries, checked).
 #include "jrx_internal.hpp"
 
@@ -71,6 +79,19 @@ __device__ __forceinline__ double weno_rhs(double vx, double vy, double fB, doub
                                            double _dx, double _dy)
 {
     double r = (fmin(vy, 0.0) * (fRE - fR)) * _dy;
+    r = fma(fmax(vy, 0.0) * (fL - fLW), _dy, r);
+    r = fma(fmin(vx, 0.0) * (fTN - fT), _dx, r);
+    return fma(fmax(vx, 0.0) * (fB - fBS), _dx, r);
+}
+
+// weno_rhs one dimension up: the two z terms innermost (fDD = fD[kD], fUU = fU[kU], clamped like the others), then the y and x chain of weno_rhs in its order.
+// With a field constant along z both z terms are exactly 0 and the result has the bits of weno_rhs.
+__device__ __forceinline__ double weno_rhs3(double vx, double vy, double vz, double fB, double fBS, double fT, double fTN, double fL, double fLW, double fR,
+                                            double fRE, double fD, double fDD, double fU, double fUU, double _dx, double _dy, double _dz)
+{
+    double r = (fmin(vz, 0.0) * (fUU - fU)) * _dz;
+    r = fma(fmax(vz, 0.0) * (fD - fDD), _dz, r);
+    r = fma(fmin(vy, 0.0) * (fRE - fR), _dy, r);
     r = fma(fmax(vy, 0.0) * (fL - fLW), _dy, r);
     r = fma(fmin(vx, 0.0) * (fTN - fT), _dx, r);
     return fma(fmax(vx, 0.0) * (fB - fBS), _dx, r);
@@ -212,6 +233,180 @@ jrx_status launch_split(jrx_handle *h, double *u, double *ut, double *fL, double
     return JRX_OK;
 }
 
+// ================================================================ 3D
+struct WenoExt { int ly, lz; };                                  // element strides of an array along y and z (its own extents: ly = n1, lz = n1 n2)
+
+// ---------------------------------------------------------------- per-kernel form (3D)
+template <int M>
+__global__ __launch_bounds__(256) void k_weno_flux3d(double *__restrict__ fL, double *__restrict__ fR, double *__restrict__ fB, double *__restrict__ fT,
+                                                     double *__restrict__ fD, double *__restrict__ fU, const double *__restrict__ src, int nx, int ny, int nz,
+                                                     WenoExt es, WenoExt ew)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = (int)(t / ((int64_t)nx * ny));
+    if (k >= nz) return;
+    const int q = (int)(t - (int64_t)k * nx * ny), j = q / nx, i = q - j * nx;
+    auto at = [&](int a, int b, int c) { return src[clampi(a, 0, nx - 1) + es.ly * clampi(b, 0, ny - 1) + es.lz * clampi(c, 0, nz - 1)]; };
+    const double uc = at(i, j, k);
+    double fb, ft, fl, fr, fd, fu;
+    weno_pair<M>(at(i - 2, j, k), at(i - 1, j, k), uc, at(i + 1, j, k), at(i + 2, j, k), fb, ft);
+    weno_pair<M>(at(i, j - 2, k), at(i, j - 1, k), uc, at(i, j + 1, k), at(i, j + 2, k), fl, fr);
+    weno_pair<M>(at(i, j, k - 2), at(i, j, k - 1), uc, at(i, j, k + 1), at(i, j, k + 2), fd, fu);
+    const int o = i + ew.ly * j + ew.lz * k;
+    fB[o] = fb; fT[o] = ft; fL[o] = fl; fR[o] = fr; fD[o] = fd; fU[o] = fu;
+}
+
+template <int S>
+__global__ __launch_bounds__(256) void k_weno_step3d(double *u, double *ut, const double *__restrict__ fL, const double *__restrict__ fR,
+                                                     const double *__restrict__ fB, const double *__restrict__ fT, const double *__restrict__ fD,
+                                                     const double *__restrict__ fU, const double *__restrict__ vx, const double *__restrict__ vy,
+                                                     const double *__restrict__ vz, int nx, int ny, int nz, WenoExt eu, WenoExt ew, WenoExt evx, WenoExt evy,
+                                                     WenoExt evz, double _dx, double _dy, double _dz, double dt)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = (int)(t / ((int64_t)nx * ny));
+    if (k >= nz) return;
+    const int q = (int)(t - (int64_t)k * nx * ny), j = q / nx, i = q - j * nx;
+    const int o = i + ew.ly * j + ew.lz * k, ou = i + eu.ly * j + eu.lz * k;
+    const int iS = clampi(i - 1, 0, nx - 1), iN = clampi(i + 1, 0, nx - 1), jW = clampi(j - 1, 0, ny - 1), jE = clampi(j + 1, 0, ny - 1);
+    const int kD = clampi(k - 1, 0, nz - 1), kU = clampi(k + 1, 0, nz - 1);
+    const double r = weno_rhs3(vx[i + evx.ly * j + evx.lz * k], vy[i + evy.ly * j + evy.lz * k], vz[i + evz.ly * j + evz.lz * k], fB[o],
+                               fB[iS + ew.ly * j + ew.lz * k], fT[o], fT[iN + ew.ly * j + ew.lz * k], fL[o], fL[i + ew.ly * jW + ew.lz * k], fR[o],
+                               fR[i + ew.ly * jE + ew.lz * k], fD[o], fD[i + ew.ly * j + ew.lz * kD], fU[o], fU[i + ew.ly * j + ew.lz * kU], _dx, _dy, _dz);
+    const double un = weno_stage<S>(u[ou], S == 1 ? 0.0 : ut[o], r, dt);
+    if (S == 3) u[ou] = un;
+    else ut[o] = un;
+}
+
+// ---------------------------------------------------------------- fused form (3D)
+constexpr int kWeno3Rows = 8, kWeno3Out = kWeno3Rows - 2;        // a block: 8 waves stacked in y (6 output rows, a y-flux row either side), 64 columns each as in 2D
+
+// One RK stage; src / dst / u0 as in k_weno_fused.  Block (bx, by, bz) of the 1D grid covers columns 62 bx - 1 .. 62 bx + 62, rows 6 by - 1 .. 6 by + 6 and planes
+// [planes bz, + planes).  Wave ty owns row 6 by - 1 + ty; waves 0 and 7 only feed the y fluxes of their row to waves 1 and 6.  Per plane: every wave puts the
+// plane's value of its vertex into sv (the first and last two waves also the row two beyond), barrier, every wave forms its y flux pair from sv and puts it
+// into sL / sR, barrier, the six inner waves read fL of the row below and fR of the row above.  The next plane's writes of sv come after the second barrier
+// (every read of sv is before it) and its writes of sL / sR after the next first barrier (every read of sL / sR is before it): single buffers suffice.
+template <int M, int S>
+__global__ __launch_bounds__(64 * kWeno3Rows) void k_weno_fused3d(double *dst, const double *__restrict__ src, const double *u0, const double *__restrict__ vx,
+                                                                  const double *__restrict__ vy, const double *__restrict__ vz, int nx, int ny, int nz, WenoExt es,
+                                                                  WenoExt ed, WenoExt eu, WenoExt evx, WenoExt evy, WenoExt evz, int nbx, int nby, int planes, double _dx,
+                                                                  double _dy, double _dz, double dt)
+{
+    __shared__ double sv[kWeno3Rows + 4][kWenoLanes], sL[kWeno3Rows][kWenoLanes], sR[kWeno3Rows][kWenoLanes];
+    const int lane = threadIdx.x, ty = threadIdx.y;
+    const int bz = blockIdx.x / (nbx * nby), bq = blockIdx.x - bz * (nbx * nby), by = bq / nbx, bx = bq - by * nbx;   // 1D grid, x fastest
+    const int k0 = bz * planes, k1 = min(k0 + planes, nz);                  // uniform over the block; k0 < nz by the grid
+    const int c = bx * kWenoOut - 1 + lane, cc = clampi(c, 0, nx - 1);
+    const int r = by * kWeno3Out - 1 + ty, rr = clampi(r, 0, ny - 1);
+    const bool inner = ty >= 1 && ty <= kWeno3Out;                           // uniform over the wave
+    const bool xedge = inner && (lane < 2 || lane >= kWenoLanes - 2);
+    const int ce = clampi(lane < 2 ? c - 2 : c + 2, 0, nx - 1);             // the column beyond the wave an end lane holds
+    const bool yedge = ty < 2 || ty >= kWeno3Rows - 2;
+    const int re = clampi(ty < 2 ? r - 2 : r + 2, 0, ny - 1);               // the row beyond the block a wave of the first / last two holds
+    const int se = ty < 2 ? ty : ty + 4;                                     // ... and its row of sv
+    const bool out = inner && lane >= 1 && lane <= kWenoOut && c < nx && r < ny;
+    const int xm = nx - 1, ym = ny - 1, zm = nz - 1;
+    auto at = [&](int col, int row, int k) { return src[col + es.ly * row + es.lz * clampi(k, 0, zm)]; };
+
+    // z window: planes k0-2 .. k0+2 after the prologue; the z fluxes of planes k0-1 (fD) and k0 (fD, fU)
+    const double w0 = at(cc, rr, k0 - 3);
+    double a0 = at(cc, rr, k0 - 2), a1 = at(cc, rr, k0 - 1), a2 = at(cc, rr, k0), a3 = at(cc, rr, k0 + 1), a4 = at(cc, rr, k0 + 2);
+    double fDm = 0.0, fDc = 0.0, fUc = 0.0, dummy;
+    if (inner) {
+        weno_pair<M>(w0, a0, a1, a2, a3, fDm, dummy);
+        weno_pair<M>(a0, a1, a2, a3, a4, fDc, fUc);
+    }
+    double nxt = at(cc, rr, k0 + 3);
+    double en = xedge ? at(ce, rr, k0) : 0.0, yn = yedge ? at(cc, re, k0) : 0.0;
+    for (int k = k0; k < k1; k++) {
+        const double a5 = nxt, ec = en, yc = yn;
+        nxt = at(cc, rr, k + 4);                                            // one plane ahead
+        en = xedge ? at(ce, rr, k + 1) : 0.0;
+        yn = yedge ? at(cc, re, k + 1) : 0.0;
+        double vxv = 0.0, vyv = 0.0, vzv = 0.0, uv = a2;
+        if (inner) {
+            vxv = vx[cc + evx.ly * rr + evx.lz * k]; vyv = vy[cc + evy.ly * rr + evy.lz * k]; vzv = vz[cc + evz.ly * rr + evz.lz * k];
+            if (S != 1) uv = u0[cc + eu.ly * rr + eu.lz * k];
+        }
+        sv[ty + 2][lane] = a2;
+        if (yedge) sv[se][lane] = yc;
+        __syncthreads();
+        double fL, fR;                                                      // y fluxes of this row
+        weno_pair<M>(sv[ty][lane], sv[ty + 1][lane], a2, sv[ty + 3][lane], sv[ty + 4][lane], fL, fR);
+        sL[ty][lane] = fL; sR[ty][lane] = fR;
+        __syncthreads();
+        if (inner) {
+            // x fluxes, as in k_weno_fused
+            const double sm2 = __shfl(a2, lane - 2, 64), sm1 = __shfl(a2, lane - 1, 64), sp1 = __shfl(a2, lane + 1, 64), sp2 = __shfl(a2, lane + 2, 64);
+            const double e1 = __shfl(ec, 1, 64), e62 = __shfl(ec, kWenoLanes - 2, 64);
+            const double um2 = lane >= 2 ? sm2 : ec, um1 = lane >= 1 ? sm1 : e1;
+            const double up1 = lane <= kWenoLanes - 2 ? sp1 : e62, up2 = lane <= kWenoLanes - 3 ? sp2 : ec;
+            double fB, fT;
+            weno_pair<M>(um2, um1, a2, up1, up2, fB, fT);
+            const double fBl = __shfl(fB, lane - 1, 64), fTr = __shfl(fT, lane + 1, 64);
+            // z fluxes of plane k + 1
+            double fDn, fUn;
+            weno_pair<M>(a1, a2, a3, a4, a5, fDn, fUn);
+            const double fLW = sL[ty - 1][lane], fRE = sR[ty + 1][lane];
+            const double rh = weno_rhs3(vxv, vyv, vzv, fB, c == 0 ? fB : fBl, fT, c == xm ? fT : fTr, fL, r == 0 ? fL : fLW, fR, r == ym ? fR : fRE, fDc,
+                                        k == 0 ? fDc : fDm, fUc, k == zm ? fUc : fUn, _dx, _dy, _dz);
+            if (out) dst[c + ed.ly * r + ed.lz * k] = weno_stage<S>(uv, a2, rh, dt);
+            fDm = fDc; fDc = fDn; fUc = fUn;
+        }
+        a0 = a1; a1 = a2; a2 = a3; a3 = a4; a4 = a5;
+    }
+    (void)a0;
+}
+
+// planes a block marches: 64, halved (down to 8) while the launch would have fewer than 1,024 blocks (8,192 waves)
+int fused_planes(const jrx_handle *h, int nx, int ny, int nz)
+{
+    if (h->weno_rows > 0) return h->weno_rows;
+    const long nb = (long)((nx + kWenoOut - 1) / kWenoOut) * ((ny + kWeno3Out - 1) / kWeno3Out);
+    int planes = 64;
+    while (planes > 8 && nb * ((nz + planes - 1) / planes) < 1024) planes /= 2;
+    return planes;
+}
+
+struct Weno3Args {
+    double *u, *ut, *f[6];                                       // f: fL, fR, fB, fT, fD, fU
+    const double *vx, *vy, *vz;
+    int nx, ny, nz;
+    WenoExt eu, ew, evx, evy, evz;
+    double _dx, _dy, _dz, dt;
+};
+
+template <int M>
+jrx_status launch_fused3d(jrx_handle *h, const Weno3Args &a)
+{
+    const int planes = fused_planes(h, a.nx, a.ny, a.nz);
+    const int nbx = (a.nx + kWenoOut - 1) / kWenoOut, nby = (a.ny + kWeno3Out - 1) / kWeno3Out, nbz = (a.nz + planes - 1) / planes;
+    const dim3 grid((unsigned)((int64_t)nbx * nby * nbz)), block(kWenoLanes, kWeno3Rows);     // below 2^31 blocks: every array is below 2^31 entries
+    double *u1 = a.f[0];
+    hipLaunchKernelGGL((k_weno_fused3d<M, 1>), grid, block, 0, h->stream, u1, a.u, a.u, a.vx, a.vy, a.vz, a.nx, a.ny, a.nz, a.eu, a.ew, a.eu, a.evx, a.evy, a.evz,
+                       nbx, nby, planes, a._dx, a._dy, a._dz, a.dt);
+    hipLaunchKernelGGL((k_weno_fused3d<M, 2>), grid, block, 0, h->stream, a.ut, u1, a.u, a.vx, a.vy, a.vz, a.nx, a.ny, a.nz, a.ew, a.ew, a.eu, a.evx, a.evy, a.evz,
+                       nbx, nby, planes, a._dx, a._dy, a._dz, a.dt);
+    hipLaunchKernelGGL((k_weno_fused3d<M, 3>), grid, block, 0, h->stream, a.u, a.ut, a.u, a.vx, a.vy, a.vz, a.nx, a.ny, a.nz, a.ew, a.eu, a.eu, a.evx, a.evy, a.evz,
+                       nbx, nby, planes, a._dx, a._dy, a._dz, a.dt);
+    return JRX_OK;
+}
+
+template <int M>
+jrx_status launch_split3d(jrx_handle *h, const Weno3Args &a)
+{
+    const dim3 grid((unsigned)(((int64_t)a.nx * a.ny * a.nz + 255) / 256)), block(256);
+    double *const *f = a.f;
+    for (int s = 1; s <= 3; s++) {
+        hipLaunchKernelGGL(k_weno_flux3d<M>, grid, block, 0, h->stream, f[0], f[1], f[2], f[3], f[4], f[5], s == 1 ? a.u : a.ut, a.nx, a.ny, a.nz,
+                           s == 1 ? a.eu : a.ew, a.ew);
+        auto step = s == 1 ? k_weno_step3d<1> : s == 2 ? k_weno_step3d<2> : k_weno_step3d<3>;
+        hipLaunchKernelGGL(step, grid, block, 0, h->stream, a.u, a.ut, f[0], f[1], f[2], f[3], f[4], f[5], a.vx, a.vy, a.vz, a.nx, a.ny, a.nz, a.eu, a.ew, a.evx,
+                           a.evy, a.evz, a._dx, a._dy, a._dz, a.dt);
+    }
+    return JRX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -257,6 +452,59 @@ jrx_status jrx_weno5_advection2d(jrx_handle *h, double *u, const int64_t udim[2]
     } else {
         if (method == 1) JRX_TRY(launch_split<1>(h, u, ut, fL, fR, fB, fT, vx, vy, nx, ny, lu, lw, lvx, lvy, _dx, _dy, dt));
         else JRX_TRY(launch_split<2>(h, u, ut, fL, fR, fB, fT, vx, vy, nx, ny, lu, lw, lvx, lvy, _dx, _dy, dt));
+    }
+    JRX_LAUNCH_CHECK(h);
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_weno5_advection3d(jrx_handle *h, double *u, const int64_t udim[3], const double *vx, const int64_t vxdim[3], const double *vy,
+                                 const int64_t vydim[3], const double *vz, const int64_t vzdim[3], double *ut, double *fL, double *fR, double *fB, double *fT,
+                                 double *fD, double *fU, const int64_t wdim[3], double dx, double dy, double dz, double dt, int32_t method)
+{
+    if (!h) return JRX_ERR_ARG;
+    if (!u || !udim || !vx || !vxdim || !vy || !vydim || !vz || !vzdim || !ut || !fL || !wdim) return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: NULL argument");
+    if (!h->weno_fused && (!fR || !fB || !fT || !fD || !fU))
+        return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: the per-kernel form (weno_fused = 0) needs all of fL, fR, fB, fT, fD, fU");
+    if (method != 1 && method != 2) return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: method must be 1 (JS) or 2 (Z), got %d", (int)method);
+    if (udim[0] < 1 || udim[1] < 1 || udim[2] < 1)
+        return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: size(u) = (%lld, %lld, %lld)", (long long)udim[0], (long long)udim[1], (long long)udim[2]);
+    const int64_t *dims[5] = {udim, vxdim, vydim, vzdim, wdim};
+    const char *names[5] = {"u", "vx", "vy", "vz", "weno.ut / fL / fR / fB / fT / fD / fU"};
+    for (int a = 1; a < 5; a++)
+        for (int d = 0; d < 3; d++)
+            if (dims[a][d] < udim[d])
+                return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: %s is smaller than u along dimension %d (%lld < %lld)", names[a], d + 1, (long long)dims[a][d],
+                                (long long)udim[d]);
+    // no two arrays may overlap, except the read-only velocities among themselves (a NULL flux array of the fused form is skipped)
+    const void *p[11] = {u, vx, vy, vz, ut, fL, fR, fB, fT, fD, fU};
+    const int64_t *pd[11] = {udim, vxdim, vydim, vzdim, wdim, wdim, wdim, wdim, wdim, wdim, wdim};
+    const char *pn[11] = {"u", "vx", "vy", "vz", "ut", "fL", "fR", "fB", "fT", "fD", "fU"};
+    for (int a = 0; a < 11; a++) {
+        if ((double)pd[a][0] * (double)pd[a][1] * (double)pd[a][2] >= 2147483648.0)
+            return jrx_fail(h, JRX_ERR_UNSUPPORTED, "WENO_advection!: %s has 2^31 or more entries (32-bit offsets)", pn[a]);
+        if (!p[a]) continue;
+        for (int b = a + 1; b < 11; b++) {
+            if (!p[b] || (a >= 1 && b <= 3)) continue;
+            const char *pa = (const char *)p[a], *pb = (const char *)p[b];
+            if (pa < pb + 8 * pd[b][0] * pd[b][1] * pd[b][2] && pb < pa + 8 * pd[a][0] * pd[a][1] * pd[a][2])
+                return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: %s and %s overlap", pn[a], pn[b]);
+        }
+    }
+    JRX_TRY(jrx_check_device(h));
+    auto ext = [](const int64_t *d) { return WenoExt{(int)d[0], (int)(d[0] * d[1])}; };
+    Weno3Args a;
+    a.u = u; a.ut = ut; a.f[0] = fL; a.f[1] = fR; a.f[2] = fB; a.f[3] = fT; a.f[4] = fD; a.f[5] = fU;
+    a.vx = vx; a.vy = vy; a.vz = vz;
+    a.nx = (int)udim[0]; a.ny = (int)udim[1]; a.nz = (int)udim[2];
+    a.eu = ext(udim); a.ew = ext(wdim); a.evx = ext(vxdim); a.evy = ext(vydim); a.evz = ext(vzdim);
+    a._dx = 1.0 / dx; a._dy = 1.0 / dy; a._dz = 1.0 / dz; a.dt = dt;                // _di = inv.(di)
+    h->stat_weno3d_calls++;
+    if (h->weno_fused) {
+        h->stat_weno3d_fused++;
+        JRX_TRY(method == 1 ? launch_fused3d<1>(h, a) : launch_fused3d<2>(h, a));
+    } else {
+        JRX_TRY(method == 1 ? launch_split3d<1>(h, a) : launch_split3d<2>(h, a));
     }
     JRX_LAUNCH_CHECK(h);
     JRX_HIP(h, hipStreamSynchronize(h->stream));

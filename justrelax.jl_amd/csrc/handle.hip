@@ -119,7 +119,8 @@ int find_opt(jrx_handle *h, const char *key, bool tuning, OptRef *out)
         {"stat_fused3d", 2, &h->stat_fused3d}, {"stat_fused2d", 2, &h->stat_fused2d}, {"stat_fused2d_b", 2, &h->stat_fused2d_b}, {"stat_sweeps3d", 2, &h->stat_sweeps3d}, {"stat_thermal_fused", 2, &h->stat_thermal_fused},
         {"stat_vep3_fused", 2, &h->stat_vep3_fused}, {"stat_graph_replays", 2, &h->stat_graph_replays},
         {"stat_fused3d_visc", 2, &h->stat_fused3d_visc}, {"stat_fused3d_inkernel", 2, &h->stat_fused3d_inkernel}, {"stat_visc_checks", 2, &h->stat_visc_checks}, {"stat_visc_fallbacks", 2, &h->stat_visc_fallbacks}, {"stat_fused3d_nof1", 2, &h->stat_fused3d_nof1}, {"stat_fused3d_nof2", 2, &h->stat_fused3d_nof2},
-        {"stat_weno_calls", 2, &h->stat_weno_calls}, {"stat_weno_fused", 2, &h->stat_weno_fused}, {"stat_principal_calls", 2, &h->stat_principal_calls},
+        {"stat_weno_calls", 2, &h->stat_weno_calls}, {"stat_weno_fused", 2, &h->stat_weno_fused}, {"stat_weno3d_calls", 2, &h->stat_weno3d_calls}, {"stat_weno3d_fused", 2, &h->stat_weno3d_fused},
+        {"stat_principal_calls", 2, &h->stat_principal_calls},
         {"stat_dyrel_launches", 2, &h->stat_dyrel_launches},
     };
     const OptRef tun[] = {

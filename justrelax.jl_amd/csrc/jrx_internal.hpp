@@ -105,8 +105,9 @@ struct jrx_handle {
     bool vep3_map = true, vep3_xcd = true;   // 3D VEP edge kernel thread mapping / XCD slab order (A/B)
     bool scratch_sets = true;            // the fused pipelines may allocate their library-owned second state set (0: never -- un-fused paths)
     bool weno_fused = true;              // tuning: WENO_advection! as three fused launches (0: the reference's six, flux arrays in memory; bit-identical)
-    int weno_rows = 0;                   // tuning: rows a wave of the fused WENO kernel marches (0: by the grid, 64 .. 8)
+    int weno_rows = 0;                   // tuning: rows a wave of the fused WENO kernel marches (3D: planes a block marches); 0: by the grid, 64 .. 8
     int64_t stat_weno_calls = 0, stat_weno_fused = 0;   // jrx_weno5_advection2d calls / those that ran the fused form
+    int64_t stat_weno3d_calls = 0, stat_weno3d_fused = 0;   // the same for jrx_weno5_advection3d
     int64_t stat_principal_calls = 0;    // jrx_principal_stresses2d / 3d calls that launched
     int64_t stat_dyrel_launches = 0;     // kernels launched by the jrx_dyrel2d_* entry points (dyrel2d.hip)
     // ---- read-only counters (jrx_get_option "stat_*"): launches of the fused kernels since jrx_create, so that tests and the bench can
