@@ -333,9 +333,10 @@ def thermal_convection2d(n=32, *, ar=8, iterMax=150_000, nout=1000) -> Setup:
     aspect ratio `ar`, half-space-cooling temperature with a +10 % circular anomaly, a single MaterialParams with an Arrhenius
     CustomRheology (test_WENO5.jl:25-42, depth = 0) + elasticity (G = 70 GPa, ν = 0.5), PT_Density(ρ0 = 3100, α = 1.5e-5, β = 0),
     g = 9.81, lithostatic initial pressure, free slip.  This is the input of the single-phase solve! (Stokes2D.jl:345-557); the WENO
-    advection and the heat-diffusion step of the script are not part of it.  arrays["T"] is thermal.T (ghosted)."""
+    advection and the heat-diffusion step of the script are not part of it.  arrays["T"] is thermal.T (ghosted).  `n`: cells per dimension, a number (n x n)
+    or (nx, ny)."""
     from ..arrays import TemperatureBoundaryConditions
-    nx = ny = n
+    nx, ny = (n, n) if isinstance(n, int) else tuple(n)
     ly = 2890.0e3
     lx = ly * ar
     ni, li = (nx, ny), (lx, ly)

@@ -185,6 +185,7 @@ void orc_adiabatic_heating(double *A, const double *P, const double *P0, int64_t
 void orc_thermal_bcs2d(double *T, const orc_thermal_params2d *p);
 void orc_thermal2d_iteration(const orc_thermal2d *t, const orc_thermal_params2d *p);
 void orc_thermal2d_check_res(const orc_thermal2d *t, const orc_thermal_params2d *p);
+void orc_thermal2d_update_pt_arrays(const orc_thermal2d *t, const orc_thermal_params2d *p);      /* phase-ratio form: update_pt_thermal_arrays! alone */
 int32_t orc_heatdiffusion_PT2d(const orc_thermal2d *t, const orc_thermal_params2d *p,
                                int64_t *iter_out, double *norm_ResT, int64_t cap, int64_t *nnorms);
 
@@ -218,6 +219,7 @@ typedef struct orc_thermal_params3d {
 void orc_thermal_bcs3d(double *T, const orc_thermal_params3d *p);
 void orc_thermal3d_iteration(const orc_thermal3d *t, const orc_thermal_params3d *p);
 void orc_thermal3d_check_res(const orc_thermal3d *t, const orc_thermal_params3d *p);
+void orc_thermal3d_update_pt_arrays(const orc_thermal3d *t, const orc_thermal_params3d *p);
 int32_t orc_heatdiffusion_PT3d(const orc_thermal3d *t, const orc_thermal_params3d *p, int64_t *iter_out, double *norm_ResT, int64_t cap,
                                int64_t *nnorms);
 

@@ -733,6 +733,25 @@ def heatdiffusion_PT_phases(arr: dict, p, m: ThermalPhases, ph: dict) -> dict:
         lib().orc_thermal_set_phases(None, None)
 
 
+def thermal_phase_iteration(arr: dict, p, m: ThermalPhases, ph: dict, check_res=False):
+    """one iteration of the phase-ratio loop on its own: update_pt_thermal_arrays!, compute_flux!, update_T!, thermal_bcs! (DiffusionPT_solver.jl:233-260);
+    check_res = True: check_res! alone (no iteration).  2D or 3D by the type of p; the phases are set for this call only, so blocks with different arrays can take turns"""
+    three = isinstance(p, ThermalParams3D)
+    f = _phase_fields(ph)
+    p.rheology_form = 2
+    t = thermal3d(arr) if three else thermal2d(arr)
+    L = lib()
+    L.orc_thermal_set_phases(C.byref(m), C.byref(f))
+    try:
+        if check_res:
+            (L.orc_thermal3d_check_res if three else L.orc_thermal2d_check_res)(C.byref(t), C.byref(p))
+        else:
+            (L.orc_thermal3d_update_pt_arrays if three else L.orc_thermal2d_update_pt_arrays)(C.byref(t), C.byref(p))
+            (L.orc_thermal3d_iteration if three else L.orc_thermal2d_iteration)(C.byref(t), C.byref(p))
+    finally:
+        L.orc_thermal_set_phases(None, None)
+
+
 def adiabatic_heating(A, P, P0, m: "ThermalPhases", phase_c, _dt):
     """adiabatic_heating!(thermal, stokes, rheology, phases, _dt) -- DiffusionPT_kernels.jl:720-746; phase_c None: phase 0 alone"""
     lib().orc_adiabatic_heating(_p(A), _p(P), _p(P0), C.c_int64(A.size), C.byref(m), _p(phase_c), C.c_double(_dt))

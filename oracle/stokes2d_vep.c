@@ -559,12 +559,18 @@ int32_t orc_stokes2d_nonlinear_solve(const orc_vep2d *f, const orc_rheology *rh,
         orc_compute_strain_rate2d(&g, &q);
         visc_single(f, rh, p, p->viscosity_relaxation, 1);                            /* compute_viscosity_τII! :433-435 */
         orc_compute_maxloc2d(etatau, f->eta, nx, ny);                              /* :437-438 */
+        { const int64_t e[3] = {nx, ny, 1}; orc_self_halo(etatau, e, e); }         /* update_halo!(ητ) :440 (the one at :417 follows a compute_maxloc! that :439 repeats) */
         orc_compute_tau_nonlinear2d(f, theta, lam, rh, p, 0);                      /* :440-458 */
         orc_center2vertex2d(f->txy, f->txy_c, nx, ny);                             /* :459 */
+        { const int64_t e[3] = {nx + 1, ny + 1, 1}, nn[3] = {nx, ny, 1}; orc_self_halo(f->txy, e, nn); }    /* update_halo!(stokes.τ.xy) :460 */
         orc_compute_V2d_fs(&g, etatau, &q, fs_dt);                                 /* :463-474 */
         orc_velocity2displacement2d(&g, &q);
         if (p->displacement_bcs) orc_flow_bcs2d(f->Ux, f->Uy, nx, ny, p->free_slip, p->no_slip, p->periodic);
         else orc_flow_bcs2d(f->Vx, f->Vy, nx, ny, p->free_slip, p->no_slip, p->periodic);
+        {   /* update_halo!(@velocity(stokes)...) :477 */
+            const int64_t nn[3] = {nx, ny, 1}, ex[3] = {nx + 1, ny + 2, 1}, ey[3] = {nx + 2, ny + 1, 1};
+            orc_self_halo(f->Vx, ex, nn); orc_self_halo(f->Vy, ey, nn);
+        }
         iter += 1;
         if (iter % p->nout == 0 && iter > 1) {
             orc_compute_Res2d_fs(&g, &q, fs_dt);

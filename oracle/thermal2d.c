@@ -161,6 +161,18 @@ void orc_thermal2d_check_res(const orc_thermal2d *t, const orc_thermal_params2d 
         }
 }
 
+/* update_pt_thermal_arrays!(pt_thermal, phase, rheology, args, _dt)  DiffusionPT_solver.jl:233-234 ; T at Idx .+ 1 (phase-ratio form: orc_thermal_set_phases first) */
+void orc_thermal2d_update_pt_arrays(const orc_thermal2d *t, const orc_thermal_params2d *p)
+{
+    const int64_t nx = p->nx, ny = p->ny;
+    for (int64_t j = 0; j < ny; j++)
+        for (int64_t i = 0; i < nx; i++) {
+            const size_t c = IDX2(nx, i, j);
+            tph_pt_coeffs(g_tph, g_tpf->phase_c + g_tph->nphase * c, t->T[IDX2(nx + 2, i + 1, j + 1)], g_tpf->P[c], inv(p->dt),
+                          &t->thetar_dtau[c], &t->dtau_rho[c]);
+        }
+}
+
 /* DiffusionPT_solver.jl:34-149 / :181-305 */
 int32_t orc_heatdiffusion_PT2d(const orc_thermal2d *t, const orc_thermal_params2d *p,
                                int64_t *iter_out, double *norm_ResT, int64_t cap, int64_t *nnorms)
@@ -172,13 +184,7 @@ int32_t orc_heatdiffusion_PT2d(const orc_thermal2d *t, const orc_thermal_params2
     int64_t iter = 0, cnt = 0;
     double err = 2 * p->eps;
     while (err > p->eps && iter < p->iterMax) {
-        if (p->rheology_form == 2)      /* update_pt_thermal_arrays!(pt_thermal, phase, rheology, args, _dt) :233-234 ; T at Idx .+ 1 */
-            for (int64_t j = 0; j < ny; j++)
-                for (int64_t i = 0; i < nx; i++) {
-                    const size_t c = IDX2(nx, i, j);
-                    tph_pt_coeffs(g_tph, g_tpf->phase_c + g_tph->nphase * c, t->T[IDX2(nx + 2, i + 1, j + 1)], g_tpf->P[c], inv(p->dt),
-                                  &t->thetar_dtau[c], &t->dtau_rho[c]);
-                }
+        if (p->rheology_form == 2) orc_thermal2d_update_pt_arrays(t, p);
         orc_thermal2d_iteration(t, p);
         iter += 1;
         if (iter % p->nout == 0) {

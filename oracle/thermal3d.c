@@ -152,6 +152,19 @@ void orc_thermal3d_check_res(const orc_thermal3d *t, const orc_thermal_params3d 
             }
 }
 
+/* update_pt_thermal_arrays! (DiffusionPT_solver.jl:233-234) of the phase-ratio form (orc_thermal_set_phases first) */
+void orc_thermal3d_update_pt_arrays(const orc_thermal3d *t, const orc_thermal_params3d *p)
+{
+    const int64_t nx = p->nx, ny = p->ny, nz = p->nz;
+    for (int64_t k = 0; k < nz; k++)
+        for (int64_t j = 0; j < ny; j++)
+            for (int64_t i = 0; i < nx; i++) {
+                const size_t c = IDX3(nx, ny, i, j, k);
+                tph_pt_coeffs(g_tph, g_tpf->phase_c + g_tph->nphase * c, t->T[IDX3(nx + 2, ny + 2, i + 1, j + 1, k + 1)], g_tpf->P[c], inv(p->dt),
+                              &t->thetar_dtau[c], &t->dtau_rho[c]);
+            }
+}
+
 int32_t orc_heatdiffusion_PT3d(const orc_thermal3d *t, const orc_thermal_params3d *p, int64_t *iter_out, double *norm_ResT, int64_t cap,
                                int64_t *nnorms)
 {
@@ -162,14 +175,7 @@ int32_t orc_heatdiffusion_PT3d(const orc_thermal3d *t, const orc_thermal_params3
     int64_t iter = 0, cnt = 0;
     double err = 2 * p->eps;
     while (err > p->eps && iter < p->iterMax) {
-        if (p->rheology_form == 2)      /* update_pt_thermal_arrays! (DiffusionPT_solver.jl:233-234) */
-            for (int64_t k = 0; k < nz; k++)
-                for (int64_t j = 0; j < ny; j++)
-                    for (int64_t i = 0; i < nx; i++) {
-                        const size_t c = IDX3(nx, ny, i, j, k);
-                        tph_pt_coeffs(g_tph, g_tpf->phase_c + g_tph->nphase * c, t->T[IDX3(nx + 2, ny + 2, i + 1, j + 1, k + 1)], g_tpf->P[c], inv(p->dt),
-                                      &t->thetar_dtau[c], &t->dtau_rho[c]);
-                    }
+        if (p->rheology_form == 2) orc_thermal3d_update_pt_arrays(t, p);
         orc_thermal3d_iteration(t, p);
         iter += 1;
         if (iter % p->nout == 0) {

@@ -1,5 +1,5 @@
-"""Host-side helpers of the two-block (N > 1) tests: cut the blocks of an ImplicitGlobalGrid decomposition out of global arrays and
-replay update_halo! between them in numpy.
+"""Host-side helpers of the two-block (N > 1) tests: cut the blocks of an ImplicitGlobalGrid decomposition out of global arrays,
+replay update_halo! between them in numpy, and (TwoBlocks) join handles of this process into an in-process group of ranks.
 
 Semantics restated from the reference's call sites (src/stokes/Stokes3D.jl:57,117-120; src/grid/Utils.jl:26-39) and SURVEY §5: local
 blocks of n cells overlap their neighbours by 2 cells, rank offset coords * (n - 2); an array of extent nA exchanges the planes
@@ -54,10 +54,33 @@ def owned_mask(shape, n, cart, name=None):
     """entries of a local array that are not duplicates of a neighbour's interior: everything except the outermost plane on a face
     with a neighbour (those planes are received, or are the overlap copy the neighbour computes with a full stencil)"""
     m = np.ones(shape, dtype=bool)
-    for d in range(3):
+    for d in range(len(shape)):
         for side in (0, 1):
             if cart.neighbor[d][side] >= 0:
-                idx = [slice(None)] * 3
+                idx = [slice(None)] * len(shape)
                 idx[d] = 0 if side == 0 else shape[d] - 1
                 m[tuple(idx)] = False
     return m
+
+
+class TwoBlocks:
+    """prod(dims) handles on the current device joined into an in-process group of ranks, one per block of the `dims` decomposition (jrx_comm_init_local); drive them with halo.run_ranks"""
+
+    def __init__(self, n, dims, periods=(0, 0, 0)):
+        import torch
+        from justrelax_jl_amd import _lib, halo
+        self.n, self.dims, self.periods = tuple(n), tuple(dims), tuple(periods)
+        self.carts = halo.make_carts(n, dims, periods)
+        self.handles = [_lib.Handle(torch.cuda.current_device()) for _ in range(len(self.carts))]
+        halo.init_comm_local(self.handles, self.carts)
+        self.ng = n_global(n, dims, periods)
+
+    def close(self):
+        for h in self.handles:
+            h.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

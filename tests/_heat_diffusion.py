@@ -19,7 +19,12 @@ builder of their inputs.  Arrays are (nx, ny[, nz]) with x first, as in Julia; T
                   thermal_bcs!; iter += 1; every nout: check_res!, err = norm(ResT) / sqrt(length(ResT)), recorded with iter; at the end update_ΔT!
   PTThermalCoeffs src/thermal_diffusion/DiffusionPT_coefficients.jl:17-26   (taken from the project's own evaluation: an input of the loop here, not restated)
 
-Not restated: the phase-ratio form, adiabatic heating, Dirichlet masks, non-uniform spacing.
+  optional terms  f["adiabatic"] (rheology form only, :553-601, :631-668): + adiabatic T inside the bracket of update_T! (T before the update) and in check_res!;
+                  f["dirichlet_mask"] (the shape of T; with f["dirichlet_value"], an array, or f["dirichlet_const"], a 0-d array): a cell whose mask is not zero takes
+                  (1 - m) T + m value (apply_mask!, src/mask/mask.jl:49-50) instead of the update and has ResT = 0 (isNotDirichlet, :1-2, :619)
+  N > 1           heatdiffusion_PT_blocks: the same loop on the blocks of an ImplicitGlobalGrid decomposition, update_halo!(thermal.T) after thermal_bcs! (:110)
+
+Not restated: the phase-ratio form, non-uniform spacing.
 
 The field names are those of the oracle's dictionaries: T, Told, dT, qTx, qTy[, qTz], qTx2, ..., H, shear_heating, ResT, K, rhoCp, thetar_dtau, dtau_rho.
 """
@@ -112,17 +117,45 @@ def _div(f, _di, suffix):
     return out
 
 
+def _adiabatic(f, rheology):
+    """thermal.adiabatic enters the rheology forms only"""
+    return f.get("adiabatic") if rheology is not None else None
+
+
+def _dirichlet(f):
+    """(mask on the cells, value on the cells) or (None, None)"""
+    m = f.get("dirichlet_mask")
+    if m is None:
+        return None, None
+    inner = (slice(1, -1),) * m.ndim
+    v = f["dirichlet_value"][inner] if f.get("dirichlet_value") is not None else m.dtype.type(f["dirichlet_const"])
+    return m[inner], v
+
+
 def update_T(f, _di, _dt, rheology=None):
     T = f["T"]
     inner = (slice(1, -1),) * T.ndim
     one = T.dtype.type(1)
     ρCp, dτ_ρ, Tc = _rhoCp(f, rheology), f["dtau_rho"], T[inner].copy()
-    T[inner] = (dτ_ρ * (-_div(f, _di, "") + f["Told"][inner] * ρCp * _dt + f["H"] + f["shear_heating"]) + Tc) / (one + dτ_ρ * ρCp * _dt)
+    src = -_div(f, _di, "") + f["Told"][inner] * ρCp * _dt + f["H"] + f["shear_heating"]
+    if _adiabatic(f, rheology) is not None:
+        src = src + f["adiabatic"] * Tc
+    Tn = (dτ_ρ * src + Tc) / (one + dτ_ρ * ρCp * _dt)
+    m, v = _dirichlet(f)
+    if m is not None:
+        Tn = np.where(m != 0, (one - m) * Tc + m * v, Tn)
+    T[inner] = Tn
 
 
 def check_res(f, _di, _dt, rheology=None):
     inner = (slice(1, -1),) * f["T"].ndim
-    f["ResT"][...] = -_rhoCp(f, rheology) * (f["T"][inner] - f["Told"][inner]) * _dt - _div(f, _di, "2") + f["H"] + f["shear_heating"]
+    res = -_rhoCp(f, rheology) * (f["T"][inner] - f["Told"][inner]) * _dt - _div(f, _di, "2") + f["H"] + f["shear_heating"]
+    if _adiabatic(f, rheology) is not None:
+        res = res + f["adiabatic"] * f["T"][inner]
+    m, _ = _dirichlet(f)
+    if m is not None:
+        res = np.where(m != 0, f["T"].dtype.type(0), res)
+    f["ResT"][...] = res
 
 
 def res_term_scale(f, _di, dt, rheology=None):
@@ -130,6 +163,8 @@ def res_term_scale(f, _di, dt, rheology=None):
     inner = (slice(1, -1),) * f["T"].ndim
     _dt = 1 / f["T"].dtype.type(dt)
     terms = (_rhoCp(f, rheology) * (f["T"][inner] - f["Told"][inner]) * _dt, _div(f, _di, "2"), f["H"], f["shear_heating"])
+    if _adiabatic(f, rheology) is not None:
+        terms += (f["adiabatic"] * f["T"][inner],)
     return float(max(np.abs(t).max() for t in terms))
 
 
@@ -153,6 +188,54 @@ def heatdiffusion_PT(f, bc, _di, dt, *, iterMax, nout, eps=0.0, rheology=None):
             iter_count.append(it)
     f["dT"][...] = T - f["Told"]
     return dict(iter_count=np.array(iter_count, dtype=np.int64), norm_ResT=np.array(norm_ResT, dtype=T.dtype))
+
+
+def heatdiffusion_PT_blocks(fs, bc, _di, dt, n, carts, L, *, iterMax, nout, eps=0.0, rheology=None, stop="max"):
+    """the PT loop on the blocks fs[r] (one dictionary per rank, every rank with the same bc: the reference applies thermal_bcs! and the constant-flux faces on every
+    face of the local array, and update_halo!(thermal.T) then replaces the ghost planes that have a neighbour, DiffusionPT_solver.jl:104-111).  n: cells of a
+    local block, carts: jrx_cart of every rank, L: the library (jrx_halo_planes names the planes; a rank that is its own periodic neighbour copies from itself).
+    stop = "local": every rank tests its own norm, as the reference does (:131, no reduction) -- a rank that has left neither computes nor receives any more,
+    the others go on with the planes it left behind (an MPI run would wait for it for ever); stop = "max": every rank tests the maximum of the local norms,
+    so all leave together, and still records its own.  Returns one dict(iter_count, norm_ResT, iterations) per rank."""
+    import _blocks
+    nr = len(fs)
+    dtype = fs[0]["T"].dtype.type
+    _dt = 1 / dtype(dt)
+    _sq = 1 / np.sqrt(dtype(fs[0]["ResT"].size))
+    for f in fs:
+        f["Told"][...] = f["T"]
+    err = [2 * eps if eps > 0 else np.inf] * nr          # what each rank's loop test sees
+    it, done = 0, [0] * nr
+    iter_count, norm_ResT = [[] for _ in range(nr)], [[] for _ in range(nr)]
+    while it < iterMax and any(e > eps for e in err):
+        active = [e > eps for e in err]
+        for r in range(nr):
+            if active[r]:
+                compute_flux(fs[r], _di, bc, rheology)
+                update_T(fs[r], _di, _dt, rheology)
+                thermal_bcs(fs[r]["T"], bc)
+        left = {r: fs[r]["T"].copy() for r in range(nr) if not active[r]}
+        _blocks.exchange([[f["T"]] for f in fs], n, carts, L)
+        for r, T in left.items():
+            fs[r]["T"][...] = T
+        it += 1
+        for r in range(nr):
+            if active[r]:
+                done[r] = it
+        if it % nout == 0:
+            for r in range(nr):
+                if active[r]:
+                    check_res(fs[r], _di, _dt, rheology)
+                    err[r] = np.sqrt((fs[r]["ResT"] * fs[r]["ResT"]).sum()) * _sq
+                    norm_ResT[r].append(err[r])
+                    iter_count[r].append(it)
+            if stop == "max":
+                err = [max(err)] * nr
+            else:
+                assert stop == "local", stop
+    for f in fs:
+        f["dT"][...] = f["T"] - f["Told"]
+    return [dict(iter_count=np.array(iter_count[r], dtype=np.int64), norm_ResT=np.array(norm_ResT[r], dtype=fs[r]["T"].dtype), iterations=done[r]) for r in range(nr)]
 
 
 def as_dtype(arrays, dtype):
@@ -204,6 +287,30 @@ def boundary_conditions(nd, name, _di):
         elif kind == "F":
             bc.constant_flux[f] = FLUX_FRACTION[f] * 3.5 * 300.0 * _di[AXIS[nd][f][0]]
     return bc
+
+
+def converging_bcs(nd):
+    """no flux on the side faces, constant values on top and bot: without a constant-flux face (which keeps the qT*2 it holds) the residual of the loop goes to zero"""
+    bc = SimpleNamespace(**{k: {f: False for f in FACES[nd]} for k in ("no_flux", "constant_value", "constant_flux", "periodic")})
+    for f in FACES[nd]:
+        if f in ("top", "bot"):
+            bc.constant_value[f] = VALUES[f]
+        else:
+            bc.no_flux[f] = True
+    return bc
+
+
+def eps_between(a, b, start=1):
+    """(ϵ, first check with min <= ϵ, first check with max <= ϵ), 0-based: ϵ half-way between the two ranks' norms at the first check from `start` on where they differ;
+    asserts that the lower norm gets under ϵ strictly before the higher one does, which is what makes ϵ tell the two stop rules apart"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    k = next(i for i in range(start, len(a)) if a[i] != b[i])
+    eps = float(0.5 * (a[k] + b[k]))
+    lo, hi = np.minimum(a, b), np.maximum(a, b)
+    assert (lo <= eps).any() and (hi <= eps).any(), (eps, list(lo), list(hi))
+    first_min, first_max = int(np.argmax(lo <= eps)), int(np.argmax(hi <= eps))
+    assert first_min < first_max, (eps, first_min, first_max)
+    return eps, first_min, first_max
 
 
 def make_inputs(ni, bc_name, seed):
@@ -265,6 +372,20 @@ def compared_fields(nd):
     return ("T", "Told", "dT", "ResT") + QNAMES[:nd] + tuple(q + "2" for q in QNAMES[:nd])
 
 
+def _yardstick_of(fl, rl, fd, rd, _di, dt, rheo):
+    """the rule in one place: per field the scale (maximum in the longdouble run; ResT: at least its largest term) and the bound TOL_FACTOR x the distance of the float64
+    run from the longdouble one, at least TOL_FLOOR, at most TOL_ITERS; the norm history relative to itself"""
+    scale, bound = {}, {}
+    for k in compared_fields(fl["T"].ndim):
+        scale[k] = float(np.abs(fl[k]).max())
+        if k == "ResT":
+            scale[k] = max(scale[k], res_term_scale(fl, _di, dt, rheo))
+        bound[k] = min(max(TOL_FACTOR * float(np.abs(fd[k] - fl[k]).max()) / scale[k], TOL_FLOOR), TOL_ITERS)
+    d = float(np.abs((rd["norm_ResT"] - rl["norm_ResT"]) / rl["norm_ResT"]).max()) if len(rl["norm_ResT"]) else 0.0
+    bound["norm_ResT"] = min(max(TOL_FACTOR * d, TOL_FLOOR), TOL_ITERS)
+    return SimpleNamespace(fields=fl, result=rl, scale=scale, bound=bound, float64=fd)
+
+
 def yardstick(inp, form, iterMax, nout):
     """the longdouble restatement of a case, the scale of every compared field and its bound: TOL_FACTOR x the distance of the float64 restatement from the
     longdouble one, at least TOL_FLOOR, at most TOL_ITERS -- from the reference's formulas alone"""
@@ -272,15 +393,19 @@ def yardstick(inp, form, iterMax, nout):
     fl, rl = restate(inp, form, iterMax, nout, np.longdouble)
     fd, rd = restate(inp, form, iterMax, nout, np.float64)
     assert list(rl["iter_count"]) == list(rd["iter_count"]) == list(range(nout, iterMax + 1, nout))
-    scale, bound = {}, {}
-    for k in compared_fields(len(inp.ni)):
-        scale[k] = float(np.abs(fl[k]).max())
-        if k == "ResT":
-            scale[k] = max(scale[k], res_term_scale(fl, inp._di, inp.dt, rheo))
-        bound[k] = min(max(TOL_FACTOR * float(np.abs(fd[k] - fl[k]).max()) / scale[k], TOL_FLOOR), TOL_ITERS)
-    d = float(np.abs((rd["norm_ResT"] - rl["norm_ResT"]) / rl["norm_ResT"]).max()) if len(rl["norm_ResT"]) else 0.0
-    bound["norm_ResT"] = min(max(TOL_FACTOR * d, TOL_FLOOR), TOL_ITERS)
-    return SimpleNamespace(fields=fl, result=rl, scale=scale, bound=bound)
+    return _yardstick_of(fl, rl, fd, rd, inp._di, inp.dt, rheo)
+
+
+def yardstick_blocks(blocks, bc, _di, dt, n, carts, L, form, iterMax, nout):
+    """yardstick for every block of a decomposed case: blocks[r] = that rank's input dictionary (float64); the same rule, block by block, against
+    heatdiffusion_PT_blocks in longdouble.  The result of rank r works with ratios_to_bound like the one of yardstick."""
+    rheo = RHEOLOGY if form == "rheology" else None
+    fl, fd = [as_dtype(b, np.longdouble) for b in blocks], [as_dtype(b, np.float64) for b in blocks]
+    rl = heatdiffusion_PT_blocks(fl, bc, _di, dt, n, carts, L, iterMax=iterMax, nout=nout, rheology=rheo)
+    rd = heatdiffusion_PT_blocks(fd, bc, _di, dt, n, carts, L, iterMax=iterMax, nout=nout, rheology=rheo)
+    for r in range(len(blocks)):
+        assert list(rl[r]["iter_count"]) == list(rd[r]["iter_count"]) == list(range(nout, iterMax + 1, nout))
+    return [_yardstick_of(fl[r], rl[r], fd[r], rd[r], _di, dt, rheo) for r in range(len(blocks))]
 
 
 def ratios_to_bound(got, result, y):

@@ -50,27 +50,7 @@ def _get(h, key):
     return v.value
 
 
-class TwoBlocks:
-    """prod(dims) handles on the current device joined into an in-process group (two ranks in most tests, 2 x 2 x 2 in the last ones)"""
-
-    def __init__(self, n, dims, periods=(0, 0, 0)):
-        import torch
-        from justrelax_jl_amd import _lib, halo
-        self.n, self.dims, self.periods = tuple(n), tuple(dims), tuple(periods)
-        self.carts = halo.make_carts(n, dims, periods)
-        self.handles = [_lib.Handle(torch.cuda.current_device()) for _ in range(len(self.carts))]
-        halo.init_comm_local(self.handles, self.carts)
-        self.ng = B.n_global(n, dims, periods)
-
-    def close(self):
-        for h in self.handles:
-            h.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+TwoBlocks = B.TwoBlocks
 
 
 def _global_setup(jr, ng, uniform, iterMax, nout, seed=5, bcs="free_slip", dt=0.25):
