@@ -594,6 +594,42 @@ def cfg_shearband3d(jr, h, n=256, iters=60):
             "needed_bytes_per_cell": 736.0, "frac_at_needed_bytes": 736.0 * n ** 3 * r.iter / el / 1e9 / 8000.0}
 
 
+def cfg_variational3d(jr, h, n=128, iters=200, air_layers=2):
+    """3D variational Stokes (variational_stokes/Stokes3D.jl) on the 3D shear band under `air_layers` layers of sticky air, against the unmasked 3D multiphase solve! on
+    the same inputs without the air, in this process.  Array passes of one iteration, every array once per kernel: the masked driver stores every output every
+    iteration -- pre 10 reads + 11 writes, stress 30 + 4 x 3 phase-ratio reads + 21 writes, velocity 18 reads + 6 writes = 108; the unmasked driver 92 (cfg_shearband3d)."""
+    import torch
+    from justrelax_jl_amd.arrays import from_numpy
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = {"workload": f"shear band {n}^3, {air_layers} air layers (3D variational Stokes) vs the unmasked 3D multiphase solve!", "passes_variational": 108, "passes_unmasked": 92}
+    members = dict(center="phase_c", vertex="phase_v", Vx="phase_vx", Vy="phase_vy", Vz="phase_vz", yz="phase_yz", xz="phase_xz", xy="phase_xy")
+    for kind, layers in (("unmasked", 0), ("variational", air_layers)):
+        s = jr.miniapps.shearband3d_variational(n, layers, iterMax=iters - 1, nout=10 ** 9)
+        s.pt.ϵ_rel = s.pt.ϵ_abs = 1e-300
+        st = jr.StokesArrays(jr.AMDGPUBackend, s.ni)
+        for k, t in dict(Vx=st.V.Vx, Vy=st.V.Vy, Vz=st.V.Vz, eta=st.viscosity.η).items():
+            t.copy_(from_numpy(s.arrays[k], dev))
+        pr = jr.PhaseRatios(jr.AMDGPUBackend, s.arrays["phase_c"].shape[0], s.ni)
+        for name, k in members.items():
+            getattr(pr, name).copy_(from_numpy(s.arrays[k], dev))
+        ρg = tuple(jr.fzeros(st._ni, dev) for _ in range(3))
+        kw = {k: v for k, v in s.kwargs.items() if k != "air_phase"}
+        if kind == "unmasked":
+            run = lambda k: jr.solve_(st, s.pt, s.grid, s.flow_bcs, ρg, pr, s.extra["phases"], None, s.dt, None, kwargs=dict(kw, iterMax=k - 1, verbose=False), handle=h)
+        else:
+            ϕ = jr.RockRatio(jr.AMDGPUBackend, s.ni)
+            jr.update_rock_ratio_(ϕ, pr, s.kwargs["air_phase"], handle=h)
+            run = lambda k: jr.solve_VariationalStokes_(st, s.pt, s.grid, s.flow_bcs, ρg, pr, ϕ, s.extra["phases"], None, s.dt, None,
+                                                        kwargs=dict(s.kwargs, iterMax=k - 1, verbose=False), handle=h)
+        el, r = _timed(run, 5, iters)
+        out[f"it_per_s_{kind}"] = r.iter / el
+        out[f"iterations_{kind}"] = int(r.iter)
+        del st, pr, ρg, s
+    out["ratio_variational_over_unmasked"] = out["it_per_s_variational"] / out["it_per_s_unmasked"]
+    out["ratio_predicted_by_passes"] = 92.0 / 108.0
+    return out
+
+
 def cfg_thermal3d(jr, h, n=256, iters=400):
     """3D PT heat diffusion, array-coefficient form (DiffusionPT_solver.jl:34-149); 22 passes = 176 B/cell-iteration as the reference's two kernels move
     them (flux: R T, K, θ, q(3) W q(3), q2(3); update: R q(3), Told, ρCp, dτ_ρ, H, SH, T W T)."""
@@ -848,7 +884,7 @@ def other_configs(jr, h):
     for key, fn in (("multi_rank_path", lambda: cfg_multi_rank_path(jr)),
                     ("solvi3d_256", lambda: cfg_solvi(jr, h, 256, 200, 20)), ("solcx_512", lambda: cfg_solcx(jr, h)),
                     ("shearband_1024", lambda: cfg_shearband(jr, h)), ("thermal2d_256", lambda: cfg_thermal2d(jr, h)),
-                    ("shearband3d_256", lambda: cfg_shearband3d(jr, h)), ("thermal3d_256", lambda: cfg_thermal3d(jr, h)),
+                    ("shearband3d_256", lambda: cfg_shearband3d(jr, h)), ("variational3d_128", lambda: cfg_variational3d(jr, h)), ("thermal3d_256", lambda: cfg_thermal3d(jr, h)),
                     ("thermal3d_phases_256", lambda: cfg_thermal3d_phases(jr, h))):
         try:
             grid.finalize_global_grid()

@@ -501,6 +501,48 @@ jrx_status jrx_vep3d_compute_viscosity_tauII(jrx_handle *h, const jrx_vep3d_fiel
 jrx_status jrx_tensor_invariant3d(jrx_handle *h, double *II, const double *xx, const double *yy, const double *zz, const double *yz,
                                   const double *xz, const double *xy, int64_t nx, int64_t ny, int64_t nz);
 
+/* ------------------------------------------------------------------ 3D variational Stokes (the 2D section above, one dimension up; it follows the 3D
+ * multiphase structs it takes)
+ * solve_VariationalStokes!(stokes, pt_stokes, grid::Geometry{3}, flow_bcs, ρg, phase_ratios, ϕ::RockRatio, rheology, args, dt, igg; air_phase, kwargs)
+ * -- src/variational_stokes/Stokes3D.jl:14-238: the 3D multiphase driver with the rock ratio ϕ on ∇V, the strain rates, the stress update and
+ * the velocity update (variational_stokes/VelocityKernels.jl:6-12,96-154, StressKernels.jl:173-508, mask.jl:180-186,220-269,324-392) and the
+ * air_phase correction of the viscosity (rheology/Viscosity.jl:638-650).  Unlike the 2D driver: no iterMin (`while iter < 2 || (... && iter <= iterMax)`),
+ * norms over ALL nodes -- norm_Ri = ‖Ri[2:end-1, 2:end-1, 2:end-1]‖ / sqrt((nx_g-1)(ny_g-1)(nz_g-1)), norm_∇V = ‖RP‖ / length(RP) (:175-181) --, relλ the
+ * literal 0.2 (:137; p->lambda_relaxation is not read), no free-surface stabilisation.
+ * The momentum kernel is NOT the reference's text: its masked 3D compute_V! (VelocityKernels.jl:408-487) calls _av_x / _av_y / _av_z(A, ϕ, ...) that nothing
+ * defines, its masked d_xi / d_yi / d_zi resolve to the N-dimensional forms of MiniKernels.jl:20-27, which in 3D difference across two planes, and they read
+ * τxy[..., k+1] at k = nz; no test or miniapp of the reference calls it.  Built instead: the working masked 2D kernel (:355-399) one dimension up, on the
+ * index triples of the unmasked 3D kernel (src/stokes/VelocityKernels.jl:215-238) -- at a valid Vx node (isvalid_vx(ϕ, i+1, j, k), (i, j, k) <= size(Rx))
+ *   Rx[i,j,k] = ((τxx ϕc)[i+1,j,k] - (τxx ϕc)[i,j,k]) _dx + ((τxy ϕxy)[i+1,j+1,k] - (τxy ϕxy)[i+1,j,k]) _dy + ((τxz ϕxz)[i+1,j,k+1] - (τxz ϕxz)[i+1,j,k]) _dz
+ *               - ((P ϕc)[i+1,j,k] - (P ϕc)[i,j,k]) _dx - 0.5 ((fx ϕc)[i,j,k] + (fx ϕc)[i+1,j,k]),     Vx[i+1,j+1,k+1] += Rx[i,j,k] ηdτ / av_x(ητ)   (ητ unmasked)
+ * and Rx = Vx = 0 at an invalid one; y and z alike with isvalid_vy(ϕ, i, j+1, k), isvalid_vz(ϕ, i, j, k+1).
+ * Built: 3D, one block, uniform spacing.  Status JRX_ERR_ARG, with a text that names it, for: inverse spacings that are not positive finite scalars (how the
+ * binding hands over a non-uniform Geometry, for which this struct has no arrays), a handle with a communicator, a DruckerPragerCap phase (is_pl = 2), an
+ * air_phase outside 0..nphase, fewer than 3 cells in a dimension.
+ * ϕ (variational_stokes/mask.jl:1-42): center ni, vertex ni .+ 1, Vx (nx+1, ny, nz), Vy (nx, ny+1, nz), Vz (nx, ny, nz+1), yz (nx, ny+1, nz+1),
+ * xz (nx+1, ny, nz+1), xy (nx+1, ny+1, nz) -- no ghost nodes. */
+typedef struct jrx_rock_ratio3d {
+    const double *center, *vertex, *Vx, *Vy, *Vz, *yz, *xz, *xy;
+} jrx_rock_ratio3d;
+/* _solve_VS! (variational_stokes/Stokes3D.jl:14-238).  air_phase: 1-based index of the air phase, 0 = none. */
+jrx_status jrx_stokes3d_vs_solve(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_rock_ratio3d *phi, const jrx_rheology *rh,
+                                 const jrx_vep3d_params *p, int32_t air_phase, jrx_solve_result *res);
+/* masked compute_∇V! + compute_strain_rate! 3D alone (variational_stokes/VelocityKernels.jl:6-12,96-154): ∇V is zero at an invalid centre; the six
+ * strain rates are written at valid nodes only and keep their values elsewhere (the reference's kernel does not zero them) -- for parity tests */
+jrx_status jrx_vs3d_strain_rates(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_rock_ratio3d *phi, const jrx_vep3d_params *p);
+/* masked update_stresses_center_vertex! 3D alone (variational_stokes/StressKernels.jl:173-508; θ, λ of extent ni; λv = {yz, xz, xy} edge arrays), relλ = 0.2.
+ * An invalid edge zeroes its τ alone; an invalid centre zeroes Pr_c = f->P, η_vep, ε_vol_pl, the six τ centre arrays and the six entries of
+ * @plastic_strain -- the shear ones are the EDGE arrays at the centre's own index -- and leaves τ.II.  Every update reads the stresses of the previous
+ * call, as jrx_vep3d_update_stresses -- for parity tests */
+jrx_status jrx_vs3d_update_stresses(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_rock_ratio3d *phi, const double *theta, double *lambda,
+                                    double *const lambda_v[3], const jrx_rheology *rh, const jrx_vep3d_params *p);
+/* the masked momentum kernel alone (replaces variational_stokes/VelocityKernels.jl:408-487 in the form stated above): V, Rx, Ry, Rz; etatau is ητ (ni) -- for parity tests */
+jrx_status jrx_vs3d_compute_V(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_rock_ratio3d *phi, const double *etatau, const jrx_vep3d_params *p);
+/* compute_viscosity! (tauII = 0) / update_viscosity_τII! (tauII != 0) 3D with the air_phase keyword (rheology/Viscosity.jl:455-503): the ratios of a cell go
+ * through correct_phase_ratio (:638-650) first.  air_phase = 0: the arithmetic of jrx_vep3d_compute_viscosity / _tauII, bit for bit. */
+jrx_status jrx_vep3d_compute_viscosity_air(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_rheology *rh, const jrx_vep3d_params *p, double nu,
+                                           int32_t air_phase, int32_t tauII);
+
 /* ------------------------------------------------------------------ 2D PT heat diffusion */
 typedef struct jrx_thermal2d_fields {
     double *T, *Told, *dT;                 /* (nx+2, ny+2): thermal.T, Told, ΔT */

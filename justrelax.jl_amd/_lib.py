@@ -99,6 +99,7 @@ VEP_NAMES = ["P", "P0", "divV", "Q", "Vx", "Vy", "Ux", "Uy", "exx", "eyy", "exy"
              "EII_pl", "evol_pl", "EVol_pl", "fx", "fy", "RP", "Rx", "Ry", "omega_xy", "phase_c", "phase_v", "T", "dexx", "deyy", "divU"]
 VEP2DFields = _ptr_struct("VEP2DFields", VEP_NAMES)
 RockRatio2D = _ptr_struct("RockRatio2D", ["center", "vertex", "Vx", "Vy"])      # jrx_rock_ratio2d
+RockRatio3D = _ptr_struct("RockRatio3D", ["center", "vertex", "Vx", "Vy", "Vz", "yz", "xz", "xy"])      # jrx_rock_ratio3d
 MAXPHASE = 8
 DYREL_NAMES = ["gamma_eff", "etab", "P_num", "Dx", "Dy", "lmaxVx", "lmaxVy", "dVxdtau", "dVydtau", "dtauVx", "dtauVy", "dVx", "dVy", "betaVx", "betaVy",
                "cVx", "cVy", "alphaVx", "alphaVy", "Rx0", "Ry0", "txx_v", "tyy_v", "toxx_v", "toyy_v", "lambda", "lambda_v", "dPpsi", "dT", "melt_fraction"]

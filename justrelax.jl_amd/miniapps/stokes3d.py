@@ -378,6 +378,51 @@ def shearband3d(n=16, *, iterMax=150_000, nout=1000) -> Setup:
                  extra=dict(li=li, di=di, phases=phases, εbg=εbg, G0=G0, η0=η0))
 
 
+def shearband3d_variational(n=16, air_layers=0, *, iterMax=150_000, nout=1000) -> Setup:
+    """`shearband3d` solved with solve_VariationalStokes! (variational_stokes/Stokes3D.jl; the reference has no 3D variational miniapp -- this is the 3D shear band
+    under the sticky-air set-up of `shearband2d_variational`).  air_layers = 0: the two rock phases, air_phase = 0, so that update_rock_ratio! gives ϕ ≡ 1.
+    air_layers > 0 adds a third phase on top -- low constant viscosity, no plasticity, a small density against the rock's (g = 1) -- with air_phase = 3: it fills the
+    top `air_layers` layers of cells and half of the layer below them (a ramp in z over one and a half cells, modulated in x and y), so that all eight locations
+    carry fractional ratios; the rock ratios are scaled by what the air leaves.  arrays["phase_*"] holds the ratios at the eight locations of a RockRatio: c, v and the
+    edges yz, xz, xy, and vx, vy, vz at the velocity nodes without ghost nodes.  A finite viscosity_cutoff is set then: correct_phase_ratio gives pure air an all-zero
+    ratio vector, whose phase viscosity is Inf before the cutoff."""
+    s = shearband3d(n, iterMax=iterMax, nout=nout)
+    nx, ny, nz = s.ni
+    a = s.arrays
+    (xc, yc, zc), (xv, yv, zv) = s.grid.xci, s.grid.xvi
+    dz = s.extra["di"][2]
+    nph = 3 if air_layers > 0 else 2
+    if not 0 <= air_layers < nz - 2:
+        raise ValueError("air_layers must leave rock layers below the partially filled one")
+    z0 = zv[nz - air_layers - 1] if air_layers > 0 else None      # bottom of the partially filled layer of cells
+    radius, o = 0.1, (0.5, 0.5, 0.5)
+    for name, (xs, ys, zs) in (("phase_c", (xc, yc, zc)), ("phase_v", (xv, yv, zv)), ("phase_vx", (xv, yc, zc)), ("phase_vy", (xc, yv, zc)),
+                               ("phase_vz", (xc, yc, zv)), ("phase_yz", (xc, yv, zv)), ("phase_xz", (xv, yc, zv)), ("phase_xy", (xv, yv, zc))):
+        X, Y, Z = np.meshgrid(xs, ys, zs, indexing="ij")
+        outside = ((X - o[0]) ** 2 + (Y - o[1]) ** 2 + (Z - o[2]) ** 2) > radius ** 2
+        A = np.zeros(X.shape)
+        if air_layers > 0:
+            R = np.clip((Z - (z0 - 0.25 * dz)) / (1.5 * dz), 0.0, 1.0)
+            A = np.where(R >= 1.0, 1.0, np.clip(R * (0.6 + 0.4 * X + 0.4 * Y), 0.0, 1.0))
+        r = np.zeros((nph,) + X.shape, order="F")
+        r[0] = np.where(outside, 1.0, 0.0) * (1.0 - A)
+        r[1] = np.where(outside, 0.0, 1.0) * (1.0 - A)
+        if nph == 3:
+            r[2] = A
+        a[name] = r
+    phases = [dict(ph) for ph in s.extra["phases"]]
+    kwargs = dict(s.kwargs, air_phase=0)
+    if nph == 3:
+        for ph in phases:
+            ph["density"] = dict(kind="constant", rho0=1.0)
+        phases[0]["g"] = 1.0
+        phases.append(dict(eta=1.0e-2, G=phases[0]["G"], Kb=phases[0]["Kb"], density=dict(kind="constant", rho0=1.0e-3)))
+        kwargs.update(air_phase=3, viscosity_cutoff=(1.0e-2, 1.0e2))
+    s.extra["phases"] = phases
+    s.kwargs = kwargs
+    return s
+
+
 def shearheating3d(n=16, *, iterMax=100_000, nout=1000) -> Setup:
     """Shearheating3D -- test/test_shearheating3D.jl:62-162 without the particles (phase ratios from 4^3 sample points per node volume): 70 x 70 x 40 km box, dislocation-creep
     matrix and inclusion of Duretz et al. 2014 (miniapps/benchmarks/stokes3D/shear_heating/Shearheating_rheology.jl:6-7: no elastic, no plastic element), sphere of

@@ -547,7 +547,7 @@ def compute_viscosity_(stokes, *rest, relaxation=1.0, handle=None, fn="εII", AI
     phase ratios -- compute_viscosity!(stokes, args, rheology::MaterialParams, cutoff; relaxation) (Viscosity.jl:118-167; args.T is thermal.T, read at I .+ 1).
     fn: "εII" (compute_viscosity!) or "τII" (compute_viscosity_τII! / update_viscosity_τII!): the invariant a power-law creep is evaluated at.
     AII (single-material form): the invariant array of compute_viscosity_εII! / _τII!(η, ν, AII, args, rheology, cutoff) (Viscosity.jl:169-196)
-    air_phase (phase-ratio form, 2D): 1-based index of the air phase whose ratio correct_phase_ratio removes before the phase average (Viscosity.jl:403-405,638-650);
+    air_phase (phase-ratio form): 1-based index of the air phase whose ratio correct_phase_ratio removes before the phase average (Viscosity.jl:403-405,638-650);
     0 (default) keeps the path without it"""
     if fn not in ("εII", "τII"):
         raise ValueError("fn must be 'εII' or 'τII'")
@@ -577,13 +577,15 @@ def compute_viscosity_(stokes, *rest, relaxation=1.0, handle=None, fn="εII", AI
     sfx = "_tauII" if fn == "τII" else ""
     pt = SimpleNamespace(r=0.0, θ_dτ=1.0, ηdτ=1.0, ϵ_rel=0.0, ϵ_abs=0.0)
     if len(stokes._ni) == 3:
-        if air_phase:
-            raise NotImplementedError("the air_phase correction of the viscosity is built in 2D only")
         fake = SimpleNamespace(_di=dict(center=(1.0, 1.0, 1.0)))
         p = vep_params3d(stokes, pt, fake, None, 1.0, viscosity_cutoff=cutoff)
         f = vep_fields3d(stokes, (stokes.P, stokes.P, stokes.P), phase_ratios, args)
         p.T_ghosted = _ghosted_T_flag(stokes, _args_T(args))
         torch.cuda.current_stream(stokes.P.device).synchronize()
+        if air_phase:
+            h.call("jrx_vep3d_compute_viscosity_air", C.byref(f), C.byref(rheology_table(rheology)), C.byref(p), C.c_double(float(relaxation)),
+                   C.c_int32(int(air_phase)), C.c_int32(int(fn == "τII")))
+            return
         h.call("jrx_vep3d_compute_viscosity" + sfx, C.byref(f), C.byref(rheology_table(rheology)), C.byref(p), C.c_double(float(relaxation)))
         return
     fake = SimpleNamespace(_di=dict(center=(1.0, 1.0)))

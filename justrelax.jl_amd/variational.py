@@ -1,8 +1,10 @@
-"""Operator API of the 2D variational Stokes solver (free surface through a rock-ratio mask) -- src/variational_stokes/ of the reference.
+"""Operator API of the variational Stokes solvers (free surface through a rock-ratio mask) -- src/variational_stokes/ of the reference.
 
-update_rock_ratio!(ϕ, phase_ratios, air_phase) (mask.jl:63-105) and solve_VariationalStokes! (Stokes2D.jl:9-332), spelled `f_`.  Every function forwards
-to C-ABI entry points of include/jrx.h (csrc/stokes2d_vs.hip); nothing is computed in Python.  Built: 2D, one block, uniform spacing, strain-rate form;
-everything else is refused by the library with status JRX_ERR_ARG and a text naming it.
+update_rock_ratio!(ϕ, phase_ratios, air_phase) (mask.jl:63-105) and solve_VariationalStokes! (Stokes2D.jl:9-332, Stokes3D.jl:14-238), spelled `f_`.  Every
+function forwards to C-ABI entry points of include/jrx.h (csrc/stokes2d_vs.hip, csrc/stokes3d_vs.hip); nothing is computed in Python.  Built: 2D (strain-rate
+form) and 3D, one block, uniform spacing; everything else is refused by the library with status JRX_ERR_ARG and a text naming it.  The 3D momentum kernel is
+the masked 2D one written one dimension up (the reference's own 3D text cannot run; include/jrx.h states the form), and free-surface stabilisation is not
+built in 3D (a flow_bcs with free_surface=True raises ValueError).
 """
 from __future__ import annotations
 
@@ -12,12 +14,21 @@ import torch
 
 from . import _lib
 from .arrays import ptr
-from .stokes import _Hist, _args_T, _as_grid, _require_gpu, rheology_table, vep_fields2d, vep_params2d
+from .stokes import _Hist, _args_T, _as_grid, _ghosted_T_flag, _require_gpu, rheology_table, vep_fields2d, vep_fields3d, vep_params2d, vep_params3d
 
 
 def rock_ratio2d(ϕ) -> _lib.RockRatio2D:
     r = _lib.RockRatio2D()
     vals = dict(center=ϕ.center, vertex=ϕ.vertex, Vx=ϕ.Vx, Vy=ϕ.Vy)
+    for k, v in vals.items():
+        setattr(r, k, ptr(v))
+    r._keep = vals
+    return r
+
+
+def rock_ratio3d(ϕ) -> _lib.RockRatio3D:
+    r = _lib.RockRatio3D()
+    vals = dict(center=ϕ.center, vertex=ϕ.vertex, Vx=ϕ.Vx, Vy=ϕ.Vy, Vz=ϕ.Vz, yz=ϕ.yz, xz=ϕ.xz, xy=ϕ.xy)
     for k, v in vals.items():
         setattr(r, k, ptr(v))
     r._keep = vals
@@ -51,17 +62,43 @@ def vs_rheology_table(rheology) -> _lib.Rheology:
     return rh
 
 
-def solve_VariationalStokes_(stokes, pt_stokes, grid_or_di, flow_bcs, ρg, phase_ratios, ϕ, rheology, args, dt, igg=None, *, kwargs=None, handle=None):
-    """solve_VariationalStokes!(stokes, pt_stokes, grid, flow_bcs, ρg, phase_ratios, ϕ, rheology, args, dt, igg; kwargs...) -- variational_stokes/Stokes2D.jl:24-332.
-    `kwargs` holds the reference's keywords (air_phase, iterMax, iterMin, nout, viscosity_cutoff, viscosity_relaxation, λ_relaxation, free_surface, verbose,
-    strain_increment).  Returns the same namespace as solve_ (iter, err_evo1, err_evo2, norm_Rx, norm_Ry, norm_∇V)."""
-    _require_gpu(stokes)
-    if len(stokes._ni) != 2:
-        raise NotImplementedError("the 3D variational Stokes solver (variational_stokes/Stokes3D.jl) is not built")
-    kw = dict(kwargs or {})
+def _solve_vs3d(stokes, pt_stokes, grid, flow_bcs, ρg, phase_ratios, ϕ, rheology, args, dt, kw, h):
+    """_solve_VS! in 3D -- variational_stokes/Stokes3D.jl:14-238; keywords air_phase, iterMax, nout, b_width, verbose, viscosity_relaxation, viscosity_cutoff"""
+    known = ("air_phase", "iterMax", "nout", "b_width", "verbose", "viscosity_relaxation", "viscosity_cutoff")
+    kw = {k: v for k, v in kw.items() if k in known}          # kwargs... of the reference swallows the rest (iterMin, λ_relaxation, free_surface: unused in 3D)
     air_phase = int(kw.pop("air_phase", 0))
+    if getattr(flow_bcs, "free_surface", False):
+        raise ValueError("solve_VariationalStokes! 3D: free-surface stabilisation (flow_bcs.free_surface) is not built in 3D")
+    if getattr(grid, "nonuniform", False):
+        # jrx_vep3d_params carries scalar spacings only; a non-uniform Geometry has none: the library refuses the NaNs it gets instead (JRX_ERR_ARG, named)
+        from types import SimpleNamespace
+        p = vep_params3d(stokes, pt_stokes, SimpleNamespace(_di=dict(center=(float("nan"),) * 3)), flow_bcs, dt, **kw)
+    else:
+        p = vep_params3d(stokes, pt_stokes, grid, flow_bcs, dt, **kw)
+    f = vep_fields3d(stokes, ρg, phase_ratios, args)
+    p.T_ghosted = _ghosted_T_flag(stokes, _args_T(args))
+    rh = vs_rheology_table(rheology)
+    r = rock_ratio3d(ϕ)
+    hist = _Hist(int(p.iterMax // p.nout + 2))
+    torch.cuda.current_stream(stokes.P.device).synchronize()
+    h.call("jrx_stokes3d_vs_solve", C.byref(f), C.byref(r), C.byref(rh), C.byref(p), C.c_int32(air_phase), C.byref(hist.c))
+    return hist.result(3)
+
+
+def solve_VariationalStokes_(stokes, pt_stokes, grid_or_di, flow_bcs, ρg, phase_ratios, ϕ, rheology, args, dt, igg=None, *, kwargs=None, handle=None):
+    """solve_VariationalStokes!(stokes, pt_stokes, grid, flow_bcs, ρg, phase_ratios, ϕ, rheology, args, dt, igg; kwargs...) -- variational_stokes/Stokes2D.jl:24-332,
+    Stokes3D.jl:14-238.  `kwargs` holds the reference's keywords: in 2D air_phase, iterMax, iterMin, nout, viscosity_cutoff, viscosity_relaxation, λ_relaxation,
+    free_surface, verbose, strain_increment; in 3D air_phase, iterMax, nout, b_width, verbose, viscosity_relaxation, viscosity_cutoff.  Returns the same namespace as
+    solve_ (iter, err_evo1, err_evo2, norm_Rx, norm_Ry, [norm_Rz,] norm_∇V)."""
+    _require_gpu(stokes)
+    if len(stokes._ni) not in (2, 3):
+        raise NotImplementedError("solve_VariationalStokes! is built for 2D (variational_stokes/Stokes2D.jl) and 3D (Stokes3D.jl) grids")
+    kw = dict(kwargs or {})
     h = handle or _lib.default_handle(stokes.P.device.index)
     grid = _as_grid(stokes, grid_or_di)
+    if len(stokes._ni) == 3:
+        return _solve_vs3d(stokes, pt_stokes, grid, flow_bcs, ρg, phase_ratios, ϕ, rheology, args, dt, kw, h)
+    air_phase = int(kw.pop("air_phase", 0))
     p = vep_params2d(stokes, pt_stokes, grid, flow_bcs, dt, **kw)
     f = vep_fields2d(stokes, ρg, phase_ratios, args, allow_ghosted_T=True, strain_increment=bool(p.strain_increment))
     T = _args_T(args)
