@@ -476,6 +476,14 @@ static void ipc_teardown(jrx_comm_state *c)
 
 jrx_status jrx_allreduce_sum_host(jrx_handle *h, double *vals, int count) { return jrx_allreduce_host(h, vals, count, 0); }
 
+jrx_status jrx_read_sums(jrx_handle *h, hipStream_t s, double out[4], bool reduce)
+{
+    JRX_HIP(h, hipMemcpyAsync(h->h_sums, h->d_sums, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+    JRX_HIP(h, hipStreamSynchronize(s));
+    for (int q = 0; q < 4; q++) out[q] = h->h_sums[q];
+    return reduce ? jrx_allreduce_sum_host(h, out, 4) : JRX_OK;
+}
+
 // op: 0 sum (norm_mpi), 1 max (maximum_mpi)
 jrx_status jrx_allreduce_host(jrx_handle *h, double *vals, int count, int op)
 {

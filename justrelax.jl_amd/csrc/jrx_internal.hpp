@@ -8,6 +8,7 @@
 #include <cstring>
 #include <cmath>
 #include "jrx.h"
+#include "pt_log.hpp"
 
 struct jrx_comm_state;   // halo.hip
 struct jrx_field_pool;   // fieldpool.hip
@@ -184,6 +185,16 @@ static inline jrx_status jrx_capture_graph(hipStream_t s, hipGraphExec_t *out, F
 // Measured (profiles/r03_small_grids_graphs.txt): +3 .. +8 % at 16^3 and 32^3, nothing at 64^3, -7 % for the heat loop at 96^3 -> up to 48^3 cells.
 static constexpr double kGraphCells3D = 48.0 * 48.0 * 48.0;
 
+// the NaN exit of a PT loop: ends the timed span at t1, drains the stream and returns the span in milliseconds (errors are not looked at: the call fails anyway)
+static inline float jrx_drain_ms(hipStream_t s, hipEvent_t t0, hipEvent_t t1)
+{
+    float ms = 0.f;
+    (void)hipEventRecord(t1, s);
+    (void)hipStreamSynchronize(s);
+    (void)hipEventElapsedTime(&ms, t0, t1);
+    return ms;
+}
+
 // A handle is bound to one device (jrx_create); entry points that launch or allocate require that device to be the calling thread's
 // current one -- checked, never changed behind the caller's back
 jrx_status jrx_check_device(jrx_handle *h);
@@ -206,6 +217,10 @@ __device__ __forceinline__ double wave_sum(double v)
 
 typedef long long i64;
 
+// entries of the three edge-centred arrays (yz, xz, xy) of a block of nx x ny x nz cells
+struct EdgeN { i64 yz, xz, xy; };
+static inline EdgeN edge_counts(i64 nx, i64 ny, i64 nz) { return EdgeN{nx * (ny + 1) * (nz + 1), (nx + 1) * ny * (nz + 1), (nx + 1) * (ny + 1) * nz}; }
+
 __device__ __forceinline__ i64 clampll(i64 v, i64 lo, i64 hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -227,6 +242,9 @@ bool jrx_comm_active(const jrx_handle *h);
 // all-reduce (sum) of `count` doubles in place on the host values (uses RCCL when active)
 jrx_status jrx_allreduce_sum_host(jrx_handle *h, double *vals, int count);
 jrx_status jrx_allreduce_host(jrx_handle *h, double *vals, int count, int op);   // op: 0 sum, 1 max
+// a check of a PT loop: the four sums the reduction kernels left in h->d_sums, read back behind everything enqueued on s (one synchronisation) and, with
+// `reduce`, summed over the ranks (norm_mpi).  Which of the four a driver reads is the driver's business
+jrx_status jrx_read_sums(jrx_handle *h, hipStream_t s, double out[4], bool reduce);
 int jrx_comm_rank(const jrx_handle *h);
 void jrx_comm_set_timeout(jrx_handle *h, double seconds);          // in-process group of the handle (no-op without one)
 bool jrx_comm_has_neighbor(const jrx_handle *h, int d, int side);   // the halo exchange receives into that boundary plane

@@ -281,5 +281,26 @@ __global__ __launch_bounds__(256) void k_copy6(double *d0, const double *s0, i64
     }
 }
 
+// multi_copy! τ -> τ_o behind a 3D solve (Stokes3D.jl:172-173), staggered set then centre set (skipped where the caller carries no centre shear arrays); F:
+// jrx_stokes3d_fields or jrx_vep3d_fields.  τ_o is an operand of the next call: a cached verdict of the operand pass (option "operand_cache") goes first.
+// BLOCKS: the launch width of the caller.  A template, so that a translation unit launches its own k_copy6 and only where it calls this
+template <int BLOCKS, class F>
+jrx_status jrx3d_copy_old_stresses(jrx_handle *h, hipStream_t s, const F *f, i64 nx, i64 ny, i64 nz)
+{
+    h->opv.valid = false;
+    const i64 nc = nx * ny * nz;
+    const EdgeN ne = edge_counts(nx, ny, nz);
+    hipLaunchKernelGGL(k_copy6, dim3(BLOCKS), dim3(256), 0, s, f->toxx, (const double *)f->txx, nc, f->toyy, (const double *)f->tyy, nc, f->tozz,
+                       (const double *)f->tzz, nc, f->toyz, (const double *)f->tyz, ne.yz, f->toxz, (const double *)f->txz, ne.xz, f->toxy,
+                       (const double *)f->txy, ne.xy);
+    JRX_LAUNCH_CHECK(h);
+    if (f->tyz_c && f->toyz_c && f->txz_c && f->toxz_c && f->txy_c && f->toxy_c) {
+        hipLaunchKernelGGL(k_copy6, dim3(BLOCKS), dim3(256), 0, s, f->toyz_c, (const double *)f->tyz_c, nc, f->toxz_c, (const double *)f->txz_c, nc,
+                           f->toxy_c, (const double *)f->txy_c, nc, (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr,
+                           (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0);
+        JRX_LAUNCH_CHECK(h);
+    }
+    return JRX_OK;
+}
 
 }   // namespace

@@ -536,11 +536,11 @@ jrx_status jrx_stokes2d_solve(jrx_handle *h, const jrx_stokes2d_fields *f, const
                            (const double *)f->Uy, (i64)(nx + 2) * (ny + 1), (double *)nullptr, (const double *)nullptr, (i64)0, 1.0 / p->dt);
         JRX_LAUNCH_CHECK(h);
     }
-    double err_it1 = 1.0, err = 1.0;
-    int64_t iter = 0, cont = 0;
+    PtLog log(res);
+    int64_t iter = 0;
     const int rank = jrx_comm_rank(h);
     JRX_HIP(h, hipEventRecord(h->ev[6], s));
-    auto keep_going = [&](int64_t it) { return it < 2 || (((err / err_it1) > p->eps_rel && err > p->eps_abs) && it <= p->iterMax); };
+    auto keep_going = [&](int64_t it) { return it < 2 || ((log.rel() > p->eps_rel && log.err() > p->eps_abs) && it <= p->iterMax); };
     auto is_check = [&](int64_t i1) { return (i1 % p->nout == 0) && i1 > 1; };
     // Fused pipeline (as in 3D): when nothing observes iteration it1 and iteration it1+1 certainly runs unobserved, compute_V! of it1,
     // flow_bcs! (by rule) and the stress sweep of it1+1 run as one launch that ping-pongs (P, τ, V) between the caller's arrays and a
@@ -683,27 +683,13 @@ jrx_status jrx_stokes2d_solve(jrx_handle *h, const jrx_stokes2d_fields *f, const
             hipLaunchKernelGGL(k_velocity2d<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);   // compute_Res! (Stokes2D.jl:274-276)
             JRX_LAUNCH_CHECK(h);
             JRX_TRY(jrx2d_sumsq(h, s, f, p));
-            JRX_HIP(h, hipMemcpyAsync(h->h_sums, h->d_sums, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-            JRX_HIP(h, hipStreamSynchronize(s));
-            double ss[3] = {h->h_sums[0], h->h_sums[1], h->h_sums[3]};
-            JRX_TRY(jrx_allreduce_sum_host(h, ss, 3));
+            double ss[4];
+            JRX_TRY(jrx_read_sums(h, s, ss, true));
             const double nRx = sqrt(ss[0]) / sqrt((double)((p->nxg - 2) * (p->nyg - 1)));
             const double nRy = sqrt(ss[1]) / sqrt((double)((p->nxg - 1) * (p->nyg - 2)));
-            const double nDV = sqrt(ss[2]) / sqrt((double)(p->nxg * p->nyg));
-            err = fmax(nRx, fmax(nRy, nDV));
-            if (std::isnan(nRx) || std::isnan(nRy) || std::isnan(nDV)) err = NAN;
-            if (cont < res->cap) {
-                if (res->norm_Rx) res->norm_Rx[cont] = nRx;
-                if (res->norm_Ry) res->norm_Ry[cont] = nRy;
-                if (res->norm_divV) res->norm_divV[cont] = nDV;
-                if (res->err_evo1) res->err_evo1[cont] = err;
-                if (res->err_evo2) res->err_evo2[cont] = iter;
-            }
-            if (cont == 0) err_it1 = err;
-            cont++;
-            if (rank == 0 && ((p->verbose && (err / err_it1) > p->eps_rel && err > p->eps_abs) || iter == p->iterMax))
-                printf("Total steps = %lld, abs_err = %1.3e , rel_err = %1.3e [norm_Rx=%1.3e, norm_Ry=%1.3e, norm_∇V=%1.3e] \n",
-                       (long long)iter, err, err / err_it1, nRx, nRy, nDV);
+            const double nDV = sqrt(ss[3]) / sqrt((double)(p->nxg * p->nyg));      // jrx2d_sumsq leaves RP in slot 3
+            const double err = log.record(iter, nRx, nRy, nDV);
+            if (rank == 0 && ((p->verbose && log.rel() > p->eps_rel && err > p->eps_abs) || iter == p->iterMax)) log.print2d(iter, nRx, nRy, nDV);
         }
     }
     gexec.reset();
@@ -724,10 +710,7 @@ jrx_status jrx_stokes2d_solve(jrx_handle *h, const jrx_stokes2d_fields *f, const
     JRX_HIP(h, hipStreamSynchronize(s));
     float ms = 0.f;
     JRX_HIP(h, hipEventElapsedTime(&ms, h->ev[6], h->ev[7]));
-    res->iter = iter;
-    res->nchecks = cont < res->cap ? cont : res->cap;
-    res->time_s = ms * 1e-3;
-    res->av_time_s = iter > 1 ? res->time_s / (double)(iter - 1) : res->time_s;
+    log.finish(iter, ms);
     return JRX_OK;
 }
 

@@ -898,8 +898,18 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
     const bool batch_pre = h->fused2d_batch && !p->inv_spacing[0] && !upd_rho;
     const bool batch_vv = h->fused2d_batch && !p->inv_spacing[0] && b.fs_dt == 0.0 && !a.vfields && a.eta_lin_c != nullptr && (a.f.eta_v == nullptr || a.eta_lin_v != nullptr);
 
-    double err_it1 = 1.0, err = 1.0;
-    int64_t iter = 0, cont = 0;
+    PtLog log(res);
+    int64_t iter = 0;
+    auto done = [&]() { return log.rel() < p->eps_rel || log.err() < p->eps_abs; };
+    // an odd number of swaps: leave τxx, τyy in the caller's arrays, and the arguments pointing at them
+    auto restore = [&]() -> jrx_status {
+        if (a.f.txx != f->txx) {
+            JRX_HIP(h, hipMemcpyAsync(f->txx, a.f.txx, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+            JRX_HIP(h, hipMemcpyAsync(f->tyy, a.f.tyy, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+            a.f.txx = f->txx; a.f.tyy = f->tyy; b.f.txx = f->txx; b.f.tyy = f->tyy; g.txx = f->txx; g.tyy = f->tyy;
+        }
+        return JRX_OK;
+    };
     JRX_HIP(h, hipEventRecord(h->ev[6], s));
     // Runs of unobserved iterations replay as a captured graph of GIT iterations (three launches each: at the sizes where the loop is launch-bound -- 17 - 18 us
     // per iteration up to 256^2 -- the gap between dependent launches is shorter inside a graph).  An even count, so that the (τxx, τyy) sets end where they
@@ -908,8 +918,8 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
     GraphExecs gexec;        // released on every exit path
     bool graphs = h->loop_graphs && !comm && !ubc && !a.si && p->periodic == 0 && (i64)(nx + 1) * (ny + 1) <= 200000;
     while (iter <= p->iterMax) {
-        if (p->iterMin < iter && ((err / err_it1) < p->eps_rel || err < p->eps_abs)) break;          // Stokes2D.jl:650-651
-        if (graphs && iter >= 1 && !((err / err_it1) < p->eps_rel || err < p->eps_abs)) {
+        if (p->iterMin < iter && done()) break;          // Stokes2D.jl:650-651
+        if (graphs && iter >= 1 && !done()) {
             // observed iterations (checks: multiples of nout; the last one: iterMax + 1) end a run; err does not change inside one
             int64_t nxt = ((iter / p->nout) + 1) * p->nout;
             if (nxt > p->iterMax + 1) nxt = p->iterMax + 1;
@@ -958,7 +968,7 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
         }
         {   // can the loop stop after the iteration launched now (a check, the last allowed one, or already converged)?  Only then are its output-only arrays stored
             const int64_t it1 = iter + 1;
-            a.obs = ((it1 % p->nout == 0) && it1 > 1) || it1 > p->iterMax || (p->iterMin < it1 && ((err / err_it1) < p->eps_rel || err < p->eps_abs)) || h->vep_store_all;
+            a.obs = ((it1 % p->nout == 0) && it1 > 1) || it1 > p->iterMax || (p->iterMin < it1 && done()) || h->vep_store_all;
         }
         if (comm) {
             hipLaunchKernelGGL(k_maxloc, dim3(gc, 1), dim3(256), 0, s, etatau, (const double *)f->eta, nx, ny, 1);
@@ -1004,7 +1014,7 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
         bool used_bcf = false;
         {
             const bool next_check = ((iter + 1) % p->nout == 0) && iter + 1 > 1;
-            const bool next_last = next_check || iter + 1 > p->iterMax || (p->iterMin < iter + 1 && ((err / err_it1) < p->eps_rel || err < p->eps_abs));
+            const bool next_last = next_check || iter + 1 > p->iterMax || (p->iterMin < iter + 1 && done());
             used_bcf = bcf && !next_last;
             // compute_viscosity! + compute_V! (free-surface form with dt*free_surface = 0) in one launch
             if (batch_vv && used_bcf) hipLaunchKernelGGL(k_vep_visc_velocity_b<true>, dim3(gv), dim3(256), 0, s, a, b);
@@ -1016,7 +1026,7 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
         iter += 1;
         const bool check = (iter % p->nout == 0) && iter > 1;
         // the loop can stop after this iteration if it is a check, the last allowed one, or already converged
-        const bool last = check || iter > p->iterMax || (p->iterMin < iter && ((err / err_it1) < p->eps_rel || err < p->eps_abs));
+        const bool last = check || iter > p->iterMax || (p->iterMin < iter && done());
         if (last || a.si) {   // U = V*dt is only observable after an iteration the loop can stop at -- or every iteration when the strains are taken from U
             hipLaunchKernelGGL(k_scale3, dim3(256), dim3(256), 0, s, f->Ux, (const double *)f->Vx, (i64)(nx + 1) * (ny + 2), f->Uy,
                                (const double *)f->Vy, (i64)(nx + 2) * (ny + 1), (double *)nullptr, (const double *)nullptr, (i64)0, p->dt);
@@ -1034,51 +1044,23 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
             hipLaunchKernelGGL(k_velocity2d<true>, dim3(gc), dim3(256), 0, s, b);  // compute_Res!
             JRX_LAUNCH_CHECK(h);
             JRX_TRY(jrx2d_sumsq(h, s, &g, &q));
-            JRX_HIP(h, hipMemcpyAsync(h->h_sums, h->d_sums, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-            JRX_HIP(h, hipStreamSynchronize(s));
-            double ss[3] = {h->h_sums[0], h->h_sums[1], h->h_sums[3]};
-            JRX_TRY(jrx_allreduce_sum_host(h, ss, 3));                                   // norm_mpi (Stokes2D.jl:803-808)
+            double ss[4];
+            JRX_TRY(jrx_read_sums(h, s, ss, true));                                      // norm_mpi (Stokes2D.jl:803-808)
             const double nRx = sqrt(ss[0]) / sqrt((double)((p->nxg - 2) * (p->nyg - 1)));
             const double nRy = sqrt(ss[1]) / sqrt((double)((p->nxg - 1) * (p->nyg - 2)));
-            const double nDV = sqrt(ss[2]) / sqrt((double)(p->nxg * p->nyg));
-            err = fmax(nRx, fmax(nRy, nDV));
-            if (std::isnan(nRx) || std::isnan(nRy) || std::isnan(nDV)) err = NAN;
-            if (cont < res->cap) {
-                if (res->norm_Rx) res->norm_Rx[cont] = nRx;
-                if (res->norm_Ry) res->norm_Ry[cont] = nRy;
-                if (res->norm_divV) res->norm_divV[cont] = nDV;
-                if (res->err_evo1) res->err_evo1[cont] = err;
-                if (res->err_evo2) res->err_evo2[cont] = iter;
-            }
-            if (cont == 0) err_it1 = err;
-            cont++;
-            if (p->verbose && jrx_comm_rank(h) == 0)      // igg.me == 0 (Stokes2D.jl:814)
-                printf("Total steps = %lld, abs_err = %1.3e , rel_err = %1.3e [norm_Rx=%1.3e, norm_Ry=%1.3e, norm_∇V=%1.3e] \n",
-                       (long long)iter, err, err / err_it1, nRx, nRy, nDV);
-            if (std::isnan(err)) {
-                // error("NaN(s)"): leave the caller's arrays consistent (the current τxx, τyy may live in the second set) and the stream drained
+            const double nDV = sqrt(ss[3]) / sqrt((double)(p->nxg * p->nyg));      // jrx2d_sumsq leaves RP in slot 3
+            const double err = log.record(iter, nRx, nRy, nDV);
+            if (p->verbose && jrx_comm_rank(h) == 0) log.print2d(iter, nRx, nRy, nDV);      // igg.me == 0 (Stokes2D.jl:814)
+            if (std::isnan(err)) {      // error("NaN(s)"): leave the caller's arrays consistent and the stream drained
                 gexec.reset();
-                if (a.f.txx != f->txx) {
-                    (void)hipMemcpyAsync(f->txx, a.f.txx, n * sizeof(double), hipMemcpyDeviceToDevice, s);
-                    (void)hipMemcpyAsync(f->tyy, a.f.tyy, n * sizeof(double), hipMemcpyDeviceToDevice, s);
-                }
-                (void)hipEventRecord(h->ev[7], s);
-                (void)hipStreamSynchronize(s);
-                float msn = 0.f;
-                (void)hipEventElapsedTime(&msn, h->ev[6], h->ev[7]);
-                res->iter = iter; res->nchecks = cont < res->cap ? cont : res->cap;
-                res->time_s = msn * 1e-3; res->av_time_s = iter > 1 ? res->time_s / (double)(iter - 1) : res->time_s;
-                return jrx_fail(h, JRX_ERR_NAN, "NaN(s)");
+                (void)restore();
+                return log.fail_nan(h, iter, jrx_drain_ms(s, h->ev[6], h->ev[7]));
             }
         }
     }
     gexec.reset();
     JRX_HIP(h, hipEventRecord(h->ev[7], s));
-    if (a.f.txx != f->txx) {      // odd number of swaps: leave τxx, τyy in the caller's arrays
-        JRX_HIP(h, hipMemcpyAsync(f->txx, a.f.txx, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-        JRX_HIP(h, hipMemcpyAsync(f->tyy, a.f.tyy, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-        a.f.txx = f->txx; a.f.tyy = f->tyy; b.f.txx = f->txx; b.f.tyy = f->tyy; g.txx = f->txx; g.tyy = f->tyy;
-    }
+    JRX_TRY(restore());
     a.txx_out = a.tyy_out = nullptr;
     hipLaunchKernelGGL(k_vep_epilogue, dim3(gv), dim3(256), 0, s, a);
     JRX_LAUNCH_CHECK(h);
@@ -1089,10 +1071,7 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
     JRX_HIP(h, hipStreamSynchronize(s));
     float ms = 0.f;
     JRX_HIP(h, hipEventElapsedTime(&ms, h->ev[6], h->ev[7]));
-    res->iter = iter;
-    res->nchecks = cont < res->cap ? cont : res->cap;
-    res->time_s = ms * 1e-3;
-    res->av_time_s = iter > 1 ? res->time_s / (double)(iter - 1) : res->time_s;
+    log.finish(iter, ms);
     return JRX_OK;
 }
 
@@ -1154,11 +1133,11 @@ jrx_status jrx_stokes2d_nonlinear_solve(jrx_handle *h, const jrx_vep2d_fields *f
                            (const double *)f->Uy, (i64)(nx + 2) * (ny + 1), (double *)nullptr, (const double *)nullptr, (i64)0, 1.0 / p->dt);
         JRX_LAUNCH_CHECK(h);
     }
-    double err_it1 = 1.0, err = 1.0;
-    int64_t iter = 0, cont = 0;
+    PtLog log(res);
+    int64_t iter = 0;
     res->iter = 0; res->nchecks = 0;
     JRX_HIP(h, hipEventRecord(h->ev[6], s));
-    auto keep_going = [&](int64_t it) { return it < 2 || (((err / err_it1) > p->eps_rel && err > p->eps_abs) && it <= p->iterMax); };
+    auto keep_going = [&](int64_t it) { return it < 2 || ((log.rel() > p->eps_rel && log.err() > p->eps_abs) && it <= p->iterMax); };
     // Runs of unobserved iterations (ten short launches each as the reference orders them, every argument constant: the loop is launch-bound at any 2D size,
     // 38 us per iteration) replay as a captured graph of GIT iterations of six launches (center2vertex! in one pass, flow_bcs! folded into compute_V!); one rank,
     // velocity boundary conditions.  Option "loop_graphs" = 0: plain launches.
@@ -1244,32 +1223,14 @@ jrx_status jrx_stokes2d_nonlinear_solve(jrx_handle *h, const jrx_vep2d_fields *f
             hipLaunchKernelGGL(k_velocity2d<true>, dim3(gc), dim3(256), 0, s, b);                    // compute_Res! :479-490
             JRX_LAUNCH_CHECK(h);
             JRX_TRY(jrx2d_sumsq(h, s, &g, &q));
-            JRX_HIP(h, hipMemcpyAsync(h->h_sums, h->d_sums, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-            JRX_HIP(h, hipStreamSynchronize(s));
-            double ss[3] = {h->h_sums[0], h->h_sums[1], h->h_sums[3]};
-            JRX_TRY(jrx_allreduce_sum_host(h, ss, 3));
+            double ss[4];
+            JRX_TRY(jrx_read_sums(h, s, ss, true));
             const double nRx = sqrt(ss[0]) / sqrt((double)((p->nxg - 2) * (p->nyg - 1)));
             const double nRy = sqrt(ss[1]) / sqrt((double)((p->nxg - 1) * (p->nyg - 2)));
-            const double nDV = sqrt(ss[2]) / sqrt((double)(p->nxg * p->nyg));
-            err = fmax(nRx, fmax(nRy, nDV));
-            if (std::isnan(nRx) || std::isnan(nRy) || std::isnan(nDV)) err = NAN;
-            if (cont < res->cap) {
-                if (res->norm_Rx) res->norm_Rx[cont] = nRx;
-                if (res->norm_Ry) res->norm_Ry[cont] = nRy;
-                if (res->norm_divV) res->norm_divV[cont] = nDV;
-                if (res->err_evo1) res->err_evo1[cont] = err;
-                if (res->err_evo2) res->err_evo2[cont] = iter;
-            }
-            if (cont == 0) err_it1 = err;
-            cont++;
-            if (jrx_comm_rank(h) == 0 && ((p->verbose && (err / err_it1) > p->eps_rel && err > p->eps_abs) || iter == p->iterMax))
-                printf("Total steps = %lld, abs_err = %1.3e , rel_err = %1.3e [norm_Rx=%1.3e, norm_Ry=%1.3e, norm_∇V=%1.3e] \n",
-                       (long long)iter, err, err / err_it1, nRx, nRy, nDV);
-            if (std::isnan(err)) {
-                res->iter = iter; res->nchecks = cont < res->cap ? cont : res->cap;
-                (void)hipStreamSynchronize(s);
-                return jrx_fail(h, JRX_ERR_NAN, "NaN(s)");
-            }
+            const double nDV = sqrt(ss[3]) / sqrt((double)(p->nxg * p->nyg));      // jrx2d_sumsq leaves RP in slot 3
+            const double err = log.record(iter, nRx, nRy, nDV);
+            if (jrx_comm_rank(h) == 0 && ((p->verbose && log.rel() > p->eps_rel && err > p->eps_abs) || iter == p->iterMax)) log.print2d(iter, nRx, nRy, nDV);
+            if (std::isnan(err)) return log.fail_nan(h, iter, jrx_drain_ms(s, h->ev[6], h->ev[7]));
         }
     }
     gexecs.reset();
@@ -1285,10 +1246,7 @@ jrx_status jrx_stokes2d_nonlinear_solve(jrx_handle *h, const jrx_vep2d_fields *f
     JRX_HIP(h, hipStreamSynchronize(s));
     float ms = 0.f;
     JRX_HIP(h, hipEventElapsedTime(&ms, h->ev[6], h->ev[7]));
-    res->iter = iter;
-    res->nchecks = cont < res->cap ? cont : res->cap;
-    res->time_s = ms * 1e-3;
-    res->av_time_s = iter > 1 ? res->time_s / (double)(iter - 1) : res->time_s;
+    log.finish(iter, ms);
     return JRX_OK;
 }
 

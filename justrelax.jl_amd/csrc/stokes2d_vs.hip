@@ -674,9 +674,9 @@ jrx_status jrx_stokes2d_vs_solve(jrx_handle *h, const jrx_vep2d_fields *f, const
     a.rho = rh->has_density && !mat_density_is_constant(rh);       // update_ρg! :133 rewrites the same values for constant densities
     const int nblk = (int)(gc < (unsigned)kMaxRedBlocks ? gc : (unsigned)kMaxRedBlocks);
 
-    double err_it1 = 1.0, err = 1.0;
-    int64_t iter = 0, cont = 0;
-    auto done = [&]() { return (err / err_it1) < p->eps_rel || err < p->eps_abs; };
+    PtLog log(res);
+    int64_t iter = 0;
+    auto done = [&]() { return log.rel() < p->eps_rel || log.err() < p->eps_abs; };
     auto restore = [&]() {      // an odd number of swaps: leave τxx, τyy, η in the caller's arrays
         if (a.f.txx != f->txx) {
             (void)hipMemcpyAsync(f->txx, a.f.txx, n * sizeof(double), hipMemcpyDeviceToDevice, s);
@@ -721,34 +721,16 @@ jrx_status jrx_stokes2d_vs_solve(jrx_handle *h, const jrx_vep2d_fields *f, const
             hipLaunchKernelGGL(k_vs_sumsq_partial, dim3(nblk), dim3(256), 0, s, a, h->d_partials);
             hipLaunchKernelGGL(k_sumsq_final, dim3(1), dim3(256), 0, s, (const double *)h->d_partials, nblk, h->d_sums);
             JRX_LAUNCH_CHECK(h);
-            JRX_HIP(h, hipMemcpyAsync(h->h_sums, h->d_sums, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-            JRX_HIP(h, hipStreamSynchronize(s));
-            const double nRx = sqrt(h->h_sums[0]) / sqrt((double)((p->nxg - 2) * (p->nyg - 1)));
-            const double nRy = sqrt(h->h_sums[1]) / sqrt((double)((p->nxg - 1) * (p->nyg - 2)));
-            const double nDV = sqrt(h->h_sums[2]) / sqrt((double)(p->nxg * p->nyg));
-            err = fmax(nRx, fmax(nRy, nDV));
-            if (std::isnan(nRx) || std::isnan(nRy) || std::isnan(nDV)) err = NAN;
-            if (cont < res->cap) {
-                if (res->norm_Rx) res->norm_Rx[cont] = nRx;
-                if (res->norm_Ry) res->norm_Ry[cont] = nRy;
-                if (res->norm_divV) res->norm_divV[cont] = nDV;
-                if (res->err_evo1) res->err_evo1[cont] = err;
-                if (res->err_evo2) res->err_evo2[cont] = iter;
-            }
-            if (cont == 0) err_it1 = err;
-            cont++;
-            if (p->verbose)
-                printf("Total steps = %lld, abs_err = %1.3e , rel_err = %1.3e [norm_Rx=%1.3e, norm_Ry=%1.3e, norm_∇V=%1.3e] \n",
-                       (long long)iter, err, err / err_it1, nRx, nRy, nDV);
+            double ss[4];
+            JRX_TRY(jrx_read_sums(h, s, ss, false));      // single block (vs_check); k_vs_sumsq_partial leaves RP in slot 2
+            const double nRx = sqrt(ss[0]) / sqrt((double)((p->nxg - 2) * (p->nyg - 1)));
+            const double nRy = sqrt(ss[1]) / sqrt((double)((p->nxg - 1) * (p->nyg - 2)));
+            const double nDV = sqrt(ss[2]) / sqrt((double)(p->nxg * p->nyg));
+            const double err = log.record(iter, nRx, nRy, nDV);
+            if (p->verbose) log.print2d(iter, nRx, nRy, nDV);
             if (std::isnan(err)) {      // error("NaN(s)"): leave the caller's arrays consistent and the stream drained
                 restore();
-                (void)hipEventRecord(h->ev[7], s);
-                (void)hipStreamSynchronize(s);
-                float msn = 0.f;
-                (void)hipEventElapsedTime(&msn, h->ev[6], h->ev[7]);
-                res->iter = iter; res->nchecks = cont < res->cap ? cont : res->cap;
-                res->time_s = msn * 1e-3; res->av_time_s = iter > 1 ? res->time_s / (double)(iter - 1) : res->time_s;
-                return jrx_fail(h, JRX_ERR_NAN, "NaN(s)");
+                return log.fail_nan(h, iter, jrx_drain_ms(s, h->ev[6], h->ev[7]));
             }
         }
     }
@@ -764,10 +746,7 @@ jrx_status jrx_stokes2d_vs_solve(jrx_handle *h, const jrx_vep2d_fields *f, const
     JRX_HIP(h, hipStreamSynchronize(s));
     float ms = 0.f;
     JRX_HIP(h, hipEventElapsedTime(&ms, h->ev[6], h->ev[7]));
-    res->iter = iter;
-    res->nchecks = cont < res->cap ? cont : res->cap;
-    res->time_s = ms * 1e-3;
-    res->av_time_s = iter > 1 ? res->time_s / (double)(iter - 1) : res->time_s;
+    log.finish(iter, ms);
     return JRX_OK;
 }
 

@@ -1315,15 +1315,15 @@ jrx_status jrx_stokes3d_solve(jrx_handle *h, const jrx_stokes3d_fields *f, const
                            1.0 / p->dt);
         JRX_LAUNCH_CHECK(h);
     }
-    double err_it1 = 1.0, err = 1.0;
-    int64_t iter = 0, cont = 0;
+    PtLog log(res);
+    int64_t iter = 0;
     res->iter = 0; res->nchecks = 0;
     const int rank = jrx_comm_rank(h);
     hipEvent_t t0 = h->ev[6], t1 = h->ev[7];
     Iter3D I;
     JRX_TRY(iter_begin(I, h, f, h->etatau, p));
     JRX_HIP(h, hipEventRecord(t0, s));
-    auto keep_going = [&](int64_t it) { return it < 2 || (((err / err_it1) > p->eps_rel && err > p->eps_abs) && it <= p->iterMax); };
+    auto keep_going = [&](int64_t it) { return it < 2 || ((log.rel() > p->eps_rel && log.err() > p->eps_abs) && it <= p->iterMax); };
     auto is_check = [&](int64_t it1) { return (it1 % p->nout == 0) && it1 > 1; };
     // Small grids (the reference's own 3D tests run at 8^3 .. 32^3, test/test_stokes_solvi3D.jl:25-55) are launch-bound: three to four dependent launches
     // of a few microseconds each per iteration.  Runs of unobserved iterations of the un-fused loop replay as a captured graph of GIT iterations
@@ -1364,59 +1364,27 @@ jrx_status jrx_stokes3d_solve(jrx_handle *h, const jrx_stokes3d_fields *f, const
         iter = it1;
         if (check) {
             JRX_TRY(launch_sumsq(h, s, &I.cur, p));
-            JRX_HIP(h, hipMemcpyAsync(h->h_sums, h->d_sums, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-            JRX_HIP(h, hipStreamSynchronize(s));
-            double ss[4] = {h->h_sums[0], h->h_sums[1], h->h_sums[2], h->h_sums[3]};
-            JRX_TRY(jrx_allreduce_sum_host(h, ss, 4));       // norm_mpi: sqrt(Allreduce(Σx²)) (Utils.jl:698-701)
+            double ss[4];
+            JRX_TRY(jrx_read_sums(h, s, ss, true));          // norm_mpi: sqrt(Allreduce(Σx²)) (Utils.jl:698-701)
             const double nRx = sqrt(ss[0]) / (double)((p->nxg - 2) * (p->nyg - 1) * (p->nzg - 1));
             const double nRy = sqrt(ss[1]) / (double)((p->nxg - 1) * (p->nyg - 2) * (p->nzg - 1));
             const double nRz = sqrt(ss[2]) / (double)((p->nxg - 1) * (p->nyg - 1) * (p->nzg - 2));
             const double nDV = sqrt(ss[3]) / (double)(p->nxg * p->nyg * p->nzg);
-            err = fmax(fmax(nRx, nRy), fmax(nRz, nDV));
-            if (std::isnan(nRx) || std::isnan(nRy) || std::isnan(nRz) || std::isnan(nDV)) err = NAN;
-            if (cont < res->cap) {
-                if (res->norm_Rx) res->norm_Rx[cont] = nRx;
-                if (res->norm_Ry) res->norm_Ry[cont] = nRy;
-                if (res->norm_Rz) res->norm_Rz[cont] = nRz;
-                if (res->norm_divV) res->norm_divV[cont] = nDV;
-                if (res->err_evo1) res->err_evo1[cont] = err;
-                if (res->err_evo2) res->err_evo2[cont] = iter;
-            }
-            if (cont == 0) err_it1 = err;
-            cont++;
-            if (rank == 0 && ((p->verbose && (err / err_it1) > p->eps_rel && err > p->eps_abs) || iter == p->iterMax))
-                printf("iter = %lld, abs_err = %1.3e, rel_err = %1.3e [norm_Rx=%1.3e, norm_Ry=%1.3e, norm_Rz=%1.3e, norm_∇V=%1.3e] \n",
-                       (long long)iter, err, err / err_it1, nRx, nRy, nRz, nDV);
+            const double err = log.record(iter, nRx, nRy, nRz, nDV);
+            if (rank == 0 && ((p->verbose && log.rel() > p->eps_rel && err > p->eps_abs) || iter == p->iterMax)) log.print3d(iter, nRx, nRy, nRz, nDV);
             if (std::isnan(err)) {
-                res->iter = iter; res->nchecks = cont < res->cap ? cont : res->cap;
                 (void)iter_end(I);
-                (void)hipStreamSynchronize(s);
-                return jrx_fail(h, JRX_ERR_NAN, "NaN(s)");
+                return log.fail_nan(h, iter, jrx_drain_ms(s, t0, t1));
             }
         }
     }
     JRX_HIP(h, hipEventRecord(t1, s));
     JRX_TRY(iter_end(I));
-    // multi_copy! τ -> τ_o, staggered set then centre set (Stokes3D.jl:172-173); τ_o is an operand of the next call: a cached verdict of the operand pass goes
-    h->opv.valid = false;
-    const i64 nc = (i64)n, nyz = (i64)nx * (ny + 1) * (nz + 1), nxz = (i64)(nx + 1) * ny * (nz + 1), nxy = (i64)(nx + 1) * (ny + 1) * nz;
-    hipLaunchKernelGGL(k_copy6, dim3(2048), dim3(256), 0, s, f->toxx, (const double *)f->txx, nc, f->toyy, (const double *)f->tyy, nc, f->tozz,
-                       (const double *)f->tzz, nc, f->toyz, (const double *)f->tyz, nyz, f->toxz, (const double *)f->txz, nxz, f->toxy,
-                       (const double *)f->txy, nxy);
-    JRX_LAUNCH_CHECK(h);
-    if (f->tyz_c && f->toyz_c && f->txz_c && f->toxz_c && f->txy_c && f->toxy_c) {
-        hipLaunchKernelGGL(k_copy6, dim3(2048), dim3(256), 0, s, f->toyz_c, (const double *)f->tyz_c, nc, f->toxz_c, (const double *)f->txz_c, nc,
-                           f->toxy_c, (const double *)f->txy_c, nc, (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr,
-                           (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0);
-        JRX_LAUNCH_CHECK(h);
-    }
+    JRX_TRY((jrx3d_copy_old_stresses<2048>(h, s, f, nx, ny, nz)));
     JRX_HIP(h, hipStreamSynchronize(s));
     float ms = 0.f;
     JRX_HIP(h, hipEventElapsedTime(&ms, t0, t1));
-    res->iter = iter;
-    res->nchecks = cont < res->cap ? cont : res->cap;
-    res->time_s = ms * 1e-3;
-    res->av_time_s = iter > 1 ? res->time_s / (double)(iter - 1) : res->time_s;
+    log.finish(iter, ms);
     return JRX_OK;
 }
 

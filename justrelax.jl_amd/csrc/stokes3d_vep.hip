@@ -1162,12 +1162,6 @@ Vep3Args make_vep3(const jrx_vep3d_fields *f, const jrx_rheology *rh, const jrx_
     return a;
 }
 
-struct EdgeN { i64 yz, xz, xy; };
-EdgeN edge_counts(const jrx_vep3d_params *p)
-{
-    return EdgeN{(i64)p->nx * (p->ny + 1) * (p->nz + 1), (i64)(p->nx + 1) * p->ny * (p->nz + 1), (i64)(p->nx + 1) * (p->ny + 1) * p->nz};
-}
-
 // the three edge passes, the commit of the new edge stresses, then the centre pass
 // commit = false: the caller adopts a.tnew as the current edge-stress arrays (pointer swap) instead of copying them back
 // which: 0 = both passes, 1 = the edge pass alone, 2 = the centre pass alone (the multi-rank driver exchanges the new edge stresses in between)
@@ -1278,7 +1272,7 @@ jrx_status launch_vep3_stress(jrx_handle *h, hipStream_t s, const Vep3Args &a, c
     JRX_LAUNCH_CHECK(h);
     }
     if (which == 1) return JRX_OK;
-    const EdgeN n = edge_counts(p);
+    const EdgeN n = edge_counts(p->nx, p->ny, p->nz);
     if (commit && which == 0) {
         hipLaunchKernelGGL(k_copy6, dim3(1024), dim3(256), 0, s, a.f.tyz, (const double *)a.tnew[0], n.yz, a.f.txz, (const double *)a.tnew[1], n.xz, a.f.txy,
                            (const double *)a.tnew[2], n.xy, (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr,
@@ -1319,7 +1313,7 @@ jrx_status jrx_vep3d_update_stresses(jrx_handle *h, const jrx_vep3d_fields *f, c
 {
     JRX_TRY(check_vep3(h, f, rh, p));
     if (!theta || !lambda || !lambda_v || !lambda_v[0] || !lambda_v[1] || !lambda_v[2]) return jrx_fail(h, JRX_ERR_ARG, "θ / λ / λv is NULL");
-    const EdgeN n = edge_counts(p);
+    const EdgeN n = edge_counts(p->nx, p->ny, p->nz);
     JRX_TRY(jrx_ensure_etatau(h, (size_t)(n.yz + n.xz + n.xy)));
     Vep3Args a = make_vep3(f, rh, p);
     a.theta = const_cast<double *>(theta); a.lam = lambda;
@@ -1409,7 +1403,7 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
     if (p->nout < 1) return jrx_fail(h, JRX_ERR_ARG, "nout must be >= 1");
     const int nx = (int)p->nx, ny = (int)p->ny, nz = (int)p->nz;
     const size_t n = (size_t)nx * ny * nz;
-    const EdgeN ne = edge_counts(p);
+    const EdgeN ne = edge_counts(p->nx, p->ny, p->nz);
     hipStream_t s = h->stream;
     // library scratch: ητ, θ, λ, K, G, a second ητ, the phase-averaged η of the linear laws (centres), λv and the new edge stresses (edges), carved out of one allocation
     JRX_TRY(jrx_ensure_etatau(h, 11 * n + 2 * (size_t)(ne.yz + ne.xz + ne.xy)));
@@ -1457,8 +1451,8 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
         JRX_LAUNCH_CHECK(h);
     }
 
-    double err_it1 = 1.0, err = INFINITY;
-    int64_t iter = 0, cont = 0;
+    PtLog log(res, INFINITY);
+    int64_t iter = 0;
     bool bcs_ordered = false;        // the reference's ordered flow_bcs! passes have run on V at least once
     res->iter = 0; res->nchecks = 0;
     const bool comm = jrx_comm_active(h);
@@ -1466,7 +1460,30 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
     const int rank = jrx_comm_rank(h);
     hipEvent_t t0 = h->ev[6], t1 = h->ev[7];
     JRX_HIP(h, hipEventRecord(t0, s));
-    auto keep_going = [&](int64_t it) { return it < 2 || (((err / err_it1) > p->eps_rel && err > p->eps_abs) && it <= p->iterMax); };
+    auto keep_going = [&](int64_t it) { return it < 2 || ((log.rel() > p->eps_rel && log.err() > p->eps_abs) && it <= p->iterMax); };
+    // an odd number of swaps: leave η, τxx, τyy, τzz (fused / forked centre pass) and the edge stresses in the caller's arrays, and the arguments pointing at them
+    auto restore = [&]() -> jrx_status {
+        if (a.f.eta != f->eta) {
+            JRX_HIP(h, hipMemcpyAsync(f->eta, a.f.eta, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+            a.f.eta = f->eta; g.eta = g.K = g.G = f->eta;
+        }
+        if (a.f.txx != f->txx) {
+            JRX_HIP(h, hipMemcpyAsync(f->txx, a.f.txx, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+            JRX_HIP(h, hipMemcpyAsync(f->tyy, a.f.tyy, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+            JRX_HIP(h, hipMemcpyAsync(f->tzz, a.f.tzz, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+            a.f.txx = f->txx; a.f.tyy = f->tyy; a.f.tzz = f->tzz;
+            g.txx = f->txx; g.tyy = f->tyy; g.tzz = f->tzz;
+        }
+        if (a.f.tyz != f->tyz) {
+            JRX_HIP(h, hipMemcpyAsync(f->tyz, a.f.tyz, (size_t)ne.yz * sizeof(double), hipMemcpyDeviceToDevice, s));
+            JRX_HIP(h, hipMemcpyAsync(f->txz, a.f.txz, (size_t)ne.xz * sizeof(double), hipMemcpyDeviceToDevice, s));
+            JRX_HIP(h, hipMemcpyAsync(f->txy, a.f.txy, (size_t)ne.xy * sizeof(double), hipMemcpyDeviceToDevice, s));
+            a.tnew[0] = a.f.tyz; a.tnew[1] = a.f.txz; a.tnew[2] = a.f.txy;
+            a.f.tyz = f->tyz; a.f.txz = f->txz; a.f.txy = f->txy;
+            g.tyz = f->tyz; g.txz = f->txz; g.txy = f->txy;
+        }
+        return JRX_OK;
+    };
     // one iteration without neighbours, enqueued on s; A / G: the kernel arguments and the view the velocity sweep takes (their edge-stress pointers swap)
     // planes per thread of k_vep3_pre: 8 where that gives the chip enough blocks, halved while the launch has fewer than 2048 (16^3: 19.3 k -> 26.0 k it/s with one plane per
     // thread, 32^3 18.1 k -> 23.3 k, 64^3 8.2 k -> 9.0 k, 128^3 +1 % with four; 256^3: eight planes stay the best, 318 against 304 it/s with one; profiles/r03_vep3d_small_grids.txt)
@@ -1685,71 +1702,21 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
         iter = it1;
         if (check) {
             JRX_TRY(jrx3d_sumsq(h, s, &g, &q));
-            JRX_HIP(h, hipMemcpyAsync(h->h_sums, h->d_sums, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-            JRX_HIP(h, hipStreamSynchronize(s));
-            double ss[4] = {h->h_sums[0], h->h_sums[1], h->h_sums[2], h->h_sums[3]};
-            JRX_TRY(jrx_allreduce_sum_host(h, ss, 4));                                                // norm_mpi
+            double ss[4];
+            JRX_TRY(jrx_read_sums(h, s, ss, true));                                                   // norm_mpi
             const double den = (double)((p->nxg - 1) * (p->nyg - 1) * (p->nzg - 1));                  // Stokes3D.jl:607-612
             const double nRx = sqrt(ss[0]) / den, nRy = sqrt(ss[1]) / den, nRz = sqrt(ss[2]) / den;
             const double nDV = sqrt(ss[3]) / (double)n;                                               // norm_mpi(RP) / length(RP): local length
-            err = fmax(fmax(nRx, nRy), fmax(nRz, nDV));
-            if (std::isnan(nRx) || std::isnan(nRy) || std::isnan(nRz) || std::isnan(nDV)) err = NAN;
-            if (cont < res->cap) {
-                if (res->norm_Rx) res->norm_Rx[cont] = nRx;
-                if (res->norm_Ry) res->norm_Ry[cont] = nRy;
-                if (res->norm_Rz) res->norm_Rz[cont] = nRz;
-                if (res->norm_divV) res->norm_divV[cont] = nDV;
-                if (res->err_evo1) res->err_evo1[cont] = err;
-                if (res->err_evo2) res->err_evo2[cont] = iter;
-            }
-            if (cont == 0) err_it1 = err;
-            cont++;
-            if (rank == 0 && ((p->verbose && (err / err_it1) > p->eps_rel && err > p->eps_abs) || iter == p->iterMax))
-                printf("iter = %lld, abs_err = %1.3e, rel_err = %1.3e [norm_Rx=%1.3e, norm_Ry=%1.3e, norm_Rz=%1.3e, norm_∇V=%1.3e] \n", (long long)iter,
-                       err, err / err_it1, nRx, nRy, nRz, nDV);
-            if (std::isnan(err)) {
-                // error("NaN(s)"): the current edge stresses may live in the second set -- leave them in the caller's arrays, drain the stream
-                if (a.f.eta != f->eta) (void)hipMemcpyAsync(f->eta, a.f.eta, n * sizeof(double), hipMemcpyDeviceToDevice, s);
-                if (a.f.txx != f->txx) {
-                    (void)hipMemcpyAsync(f->txx, a.f.txx, n * sizeof(double), hipMemcpyDeviceToDevice, s);
-                    (void)hipMemcpyAsync(f->tyy, a.f.tyy, n * sizeof(double), hipMemcpyDeviceToDevice, s);
-                    (void)hipMemcpyAsync(f->tzz, a.f.tzz, n * sizeof(double), hipMemcpyDeviceToDevice, s);
-                }
-                if (a.f.tyz != f->tyz) {
-                    (void)hipMemcpyAsync(f->tyz, a.f.tyz, (size_t)ne.yz * sizeof(double), hipMemcpyDeviceToDevice, s);
-                    (void)hipMemcpyAsync(f->txz, a.f.txz, (size_t)ne.xz * sizeof(double), hipMemcpyDeviceToDevice, s);
-                    (void)hipMemcpyAsync(f->txy, a.f.txy, (size_t)ne.xy * sizeof(double), hipMemcpyDeviceToDevice, s);
-                }
-                (void)hipEventRecord(t1, s);
-                (void)hipStreamSynchronize(s);
-                float msn = 0.f;
-                (void)hipEventElapsedTime(&msn, t0, t1);
-                res->iter = iter; res->nchecks = cont < res->cap ? cont : res->cap;
-                res->time_s = msn * 1e-3; res->av_time_s = iter > 1 ? res->time_s / (double)(iter - 1) : res->time_s;
-                return jrx_fail(h, JRX_ERR_NAN, "NaN(s)");
+            const double err = log.record(iter, nRx, nRy, nRz, nDV);
+            if (rank == 0 && ((p->verbose && log.rel() > p->eps_rel && err > p->eps_abs) || iter == p->iterMax)) log.print3d(iter, nRx, nRy, nRz, nDV);
+            if (std::isnan(err)) {      // error("NaN(s)")
+                (void)restore();
+                return log.fail_nan(h, iter, jrx_drain_ms(s, t0, t1));
             }
         }
     }
     JRX_HIP(h, hipEventRecord(t1, s));
-    if (a.f.eta != f->eta) {       // the relaxed η of the fused pre / centre kernel
-        JRX_HIP(h, hipMemcpyAsync(f->eta, a.f.eta, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-        a.f.eta = f->eta; g.eta = g.K = g.G = f->eta;
-    }
-    if (a.f.txx != f->txx) {       // the same for the normal stresses of the fused / forked centre pass
-        JRX_HIP(h, hipMemcpyAsync(f->txx, a.f.txx, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-        JRX_HIP(h, hipMemcpyAsync(f->tyy, a.f.tyy, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-        JRX_HIP(h, hipMemcpyAsync(f->tzz, a.f.tzz, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-        a.f.txx = f->txx; a.f.tyy = f->tyy; a.f.tzz = f->tzz;
-        g.txx = f->txx; g.tyy = f->tyy; g.tzz = f->tzz;
-    }
-    if (a.f.tyz != f->tyz) {       // odd number of swaps: leave the edge stresses in the caller's arrays
-        JRX_HIP(h, hipMemcpyAsync(f->tyz, a.f.tyz, (size_t)ne.yz * sizeof(double), hipMemcpyDeviceToDevice, s));
-        JRX_HIP(h, hipMemcpyAsync(f->txz, a.f.txz, (size_t)ne.xz * sizeof(double), hipMemcpyDeviceToDevice, s));
-        JRX_HIP(h, hipMemcpyAsync(f->txy, a.f.txy, (size_t)ne.xy * sizeof(double), hipMemcpyDeviceToDevice, s));
-        a.tnew[0] = a.f.tyz; a.tnew[1] = a.f.txz; a.tnew[2] = a.f.txy;
-        a.f.tyz = f->tyz; a.f.txz = f->txz; a.f.txy = f->txy;
-        g.tyz = f->tyz; g.txz = f->txz; g.txy = f->txy;
-    }
+    JRX_TRY(restore());
     // epilogue: vorticity, shear2center!, accumulate_tensor!/accumulate_vol!, τ -> τ_o (Stokes3D.jl:640-658)
     if (f->omega_yz && f->omega_xz && f->omega_xy)
         hipLaunchKernelGGL(k_vorticity3d, gv, dim3(256), 0, s, f->omega_yz, f->omega_xz, f->omega_xy, (const double *)f->Vx,
@@ -1765,22 +1732,11 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
                            (const double *)f->dexy, nx, ny, nz);
     hipLaunchKernelGGL(k_vep3_accumulate, g0, dim3(256), 0, s, a);
     JRX_LAUNCH_CHECK(h);
-    const i64 nc = (i64)n;
-    h->opv.valid = false;      // τ_o is written: a cached verdict of the 3D visco-elastic operand pass (option operand_cache) may describe these arrays
-    hipLaunchKernelGGL(k_copy6, dim3(1024), dim3(256), 0, s, f->toxx, (const double *)f->txx, nc, f->toyy, (const double *)f->tyy, nc, f->tozz,
-                       (const double *)f->tzz, nc, f->toyz, (const double *)f->tyz, ne.yz, f->toxz, (const double *)f->txz, ne.xz, f->toxy,
-                       (const double *)f->txy, ne.xy);
-    hipLaunchKernelGGL(k_copy6, dim3(1024), dim3(256), 0, s, f->toyz_c, (const double *)f->tyz_c, nc, f->toxz_c, (const double *)f->txz_c, nc, f->toxy_c,
-                       (const double *)f->txy_c, nc, (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0,
-                       (double *)nullptr, (const double *)nullptr, (i64)0);
-    JRX_LAUNCH_CHECK(h);
+    JRX_TRY((jrx3d_copy_old_stresses<1024>(h, s, f, nx, ny, nz)));
     JRX_HIP(h, hipStreamSynchronize(s));
     float ms = 0.f;
     JRX_HIP(h, hipEventElapsedTime(&ms, t0, t1));
-    res->iter = iter;
-    res->nchecks = cont < res->cap ? cont : res->cap;
-    res->time_s = ms * 1e-3;
-    res->av_time_s = iter > 1 ? res->time_s / (double)(iter - 1) : res->time_s;
+    log.finish(iter, ms);
     return JRX_OK;
 }
 

@@ -463,12 +463,6 @@ __global__ __launch_bounds__(256) void k_vs3_phase_avg(double *__restrict__ Kc, 
 #undef VY
 #undef VZ
 
-struct EdgeN3 { i64 yz, xz, xy; };
-EdgeN3 vs3_edge_counts(const jrx_vep3d_params *p)
-{
-    return EdgeN3{(i64)p->nx * (p->ny + 1) * (p->nz + 1), (i64)(p->nx + 1) * p->ny * (p->nz + 1), (i64)(p->nx + 1) * (p->ny + 1) * p->nz};
-}
-
 // what the 3D variational driver and its kernel entry points refuse (status JRX_ERR_ARG, each named).  jrx_vep3d_params carries scalar spacings only: a non-uniform
 // Geometry cannot reach the library and is refused by the binding
 jrx_status vs3_check(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_rock_ratio3d *phi, const jrx_rheology *rh, const jrx_vep3d_params *p, int air_phase, bool solver = true)
@@ -580,7 +574,7 @@ jrx_status jrx_vs3d_update_stresses(jrx_handle *h, const jrx_vep3d_fields *f, co
                          f->toxy_c, f->eta, f->eta_vep, f->EII_pl, f->evol_pl, f->phase_c, f->phase_yz, f->phase_xz, f->phase_xy};
     for (const void *q : req)
         if (!q) return jrx_fail(h, JRX_ERR_ARG, "update_stresses_center_vertex!: a required field pointer is NULL");
-    const EdgeN3 ne = vs3_edge_counts(p);
+    const EdgeN ne = edge_counts(p->nx, p->ny, p->nz);
     const size_t n = (size_t)p->nx * p->ny * p->nz, nedge = (size_t)(ne.yz + ne.xz + ne.xy);
     Vs3Args a = vs3_make(f, phi, rh, p, 0);
     JRX_TRY(vs3_flags(h, a, nedge + 3 * n));
@@ -633,7 +627,7 @@ jrx_status jrx_stokes3d_vs_solve(jrx_handle *h, const jrx_vep3d_fields *f, const
         if (!q) return jrx_fail(h, JRX_ERR_ARG, "a required 3D VEP field pointer is NULL");
     const int nx = (int)p->nx, ny = (int)p->ny, nz = (int)p->nz;
     const size_t n = (size_t)nx * ny * nz;
-    const EdgeN3 ne = vs3_edge_counts(p);
+    const EdgeN ne = edge_counts(p->nx, p->ny, p->nz);
     const size_t nedge = (size_t)(ne.yz + ne.xz + ne.xy);
     hipStream_t s = h->stream;
     // library scratch: ητ, θ, λ, K, G, the second η, the second τxx, τyy, τzz, the phase viscosity of linear laws (centres), λv and the second edge stresses, then the byte flags
@@ -679,10 +673,10 @@ jrx_status jrx_stokes3d_vs_solve(jrx_handle *h, const jrx_vep3d_fields *f, const
     memset(&q, 0, sizeof(q));
     q.nx = nx; q.ny = ny; q.nz = nz;
 
-    double err_it1 = 1.0, err = INFINITY;
-    int64_t iter = 0, cont = 0;
+    PtLog log(res, INFINITY);
+    int64_t iter = 0;
     res->iter = 0; res->nchecks = 0;
-    auto keep_going = [&](int64_t it) { return it < 2 || (((err / err_it1) > p->eps_rel && err > p->eps_abs) && it <= p->iterMax); };      // :79: no iterMin
+    auto keep_going = [&](int64_t it) { return it < 2 || ((log.rel() > p->eps_rel && log.err() > p->eps_abs) && it <= p->iterMax); };      // :79: no iterMin
     auto swap = [](double *&x, double *&y) { double *t_ = x; x = y; y = t_; };
     auto restore = [&]() {      // an odd number of swaps: leave η, τxx, τyy, τzz and the edge stresses in the caller's arrays
         if (a.f.eta != f->eta) {
@@ -724,35 +718,16 @@ jrx_status jrx_stokes3d_vs_solve(jrx_handle *h, const jrx_vep3d_fields *f, const
         else if (last) JRX_TRY(jrx3d_bcs(h, s, f->Ux, f->Uy, f->Uz, nx, ny, nz, p->free_slip, p->no_slip, p->periodic));
         if (check) {
             JRX_TRY(jrx3d_sumsq(h, s, &g, &q));       // Ri[2:end-1, 2:end-1, 2:end-1] and RP, not restricted to valid nodes :175-181
-            JRX_HIP(h, hipMemcpyAsync(h->h_sums, h->d_sums, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-            JRX_HIP(h, hipStreamSynchronize(s));
+            double ss[4];
+            JRX_TRY(jrx_read_sums(h, s, ss, false));      // single block (vs3_check)
             const double den = sqrt((double)((p->nxg - 1) * (p->nyg - 1) * (p->nzg - 1)));      // a square root here, unlike the unmasked 3D driver
-            const double nRx = sqrt(h->h_sums[0]) / den, nRy = sqrt(h->h_sums[1]) / den, nRz = sqrt(h->h_sums[2]) / den;
-            const double nDV = sqrt(h->h_sums[3]) / (double)n;
-            err = fmax(fmax(nRx, nRy), fmax(nRz, nDV));
-            if (std::isnan(nRx) || std::isnan(nRy) || std::isnan(nRz) || std::isnan(nDV)) err = NAN;
-            if (cont < res->cap) {
-                if (res->norm_Rx) res->norm_Rx[cont] = nRx;
-                if (res->norm_Ry) res->norm_Ry[cont] = nRy;
-                if (res->norm_Rz) res->norm_Rz[cont] = nRz;
-                if (res->norm_divV) res->norm_divV[cont] = nDV;
-                if (res->err_evo1) res->err_evo1[cont] = err;
-                if (res->err_evo2) res->err_evo2[cont] = iter;
-            }
-            if (cont == 0) err_it1 = err;
-            cont++;
-            if ((p->verbose && (err / err_it1) > p->eps_rel && err > p->eps_abs) || iter == p->iterMax)
-                printf("iter = %lld, abs_err = %1.3e, rel_err = %1.3e [norm_Rx=%1.3e, norm_Ry=%1.3e, norm_Rz=%1.3e, norm_∇V=%1.3e] \n", (long long)iter, err,
-                       err / err_it1, nRx, nRy, nRz, nDV);
+            const double nRx = sqrt(ss[0]) / den, nRy = sqrt(ss[1]) / den, nRz = sqrt(ss[2]) / den;
+            const double nDV = sqrt(ss[3]) / (double)n;
+            const double err = log.record(iter, nRx, nRy, nRz, nDV);
+            if ((p->verbose && log.rel() > p->eps_rel && err > p->eps_abs) || iter == p->iterMax) log.print3d(iter, nRx, nRy, nRz, nDV);
             if (std::isnan(err)) {      // error("NaN(s)"): leave the caller's arrays consistent and the stream drained
                 restore();
-                (void)hipEventRecord(h->ev[7], s);
-                (void)hipStreamSynchronize(s);
-                float msn = 0.f;
-                (void)hipEventElapsedTime(&msn, h->ev[6], h->ev[7]);
-                res->iter = iter; res->nchecks = cont < res->cap ? cont : res->cap;
-                res->time_s = msn * 1e-3; res->av_time_s = iter > 1 ? res->time_s / (double)(iter - 1) : res->time_s;
-                return jrx_fail(h, JRX_ERR_NAN, "NaN(s)");
+                return log.fail_nan(h, iter, jrx_drain_ms(s, h->ev[6], h->ev[7]));
             }
         }
     }
@@ -769,19 +744,9 @@ jrx_status jrx_stokes3d_vs_solve(jrx_handle *h, const jrx_vep3d_fields *f, const
         JRX_TRY(jrx_shear2center3d(h, f->deyz_c, f->dexz_c, f->dexy_c, f->deyz, f->dexz, f->dexy, nx, ny, nz));
     JRX_TRY(jrx_accumulate_tensor3d(h, f->EII_pl, f->eplxx, f->eplyy, f->eplzz, f->eplyz, f->eplxz, f->eplxy, p->dt, nx, ny, nz));
     JRX_TRY(jrx_accumulate_vol(h, f->EVol_pl, f->evol_pl, p->dt, (int64_t)n));
-    h->opv.valid = false;      // τ_o is written: a cached verdict of the operand pass may describe these arrays
-    const i64 nc = (i64)n;
-    hipLaunchKernelGGL(k_copy6, dim3(1024), dim3(256), 0, s, f->toxx, (const double *)f->txx, nc, f->toyy, (const double *)f->tyy, nc, f->tozz, (const double *)f->tzz, nc,
-                       f->toyz, (const double *)f->tyz, ne.yz, f->toxz, (const double *)f->txz, ne.xz, f->toxy, (const double *)f->txy, ne.xy);
-    hipLaunchKernelGGL(k_copy6, dim3(1024), dim3(256), 0, s, f->toyz_c, (const double *)f->tyz_c, nc, f->toxz_c, (const double *)f->txz_c, nc, f->toxy_c,
-                       (const double *)f->txy_c, nc, (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0,
-                       (double *)nullptr, (const double *)nullptr, (i64)0);
-    JRX_LAUNCH_CHECK(h);
+    JRX_TRY((jrx3d_copy_old_stresses<1024>(h, s, f, nx, ny, nz)));
     JRX_HIP(h, hipStreamSynchronize(s));
-    res->iter = iter;
-    res->nchecks = cont < res->cap ? cont : res->cap;
-    res->time_s = ms * 1e-3;
-    res->av_time_s = iter > 1 ? res->time_s / (double)(iter - 1) : res->time_s;
+    log.finish(iter, ms);
     return JRX_OK;
 }
 

@@ -337,3 +337,33 @@ def test_viscosity_air_phase_with_power_law_creep_matches_restatement(jr, tau):
     assert max_rel_diff(got["eta"], a["eta"]) <= 1e-12 and max_rel_diff(got["eta_v"], a["eta_v"]) <= 1e-12
     inside = (a["eta"] > cutoff[0]) & (a["eta"] < cutoff[1])
     assert inside.mean() > 0.3 and (a["eta"] != eta0).all() and (a["eta"] == cutoff[1]).any()
+
+
+def test_nan_exit_leaves_the_current_stresses_in_the_callers_arrays(jr):
+    """error("NaN(s)") at the first check, iteration 3: after an odd number of pointer swaps the current τxx, τyy and η live in the library's second set and the NaN
+    exit has to copy them back.  One phase, linear viscosity, 8 x 8 cells, one NaN in an interior Vx entry; the caller's arrays after the failed call equal those of
+    a call that runs the same three iterations unchecked (nout > iterMax, iterMax = 2: the loop runs while iter <= iterMax) and returns normally."""
+    from justrelax_jl_amd._lib import JrxError
+    outs = []
+    for iterMax, nout in ((20, 3), (2, 100)):
+        s = jr.miniapps.shearband2d_variational(8, iterMax=iterMax, nout=nout)
+        phases = [s.extra["phases"][0]]
+        for k in ("phase_c", "phase_v", "phase_vx", "phase_vy"):
+            s.arrays[k] = np.ones((1,) + s.arrays[k].shape[1:], order="F")
+        s.arrays["Vx"][1, 1] = np.nan
+        stokes, pr, ρg = _upload(jr, s)
+        ϕ = jr.RockRatio(jr.AMDGPUBackend, s.ni)
+        jr.update_rock_ratio_(ϕ, pr, 0)
+        solve = lambda: jr.solve_VariationalStokes_(stokes, s.pt, s.grid, s.flow_bcs, ρg, pr, ϕ, phases, None, s.dt, None, kwargs=s.kwargs)
+        if nout == 3:
+            with pytest.raises(JrxError) as e:
+                solve()
+            assert e.value.status == 1 and "JRX_ERR_NAN" in str(e.value)
+        else:
+            r = solve()
+            assert r.iter == 3 and len(r.err_evo1) == 0
+        outs.append(_download(jr, stokes))
+    assert np.isnan(outs[0]["txx"]).any()
+    for k in ("txx", "tyy", "txy", "txy_c", "eta"):
+        assert np.array_equal(outs[0][k], outs[1][k], equal_nan=True), k
+        assert np.isfinite(outs[0][k]).any(), k

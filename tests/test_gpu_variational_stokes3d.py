@@ -327,3 +327,35 @@ def test_viscosity_air_phase_matches_restatement(jr, tau):
     assert inside.mean() > 0.3 and (a["eta"] != eta0).all() and (a["eta"] == cutoff[1]).any()
     mixed = (a["phase_c"][:2] > 0).all(axis=0) | ((a["phase_c"][2] > 0) & (a["phase_c"][2] < 1))
     assert mixed.any()
+
+
+def test_nan_exit_leaves_the_current_stresses_in_the_callers_arrays(jr):
+    """error("NaN(s)") at the first check, iteration 3: after an odd number of pointer swaps the current η, τxx, τyy, τzz and edge stresses live in the library's
+    second sets and the NaN exit has to copy them back.  One phase, linear viscosity, 8^3 cells, one NaN in an interior Vx entry; the caller's arrays after the
+    failed call equal those of a call that runs the same three iterations unchecked (nout > iterMax, iterMax = 2: the loop runs while iter <= iterMax) and
+    returns normally."""
+    from justrelax_jl_amd._lib import JrxError
+    outs = []
+    for iterMax, nout in ((20, 3), (2, 100)):
+        s = jr.miniapps.shearband3d_variational((8, 8, 8), iterMax=iterMax, nout=nout)
+        phases = [s.extra["phases"][0]]
+        for k in PHASE_MEMBERS.values():
+            s.arrays[k] = np.ones((1,) + s.arrays[k].shape[1:], order="F")
+        s.arrays["eta"][...] = phases[0]["eta"]
+        s.arrays["Vx"][1, 1, 1] = np.nan
+        stokes, pr, ρg = _upload(jr, s)
+        ϕ = jr.RockRatio(jr.AMDGPUBackend, s.ni)
+        jr.update_rock_ratio_(ϕ, pr, 0)
+        solve = lambda: jr.solve_VariationalStokes_(stokes, s.pt, s.grid, s.flow_bcs, ρg, pr, ϕ, phases, None, s.dt, None, kwargs=s.kwargs)
+        if nout == 3:
+            with pytest.raises(JrxError) as e:
+                solve()
+            assert e.value.status == 1 and "JRX_ERR_NAN" in str(e.value)
+        else:
+            r = solve()
+            assert r.iter == 3 and len(r.err_evo1) == 0
+        outs.append(_download(jr, stokes))
+    assert np.isnan(outs[0]["txx"]).any()
+    for k in ("txx", "tyy", "tzz", "tyz", "txz", "txy", "eta"):
+        assert np.array_equal(outs[0][k], outs[1][k], equal_nan=True), k
+        assert np.isfinite(outs[0][k]).any(), k

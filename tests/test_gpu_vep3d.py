@@ -31,7 +31,7 @@ def _upload(jr, s):
     st = jr.StokesArrays(jr.AMDGPUBackend, s.ni)
     for k, path in VEP3_MAP.items():
         _get(st, path).copy_(from_numpy(s.arrays[k], dev))
-    pr = jr.PhaseRatios(jr.AMDGPUBackend, 2, s.ni)
+    pr = jr.PhaseRatios(jr.AMDGPUBackend, s.arrays["phase_c"].shape[0], s.ni)
     for k, name in (("phase_c", "center"), ("phase_yz", "yz"), ("phase_xz", "xz"), ("phase_xy", "xy")):
         getattr(pr, name).copy_(from_numpy(s.arrays[k], dev))
     ρg = tuple(from_numpy(s.arrays[k], dev) for k in ("fx", "fy", "fz"))
@@ -406,3 +406,36 @@ def test_vep3d_solve_with_other_phase_counts_fused_equals_unfused(jr, nphase):
     for v in (1, 2, 3):
         for k in outs[0]:
             assert np.array_equal(outs[0][k], outs[v][k], equal_nan=True), (v, k)
+
+
+def test_nan_exit_leaves_the_current_stresses_in_the_callers_arrays(jr):
+    """error("NaN(s)") at the first check, iteration 3: after an odd number of pointer swaps the current η, τxx, τyy, τzz (fused pre / centre kernel) and edge stresses
+    live in the library's second sets and the NaN exit has to copy them back.  One phase, linear viscosity, 8^3 cells, one NaN in an interior Vx entry; the caller's
+    arrays after the failed call equal those of a call that runs the same three iterations unchecked (nout > iterMax, iterMax = 2: the loop runs while
+    iter <= iterMax) and returns normally."""
+    from justrelax_jl_amd import _lib
+    h = _lib.default_handle()
+    outs = []
+    for iterMax, nout in ((20, 3), (2, 100)):
+        s = jr.miniapps.shearband3d((8, 8, 8), iterMax=iterMax, nout=nout)
+        phases = [s.extra["phases"][0]]
+        for k in ("phase_c", "phase_yz", "phase_xz", "phase_xy"):
+            s.arrays[k] = np.ones((1,) + s.arrays[k].shape[1:], order="F")
+        s.arrays["eta"][...] = phases[0]["eta"]
+        s.arrays["Vx"][1, 1, 1] = np.nan
+        stokes, pr, ρg = _upload(jr, s)
+        n0 = h.get_option("stat_vep3_fused")
+        solve = lambda: jr.solve_(stokes, s.pt, s.grid, s.flow_bcs, ρg, pr, phases, None, s.dt, None, kwargs=s.kwargs)
+        if nout == 3:
+            with pytest.raises(_lib.JrxError) as e:
+                solve()
+            assert e.value.status == 1 and "JRX_ERR_NAN" in str(e.value)
+        else:
+            r = solve()
+            assert r.iter == 3 and len(r.err_evo1) == 0
+        assert h.get_option("stat_vep3_fused") == n0 + 3          # η and the normal stresses swap too
+        outs.append(_download(jr, stokes))
+    assert np.isnan(outs[0]["txx"]).any()
+    for k in ("txx", "tyy", "tzz", "tyz", "txz", "txy", "eta"):
+        assert np.array_equal(outs[0][k], outs[1][k], equal_nan=True), k
+        assert np.isfinite(outs[0][k]).any(), k
