@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cmath>
+#include <type_traits>
 #include "jrx.h"
 #include "pt_log.hpp"
 
@@ -84,7 +85,6 @@ struct jrx_handle {
     int thermal_tile = 0;                // tuning (round 6): fused 3D heat diffusion, array / rheology form: 4 / 8 = 64 x TY tiles with the rows j +- 1 through LDS (k_thermal3d_fused_t)
     bool fused2d = true;                 // 2D visco-elastic loop: one-launch iterations on launch-bound grids
     bool vep3_peel = true;                   // z-marching edge kernel: a nearly empty last lane segment goes to the node kernel (A/B)
-    bool vep3_peel_fork = false;             // ... that thin launch on the halo stream beside the main edge kernel (measured 1 % slower at 256^3: off; A/B)
     bool vep3_nt = false;                    // 3D VEP kernels: non-temporal stores of the outputs (measured neutral at 256^3: off; A/B)
     int vep3_prekz = 0;                      // planes per thread of k_vep3_pre: 0 = by the number of blocks (default), 1 .. 32 force a depth (A/B)
     int vep3_cfg = 0;                        // z-marching edge kernel: KZ * 10 + min blocks per CU, 0 = default
@@ -101,8 +101,6 @@ struct jrx_handle {
     int vep3_prec_tile = 2;                  // fused pre / centre kernel: 1 = 64 x 4 tiles of node columns per block, 0 = 256 consecutive nodes of the flattened plane, 2 (default) = tiles from 16,384 node columns per plane
     bool vep3_np_const = true;               // 3D VEP centre pass (and the fused pre / centre kernel): instantiations with the phase count as a constant (1..4): ratios loaded in one batch, phase loops unrolled
     bool vep3_fuse_pc = true;                // 3D VEP driver without neighbours, linear laws: k_vep3_pre + k_vep3_visc + k_vep3_centre as one kernel ahead of the edge pass (k_vep3_prec; second sets of η and τxx, τyy, τzz)
-    bool vep3_fork = false;                  // 3D VEP driver without neighbours: the centre pass of the stress update on the halo stream beside the edge pass (second set of τxx, τyy, τzz).
-                                             // Measured 256^3 311.6 / 311.4 / 312.2 it/s forked vs 312.7 / 313.2 / 312.2 in order (profiles/r04_vep3d_fork.txt): nothing to gain, off
     bool vep3_map = true, vep3_xcd = true;   // 3D VEP edge kernel thread mapping / XCD slab order (A/B)
     bool scratch_sets = true;            // the fused pipelines may allocate their library-owned second state set (0: never -- un-fused paths)
     bool weno_fused = true;              // tuning: WENO_advection! as three fused launches (0: the reference's six, flux arrays in memory; bit-identical)
@@ -154,6 +152,14 @@ static inline jrx_status jrx_fail(jrx_handle *h, jrx_status st, const char *fmt,
     } while (0)
 
 #define JRX_LAUNCH_CHECK(h) JRX_HIP(h, hipGetLastError())
+
+// A run-time integer as a template argument: calls f(std::integral_constant<int, V>) for the V among VS... that equals v and returns true; false, and no call, when none
+// does.  Only the listed values are instantiated -- the list is the set of kernels a call site builds, e.g. dispatch_const<0, 1, 2, 3, 4>(np, [&](auto NP) { launch k<NP()> })
+template <int... VS, class F>
+static inline bool dispatch_const(int v, F &&f)
+{
+    return ((v == VS && (f(std::integral_constant<int, VS>{}), true)) || ...);
+}
 
 // the instantiated hipGraphs of one driver call: released on every exit path (error returns included)
 struct GraphExecs {

@@ -16,6 +16,7 @@
 #include "jrx_internal.hpp"
 #include "jrx_kernels.hpp"
 #include "jrx_material.hpp"
+#include "vep3_plan.hpp"
 
 namespace {
 
@@ -26,7 +27,7 @@ struct Vep3Args {
     const double *eta_lin = nullptr;   // linear laws: the phase average of η (constant over a solve), precomputed by k_vep3_phase_avg; nullptr: computed per call
     double *theta, *lam;
     double *lamv[3], *tnew[3];
-    double *cnew[3] = {nullptr, nullptr, nullptr};   // centre pass: where the new τxx, τyy, τzz go (nullptr: in place).  A second set lets the centre pass run BESIDE the edge pass, which averages the OLD normal stresses
+    double *cnew[3] = {nullptr, nullptr, nullptr};   // centre pass: where the new τxx, τyy, τzz go (nullptr: in place).  A second set lets the centre pass run AHEAD of the edge pass (k_vep3_prec), which averages the OLD normal stresses
     double _dx, _dy, _dz, dt, r, theta_dtau, rel, nu, cut_lo, cut_hi;
     int nx, ny, nz;
     bool soft;            // some phase has a softening law: the yield function then reads EII_pl
@@ -1162,131 +1163,107 @@ Vep3Args make_vep3(const jrx_vep3d_fields *f, const jrx_rheology *rh, const jrx_
     return a;
 }
 
-// the three edge passes, the commit of the new edge stresses, then the centre pass
-// commit = false: the caller adopts a.tnew as the current edge-stress arrays (pointer swap) instead of copying them back
-// which: 0 = both passes, 1 = the edge pass alone, 2 = the centre pass alone (the multi-rank driver exchanges the new edge stresses in between)
-// loop: called by the solve loop -- the form of the edge pass then follows the grid size (the kernel-level entry points keep the form the switch names)
-jrx_status launch_vep3_stress(jrx_handle *h, hipStream_t s, const Vep3Args &a, const jrx_vep3d_params *p, bool commit = true, int which = 0, bool loop = false)
+// the plan of the edge pass for this handle's options (vep3_plan.hpp); a combination no kernel is built for is an argument error before anything is launched
+jrx_status plan_vep3_edges(jrx_handle *h, const Vep3Args &a, bool loop, Vep3EdgePlan *pl)
 {
-    const int nx = a.nx, ny = a.ny, nz = a.nz;
-    // Small grids (the reference's own 3D tests run at 16^3 .. 32^3): the z-marching edge kernel has a few hundred blocks, each a chain of 16 dependent planes, and the
-    // one-node-per-thread kernel is the faster form -- 16^3 14.1 k -> 19.4 k it/s, 32^3 13.0 k -> 18.1 k, 48^3 10.5 k -> 12.4 k; equal at 56^3, z-marching from there on
-    // (scripts/bench_vep3d_sizes.py, profiles/r03_vep3d_small_grids.txt)
-    const int edges = (loop && h->vep3_edges == 4 && (double)(nx + 1) * (ny + 1) * (nz + 1) <= 125000.0) ? 0 : h->vep3_edges;
-    if (which != 2) {
-    const bool p4 = h->vep3_map, xs = h->vep3_xcd;     // options "vep3_map", "vep3_xcd" (XCD slab order: +1-2 % measured)
-    if (edges >= 1 && a.rh.nphase <= 4) {
-        // option "vep3_edges": 0 one node per thread (k_vep3_edges; also the form more than 4 phases use), 1 (default) the z-marching
-        // kernel with one family per block and the three blocks of a tile on one XCD, 2 the same kernel as one launch per family (A/B: the L2 sharing)
-        const int cfg = h->vep3_cfg ? h->vep3_cfg : 162;           // option "vep3_cfg" = KZ * 10 + min blocks per CU (tuning); 0: KZ by the grid size (below)
-        int kz = cfg / 10;
-        const int mb = cfg % 10, np_ = a.rh.nphase;
-        // lane segments of 62 node columns; a last segment that would be less than 40 % full (256^3: 257 = 4 x 62 + 9) is not launched -- its node columns
-        // go to the one-node-per-thread kernel in a thin launch of their own (the two launches write disjoint nodes and read old values only)
-        const int nfull = (nx + 1) / 62, rem = (nx + 1) - 62 * nfull;
-        // (a thin last segment is only worth a launch of its own behind at least two full ones: 72^3 6.9 k -> 7.3 k, 80^3 5.5 k -> 6.4 k it/s without it, 128^3 2.03 k with against 1.98 k without)
-        const bool peel = nfull >= 2 && rem > 0 && rem <= 24 && h->vep3_peel;
-        const int nseg = peel ? nfull : (nx + 1 + 61) / 62, ilim = peel ? 62 * nfull : nx + 1;
-        // chunk depth of the LDS-sharing form: 16 planes where that gives the chip enough blocks, halved (down to 4) while the launch has fewer than 3000 -- 56^3 12.6 k -> 15.6 k it/s,
-        // 64^3 9.6 k -> 10.7 k, 96^3 4.12 k -> 4.33 k, 128^3 +1.4 %; from 160^3 on 16 planes are the best (profiles/r03_vep3d_small_grids.txt)
-        if (!h->vep3_cfg && edges == 4 && !a.soft)
-            while (kz > 4 && (i64)nseg * (ny + 1) * ((nz + kz) / kz) < 3000) kz /= 2;
-        const int ntxy = nseg * ((ny + 1 + 3) / 4), nzc = (nz + 1 + kz - 1) / kz, nt = ntxy * nzc;
-        bool ok = false;
-        // the peeled columns are independent of the main launch (disjoint nodes written, only old values read); tuning switch "vep3_peel_fork" runs the thin,
-        // load-instruction-bound node kernel (0.14 ms for 3.5 % of the nodes at 256^3) on the halo stream beside the main kernel -- measured 266.1 / 267.6 it/s
-        // forked vs 269.2 / 269.8 in order (256^3, same box, alternating): off
-        const bool fork = peel && h->vep3_peel_fork && s == h->stream && !jrx_comm_active(h);      // (with neighbours the halo stream carries the exchanges)
-        hipStream_t ps = fork ? h->halo_stream : s;
-        if (fork) {
-            JRX_HIP(h, hipEventRecord(h->ev[5], s));
-            JRX_HIP(h, hipStreamWaitEvent(ps, h->ev[5], 0));
-        }
-        if (peel) {
-            const dim3 gp((unsigned)(((i64)rem * (ny + 1) + 63) / 64), (unsigned)((nz + 1 + 3) / 4));
-            if (a.soft) hipLaunchKernelGGL((k_vep3_edges<true, false, true>), gp, dim3(256), 0, ps, a, ilim, rem);
-            else switch (h->vep3_np_const ? np_ : 0) {
-            case 1: hipLaunchKernelGGL((k_vep3_edges<true, false, false, 1>), gp, dim3(256), 0, ps, a, ilim, rem); break;
-            case 2: hipLaunchKernelGGL((k_vep3_edges<true, false, false, 2>), gp, dim3(256), 0, ps, a, ilim, rem); break;
-            case 3: hipLaunchKernelGGL((k_vep3_edges<true, false, false, 3>), gp, dim3(256), 0, ps, a, ilim, rem); break;
-            case 4: hipLaunchKernelGGL((k_vep3_edges<true, false, false, 4>), gp, dim3(256), 0, ps, a, ilim, rem); break;
-            default: hipLaunchKernelGGL((k_vep3_edges<true, false, false>), gp, dim3(256), 0, ps, a, ilim, rem);
-            }
-        }
-        struct Join { jrx_handle *h; hipStream_t s, ps; bool on; ~Join() { if (on) { (void)hipEventRecord(h->ev[5], ps); (void)hipStreamWaitEvent(s, h->ev[5], 0); } } } join{h, s, ps, fork};
-        if (a.soft && edges == 5) {       // softening laws: the yield function also reads the edge average of EII_pl (a twelfth shared centre array);
-                                                  // measured at 256^3: 195.7 it/s through LDS vs 214.9 with one family per block (254 VGPRs either way): only on request
-            const int ntxy_l = nseg * (ny + 1), nt_l = ntxy_l * nzc;
-            const dim3 gl((unsigned)(((nt_l + 7) / 8) * 8));
-#define EZLS(NP_) if (kz == 16 && np_ == NP_) { hipLaunchKernelGGL((k_vep3_edges_zl<16, NP_, true>), gl, dim3(192), 0, s, a, nseg, ntxy_l, nt_l, ilim); ok = true; }
-            EZLS(1) EZLS(2) EZLS(3) EZLS(4)
-#undef EZLS
-        } else if (a.soft) {
-            const dim3 gf((unsigned)(((nt + 7) / 8) * 8 * 3));
-#define EZS(NP_) if (kz == 16 && np_ == NP_) { hipLaunchKernelGGL((k_vep3_edges_zf<16, NP_, 2, true>), gf, dim3(256), 0, s, a, nseg, ntxy, nt, ilim); ok = true; }
-            EZS(1) EZS(2) EZS(3) EZS(4)
-#undef EZS
-        } else if (edges == 6) {
-            const int ntxy_l = nseg * (ny + 1), nt_l = ntxy_l * nzc;
-            const dim3 gl((unsigned)(((nt_l + 7) / 8) * 8));
-#define EZP(KZ_, NP_) if (kz == KZ_ && np_ == NP_) { hipLaunchKernelGGL((k_vep3_edges_zp<KZ_, NP_>), gl, dim3(256), 0, s, a, nseg, ntxy_l, nt_l, ilim); ok = true; }
-            EZP(16, 1) EZP(16, 2) EZP(16, 3) EZP(16, 4)
-#undef EZP
-        } else if (edges == 3 || edges == 4) {
-            const int ntxy_l = nseg * (ny + 1), nt_l = ntxy_l * nzc;
-            const dim3 gl((unsigned)(((nt_l + 7) / 8) * 8));
-#define EZL(NP_) if (kz == 16 && np_ == NP_) { if (edges == 4) hipLaunchKernelGGL((k_vep3_edges_zl<16, NP_, false, true>), gl, dim3(192), 0, s, a, nseg, ntxy_l, nt_l, ilim); \
-                else hipLaunchKernelGGL((k_vep3_edges_zl<16, NP_>), gl, dim3(192), 0, s, a, nseg, ntxy_l, nt_l, ilim); ok = true; }
-            EZL(1) EZL(2) EZL(3) EZL(4)
-#undef EZL
-#define EZLK(KZ_, NP_) if (!ok && kz == KZ_ && np_ == NP_ && edges == 4) { hipLaunchKernelGGL((k_vep3_edges_zl<KZ_, NP_, false, true>), gl, dim3(192), 0, s, a, nseg, ntxy_l, nt_l, ilim); ok = true; }
-            EZLK(8, 1) EZLK(8, 2) EZLK(8, 3) EZLK(8, 4) EZLK(4, 1) EZLK(4, 2) EZLK(4, 3) EZLK(4, 4)
-#undef EZLK
+    *pl = vep3_plan_edges(a.nx, a.ny, a.nz, a.rh.nphase, a.soft, loop, h->vep3_edges, h->vep3_cfg, h->vep3_peel);
+    return pl->refused ? jrx_fail(h, JRX_ERR_ARG, "%s", pl->refused) : JRX_OK;
+}
 
-        } else if (edges == 2) {
-            const dim3 g((unsigned)ntxy, (unsigned)nzc);
-#define EZ(NP_) if (kz == 16 && np_ == NP_) { hipLaunchKernelGGL((k_vep3_edges_z<16, NP_, 1>), g, dim3(256), 0, s, a, nseg, ilim); \
-                hipLaunchKernelGGL((k_vep3_edges_z<16, NP_, 2>), g, dim3(256), 0, s, a, nseg, ilim); \
-                hipLaunchKernelGGL((k_vep3_edges_z<16, NP_, 4>), g, dim3(256), 0, s, a, nseg, ilim); ok = true; }
-            EZ(1) EZ(2) EZ(3) EZ(4)
-#undef EZ
-        } else {
-            const dim3 gf((unsigned)(((nt + 7) / 8) * 8 * 3));
-#define EZG(KZ_, NP_, MB_) if (kz == KZ_ && mb == MB_ && np_ == NP_) { hipLaunchKernelGGL((k_vep3_edges_zf<KZ_, NP_, MB_>), gf, dim3(256), 0, s, a, nseg, ntxy, nt, ilim); ok = true; }
-#define EZN(KZ_, MB_) EZG(KZ_, 1, MB_) EZG(KZ_, 2, MB_) EZG(KZ_, 3, MB_) EZG(KZ_, 4, MB_)
-            EZN(16, 2) EZN(16, 3) EZN(8, 2)
-#undef EZN
-#undef EZG
-        }
-        if (!ok) return jrx_fail(h, JRX_ERR_ARG, "vep3_cfg: no such configuration");
-    } else if (a.soft) hipLaunchKernelGGL((k_vep3_edges<true, true, true>), GRID_IJK4(nx + 1, ny + 1, nz + 1), dim3(256), 0, s, a, 0, nx + 1);
-    else if (p4 && xs) switch (h->vep3_np_const && a.rh.nphase <= 4 ? a.rh.nphase : 0) {
-        case 1: hipLaunchKernelGGL((k_vep3_edges<true, true, false, 1>), GRID_IJK4(nx + 1, ny + 1, nz + 1), dim3(256), 0, s, a, 0, nx + 1); break;
-        case 2: hipLaunchKernelGGL((k_vep3_edges<true, true, false, 2>), GRID_IJK4(nx + 1, ny + 1, nz + 1), dim3(256), 0, s, a, 0, nx + 1); break;
-        case 3: hipLaunchKernelGGL((k_vep3_edges<true, true, false, 3>), GRID_IJK4(nx + 1, ny + 1, nz + 1), dim3(256), 0, s, a, 0, nx + 1); break;
-        case 4: hipLaunchKernelGGL((k_vep3_edges<true, true, false, 4>), GRID_IJK4(nx + 1, ny + 1, nz + 1), dim3(256), 0, s, a, 0, nx + 1); break;
-        default: hipLaunchKernelGGL((k_vep3_edges<true, true>), GRID_IJK4(nx + 1, ny + 1, nz + 1), dim3(256), 0, s, a, 0, nx + 1);
-    }
-    else if (p4) hipLaunchKernelGGL(k_vep3_edges<true>, GRID_IJK4(nx + 1, ny + 1, nz + 1), dim3(256), 0, s, a, 0, nx + 1);
-    else hipLaunchKernelGGL(k_vep3_edges<false>, GRID_IJK(nx + 1, ny + 1, nz + 1), dim3(256), 0, s, a, 0, nx + 1);
-    JRX_LAUNCH_CHECK(h);
-    }
-    if (which == 1) return JRX_OK;
-    const EdgeN n = edge_counts(p->nx, p->ny, p->nz);
-    if (commit && which == 0) {
-        hipLaunchKernelGGL(k_copy6, dim3(1024), dim3(256), 0, s, a.f.tyz, (const double *)a.tnew[0], n.yz, a.f.txz, (const double *)a.tnew[1], n.xz, a.f.txy,
-                           (const double *)a.tnew[2], n.xy, (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr,
-                           (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0);
+// the three edge families: the new edge stresses go to a.tnew (every update reads last iteration's stresses), the caller adopts or copies them
+jrx_status launch_vep3_edges(jrx_handle *h, hipStream_t s, const Vep3Args &a, const Vep3EdgePlan &pl)
+{
+    const int nx = a.nx, ny = a.ny, nz = a.nz, np = a.rh.nphase;
+    const int npc = h->vep3_np_const && np <= 4 ? np : 0;      // option "vep3_np_const": the node kernel's instantiations with a constant phase count; 0 = its run-time loops
+    if (pl.form == 0) {
+        const bool p4 = h->vep3_map, xs = h->vep3_xcd;     // options "vep3_map", "vep3_xcd" (XCD slab order: +1-2 % measured)
+        const dim3 g4 = GRID_IJK4(nx + 1, ny + 1, nz + 1);
+        if (a.soft) hipLaunchKernelGGL((k_vep3_edges<true, true, true>), g4, dim3(256), 0, s, a, 0, nx + 1);
+        else if (p4 && xs) dispatch_const<0, 1, 2, 3, 4>(npc, [&](auto NP) { hipLaunchKernelGGL((k_vep3_edges<true, true, false, decltype(NP)::value>), g4, dim3(256), 0, s, a, 0, nx + 1); });
+        else if (p4) hipLaunchKernelGGL(k_vep3_edges<true>, g4, dim3(256), 0, s, a, 0, nx + 1);
+        else hipLaunchKernelGGL(k_vep3_edges<false>, GRID_IJK(nx + 1, ny + 1, nz + 1), dim3(256), 0, s, a, 0, nx + 1);
         JRX_LAUNCH_CHECK(h);
+        return JRX_OK;
     }
-    if (a.soft) hipLaunchKernelGGL(k_vep3_centre<true>, GRID_IJK(nx, ny, nz), dim3(256), 0, s, a);
-    else switch (h->vep3_np_const ? a.rh.nphase : 0) {
-    case 1: hipLaunchKernelGGL((k_vep3_centre<false, 1>), GRID_IJK(nx, ny, nz), dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((k_vep3_centre<false, 2>), GRID_IJK(nx, ny, nz), dim3(256), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((k_vep3_centre<false, 3>), GRID_IJK(nx, ny, nz), dim3(256), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((k_vep3_centre<false, 4>), GRID_IJK(nx, ny, nz), dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL(k_vep3_centre<false>, GRID_IJK(nx, ny, nz), dim3(256), 0, s, a);
+    const int nseg = pl.nseg, ilim = pl.ilim;
+    if (pl.peel) {      // the node columns behind the last full segment, one node per thread
+        const dim3 gp(pl.peel_gx, pl.peel_gy);
+        if (a.soft) hipLaunchKernelGGL((k_vep3_edges<true, false, true>), gp, dim3(256), 0, s, a, ilim, pl.rem);
+        else dispatch_const<0, 1, 2, 3, 4>(npc, [&](auto NP) { hipLaunchKernelGGL((k_vep3_edges<true, false, false, decltype(NP)::value>), gp, dim3(256), 0, s, a, ilim, pl.rem); });
     }
+    // the z-marching kernels are built for 1..4 phases (more take form 0) and for the (form, KZ, min blocks) the plan admits
+    dispatch_const<1, 2, 3, 4>(np, [&](auto NP_) {
+        constexpr int NP = decltype(NP_)::value;
+        const dim3 gf(pl.grid_f), gl(pl.grid_l), g2((unsigned)pl.ntxy, (unsigned)pl.nzc);
+        if (a.soft) hipLaunchKernelGGL((k_vep3_edges_zf<16, NP, 2, true>), gf, dim3(256), 0, s, a, nseg, pl.ntxy, pl.nt, ilim);
+        else if (pl.form == 6) hipLaunchKernelGGL((k_vep3_edges_zp<16, NP>), gl, dim3(256), 0, s, a, nseg, pl.ntxy_l, pl.nt_l, ilim);
+        else if (pl.form == 4)
+            dispatch_const<16, 8, 4>(pl.kz, [&](auto KZ) { hipLaunchKernelGGL((k_vep3_edges_zl<decltype(KZ)::value, NP, false, true>), gl, dim3(192), 0, s, a, nseg, pl.ntxy_l, pl.nt_l, ilim); });
+        else if (pl.form == 3) hipLaunchKernelGGL((k_vep3_edges_zl<16, NP>), gl, dim3(192), 0, s, a, nseg, pl.ntxy_l, pl.nt_l, ilim);
+        else if (pl.form == 2) {
+            hipLaunchKernelGGL((k_vep3_edges_z<16, NP, 1>), g2, dim3(256), 0, s, a, nseg, ilim);
+            hipLaunchKernelGGL((k_vep3_edges_z<16, NP, 2>), g2, dim3(256), 0, s, a, nseg, ilim);
+            hipLaunchKernelGGL((k_vep3_edges_z<16, NP, 4>), g2, dim3(256), 0, s, a, nseg, ilim);
+        } else
+            dispatch_const<162, 163, 82>(pl.kz * 10 + pl.mb, [&](auto CFG) {
+                hipLaunchKernelGGL((k_vep3_edges_zf<decltype(CFG)::value / 10, NP, decltype(CFG)::value % 10>), gf, dim3(256), 0, s, a, nseg, pl.ntxy, pl.nt, ilim);
+            });
+    });
+    JRX_LAUNCH_CHECK(h);
+    return JRX_OK;
+}
+
+// the centre pass: in place, or into a.cnew where the caller has set it
+jrx_status launch_vep3_centre(jrx_handle *h, hipStream_t s, const Vep3Args &a)
+{
+    const dim3 g = GRID_IJK(a.nx, a.ny, a.nz);
+    if (a.soft) hipLaunchKernelGGL(k_vep3_centre<true>, g, dim3(256), 0, s, a);
+    else dispatch_const<0, 1, 2, 3, 4>(h->vep3_np_const && a.rh.nphase <= 4 ? a.rh.nphase : 0, [&](auto NP) { hipLaunchKernelGGL((k_vep3_centre<false, decltype(NP)::value>), g, dim3(256), 0, s, a); });
+    JRX_LAUNCH_CHECK(h);
+    return JRX_OK;
+}
+
+// update_stresses_center_vertex_ps! as one call: the three edge passes, the commit of the new edge stresses (a copy; the solve loop swaps pointers instead), then the centre pass
+jrx_status launch_vep3_stress(jrx_handle *h, hipStream_t s, const Vep3Args &a, const Vep3EdgePlan &pl)
+{
+    JRX_TRY(launch_vep3_edges(h, s, a, pl));
+    const EdgeN n = edge_counts(a.nx, a.ny, a.nz);
+    hipLaunchKernelGGL(k_copy6, dim3(1024), dim3(256), 0, s, a.f.tyz, (const double *)a.tnew[0], n.yz, a.f.txz, (const double *)a.tnew[1], n.xz, a.f.txy,
+                       (const double *)a.tnew[2], n.xy, (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr,
+                       (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0);
+    JRX_LAUNCH_CHECK(h);
+    return launch_vep3_centre(h, s, a);
+}
+
+// k_vep3_pre (∇V, θ, RP, ε; ML: compute_maxloc! folded in -- ranks with neighbours exchange ητ instead; RHO: update_ρg!), prekz planes per thread.  The depth is a template
+// argument: the forms with neighbours or densities are built for 8 planes only
+void launch_vep3_pre(hipStream_t s, const Vep3Args &a, bool ml, bool rho, int prekz)
+{
+    const unsigned gx = (unsigned)(((i64)(a.nx + 1) * (a.ny + 1) + 255) / 256);
+    const dim3 g8(gx, (unsigned)((a.nz + 1 + 7) / 8));
+    if (!ml && rho) hipLaunchKernelGGL((k_vep3_pre<false, true, 8>), g8, dim3(256), 0, s, a);
+    else if (!ml) hipLaunchKernelGGL((k_vep3_pre<false, false, 8>), g8, dim3(256), 0, s, a);
+    else if (rho) hipLaunchKernelGGL((k_vep3_pre<true, true, 8>), g8, dim3(256), 0, s, a);
+    else dispatch_const<1, 2, 4, 8, 16, 32>(vep3_pre_depth(prekz), [&](auto KZ) {
+        hipLaunchKernelGGL((k_vep3_pre<true, false, decltype(KZ)::value>), dim3(gx, (unsigned)((a.nz + decltype(KZ)::value) / decltype(KZ)::value)), dim3(256), 0, s, a);
+    });
+}
+
+// k_vep3_prec (pre + viscosity relaxation + centre pass): ML as for k_vep3_pre, RHO update_ρg!, OBS from a.obs, the phase count a constant where the instantiation exists:
+// 0..4 without neighbours (0 = run-time loops: more than four phases, "vep3_np_const" = 0, and the density update), 1..4 with them (the driver fuses nothing else there)
+jrx_status launch_vep3_prec(jrx_handle *h, hipStream_t s, const Vep3Args &a, double *eta_out, const Vep3PrecPlan &pl, bool ml, bool rho)
+{
+    const dim3 g(pl.gx, pl.gy);
+    const int np = (h->vep3_np_const && !rho && a.rh.nphase <= 4) ? a.rh.nphase : 0;
+    auto launch = [&](auto ML, auto RHO, auto NP, int tntx) {
+        if (a.obs) hipLaunchKernelGGL((k_vep3_prec<false, decltype(RHO)::value, decltype(NP)::value, true, decltype(ML)::value>), g, dim3(256), 0, s, a, eta_out, pl.kz, tntx);
+        else hipLaunchKernelGGL((k_vep3_prec<false, decltype(RHO)::value, decltype(NP)::value, false, decltype(ML)::value>), g, dim3(256), 0, s, a, eta_out, pl.kz, tntx);
+    };
+    const std::true_type yes{};
+    const std::false_type no{};
+    if (!ml) dispatch_const<1, 2, 3, 4>(np, [&](auto NP) { launch(no, no, NP, pl.tntx); });      // (see `fuse_c` in the solve loop)
+    else if (rho) launch(yes, yes, std::integral_constant<int, 0>{}, 0);      // (the density-updating form has always run the flattened map, on the plan's grid: with tiles that grid is no smaller)
+    else dispatch_const<0, 1, 2, 3, 4>(np, [&](auto NP) { launch(yes, no, NP, pl.tntx); });
     JRX_LAUNCH_CHECK(h);
     return JRX_OK;
 }
@@ -1304,6 +1281,65 @@ jrx_stokes3d_fields view3d(const jrx_vep3d_fields *f)
     return g;
 }
 
+// What one PT iteration of the solve loop works on: the kernel arguments, the view the velocity sweep and the norms take, and the library's alternate of every array an
+// iteration writes out of place.  a.f.* (mirrored in g) are the current arrays; a kernel writes the alternate and adopting its output is a swap -- the old current array is the
+// next alternate.  Every iteration swaps everything it swaps at all, so the captured graphs of an even number of iterations, which run on a copy, end where they began.
+struct Vep3Iter {
+    Vep3Args a;                      // a.tnew is the alternate edge set (the edge pass always writes out of place); a.cnew is null whenever k_vep3_centre is to write in place
+    jrx_stokes3d_fields g;
+    const jrx_vep3d_fields *f;       // the caller's arrays
+    double *eta_alt, *c_alt[3];      // second η, second τxx / τyy / τzz
+    double *etatau_alt;              // second ητ (ranks with neighbours exchange the next iteration's while this one's is read)
+
+    static void swap(double *&x, double *&y) { double *t_ = x; x = y; y = t_; }
+    void begin_out_of_place() { for (int c = 0; c < 3; c++) a.cnew[c] = c_alt[c]; }      // the centre pass (inside k_vep3_prec) writes the second τxx, τyy, τzz
+    void adopt_centres()
+    {
+        swap(a.f.txx, c_alt[0]); swap(a.f.tyy, c_alt[1]); swap(a.f.tzz, c_alt[2]);
+        a.cnew[0] = a.cnew[1] = a.cnew[2] = nullptr;
+        g.txx = a.f.txx; g.tyy = a.f.tyy; g.tzz = a.f.tzz;
+    }
+    void swap_eta() { swap(a.f.eta, eta_alt); g.eta = g.K = g.G = a.f.eta; }
+    // the new edge stresses become the current ones: swap the pointers instead of copying three arrays back
+    void swap_edges()
+    {
+        swap(a.f.tyz, a.tnew[0]); swap(a.f.txz, a.tnew[1]); swap(a.f.txy, a.tnew[2]);
+        g.tyz = a.f.tyz; g.txz = a.f.txz; g.txy = a.f.txy;
+    }
+    void swap_etatau() { double *cur = const_cast<double *>(a.etatau); a.etatau = etatau_alt; etatau_alt = cur; }
+    bool odd() const { return a.f.tyz != f->tyz; }      // an odd number of iterations so far
+    // an odd number of swaps: leave η, τxx, τyy, τzz (fused centre pass) and the edge stresses in the caller's arrays, and the arguments pointing at them
+    jrx_status restore(jrx_handle *h, hipStream_t s)
+    {
+        const size_t n = (size_t)a.nx * a.ny * a.nz;
+        const EdgeN ne = edge_counts(a.nx, a.ny, a.nz);
+        double *const cur[7] = {a.f.eta, a.f.txx, a.f.tyy, a.f.tzz, a.f.tyz, a.f.txz, a.f.txy}, *const usr[7] = {f->eta, f->txx, f->tyy, f->tzz, f->tyz, f->txz, f->txy};
+        const size_t cnt[7] = {n, n, n, n, (size_t)ne.yz, (size_t)ne.xz, (size_t)ne.xy};
+        for (int q = 0; q < 7; q++)
+            if (cur[q] != usr[q]) JRX_HIP(h, hipMemcpyAsync(usr[q], cur[q], cnt[q] * sizeof(double), hipMemcpyDeviceToDevice, s));
+        if (a.f.eta != f->eta) swap_eta();
+        if (a.f.txx != f->txx) adopt_centres();
+        if (odd()) swap_edges();
+        return JRX_OK;
+    }
+};
+
+// flow_bcs! behind the velocity sweep of one iteration; the values are the bc_kind of jrx3d_velocity_hidden
+enum Vep3Bc {
+    BC_V_ORDERED = 0,       // on V, in the reference's pass order
+    BC_V_FACES = 1,         // on V, all faces in one launch: the one-launch form leaves the ghost edges and corners, which no stencil reads, to whichever thread wrote last
+    BC_U_ORDERED = 2,       // DisplacementBoundaryConditions: on U = V dt, which the next iteration overwrites (only observable when U is)
+    BC_NONE = 3
+};
+jrx_status apply_vep3_bc(jrx_handle *h, hipStream_t s, Vep3Bc bc, const jrx_vep3d_fields *f, const jrx_vep3d_params *p)
+{
+    const int nx = (int)p->nx, ny = (int)p->ny, nz = (int)p->nz;
+    if (bc == BC_V_FACES) return jrx3d_bcs_faces(h, s, f->Vx, f->Vy, f->Vz, nx, ny, nz, p->free_slip, p->no_slip);
+    if (bc == BC_V_ORDERED) return jrx3d_bcs(h, s, f->Vx, f->Vy, f->Vz, nx, ny, nz, p->free_slip, p->no_slip, p->periodic);
+    if (bc == BC_U_ORDERED) return jrx3d_bcs(h, s, f->Ux, f->Uy, f->Uz, nx, ny, nz, p->free_slip, p->no_slip, p->periodic);
+    return JRX_OK;
+}
+
 }   // namespace
 
 extern "C" {
@@ -1319,7 +1355,9 @@ jrx_status jrx_vep3d_update_stresses(jrx_handle *h, const jrx_vep3d_fields *f, c
     a.theta = const_cast<double *>(theta); a.lam = lambda;
     for (int t = 0; t < 3; t++) a.lamv[t] = lambda_v[t];
     a.tnew[0] = h->etatau; a.tnew[1] = a.tnew[0] + n.yz; a.tnew[2] = a.tnew[1] + n.xz;
-    JRX_TRY(launch_vep3_stress(h, h->stream, a, p));
+    Vep3EdgePlan pl;
+    JRX_TRY(plan_vep3_edges(h, a, false, &pl));      // the form the switch names, at any size
+    JRX_TRY(launch_vep3_stress(h, h->stream, a, pl));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -1414,9 +1452,12 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
     double *eta_lin = etatau_next + n;
     a.lamv[0] = eta_lin + n; a.lamv[1] = a.lamv[0] + ne.yz; a.lamv[2] = a.lamv[1] + ne.xz;
     a.tnew[0] = a.lamv[2] + ne.xy; a.tnew[1] = a.tnew[0] + ne.yz; a.tnew[2] = a.tnew[1] + ne.xz;
-    double *const cset[3] = {a.tnew[2] + ne.xy, a.tnew[2] + ne.xy + n, a.tnew[2] + ne.xy + 2 * n};      // second set of τxx, τyy, τzz (see `fuse` / `fork` below)
-    double *const eta2 = cset[2] + n;                                                                   // second η (see `fuse`)
-    jrx_stokes3d_fields g = view3d(f);
+    double *const cset = a.tnew[2] + ne.xy;      // second set of τxx, τyy, τzz, then a second η (see `fuse` below)
+    const bool comm = jrx_comm_active(h);
+    Vep3EdgePlan eplan;      // the launch plan (vep3_plan.hpp), once per solve; k_vep3_pre is built for 8 planes only where ητ is exchanged
+    JRX_TRY(plan_vep3_edges(h, a, true, &eplan));
+    const int prekz = comm ? 8 : vep3_plan_prekz(nx, ny, nz, h->vep3_prekz);
+    const Vep3PrecPlan pplan = vep3_plan_prec(nx, ny, nz, prekz, h->vep3_prec_tile);
     jrx_stokes3d_params q;
     memset(&q, 0, sizeof(q));
     q.nx = nx; q.ny = ny; q.nz = nz; q.nxg = p->nxg; q.nyg = p->nyg; q.nzg = p->nzg; q._dx = p->_dx; q._dy = p->_dy; q._dz = p->_dz;
@@ -1425,8 +1466,6 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
     for (int d = 0; d < 3; d++) q.b_width[d] = p->b_width[d];
     const unsigned gc = (unsigned)((n + 255) / 256);
     const dim3 gv = GRID_IJK(nx + 1, ny + 1, nz + 1), g0 = GRID_IJK(nx, ny, nz);
-    constexpr int PRE_KZ = 8;        // planes per thread of k_vep3_pre
-    const dim3 gpre((unsigned)(((i64)(nx + 1) * (ny + 1) + 255) / 256), (unsigned)((nz + 1 + PRE_KZ - 1) / PRE_KZ));
 
     JRX_HIP(h, hipMemcpyAsync(f->P0, f->P, n * sizeof(double), hipMemcpyDeviceToDevice, s));        // @copy stokes.P0 stokes.P
     JRX_HIP(h, hipMemcpyAsync(theta, f->P, n * sizeof(double), hipMemcpyDeviceToDevice, s));        // θ = deepcopy(stokes.P)
@@ -1455,120 +1494,100 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
     int64_t iter = 0;
     bool bcs_ordered = false;        // the reference's ordered flow_bcs! passes have run on V at least once
     res->iter = 0; res->nchecks = 0;
-    const bool comm = jrx_comm_active(h);
     const int64_t nn[3] = {nx, ny, nz};
     const int rank = jrx_comm_rank(h);
     hipEvent_t t0 = h->ev[6], t1 = h->ev[7];
     JRX_HIP(h, hipEventRecord(t0, s));
     auto keep_going = [&](int64_t it) { return it < 2 || ((log.rel() > p->eps_rel && log.err() > p->eps_abs) && it <= p->iterMax); };
-    // an odd number of swaps: leave η, τxx, τyy, τzz (fused / forked centre pass) and the edge stresses in the caller's arrays, and the arguments pointing at them
-    auto restore = [&]() -> jrx_status {
-        if (a.f.eta != f->eta) {
-            JRX_HIP(h, hipMemcpyAsync(f->eta, a.f.eta, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-            a.f.eta = f->eta; g.eta = g.K = g.G = f->eta;
-        }
-        if (a.f.txx != f->txx) {
-            JRX_HIP(h, hipMemcpyAsync(f->txx, a.f.txx, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-            JRX_HIP(h, hipMemcpyAsync(f->tyy, a.f.tyy, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-            JRX_HIP(h, hipMemcpyAsync(f->tzz, a.f.tzz, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-            a.f.txx = f->txx; a.f.tyy = f->tyy; a.f.tzz = f->tzz;
-            g.txx = f->txx; g.tyy = f->tyy; g.tzz = f->tzz;
-        }
-        if (a.f.tyz != f->tyz) {
-            JRX_HIP(h, hipMemcpyAsync(f->tyz, a.f.tyz, (size_t)ne.yz * sizeof(double), hipMemcpyDeviceToDevice, s));
-            JRX_HIP(h, hipMemcpyAsync(f->txz, a.f.txz, (size_t)ne.xz * sizeof(double), hipMemcpyDeviceToDevice, s));
-            JRX_HIP(h, hipMemcpyAsync(f->txy, a.f.txy, (size_t)ne.xy * sizeof(double), hipMemcpyDeviceToDevice, s));
-            a.tnew[0] = a.f.tyz; a.tnew[1] = a.f.txz; a.tnew[2] = a.f.txy;
-            a.f.tyz = f->tyz; a.f.txz = f->txz; a.f.txy = f->txy;
-            g.tyz = f->tyz; g.txz = f->txz; g.txy = f->txy;
-        }
-        return JRX_OK;
-    };
-    // one iteration without neighbours, enqueued on s; A / G: the kernel arguments and the view the velocity sweep takes (their edge-stress pointers swap)
-    // planes per thread of k_vep3_pre: 8 where that gives the chip enough blocks, halved while the launch has fewer than 2048 (16^3: 19.3 k -> 26.0 k it/s with one plane per
-    // thread, 32^3 18.1 k -> 23.3 k, 64^3 8.2 k -> 9.0 k, 128^3 +1 % with four; 256^3: eight planes stay the best, 318 against 304 it/s with one; profiles/r03_vep3d_small_grids.txt)
-    int prekz = h->vep3_prekz;
-    if (prekz == 0)
-        for (prekz = 8; prekz > 1 && (i64)gpre.x * ((nz + prekz) / prekz) < 2048; prekz /= 2) {}
-    // tuning switch "vep3_fork" (default off: measured equal, profiles/r04_vep3d_fork.txt): the centre pass beside the edge pass (see enqueue_iteration); not inside captured graphs (small grids), not with neighbours
-    // (there the halo stream carries the exchanges and the centre pass already runs beside one)
+    Vep3Iter st{a, view3d(f), f, cset + 3 * n, {cset, cset + n, cset + 2 * n}, etatau_next};
     // "vep3_fuse_pc" (default): pre, viscosity relaxation and centre pass as one kernel AHEAD of the edge pass (k_vep3_prec).  The relaxed η and the new τxx, τyy, τzz go to second arrays -- the neighbours'
-    // compute_maxloc! reads the old η, the edge pass averages the old normal stresses -- which are adopted by pointer swap like the edge stresses; every iteration swaps all of them, so the captured graphs of
-    // an even number of iterations end where they began.  Laws whose η reads fields (invariants gathered from the neighbours) and ranks with neighbours (ητ is exchanged) keep the three kernels.
-    const bool fuse = h->vep3_fuse_pc && !comm && lin && !a.soft;      // (softening laws: 255 VGPRs, one wave per SIMD -- they keep the three kernels)
-    const bool fork = !fuse && h->vep3_fork && !comm && !((h->loop_graphs && !ubc && p->periodic == 0 && (double)n <= kGraphCells3D));
-    double *const user_c[3] = {f->txx, f->tyy, f->tzz};
-    // ordered_: flow_bcs! in the reference's pass order (always on observed iterations; also on the iteration BEFORE one, whose ghost edges and corners velocity2displacement! copies into U --
-    // the one-launch form of the faces leaves those entries, which no stencil reads, to whichever thread wrote last)
-    auto enqueue_iteration = [&](Vep3Args &A, jrx_stokes3d_fields &G, bool diag_, bool ordered_ = false) -> jrx_status {
-        A.obs = diag_ || h->vep_store_all;
-        if (fuse) {
-            for (int c_ = 0; c_ < 3; c_++) A.cnew[c_] = (c_ == 0 ? A.f.txx : (c_ == 1 ? A.f.tyy : A.f.tzz)) == cset[c_] ? user_c[c_] : cset[c_];
-            double *const eta_out = A.f.eta == f->eta ? eta2 : f->eta;
-            // thread map of the fused kernel: 64 x 4 tiles of node columns where a plane has enough of them ("vep3_prec_tile" = 2, default: from 16,384 node columns per plane), else 256
-            // consecutive nodes of the flattened plane.  With tiles the rows of a velocity / η window that a block's rows share are requested by waves of one block: 35.4 -> 30.1 fetched passes,
-            // 256^3 350 -> 365 it/s (128^3 +3 %, 160^3 +4 %, 224^3 +5 %, 320^3 +2 %); on small planes the partly filled tiles cost more: 96^3 -7 %, 64^3 -8 %, 32^3 -6 % (gpurun_out/r04pt)
-            const bool tiled = h->vep3_prec_tile == 1 || (h->vep3_prec_tile == 2 && (i64)(nx + 1) * (ny + 1) >= 16384);
-            const int tntx = tiled ? (nx + 1 + 63) / 64 : 0;
-            const dim3 gpc(tntx ? (unsigned)(tntx * ((ny + 1 + 3) / 4)) : gpre.x, (unsigned)((nz + 1 + prekz - 1) / prekz));
-            const int npc = (h->vep3_np_const && !upd_rho) ? A.rh.nphase : 0;
-            switch ((npc <= 4 ? npc : 0) * 2 + (A.obs ? 1 : 0) + (upd_rho ? 100 : 0)) {
-#define PREC(NP_, OBS_) case NP_ * 2 + OBS_: hipLaunchKernelGGL((k_vep3_prec<false, false, NP_, OBS_ != 0>), gpc, dim3(256), 0, s, A, eta_out, prekz, tntx); break;
-            PREC(0, 0) PREC(0, 1) PREC(1, 0) PREC(1, 1) PREC(2, 0) PREC(2, 1) PREC(3, 0) PREC(3, 1) PREC(4, 0) PREC(4, 1)
-#undef PREC
-            case 100: hipLaunchKernelGGL((k_vep3_prec<false, true, 0, false>), gpc, dim3(256), 0, s, A, eta_out, prekz); break;
-            default: hipLaunchKernelGGL((k_vep3_prec<false, true, 0, true>), gpc, dim3(256), 0, s, A, eta_out, prekz);
-            }
-            JRX_LAUNCH_CHECK(h);
-            A.f.eta = eta_out;
-            JRX_TRY(launch_vep3_stress(h, s, A, p, false, 1, true));       // edge pass: the relaxed η, the OLD normal stresses
-            A.f.txx = A.cnew[0]; A.f.tyy = A.cnew[1]; A.f.tzz = A.cnew[2];
-            A.cnew[0] = A.cnew[1] = A.cnew[2] = nullptr;
-            G.txx = A.f.txx; G.tyy = A.f.tyy; G.tzz = A.f.tzz;
-            G.eta = G.K = G.G = A.f.eta;
+    // compute_maxloc! reads the old η, the edge pass averages the old normal stresses -- which are adopted by pointer swap like the edge stresses.  Laws whose η reads fields (invariants gathered from the
+    // neighbours) keep the three kernels, and so do softening laws (255 VGPRs, one wave per SIMD).
+    // With neighbours (k_vep3_prec<ML = false>: ητ is the exchanged array) the kernel is built for a constant phase count and constant densities only; the centre pass then no longer runs beside
+    // update_halo!(τ.yz, τ.xz, τ.xy), which waits in line instead -- three thin planes against the ~0.3 ms the fusion saves at 256^3
+    const bool fusable = h->vep3_fuse_pc && lin && !a.soft;
+    const bool fuse = fusable && !comm;
+    const bool fuse_c = fusable && comm && !upd_rho && h->vep3_np_const && a.rh.nphase <= 4;
+    const bool fused = fuse || fuse_c;
+    // Hidden communication.  The reference hides update_halo!(V) behind compute_V! (@hide_communication, Stokes3D.jl:582-597);
+    // its other two exchanges of the iteration block.  Here all three run on the halo stream beside kernels that do not depend on them:
+    //   update_halo!(ητ) of the NEXT iteration (compute_maxloc! of the η that update_viscosity_τII! has just left, into a second ητ array)
+    //                        beside the edge pass of the stress update,
+    //   update_halo!(τ.yz, τ.xz, τ.xy) beside the centre pass (which reads no edge stress),
+    //   update_halo!(V) behind the boundary slabs of compute_V!, beside its interior.
+    // Same kernels, same operands: results are those of the serial order, bit for bit (tests/test_gpu_two_blocks.py, tests/test_gpu_halo.py).
+    // tuning switch "vep3_hide_comm": 2 as described; 1 = ητ and the edge stresses hidden, update_halo!(V) in order behind the whole sweep;
+    // 0 (default) = the same sequence on the compute stream alone -- ητ of the next iteration is first read by that iteration's velocity sweep, so its planes then travel with the
+    // edge stresses: two exchanges (pack, copies, flags, unpack each) per iteration instead of three; same values in the same places
+    const bool hide = h->vep3_hide_comm >= 2, merged = h->vep3_hide_comm == 0;
+    hipStream_t hs = h->vep3_hide_comm >= 1 ? h->halo_stream : s;
+    const dim3 gml((unsigned)(((i64)nx * ny + 255) / 256), (unsigned)nz);
+    auto exchange_etatau = [&](hipStream_t on, double *etatau_) -> jrx_status {
+        double *arrs[1] = {etatau_};
+        const int64_t ext[1][3] = {{nx, ny, nz}};
+        return jrx_halo_exchange(h, on, 1, arrs, ext, nn);
+    };
+    // One iteration, enqueued on s (the steps marked `comm` only on ranks with neighbours).  first: ητ has not been exchanged yet.  diag: R and U are observable afterwards.
+    // ordered: flow_bcs! in the reference's pass order although nothing is observed -- the iteration BEFORE an observed one, whose ghost edges and corners velocity2displacement! copies into U
+    auto enqueue_iteration = [&](Vep3Iter &it, bool first, bool diag, bool ordered) -> jrx_status {
+        Vep3Args &A = it.a;
+        A.obs = diag || h->vep_store_all;
+        if (comm && first) {        // ητ of the first iteration: nothing to hide it behind
+            double *cur = const_cast<double *>(A.etatau);
+            hipLaunchKernelGGL(k_maxloc, gml, dim3(256), 0, s, cur, (const double *)f->eta, nx, ny, nz);
+            JRX_TRY(exchange_etatau(s, cur));      // update_halo!(ητ) (Stokes3D.jl:515)
+        }
+        if (fused) {
+            it.begin_out_of_place();
+            JRX_TRY(launch_vep3_prec(h, s, A, it.eta_alt, pplan, !comm, upd_rho));
+            it.swap_eta();       // the edge pass reads the relaxed η, and the OLD normal stresses
             h->stat_vep3_fused++;
         } else {
-        if (upd_rho) hipLaunchKernelGGL((k_vep3_pre<true, true, PRE_KZ>), gpre, dim3(256), 0, s, A);
-        else if (prekz == 16) hipLaunchKernelGGL((k_vep3_pre<true, false, 16>), dim3(gpre.x, (unsigned)((nz + 1 + 15) / 16)), dim3(256), 0, s, A);
-        else if (prekz == 32) hipLaunchKernelGGL((k_vep3_pre<true, false, 32>), dim3(gpre.x, (unsigned)((nz + 1 + 31) / 32)), dim3(256), 0, s, A);
-        else if (prekz == 4) hipLaunchKernelGGL((k_vep3_pre<true, false, 4>), dim3(gpre.x, (unsigned)((nz + 1 + 3) / 4)), dim3(256), 0, s, A);
-        else if (prekz == 2) hipLaunchKernelGGL((k_vep3_pre<true, false, 2>), dim3(gpre.x, (unsigned)((nz + 1 + 1) / 2)), dim3(256), 0, s, A);
-        else if (prekz == 1) hipLaunchKernelGGL((k_vep3_pre<true, false, 1>), dim3(gpre.x, (unsigned)(nz + 1)), dim3(256), 0, s, A);
-        else hipLaunchKernelGGL((k_vep3_pre<true, false, PRE_KZ>), gpre, dim3(256), 0, s, A);        // compute_maxloc! folded in
-        launch_vep3_visc(s, gc, A, p->viscosity_relaxation, true);                               // update_viscosity_τII! :541
-        JRX_LAUNCH_CHECK(h);
-        if (fork) {
-            // Edge pass and centre pass of update_stresses_center_vertex_ps! side by side on two streams.  They are independent except that the edge pass averages the OLD
-            // τxx, τyy, τzz to its nodes while the centre pass overwrites them: the centre pass writes a second set, adopted by pointer swap like the edge stresses.  The
-            // edge kernel is latency-bound (4.0 TB/s), the centre kernel streams (5.3 TB/s): the hope was that together they would fill the memory system -- they do not (profiles/r04_vep3d_fork.txt)
-            hipStream_t hs = h->halo_stream;
-            for (int c_ = 0; c_ < 3; c_++) A.cnew[c_] = (c_ == 0 ? A.f.txx : (c_ == 1 ? A.f.tyy : A.f.tzz)) == cset[c_] ? user_c[c_] : cset[c_];
+            launch_vep3_pre(s, A, !comm, upd_rho, prekz);
+            launch_vep3_visc(s, gc, A, p->viscosity_relaxation, true);                               // update_viscosity_τII! :541
+            JRX_LAUNCH_CHECK(h);
+        }
+        if (comm) {     // update_halo!(ητ) of the next iteration
             JRX_HIP(h, hipEventRecord(h->ev[3], s));
             JRX_HIP(h, hipStreamWaitEvent(hs, h->ev[3], 0));
-            JRX_TRY(launch_vep3_stress(h, hs, A, p, false, 2, true));      // centre pass
-            JRX_TRY(launch_vep3_stress(h, s, A, p, false, 1, true));       // edge pass
-            JRX_HIP(h, hipEventRecord(h->ev[4], hs));
-            JRX_HIP(h, hipStreamWaitEvent(s, h->ev[4], 0));
-            A.f.txx = A.cnew[0]; A.f.tyy = A.cnew[1]; A.f.tzz = A.cnew[2];
-            A.cnew[0] = A.cnew[1] = A.cnew[2] = nullptr;
-            G.txx = A.f.txx; G.tyy = A.f.tyy; G.tzz = A.f.tzz;
-        } else JRX_TRY(launch_vep3_stress(h, s, A, p, false, 0, true));
+            hipLaunchKernelGGL(k_maxloc, gml, dim3(256), 0, hs, it.etatau_alt, (const double *)A.f.eta, nx, ny, nz);
+            JRX_LAUNCH_CHECK(h);
+            if (!merged) JRX_TRY(exchange_etatau(hs, it.etatau_alt));
         }
-        // the new edge stresses become the current ones: swap the pointers instead of copying three arrays back
-        { double *t0_ = A.f.tyz; A.f.tyz = A.tnew[0]; A.tnew[0] = t0_; }
-        { double *t1_ = A.f.txz; A.f.txz = A.tnew[1]; A.tnew[1] = t1_; }
-        { double *t2_ = A.f.txy; A.f.txy = A.tnew[2]; A.tnew[2] = t2_; }
-        G.tyz = A.f.tyz; G.txz = A.f.txz; G.txy = A.f.txy;
-        JRX_TRY(jrx3d_velocity_sweep(h, s, &G, A.etatau, &q, diag_, vnof));
-        if (diag_) JRX_TRY(jrx3d_scaleU(h, s, &G, &q));
-        // flow_bcs!: on V, or -- DisplacementBoundaryConditions -- on U = V dt, which the next iteration overwrites (only observable when U is)
-        if (!ubc && !diag_ && !ordered_ && bcs_ordered && p->periodic == 0) JRX_TRY(jrx3d_bcs_faces(h, s, f->Vx, f->Vy, f->Vz, nx, ny, nz, p->free_slip, p->no_slip));
-        else if (!ubc) { JRX_TRY(jrx3d_bcs(h, s, f->Vx, f->Vy, f->Vz, nx, ny, nz, p->free_slip, p->no_slip, p->periodic)); bcs_ordered = true; }
-        else if (diag_) JRX_TRY(jrx3d_bcs(h, s, f->Ux, f->Uy, f->Uz, nx, ny, nz, p->free_slip, p->no_slip, p->periodic));
+        JRX_TRY(launch_vep3_edges(h, s, A, eplan));
+        if (comm) {     // update_halo!(τ.yz), (τ.xz), (τ.xy) (Stokes3D.jl:578-580) [+ ητ of the next iteration, see above] of the adopted arrays, beside the centre pass
+            it.swap_edges();
+            JRX_HIP(h, hipEventRecord(h->ev[3], s));
+            JRX_HIP(h, hipStreamWaitEvent(hs, h->ev[3], 0));
+            double *arrs[4] = {A.f.tyz, A.f.txz, A.f.txy, it.etatau_alt};
+            const int64_t ext[4][3] = {{nx, ny + 1, nz + 1}, {nx + 1, ny, nz + 1}, {nx + 1, ny + 1, nz}, {nx, ny, nz}};
+            JRX_TRY(jrx_halo_exchange(h, hs, merged ? 4 : 3, arrs, ext, nn));
+            JRX_HIP(h, hipEventRecord(h->ev[4], hs));
+        }
+        if (fused) it.adopt_centres();       // the centre pass ran inside k_vep3_prec
+        else JRX_TRY(launch_vep3_centre(h, s, A));
+        if (comm) JRX_HIP(h, hipStreamWaitEvent(s, h->ev[4], 0));
+        else it.swap_edges();
+        Vep3Bc bc = BC_NONE;
+        if (!ubc && !diag && !ordered && bcs_ordered && p->periodic == 0) bc = BC_V_FACES;
+        else if (!ubc) { bc = BC_V_ORDERED; bcs_ordered = true; }
+        else if (diag) bc = BC_U_ORDERED;
+        if (comm && hide) JRX_TRY(jrx3d_velocity_hidden(h, &it.g, A.etatau, &q, diag, bc));      // sweep, BCs and update_halo!(V); joins the two streams
+        else {
+            JRX_TRY(jrx3d_velocity_sweep(h, s, &it.g, A.etatau, &q, diag, vnof));
+            if (diag) JRX_TRY(jrx3d_scaleU(h, s, &it.g, &q));
+            JRX_TRY(apply_vep3_bc(h, s, bc, f, p));
+            if (comm) {
+                double *arrs[3] = {f->Vx, f->Vy, f->Vz};
+                const int64_t ext[3][3] = {{nx + 1, ny + 2, nz + 2}, {nx + 2, ny + 1, nz + 2}, {nx + 2, ny + 2, nz + 1}};
+                JRX_TRY(jrx_halo_exchange(h, s, 3, arrs, ext, nn));       // update_halo!(@velocity(stokes)...) (Stokes3D.jl:596)
+            }
+        }
+        if (comm) it.swap_etatau();
         return JRX_OK;
     };
     // small grids are launch-bound (seven dependent launches per iteration): runs of unobserved iterations replay as a captured graph of GIT iterations
-    // (an even count, so the swapped edge-stress pointers end where they began; one graph per parity; option "loop_graphs")
+    // (an even count, so the swapped pointers end where they began; one graph per parity; option "loop_graphs")
     constexpr int GIT = 16;
     GraphExecs gexec;
     bool graphs = h->loop_graphs && !comm && !ubc && p->periodic == 0 && (double)n <= kGraphCells3D;
@@ -1578,13 +1597,12 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
             if (nxt > p->iterMax + 1) nxt = p->iterMax + 1;
             int64_t run = nxt - 2 - iter;                           // (the iteration before an observed one runs its boundary conditions in the reference's pass order: not part of a replay)
             if (run >= GIT) {
-                const int par = a.f.tyz == f->tyz ? 0 : 1;
+                const int par = st.odd() ? 1 : 0;
                 if (!gexec[par]) {
                     const int64_t stat0 = h->stat_vep3_fused;
                     JRX_TRY(jrx_capture_graph(s, &gexec[par], [&]() -> jrx_status {
-                        Vep3Args A = a;
-                        jrx_stokes3d_fields G = g;
-                        for (int r_ = 0; r_ < GIT; r_++) JRX_TRY(enqueue_iteration(A, G, false));
+                        Vep3Iter T = st;
+                        for (int r_ = 0; r_ < GIT; r_++) JRX_TRY(enqueue_iteration(T, false, false, false));
                         return JRX_OK;
                     }));
                     h->stat_vep3_fused = stat0;
@@ -1603,105 +1621,11 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
         const int64_t it1 = iter + 1;
         const bool check = (it1 % p->nout == 0) && it1 > 1;
         const bool diag = check || !keep_going(it1);      // R and U are only observable after such an iteration
-        a.obs = diag || h->vep_store_all;
         const bool pre_diag = ((it1 + 1) % p->nout == 0) || it1 + 1 > p->iterMax;       // the next iteration, if there is one, is observed
-        if (comm) {
-            // Hidden communication.  The reference hides update_halo!(V) behind compute_V! (@hide_communication, Stokes3D.jl:582-597);
-            // its other two exchanges of the iteration block.  Here all three run on the halo stream beside kernels that do not depend on them:
-            //   update_halo!(ητ) of the NEXT iteration (compute_maxloc! of the η that update_viscosity_τII! has just left, into a second ητ array)
-            //                        beside the edge pass of the stress update,
-            //   update_halo!(τ.yz, τ.xz, τ.xy) beside the centre pass (which reads no edge stress),
-            //   update_halo!(V) behind the boundary slabs of compute_V!, beside its interior.
-            // Same kernels, same operands: results are those of the serial order, bit for bit (tests/test_gpu_two_blocks.py, tests/test_gpu_halo.py).
-            // tuning switch "vep3_hide_comm": 2 (default) as described; 1 = ητ and the edge stresses hidden, update_halo!(V) in order behind the whole sweep;
-            // 0 = the same sequence on the compute stream alone (A/B)
-            const bool hide = h->vep3_hide_comm >= 2;
-            hipStream_t hs = h->vep3_hide_comm >= 1 ? h->halo_stream : s;
-            if (iter == 0) {        // ητ of the first iteration: nothing to hide it behind
-                double *cur = const_cast<double *>(a.etatau);
-                hipLaunchKernelGGL(k_maxloc, dim3((unsigned)(((i64)nx * ny + 255) / 256), (unsigned)nz), dim3(256), 0, s, cur, (const double *)f->eta, nx, ny, nz);
-                double *arrs[1] = {cur};
-                const int64_t ext[1][3] = {{nx, ny, nz}};
-                JRX_TRY(jrx_halo_exchange(h, s, 1, arrs, ext, nn));      // update_halo!(ητ) (Stokes3D.jl:515)
-            }
-            // "vep3_fuse_pc" with neighbours: pre, viscosity relaxation and centre pass as one kernel here too (k_vep3_prec<ML = false>: ητ is the exchanged array); the centre pass then no longer
-            // runs beside update_halo!(τ.yz, τ.xz, τ.xy), which waits in line instead -- three thin planes against the ~0.3 ms the fusion saves at 256^3
-            const bool fuse_c = h->vep3_fuse_pc && lin && !a.soft && !upd_rho && h->vep3_np_const && a.rh.nphase <= 4;
-            if (fuse_c) {
-                for (int c_ = 0; c_ < 3; c_++) a.cnew[c_] = (c_ == 0 ? a.f.txx : (c_ == 1 ? a.f.tyy : a.f.tzz)) == cset[c_] ? user_c[c_] : cset[c_];
-                double *const eta_out = a.f.eta == f->eta ? eta2 : f->eta;
-                // the same thread map as without neighbours: 64 x 4 tiles of node columns where a plane has enough of them ("vep3_prec_tile")
-                const bool tiled_c = h->vep3_prec_tile == 1 || (h->vep3_prec_tile == 2 && (i64)(nx + 1) * (ny + 1) >= 16384);
-                const int tntx_c = tiled_c ? (nx + 1 + 63) / 64 : 0;
-                const dim3 gpc(tntx_c ? (unsigned)(tntx_c * ((ny + 1 + 3) / 4)) : gpre.x, (unsigned)((nz + 1 + PRE_KZ - 1) / PRE_KZ));
-                switch (a.rh.nphase * 2 + (a.obs ? 1 : 0)) {
-#define PRECC(NP_, OBS_) case NP_ * 2 + OBS_: hipLaunchKernelGGL((k_vep3_prec<false, false, NP_, OBS_ != 0, false>), gpc, dim3(256), 0, s, a, eta_out, PRE_KZ, tntx_c); break;
-                PRECC(1, 0) PRECC(1, 1) PRECC(2, 0) PRECC(2, 1) PRECC(3, 0) PRECC(3, 1) PRECC(4, 0) PRECC(4, 1)
-#undef PRECC
-                }
-                a.f.eta = eta_out;
-                g.eta = g.K = g.G = a.f.eta;
-                h->stat_vep3_fused++;
-            } else {
-            if (upd_rho) hipLaunchKernelGGL((k_vep3_pre<false, true, PRE_KZ>), gpre, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_vep3_pre<false, false, PRE_KZ>), gpre, dim3(256), 0, s, a);
-            launch_vep3_visc(s, gc, a, p->viscosity_relaxation, true);                               // update_viscosity_τII! :541
-            }
-            JRX_LAUNCH_CHECK(h);
-            JRX_HIP(h, hipEventRecord(h->ev[3], s));
-            JRX_HIP(h, hipStreamWaitEvent(hs, h->ev[3], 0));
-            // in-order pipeline ("vep3_hide_comm" = 0, the default): ητ of the next iteration is first read by that iteration's velocity sweep, so its planes travel with the
-            // edge stresses below -- two exchanges (pack, copies, flags, unpack each) per iteration instead of three; same values in the same places
-            const bool merged = h->vep3_hide_comm == 0;
-            double *const nxt = a.etatau == etatau ? etatau_next : etatau;
-            {
-                hipLaunchKernelGGL(k_maxloc, dim3((unsigned)(((i64)nx * ny + 255) / 256), (unsigned)nz), dim3(256), 0, hs, nxt, (const double *)a.f.eta, nx, ny, nz);
-                JRX_LAUNCH_CHECK(h);
-                if (!merged) {
-                    double *arrs[1] = {nxt};
-                    const int64_t ext[1][3] = {{nx, ny, nz}};
-                    JRX_TRY(jrx_halo_exchange(h, hs, 1, arrs, ext, nn));     // update_halo!(ητ) of iteration it1 + 1
-                }
-            }
-            JRX_TRY(launch_vep3_stress(h, s, a, p, false, 1, true));     // edge pass
-            { double *t0_ = a.f.tyz; a.f.tyz = a.tnew[0]; a.tnew[0] = t0_; }
-            { double *t1_ = a.f.txz; a.f.txz = a.tnew[1]; a.tnew[1] = t1_; }
-            { double *t2_ = a.f.txy; a.f.txy = a.tnew[2]; a.tnew[2] = t2_; }
-            g.tyz = a.f.tyz; g.txz = a.f.txz; g.txy = a.f.txy;
-            JRX_HIP(h, hipEventRecord(h->ev[3], s));
-            JRX_HIP(h, hipStreamWaitEvent(hs, h->ev[3], 0));
-            {   // update_halo!(τ.yz), (τ.xz), (τ.xy) (Stokes3D.jl:578-580) [+ ητ of the next iteration, see above]
-                double *arrs[4] = {a.f.tyz, a.f.txz, a.f.txy, nxt};
-                const int64_t ext[4][3] = {{nx, ny + 1, nz + 1}, {nx + 1, ny, nz + 1}, {nx + 1, ny + 1, nz}, {nx, ny, nz}};
-                JRX_TRY(jrx_halo_exchange(h, hs, merged ? 4 : 3, arrs, ext, nn));
-            }
-            JRX_HIP(h, hipEventRecord(h->ev[4], hs));
-            if (fuse_c) {       // the centre pass ran inside k_vep3_prec: adopt its normal stresses
-                a.f.txx = a.cnew[0]; a.f.tyy = a.cnew[1]; a.f.tzz = a.cnew[2];
-                a.cnew[0] = a.cnew[1] = a.cnew[2] = nullptr;
-                g.txx = a.f.txx; g.tyy = a.f.tyy; g.tzz = a.f.tzz;
-            } else JRX_TRY(launch_vep3_stress(h, s, a, p, false, 2, true));     // centre pass, beside the exchange
-            JRX_HIP(h, hipStreamWaitEvent(s, h->ev[4], 0));
-            int bc_kind = 3;
-            if (!ubc && !diag && !pre_diag && bcs_ordered && p->periodic == 0) bc_kind = 1;
-            else if (!ubc) { bc_kind = 0; bcs_ordered = true; }
-            else if (diag) bc_kind = 2;
-            if (hide) JRX_TRY(jrx3d_velocity_hidden(h, &g, a.etatau, &q, diag, bc_kind));      // joins the two streams
-            else {
-                JRX_TRY(jrx3d_velocity_sweep(h, s, &g, a.etatau, &q, diag, vnof));
-                if (diag) JRX_TRY(jrx3d_scaleU(h, s, &g, &q));
-                if (bc_kind == 1) JRX_TRY(jrx3d_bcs_faces(h, s, f->Vx, f->Vy, f->Vz, nx, ny, nz, p->free_slip, p->no_slip));
-                else if (bc_kind == 0) JRX_TRY(jrx3d_bcs(h, s, f->Vx, f->Vy, f->Vz, nx, ny, nz, p->free_slip, p->no_slip, p->periodic));
-                else if (bc_kind == 2) JRX_TRY(jrx3d_bcs(h, s, f->Ux, f->Uy, f->Uz, nx, ny, nz, p->free_slip, p->no_slip, p->periodic));
-                double *arrs[3] = {f->Vx, f->Vy, f->Vz};
-                const int64_t ext[3][3] = {{nx + 1, ny + 2, nz + 2}, {nx + 2, ny + 1, nz + 2}, {nx + 2, ny + 2, nz + 1}};
-                JRX_TRY(jrx_halo_exchange(h, s, 3, arrs, ext, nn));       // update_halo!(@velocity(stokes)...) (Stokes3D.jl:596)
-            }
-            a.etatau = a.etatau == etatau ? etatau_next : etatau;
-        } else JRX_TRY(enqueue_iteration(a, g, diag, pre_diag));
+        JRX_TRY(enqueue_iteration(st, iter == 0, diag, pre_diag));
         iter = it1;
         if (check) {
-            JRX_TRY(jrx3d_sumsq(h, s, &g, &q));
+            JRX_TRY(jrx3d_sumsq(h, s, &st.g, &q));
             double ss[4];
             JRX_TRY(jrx_read_sums(h, s, ss, true));                                                   // norm_mpi
             const double den = (double)((p->nxg - 1) * (p->nyg - 1) * (p->nzg - 1));                  // Stokes3D.jl:607-612
@@ -1710,13 +1634,13 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
             const double err = log.record(iter, nRx, nRy, nRz, nDV);
             if (rank == 0 && ((p->verbose && log.rel() > p->eps_rel && err > p->eps_abs) || iter == p->iterMax)) log.print3d(iter, nRx, nRy, nRz, nDV);
             if (std::isnan(err)) {      // error("NaN(s)")
-                (void)restore();
+                (void)st.restore(h, s);
                 return log.fail_nan(h, iter, jrx_drain_ms(s, t0, t1));
             }
         }
     }
     JRX_HIP(h, hipEventRecord(t1, s));
-    JRX_TRY(restore());
+    JRX_TRY(st.restore(h, s));
     // epilogue: vorticity, shear2center!, accumulate_tensor!/accumulate_vol!, τ -> τ_o (Stokes3D.jl:640-658)
     if (f->omega_yz && f->omega_xz && f->omega_xy)
         hipLaunchKernelGGL(k_vorticity3d, gv, dim3(256), 0, s, f->omega_yz, f->omega_xz, f->omega_xy, (const double *)f->Vx,
@@ -1730,7 +1654,7 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
     if (f->deyz_c && f->dexz_c && f->dexy_c && f->deyz && f->dexz && f->dexy)
         hipLaunchKernelGGL(k_shear2center3d, g0, dim3(256), 0, s, f->deyz_c, f->dexz_c, f->dexy_c, (const double *)f->deyz, (const double *)f->dexz,
                            (const double *)f->dexy, nx, ny, nz);
-    hipLaunchKernelGGL(k_vep3_accumulate, g0, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_vep3_accumulate, g0, dim3(256), 0, s, st.a);
     JRX_LAUNCH_CHECK(h);
     JRX_TRY((jrx3d_copy_old_stresses<1024>(h, s, f, nx, ny, nz)));
     JRX_HIP(h, hipStreamSynchronize(s));

@@ -115,6 +115,58 @@ def test_update_stresses_3d_matches_oracle(jr, oracle, edges, ni):
         assert max_rel_diff(jr.to_numpy(a), b) <= 1e-12
 
 
+def test_retired_switches_are_unknown_and_edges_5_is_refused_before_anything_runs(jr, oracle):
+    """vep3_fork and vep3_peel_fork are no keys any more; vep3_edges = 5 (no such form: the launch plan refuses it) makes jrx_vep3d_update_stresses return JRX_ERR_ARG with
+    every stress array as it was, and the same call with the switch back at 4 matches the oracle"""
+    from justrelax_jl_amd import _lib, stokes as st_mod
+    from justrelax_jl_amd.arrays import from_numpy
+    from justrelax_jl_amd.checks import max_rel_diff
+    h = _lib.default_handle()
+    for key in (b"vep3_fork", b"vep3_peel_fork"):
+        with pytest.raises(_lib.JrxError) as e:
+            h.call("jrx_tuning_set", C.c_char_p(key), C.c_int64(0))
+        assert e.value.status == 4 and "unknown key" in str(e.value)
+    s = jr.miniapps.shearband3d((13, 9, 7))
+    phases = _randomize(s)
+    rh = oracle.rheology_struct(phases)
+    ref = {k: v.copy(order="F") for k, v in s.arrays.items()}
+    rng = np.random.default_rng(9)
+    theta = np.asfortranarray(rng.uniform(-1, 1, size=s.ni))
+    lam = np.asfortranarray(rng.uniform(0, 0.1, size=s.ni))
+    lamv = [np.asfortranarray(rng.uniform(0, 0.1, size=s.arrays[k].shape)) for k in ("tyz", "txz", "txy")]
+    lam_r, lamv_r = lam.copy(order="F"), [x.copy(order="F") for x in lamv]
+    oracle.vep3d_stress(ref, theta, lam_r, lamv_r, rh, _params(oracle, s))
+    stokes, pr, ρg = _upload(jr, s)
+    dev = stokes.P.device
+    th_d, lam_d = from_numpy(theta, dev), from_numpy(lam, dev)
+    lamv_d = [from_numpy(x, dev) for x in lamv]
+    fd = st_mod.vep_fields3d(stokes, ρg, pr)
+    pd = st_mod.vep_params3d(stokes, s.pt, s.grid, s.flow_bcs, s.dt)
+    lv = (C.c_void_p * 3)(*[x.data_ptr() for x in lamv_d])
+    update = lambda: h.call("jrx_vep3d_update_stresses", C.byref(fd), C.c_void_p(th_d.data_ptr()), C.c_void_p(lam_d.data_ptr()), lv,
+                            C.byref(st_mod.rheology_table(phases)), C.byref(pd))
+    stress = ("txx", "tyy", "tzz", "tyz", "txz", "txy", "tyz_c", "txz_c", "txy_c")
+    h.call("jrx_tuning_set", C.c_char_p(b"vep3_edges"), C.c_int64(5))
+    try:
+        with pytest.raises(_lib.JrxError) as e:
+            update()
+        assert e.value.status == 4 and "vep3_edges: no such form" in str(e.value)
+        out = _download(jr, stokes)
+        for k in stress + ("P", "tII", "eplxx", "eplxz"):
+            assert np.array_equal(out[k], s.arrays[k]), k
+        assert np.array_equal(jr.to_numpy(lam_d), lam) and all(np.array_equal(jr.to_numpy(a), b) for a, b in zip(lamv_d, lamv))
+    finally:
+        h.call("jrx_tuning_set", C.c_char_p(b"vep3_edges"), C.c_int64(4))
+    update()
+    out = _download(jr, stokes)
+    assert (lam_r != lam).any() and (ref["eplxz"] != 0).any()
+    for k in stress + ("tII", "eta_vep", "P", "eplxx", "eplyy", "eplzz", "eplyz", "eplxz", "eplxy", "evol_pl"):
+        assert max_rel_diff(out[k], ref[k]) <= 1e-12, k
+    assert max_rel_diff(jr.to_numpy(lam_d), lam_r) <= 1e-12
+    for a, b in zip(lamv_d, lamv_r):
+        assert max_rel_diff(jr.to_numpy(a), b) <= 1e-12
+
+
 def test_vep3d_solve_matches_oracle_over_iterations(jr, oracle):
     """the whole driver (pressure with phase ratios, viscosity relaxation, stress kernel, velocity sweep, BCs, norms, epilogue)
     for a fixed number of iterations on a yielding state"""
