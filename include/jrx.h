@@ -130,6 +130,7 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   "stat_fused2d_b" = those of "stat_fused2d" that ran the batch form k_fused2d_b (32-bit byte offsets: only below 2^29 nodes, see "fused2d_batch" in jrx_tuning.h),
  *   "stat_weno_calls" / "stat_weno_fused" = jrx_weno5_advection2d calls / those that ran the fused three-launch form,
  *   "stat_weno3d_calls" / "stat_weno3d_fused" = the same for jrx_weno5_advection3d (the 2D pair counts 2D calls only),
+ *   "stat_phase_ratios_calls" / "stat_phase_ratios_fused" = jrx_update_phase_ratios2d / 3d calls that launched / those that ran the one-launch form,
  *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* entry points -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
@@ -801,6 +802,33 @@ jrx_status jrx_weno5_advection3d(jrx_handle *h, double *u, const int64_t udim[3]
 jrx_status jrx_principal_stresses2d(jrx_handle *h, double *s1, double *s2, const double *xx, const double *yy, const double *xy_c, int64_t nx, int64_t ny);
 jrx_status jrx_principal_stresses3d(jrx_handle *h, double *s1, double *s2, double *s3, const double *xx, const double *yy, const double *zz,
                                     const double *yz_c, const double *xz_c, const double *xy_c, int64_t nx, int64_t ny, int64_t nz);
+
+/* ------------------------------------------------------------------ phase ratios from phase fields
+ * update_phase_ratios_2D!(phase_ratios, phase_arrays, xci, xvi) / update_phase_ratios_3D!(...) -- src/phases/PhaseRatios.jl:24-35 / :61-78 (centres :89-116,
+ * vertices :135-211, faces :231-293, edges :324-383): the particle-free route to a PhaseRatios -- advect N cell-centred phase fields (values nominally in
+ * [0, 1]), then rebuild every member from them.  phase_arrays is a HOST array of nphase DEVICE pointers to (nx, ny[, nz]) arrays; xc[d] / xv[d] are device
+ * pointers to the n_d cell centres / n_d + 1 vertices of dimension d; dx[d] = xv[d][1] - xv[d][0] (compute_dx needs ranges: the grid is uniform).  Outputs in
+ * CellArray layout, the phase index fastest: center (N, ni...), vertex (N, ni .+ 1 ...), Vx (N, nx+1, ny[, nz]), Vy, Vz and in 3D the edges yz (N, nx, ny+1, nz+1),
+ * xz (N, nx+1, ny, nz+1), xy (N, nx+1, ny+1, nz).  Rules kept from the reference, operation for operation:
+ *  - every member accumulates w_k += weight * p_k[cell], W += weight over its cells, skipping the cells outside the grid, then applies one tail, every sum over
+ *    k = 1..N left to right: w_k / W; clamp to [0, 1]; values < 1e-5 become 0; s = sum; write w_k / s.  Centres: w_k = p_k[I] divided by t = sum of p_k[I];
+ *  - faces: the cells I_d - 1, then I_d across the face, weight 0.5 each (a boundary face has W = 0.5); edges: the four cells at offsets (-1,-1), (-1,0),
+ *    (0,-1), (0,0) in (first, second staggered dimension), weight 0.25 each;
+ *  - vertices: the 2^ndim cells at offsets {-1, 0}, the first dimension's offset outermost, -1 before 0; 2D weight wx wy with
+ *    wx = fma(-|xv_1[i] - xc_1[ic]|, 1/dx_1, 1) (the reference's muladd), 3D weight ((1 - |xv_1 - xc_1| (1/dx_1)) (1 - ...)) (1 - ...) without fma.  The weights
+ *    come from the coordinates passed in, not from an assumed 0.5;
+ *  - a cell whose arrays sum to 0, or that holds a NaN, gives NaN for every phase at exactly the nodes that read it.
+ * Two kernel forms with identical bits in every member (tuning key "phase_ratios_fused", include/jrx_tuning.h): the default is ONE launch, a thread per node
+ * of the ni .+ 1 box that reads its 2^ndim cells once and writes every member it owns; 0 runs one launch per member (4 in 2D, 8 in 3D).  No halo exchange
+ * (the reference has none).  Synchronous.
+ * JRX_ERR_ARG without a launch, with a text naming the cause: a NULL pointer (an entry of phase_arrays, xc, xv included), nphase outside 1..JRX_MAXPHASE, an
+ * extent < 1, a dx that is not positive and finite, an output overlapping an input or another output.  JRX_ERR_UNSUPPORTED: an output of 2^31 or more entries
+ * (32-bit offsets).  Counters "stat_phase_ratios_calls" / "stat_phase_ratios_fused" (jrx_get_option). */
+jrx_status jrx_update_phase_ratios2d(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, const double *const *phase_arrays, int32_t nphase,
+                                     int64_t nx, int64_t ny, const double *const xc[2], const double *const xv[2], const double dx[2]);
+jrx_status jrx_update_phase_ratios3d(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, double *Vz, double *yz, double *xz, double *xy,
+                                     const double *const *phase_arrays, int32_t nphase, int64_t nx, int64_t ny, int64_t nz, const double *const xc[3],
+                                     const double *const xv[3], const double dx[3]);
 
 /* ------------------------------------------------------------------ timing hooks for bench.py */
 /* Runs `iters` PT iterations of the 3D loop body back to back (no norm checks) and reports device times

@@ -71,6 +71,8 @@
  *                                 fluxes in fL, fR, fB, fT (3D: and fD, fU; bit-identical u and ut)
  *   "weno_rows" (0)              fused WENO kernel: rows a wave marches (0 = by the grid: 64, halved down to 8 while the launch has fewer than 4,096 waves); 3D: planes a
  *                                 block of 8 waves marches (0 = 64, halved down to 8 while the launch has fewer than 1,024 blocks)
+ *   "phase_ratios_fused" (1)     jrx_update_phase_ratios2d / 3d: one launch, a thread per node of the ni .+ 1 box writes every member it owns from one read of its 2^ndim cells;
+ *                                 0 = the reference's one launch per member (4 in 2D, 8 in 3D; bit-identical in every member)
  *   "general_hif" (0)            3D fused kernel, general form (any dt), 64 x 4 tile: the stress nodes on the high faces i = nx, j = ny, k = nz are updated inside the kernel (one launch per
  *                                 unobserved iteration) and, with neighbours, the kernel's boundary tiles read the received planes ("fused_overlap" = 3: no flow_bcs! launch, no fix-up):
  *                                 4 / 3 = the instantiation built for four (128 VGPRs + 28 dwords of scratch: 10.99 ms at 512^3) / three (155 VGPRs: 7.95 ms) waves per SIMD; 0 = boundary-layer launch (7.47 + 0.11 ms)

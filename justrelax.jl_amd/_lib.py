@@ -222,6 +222,10 @@ def load(check_symbols: bool = False):
             fn = getattr(L, name)          # raises AttributeError if the symbol is not exported
             if name not in ("jrx_last_error", "jrx_n_global", "jrx_version", "jrx_build_id"):
                 fn.restype = C.c_int32
+        # jrx_update_phase_ratios2d / 3d: handle, the outputs, a host array of device pointers, the phase count, the extents, xc[], xv[] (host arrays of device pointers), dx[]
+        _vpp = C.POINTER(C.c_void_p)
+        L.jrx_update_phase_ratios2d.argtypes = [C.c_void_p] * 5 + [_vpp, C.c_int32] + [C.c_int64] * 2 + [_vpp, _vpp, _dp]
+        L.jrx_update_phase_ratios3d.argtypes = [C.c_void_p] * 9 + [_vpp, C.c_int32] + [C.c_int64] * 3 + [_vpp, _vpp, _dp]
         _lib = L
     if check_symbols:
         missing = [s for s in declared_symbols() if not hasattr(_lib, s)]
