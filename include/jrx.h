@@ -131,6 +131,7 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   "stat_weno_calls" / "stat_weno_fused" = jrx_weno5_advection2d calls / those that ran the fused three-launch form,
  *   "stat_weno3d_calls" / "stat_weno3d_fused" = the same for jrx_weno5_advection3d (the 2D pair counts 2D calls only),
  *   "stat_phase_ratios_calls" / "stat_phase_ratios_fused" = jrx_update_phase_ratios2d / 3d calls that launched / those that ran the one-launch form,
+ *   "stat_rotate_stress_calls" = jrx_rotate_stress2d / 3d calls that launched,
  *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* entry points -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
@@ -829,6 +830,53 @@ jrx_status jrx_update_phase_ratios2d(jrx_handle *h, double *center, double *vert
 jrx_status jrx_update_phase_ratios3d(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, double *Vz, double *yz, double *xz, double *xy,
                                      const double *const *phase_arrays, int32_t nphase, int64_t nx, int64_t ny, int64_t nz, const double *const xc[3],
                                      const double *const xv[3], const double dx[3]);
+
+/* ------------------------------------------------------------------ grid-based stress rotation and advection
+ * rotate_stress!(stokes, grid, dt; method, advection) on grids: carries stokes.τ to stokes.τ_o through one time step -- rotated by the vorticity (Jaumann rate)
+ * and advected by the velocity -- where every driver's epilogue leaves a plain copy.  The reference does this on particles (rotate_stress!(pτ, stokes,
+ * particles, dt) then stress2grid!, src/stress_rotation/stress_rotation_particles.jl:205-299); it also exports a grid form, rotate_stress!(V, τ, _di, dt),
+ * src/stress_rotation/stress_rotation_grid.jl, which is the counterpart built here.  That text is a stub and is NOT restated.  Its defects, not followed:
+ *  - :68 multiplies the advective term by 0 and overwrites the stress with τR - Rτ (:54-63): no dt, and the old stress is gone;
+ *  - advection_term (:157-168) takes the downwind difference (Vx > 0 ? dx_right : dx_left);
+ *  - upwind_derivatives (:115-154) replaces the neighbour of the second and of the last-but-one row by 0 (i - 1 > 1, i + 1 < nx);
+ *  - it writes τ in place while other threads read the neighbours;
+ *  - the "3D" method calls rotate_elastic_stress2D and the 2D matrices, and tensor2voigt (:16-24) indexes 3D arrays with two indices;
+ *  - its Jaumann sibling on particles (stress_rotation_particles.jl:151-167) adds +2 dt ω τxy to both xx and yy, which changes the trace; the rate is
+ *    -2 dt ω τxy on xx and +2 dt ω τxy on yy.
+ * Kept from the reference: the per-point rotation-matrix form rotate_stress_particles_rotation_matrix! (stress_rotation_particles.jl:169-201), the ω
+ * convention of compute_vorticity! (:17-80; jrx_compute_vorticity2d / 3d) and velocity2center (stress_rotation_grid.jl:171-176).
+ *
+ * Definition (uniform grids; indices 1-based).  One explicit step, out of place, both terms from the input state:
+ *     τ_o[c](I) = Rot_c(τ, ω dt)(I) - dt Adv(τ[c], v)(I)        for every member c at its own node I.
+ * Members.  2D, tau / tau_o = {xx, yy, xy_c (centres, ni), xy (vertices, ni .+ 1), xx_v, yy_v (vertices; optional: all four pointers or they are skipped)}.
+ * 3D, tau / tau_o = {xx, yy, zz, yz_c, xz_c, xy_c (centres), yz (nx, ny+1, nz+1), xz (nx+1, ny, nz+1), xy (nx+1, ny+1, nz)}.  The _c members are inputs as the
+ * drivers leave them, not rebuilt from the edges.  ω: 2D omega_xy (ni .+ 1); 3D omega = {yz, xz, xy} on the edge arrays.  V = {Vx, Vy[, Vz]} with ghost layers.
+ * Interpolation.  A quantity that does not live at the target node is the mean of the 2^m nearest nodes of its own array, m = the number of axes along which
+ * the two locations are half a cell apart: indices clamped into the source's extent, the 2^m values summed in index order (x fastest), times 1 / 2^m.  So the
+ * normals at a vertex / edge come from 4 centres, ω at a centre from 4 vertices / edges, a foreign shear or ω component at an edge from 4 nodes of the other
+ * edge family; the 2D xx_v, yy_v are rotated from their own node (xx_v, yy_v, xy) without interpolation.  Velocities alike, every node existing thanks to
+ * the ghost layers: 2D centre vx = ½(Vx[i,j+1] + Vx[i+1,j+1]), vy = ½(Vy[i+1,j] + Vy[i+1,j+1]); 2D vertex vx = ½(Vx[i,j] + Vx[i,j+1]), vy = ½(Vy[i,j] +
+ * Vy[i+1,j]); 3D: 2 nodes for the in-plane components of an edge, 8 for the one normal to its plane.
+ * Rotation.  JRX_ROTATE_MATRIX: 2D θ = dt ω, τ' = R (τ R') with R = [c -s; s c], multiplied out in the order of :182-197.  3D: the axial vector
+ * w = (ω_yz, ω_xz, ω_xy) (half the curl), θ = dt |w|, n = w / |w|, R = I + sinθ K + (1 - cosθ) K², K = [n]x, τ' = R (τ R'); |w| == 0 gives R = I without a
+ * division.  JRX_ROTATE_JAUMANN: τ' = τ + dt (W τ - τ W), W = [w]x; in 2D xx - 2θ xy, yy + 2θ xy, xy + θ (xx - yy).
+ * Advection.  JRX_ADVECT_UPWIND: Adv(A, v)(I) = Σ_d v_d (v_d > 0 ? A[I] - A[I - e_d] : A[I + e_d] - A[I]) _d_d, a neighbour outside the array replaced by A[I].
+ * JRX_ADVECT_NONE: the term is not evaluated and V (or its entries) may be NULL.  There is no CFL check: dt must come from compute_dt.  compute_dt bounds the
+ * Courant number of each axis by 0.9; the unsplit upwind step is stable while their SUM over the axes stays <= 1 at every node, so a flow whose components reach
+ * their maxima at the same nodes (the corners of a box in solid-body rotation) needs compute_dt / ndims (examples/stress_rotation2d.py).
+ * No fma anywhere: every product and sum is rounded once in the order stated (tests/_stress_rotation.py is the same text in NumPy).  One launch, a thread per
+ * node of the ni .+ 1 box writes every member that node owns.  No halo exchange inside the call.  Synchronous.  Counter "stat_rotate_stress_calls".
+ * tau_o, tau, omega, V are HOST arrays of DEVICE pointers.  JRX_ERR_ARG (4) with a text naming the cause, nothing launched and nothing written: an output
+ * that overlaps an input (or another output), a NULL required member, an unknown method or advection kind, an extent < 1, 2^31 or more entries in the
+ * ni .+ 2 box that holds every array (32-bit offsets). */
+#define JRX_ROTATE_MATRIX 0
+#define JRX_ROTATE_JAUMANN 1
+#define JRX_ADVECT_NONE 0
+#define JRX_ADVECT_UPWIND 1
+jrx_status jrx_rotate_stress2d(jrx_handle *h, double *const tau_o[6], const double *const tau[6], const double *omega_xy, const double *const V[2], int64_t nx,
+                               int64_t ny, const double _di[2], double dt, int32_t method, int32_t advection);
+jrx_status jrx_rotate_stress3d(jrx_handle *h, double *const tau_o[9], const double *const tau[9], const double *const omega[3], const double *const V[3],
+                               int64_t nx, int64_t ny, int64_t nz, const double _di[3], double dt, int32_t method, int32_t advection);
 
 /* ------------------------------------------------------------------ timing hooks for bench.py */
 /* Runs `iters` PT iterations of the 3D loop body back to back (no norm checks) and reports device times

@@ -226,6 +226,9 @@ def load(check_symbols: bool = False):
         _vpp = C.POINTER(C.c_void_p)
         L.jrx_update_phase_ratios2d.argtypes = [C.c_void_p] * 5 + [_vpp, C.c_int32] + [C.c_int64] * 2 + [_vpp, _vpp, _dp]
         L.jrx_update_phase_ratios3d.argtypes = [C.c_void_p] * 9 + [_vpp, C.c_int32] + [C.c_int64] * 3 + [_vpp, _vpp, _dp]
+        # jrx_rotate_stress2d / 3d: handle, tau_o[], tau[] (host arrays of device pointers), ω (2D: one pointer; 3D: an array of three), V[], the extents, _di[], dt, method, advection
+        L.jrx_rotate_stress2d.argtypes = [C.c_void_p, _vpp, _vpp, C.c_void_p, _vpp] + [C.c_int64] * 2 + [_dp, C.c_double, C.c_int32, C.c_int32]
+        L.jrx_rotate_stress3d.argtypes = [C.c_void_p, _vpp, _vpp, _vpp, _vpp] + [C.c_int64] * 3 + [_dp, C.c_double, C.c_int32, C.c_int32]
         _lib = L
     if check_symbols:
         missing = [s for s in declared_symbols() if not hasattr(_lib, s)]

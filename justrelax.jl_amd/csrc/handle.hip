@@ -122,6 +122,7 @@ int find_opt(jrx_handle *h, const char *key, bool tuning, OptRef *out)
         {"stat_weno_calls", 2, &h->stat_weno_calls}, {"stat_weno_fused", 2, &h->stat_weno_fused}, {"stat_weno3d_calls", 2, &h->stat_weno3d_calls}, {"stat_weno3d_fused", 2, &h->stat_weno3d_fused},
         {"stat_principal_calls", 2, &h->stat_principal_calls},
         {"stat_phase_ratios_calls", 2, &h->stat_phase_ratios_calls}, {"stat_phase_ratios_fused", 2, &h->stat_phase_ratios_fused},
+        {"stat_rotate_stress_calls", 2, &h->stat_rotate_stress_calls},
         {"stat_dyrel_launches", 2, &h->stat_dyrel_launches},
     };
     const OptRef tun[] = {
