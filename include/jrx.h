@@ -132,7 +132,7 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   "stat_weno3d_calls" / "stat_weno3d_fused" = the same for jrx_weno5_advection3d (the 2D pair counts 2D calls only),
  *   "stat_phase_ratios_calls" / "stat_phase_ratios_fused" = jrx_update_phase_ratios2d / 3d calls that launched / those that ran the one-launch form,
  *   "stat_rotate_stress_calls" = jrx_rotate_stress2d / 3d calls that launched,
- *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* entry points -- so that a caller
+ *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* and jrx_dyrel3d_* entry points -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
 /* the caller has written to an operand array (tau_o, P0, Q, K, G, eta, rho g) since the last driver call: a cached verdict of the operand pass ("operand_cache") is dropped */
@@ -950,6 +950,81 @@ jrx_status jrx_dyrel2d_update_dtauV_alpha_beta(jrx_handle *h, const jrx_dyrel2d_
 /* compute_bulk_viscosity_and_penalty! (constructors.jl:230-254): ηb, γ_eff; the mean of the finite η is reduced on the device */
 jrx_status jrx_dyrel2d_bulk_viscosity_and_penalty(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rheology *rh,
                                                   const jrx_vep2d_params *p, double gamma_fact);
+
+/* ------------------------------------------------------------------ 3D DYREL (the 2D section above, one dimension up; it takes the 3D multiphase structs)
+ * solve_DYREL!(stokes, ρg, dyrel, flow_bcs, phase_ratios, rheology, args, grid, dt, igg; kwargs...) on 3D grids.  The reference's 3D DYREL is half written.
+ * Restated literally: the allocator DYREL(ni::NTuple{3}) (src/DYREL/constructors.jl:61-111), dyrel_fields(Val(3)), velocity_dofs, pressure_dof, compute_λminV!
+ * (solver.jl:329-365), compute_∇V_strain_rate_RP! 3D (velocity_kernels.jl:242-322), compute_DR_residual_update_V! 3D (:729-828) and compute_PH_residual_V! 3D (:441-477)
+ * apart from their shear differences (below), the N-dimensional update_α_β! / update_dτV_α_β! (Gershgorin.jl:171-310), compute_dV!, update_cV!,
+ * compute_bulk_viscosity_and_penalty! (constructors.jl:230-254), the local law compute_local_stress / _compute_local_stress with its 6-component
+ * empty_stress_solution (stress_kernels.jl:224-315) and the loop _solve_DYREL! (solver.jl:44-294).
+ * No reference text -- the reference's compute_stress_viscosity_DRYEL! is 2D text and only Gershgorin_Stokes2D_SchurComplement! exists, so it cannot run a 3D solve:
+ *   Stress kernel: compute_stress_viscosity_DRYEL! laid out as update_stresses_center_vertex_ps! 3D (src/stokes/StressKernels.jl:672-989).
+ *     Centre: ε normals at the cell, each shear component the mean of the four surrounding edges of its family, τ_o = (xx, yy, zz, yz_c, xz_c, xy_c), η, P, λ,
+ *     EII_pl and the centre ratios at the cell; the local law with 6 components; written: τ normals and the three centre shear copies, ε_pl normals, ε_vol_pl,
+ *     τ.II, η_vep, λ, ΔPψ, θc = γ_eff RP + ΔPψ (P_num) and, unless linear_viscosity, η from the τII law (_update_τII_viscosity; its allzero·eps guard is taken
+ *     over all six components and applied as compute_viscosity! 3D applies it, rheology/Viscosity.jl:481-492: τxx + ε, τyy - ε/2, τzz - ε/2), continuation ν, cutoff.
+ *     Each edge family (yz, xz, xy) at its own extent, gathered as StressKernels.jl:705-733 and its siblings: η = harm_clamped_*(η); av_clamped_* of P, EII_pl,
+ *     the ε normals and the τ_o normals; the edge's own shear of ε and τ_o; the other two shears through av_clamped_*_y / _z / _x; the ratios phase_ratios.yz / xz /
+ *     xy; the local law with 6 components; kept: the edge's own shear stress, its plastic shear strain rate, its λv (three edge arrays).
+ *     Departures from the 2D text: no vertex-normal stresses τ.xx_v / yy_v / zz_v (nor their τ_o twins) are read or written, so the epilogue's
+ *     copy_stress_vertices!(..., Val(3)) is not performed; stokes.viscosity.ηv is neither read nor written; the τII refresh happens at the centres only, the
+ *     edge viscosity being derived from η.  The edges of a call see the η of the previous call (the edge half runs before the centre half).
+ *   Eigenvalue bound: Gershgorin_Stokes2D_SchurComplement! (Gershgorin.jl:21-155) one dimension up, over the operator these kernels apply.  Effective viscosity
+ *     at every node 1 / (1/η + 1/(G dt)), η at an edge = harm_clamped_*(η), G from the node's own ratios.  For Vx at (i, j, k) of (nx-1, ny, nz), 1-based:
+ *     E / W the centres [i+1,j,k] / [i,j,k], N / S the xy edges [i+1,j+1,k] / [i+1,j,k], T / B the xz edges [i+1,j,k+1] / [i+1,j,k];
+ *       Dx  = (ηN+ηS)/dy² + (ηT+ηB)/dz² + (γE+γW + 4/3 (ηE+ηW))/dx²
+ *       Cxx = |ηN|/dy² + |ηS|/dy² + |ηT|/dz² + |ηB|/dz² + |γE+4/3ηE|/dx² + |γW+4/3ηW|/dx² + |Dx|
+ *       Cxy = (|γE-2/3ηE+ηN| + |γE-2/3ηE+ηS| + |γW-2/3ηW+ηN| + |γW-2/3ηW+ηS|)/(dx dy),   Cxz alike with T / B and dz;   λmaxVx = (Cxx + Cxy + Cxz)/Dx;
+ *     Vy and Vz by cyclic permutation of the roles (Vy: yz edges across dz, xy edges across dx; Vz: xz edges across dx, yz edges across dy).
+ *   Momentum residuals: the reference's 3D text takes the shear differences from _d_xi / _d_yi / _d_zi of MiniKernels.jl:53-55, which read A[i+1, j+1, k+1] --
+ *     one plane past τxy, across two planes elsewhere.  Built instead: the index triples of the unmasked 3D velocity kernel (src/stokes/VelocityKernels.jl:215-238),
+ *       Rx[i,j,k] = (τxx[i+1,j,k]-τxx[i,j,k])/dx + (τxy[i+1,j+1,k]-τxy[i+1,j,k])/dy + (τxz[i+1,j,k+1]-τxz[i+1,j,k])/dz - d_xa(P) - d_xa(θ) - av_x(ρgx),
+ *     y and z alike; θ = ΔPψ (PH residual) or θc (DR residual).  These are the neighbours of the bound above.
+ * Built: 3D, one block, uniform spacing, the table rheology of jrx_rheology (every visc_kind, ConstantElasticity, an optional DruckerPrager_regularised with the
+ * softening laws, the density laws), free-slip / no-slip velocity boundary conditions, the plain pressure residual -∇V - (P - P0)/ηb + Q/dt, both values of
+ * linear_viscosity.  Status JRX_ERR_ARG before anything is launched, with a text that names the cause, for: a handle with a communicator; a non-uniform Geometry
+ * (inverse spacings that are not positive finite scalars: how a binding hands one over, this struct having no arrays for it); a RockRatio (phi non-NULL); an is_pl
+ * other than 0 or 1; d->dT or d->melt_fraction non-NULL; periodic faces; a free_surface boundary condition (handed over as p->displacement_bcs = -1, this struct
+ * having no member for it); fewer than 3 cells in a dimension; 2^31 or more entries in an array.
+ * Of jrx_vep3d_params these entry points read nx, ny, nz, nxg, nyg, nzg, _dx, _dy, _dz, dt, free_slip, no_slip, periodic, displacement_bcs and T_ghosted.
+ * jrx_dyrel2d_params and jrx_dyrel2d_result are reused: nothing in them is 2D-specific.  Counter "stat_dyrel_launches" counts these launches too.
+ * jrx_dyrel3d_fields: the arrays of the DYREL struct (types.jl:24-59): γ_eff, ηb, P_num (ni); Dx, λmaxVx, dVxdτ, dτVx, dVx, βVx, cVx, αVx, Rx0 (nx-1, ny, nz), their y
+ * members (nx, ny-1, nz) and z members (nx, ny, nz-1); then λ (ni), the three λv on the yz / xz / xy edges, ΔPψ (ni); then args.ΔT and args.melt_fraction (NULL). */
+typedef struct jrx_dyrel3d_fields {
+    double *gamma_eff, *etab, *P_num;
+    double *Dx, *Dy, *Dz, *lmaxVx, *lmaxVy, *lmaxVz, *dVxdtau, *dVydtau, *dVzdtau, *dtauVx, *dtauVy, *dtauVz, *dVx, *dVy, *dVz;
+    double *betaVx, *betaVy, *betaVz, *cVx, *cVy, *cVz, *alphaVx, *alphaVy, *alphaVz, *Rx0, *Ry0, *Rz0;
+    double *lambda, *lambda_yz, *lambda_xz, *lambda_xy, *dPpsi;
+    const double *dT, *melt_fraction;
+} jrx_dyrel3d_fields;
+/* DYREL!(dyrel, stokes, rheology, phase_ratios, di, dt; CFL, γfact) -- constructors.jl:178-190 with the 3D bound (no reference text) in the place of its 2D call */
+jrx_status jrx_dyrel3d_init(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_rock_ratio3d *phi, const jrx_rheology *rh,
+                            const jrx_vep3d_params *p, const jrx_dyrel2d_params *dp);
+/* _solve_DYREL! (solver.jl:44-294) on a 3D grid.  At entry P0 = P and the centre members of ε_pl, λ and the three λv are zeroed; compute_viscosity!, compute_ρg!
+ * (into ρg[3]), DYREL!; the Powell-Hestenes loop with rel_drop and err_min; norms over velocity_dofs(Val(3)) and pressure_dof, norm(D .* R) at the checks, errV00
+ * from the first check; per check compute_λminV!, update_cV!, the 3D bound, update_dτV_α_β!; P += γ_eff RP after each velocity solve; epilogue P += ΔPψ,
+ * compute_∇V!, compute_vorticity! 3D, shear2center! of ε / ε_pl / Δε, accumulate_tensor!, accumulate_vol!, τ_o = τ (normals, edge shears, centre shears).  An inner
+ * iteration is four launches (strain rate + RP, stress edges, stress centres, update) plus flow_bcs!; the host reads the device sums once per Powell-Hestenes
+ * iteration and once per nout inner iterations.  JRX_ERR_NAN for the reference's error("NaN detected ...") / error("Kaboom! ..."). */
+jrx_status jrx_dyrel3d_solve(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_rock_ratio3d *phi, const jrx_rheology *rh,
+                             const jrx_vep3d_params *p, const jrx_dyrel2d_params *dp, jrx_dyrel2d_result *res);
+/* the kernels alone, for parity tests.  compute_∇V_strain_rate_RP! 3D (velocity_kernels.jl:242-322): the six strain rates (do_strain_rate != 0) and R.RP */
+jrx_status jrx_dyrel3d_strain_rate_RP(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_vep3d_params *p, int32_t do_strain_rate);
+/* the 3D stress kernel (no reference text; the form stated above); of dp it reads viscosity_relaxation, the cutoff and linear_viscosity */
+jrx_status jrx_dyrel3d_stress_viscosity(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_rheology *rh, const jrx_vep3d_params *p,
+                                        const jrx_dyrel2d_params *dp, double lambda_relaxation);
+/* compute_PH_residual_V! 3D (velocity_kernels.jl:441-477, shear differences as stated above): R.Rx, R.Ry, R.Rz from τ, P, ΔPψ, ρg */
+jrx_status jrx_dyrel3d_PH_residual(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_vep3d_params *p);
+/* compute_DR_residual_update_V! 3D (velocity_kernels.jl:729-828, shear differences as stated above): R / D, dVdτ <- α dVdτ + R, V += dVdτ β dτ; ghosts left to flow_bcs! */
+jrx_status jrx_dyrel3d_DR_residual_update_V(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_vep3d_params *p);
+/* the 3D eigenvalue bound (no reference text; the form stated above): Dx, Dy, Dz, λmaxVx, λmaxVy, λmaxVz */
+jrx_status jrx_dyrel3d_gershgorin(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_rheology *rh, const jrx_vep3d_params *p);
+/* update_dτV_α_β! (Gershgorin.jl:216-247, 290-310; from_lambda_max != 0) or update_α_β! (:171-198, 272-288; dτV as it is, CFL not read), three components */
+jrx_status jrx_dyrel3d_update_dtauV_alpha_beta(jrx_handle *h, const jrx_dyrel3d_fields *d, const jrx_vep3d_params *p, double CFL, int32_t from_lambda_max);
+/* compute_bulk_viscosity_and_penalty! (constructors.jl:230-254): ηb, γ_eff; the mean of the finite η is reduced on the device */
+jrx_status jrx_dyrel3d_bulk_viscosity_and_penalty(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_rheology *rh,
+                                                  const jrx_vep3d_params *p, double gamma_fact);
 
 #ifdef __cplusplus
 }

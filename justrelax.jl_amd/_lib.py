@@ -104,6 +104,10 @@ MAXPHASE = 8
 DYREL_NAMES = ["gamma_eff", "etab", "P_num", "Dx", "Dy", "lmaxVx", "lmaxVy", "dVxdtau", "dVydtau", "dtauVx", "dtauVy", "dVx", "dVy", "betaVx", "betaVy",
                "cVx", "cVy", "alphaVx", "alphaVy", "Rx0", "Ry0", "txx_v", "tyy_v", "toxx_v", "toyy_v", "lambda", "lambda_v", "dPpsi", "dT", "melt_fraction"]
 DYREL2DFields = _ptr_struct("DYREL2DFields", DYREL_NAMES)      # jrx_dyrel2d_fields
+DYREL3_NAMES = ["gamma_eff", "etab", "P_num"] + [k + c for k in ("D", "lmaxV") for c in "xyz"] + [f"dV{c}dtau" for c in "xyz"] + \
+               [k + c for k in ("dtauV", "dV", "betaV", "cV", "alphaV") for c in "xyz"] + ["Rx0", "Ry0", "Rz0"] + \
+               ["lambda", "lambda_yz", "lambda_xz", "lambda_xy", "dPpsi", "dT", "melt_fraction"]
+DYREL3DFields = _ptr_struct("DYREL3DFields", DYREL3_NAMES)      # jrx_dyrel3d_fields
 
 
 class Rheology(C.Structure):

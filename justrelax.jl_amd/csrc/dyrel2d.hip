@@ -16,11 +16,12 @@
 // plasticity helpers (plastic_params, yield_F, plastic_grad) average the PARAMETERS over the phases of a node; DYREL's compute_local_stress evaluates the whole
 // return mapping per phase and averages the RESULTS, so those three do not apply: the yield function and the flow direction of one phase are formed here from
 // the same per-phase laws.  32-bit element offsets (the extents are checked against 2^31).  fma only in update_α_β (the reference's @muladd).
-// Not built: 3D, more than one rank, non-uniform spacing, a RockRatio, the thermal / melt-fraction forms of _RP_cell.
+// Not built here: 3D (dyrel3d.hip), more than one rank, non-uniform spacing, a RockRatio, the thermal / melt-fraction forms of _RP_cell.
 #include <initializer_list>
 #include "jrx_internal.hpp"
 #include "jrx_kernels.hpp"
 #include "jrx_material.hpp"
+#include "dyrel_local.hpp"
 #include "stokes2d_kernels.hpp"
 
 namespace {
@@ -70,80 +71,7 @@ __global__ __launch_bounds__(256) void k_dy_strain_rp(double *__restrict__ exx, 
 #undef VY
 }
 
-// the 11 values compute_local_stress returns: τ (xx, yy, xy), ε_pl (xx, yy, xy), τII, λ, ΔPψ, η_vep, ε_vol_pl
-struct DyLocal { double v[11]; };
-
-// compute_local_stress (stress_kernels.jl:224-247) with _compute_local_stress (:249-307) per phase: ratio .* result, summed in phase order
-template <bool SOFT>
-__device__ __forceinline__ DyLocal dy_local_stress(const jrx_rheology &rh, const double *__restrict__ r, const double e0, const double e1, const double e2,
-                                                   const double to0, const double to1, const double to2, const double eta, const double P, const double lam,
-                                                   const double rel, const double dt, const double EII)
-{
-    DyLocal acc;
-#pragma unroll
-    for (int s = 0; s < 11; s++) acc.v[s] = 0.0;
-    const double eII_in = sinv2(e0, e1, e2);
-    for (int q = 0; q < rh.nphase; q++) {
-        const double rq = r[q];
-        double o[11];
-#pragma unroll
-        for (int s = 0; s < 11; s++) o[s] = 0.0;      // empty_stress_solution / the early return
-        if (rq != 0.0) {
-            const double G = rh.G[q], Kb = rh.Kb[q];
-            const bool ispl = rh.is_pl[q] != 0;
-            const double eta_reg = ispl ? rh.eta_vp[q] : 0.0;
-            const double eta_ve = isinf(G) ? 1.0 / (1.0 / eta + 1.0 / (G * dt)) : (eta * G * dt) / (eta + G * dt);
-            const double inv_2Gdt = 1.0 / (2 * G * dt);
-            const double f0 = e0 + to0 * inv_2Gdt, f1 = e1 + to1 * inv_2Gdt, f2 = e2 + to2 * inv_2Gdt;
-            if (sinv2(f0, f1, f2) == 0.0) o[9] = eta;
-            else {
-                double t0 = 2 * eta_ve * f0, t1 = 2 * eta_ve * f1, t2 = 2 * eta_ve * f2;
-                double tII = sinv2(t0, t1, t2);
-                double F = tII, g0 = 0.0, g1 = 0.0, g2 = 0.0, dQdP = 0.0, dFdP = 0.0;
-                if (ispl) {      // Drucker-Prager: F = τII - cosϕ(EII) C(EII) - sinϕ(EII) P; ∂Q/∂τ = τ / (2 τII), shear slot halved once; ∂Q/∂P = -sinψ; ∂F/∂P = -sinϕ
-                    double sp = rh.sinphi[q], cp = rh.cosphi[q], C = rh.C[q];
-                    if (SOFT) { mat_friction(rh, q, EII, sp, cp); C = mat_cohesion(rh, q, EII); }
-                    F = tII - cp * C - sp * P;
-                    g0 = 0.5 * t0 / tII; g1 = 0.5 * t1 / tII; g2 = 0.5 * (t2 / tII);
-                    dQdP = -rh.sinpsi[q]; dFdP = -rh.sinphi[q];
-                }
-                double l = 0.0, evol = 0.0;
-                if (ispl && F >= 0) {
-                    const double bulk = isinf(Kb) ? 0.0 : Kb * dt * dFdP * dQdP;
-                    const double lnew = F / (eta_ve + eta_reg + bulk);
-                    l = rel * lnew + (1 - rel) * lam;
-                    evol = -l * dQdP;
-                }
-                double p0 = 0.0, p1 = 0.0, p2 = 0.0, dP = 0.0;
-                if (l > 0) {
-                    p0 = l * g0; p1 = l * g1; p2 = l * g2;
-                    t0 = t0 - 2.0 * eta_ve * p0; t1 = t1 - 2.0 * eta_ve * p1; t2 = t2 - 2.0 * eta_ve * p2;
-                    tII = sinv2(t0, t1, t2);
-                    dP = dQdP == 0.0 ? 0.0 : -l * dQdP * Kb * dt;
-                }
-                o[0] = t0; o[1] = t1; o[2] = t2; o[3] = p0; o[4] = p1; o[5] = p2; o[6] = tII; o[7] = l; o[8] = dP;
-                o[9] = tII * 0.5 * (1.0 / eII_in);
-                o[10] = evol;
-            }
-#pragma unroll
-            for (int s = 0; s < 11; s++) o[s] = rq * o[s];
-        }
-#pragma unroll
-        for (int s = 0; s < 11; s++) acc.v[s] = q == 0 ? o[s] : acc.v[s] + o[s];
-    }
-    return acc;
-}
-
-// _update_τII_viscosity (stress_kernels.jl:129-135): the creep viscosity at the invariant of the fresh stress, continuation_linear with the old value, cutoff
-__device__ __forceinline__ double dy_visc(const DyArgs &a, const double *r, const double txx, const double tyy, const double txy, const double T, const double P,
-                                          const double eta_old)
-{
-    const double tII = mat_visc_invariant2(txx, tyy, txy);
-    const double e = mat_phase_viscosity(a.rh, r, tII, T, P, true);
-    const double x = (1 - a.nu) * eta_old + a.nu * e;
-    return fmin(fmax(x, a.cut_lo), a.cut_hi);
-}
-
+// the local law (compute_local_stress, _update_τII_viscosity) is dyrel_local.hpp's, with NC = 3 components (xx, yy, xy): 11 values per node
 // compute_stress_viscosity_DRYEL! (stress_kernels.jl:137-222): one thread per vertex index; the vertex half, then the centre half of the cell with the same index
 template <bool SOFT, bool LIN>
 __global__ __launch_bounds__(256) void k_dy_stress(const DyArgs a)
@@ -161,7 +89,8 @@ __global__ __launch_bounds__(256) void k_dy_stress(const DyArgs a)
 #undef AVC
         const double etav = a.f.eta_v[t];
         const double *rv = a.f.phase_v + np * t;
-        const DyLocal o = dy_local_stress<SOFT>(a.rh, rv, e0, e1, exy[t], a.d.toxx_v[t], a.d.toyy_v[t], a.f.toxy[t], etav, Pv, a.d.lambda_v[t], a.rel, a.dt, EIIv);
+        const double ev[3] = {e0, e1, exy[t]}, tov[3] = {a.d.toxx_v[t], a.d.toyy_v[t], a.f.toxy[t]};
+        const DyLocal<3> o = dy_local_stress<SOFT, 3>(a.rh, rv, ev, tov, etav, Pv, a.d.lambda_v[t], a.rel, a.dt, EIIv);
         a.d.txx_v[t] = o.v[0]; a.d.tyy_v[t] = o.v[1]; a.f.txy[t] = o.v[2];
         a.f.eplxy[t] = o.v[5];
         a.d.lambda_v[t] = o.v[7];
@@ -172,7 +101,7 @@ __global__ __launch_bounds__(256) void k_dy_stress(const DyArgs a)
                 else T = 0.25 * (C2(a.f.T, i0, j0) + C2(a.f.T, ic, j0) + C2(a.f.T, i0, jc) + C2(a.f.T, ic, jc));
             }
             const double Pa = vfields ? 0.25 * (C2(P, i0, j0) + C2(P, ic, j0) + C2(P, i0, jc) + C2(P, ic, jc)) : 0.0;
-            a.f.eta_v[t] = dy_visc(a, rv, o.v[0], o.v[1], o.v[2], T, Pa, etav);
+            a.f.eta_v[t] = dy_visc<3>(a.rh, a.nu, a.cut_lo, a.cut_hi, rv, o.v, T, Pa, etav);
         }
     }
     if (i < nx && j < ny) {      // centre (i, j)
@@ -180,7 +109,8 @@ __global__ __launch_bounds__(256) void k_dy_stress(const DyArgs a)
         const double e2 = (V2(exy, i, j) + V2(exy, i + 1, j) + V2(exy, i, j + 1) + V2(exy, i + 1, j + 1)) / 4;      // sum(_gather(ε.xy)) / 4
         const double eta = a.f.eta[c], Pc = P[c];
         const double *rc = a.f.phase_c + np * c;
-        const DyLocal o = dy_local_stress<SOFT>(a.rh, rc, exx[c], eyy[c], e2, a.f.toxx[c], a.f.toyy[c], a.f.toxy_c[c], eta, Pc, a.d.lambda[c], a.rel, a.dt, EIIa[c]);
+        const double ec[3] = {exx[c], eyy[c], e2}, toc[3] = {a.f.toxx[c], a.f.toyy[c], a.f.toxy_c[c]};
+        const DyLocal<3> o = dy_local_stress<SOFT, 3>(a.rh, rc, ec, toc, eta, Pc, a.d.lambda[c], a.rel, a.dt, EIIa[c]);
         a.f.txx[c] = o.v[0]; a.f.tyy[c] = o.v[1]; a.f.txy_c[c] = o.v[2];
         a.f.eplxx[c] = o.v[3]; a.f.eplyy[c] = o.v[4];
         a.f.evol_pl[c] = o.v[10];
@@ -191,7 +121,7 @@ __global__ __launch_bounds__(256) void k_dy_stress(const DyArgs a)
         a.d.P_num[c] = a.d.gamma_eff[c] * a.f.RP[c] + o.v[8];      // θc = γ_eff RP + ΔPψ
         if (!LIN) {
             const double T = (vfields && a.f.T) ? (a.tg ? a.f.T[(i + 1) + (nx + 2) * (j + 1)] : a.f.T[c]) : 0.0;      // local_viscosity_args: T[I .+ 1]
-            a.f.eta[c] = dy_visc(a, rc, o.v[0], o.v[1], o.v[2], T, Pc, eta);
+            a.f.eta[c] = dy_visc<3>(a.rh, a.nu, a.cut_lo, a.cut_hi, rc, o.v, T, Pc, eta);
         }
     }
 }

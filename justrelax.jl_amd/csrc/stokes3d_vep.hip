@@ -16,6 +16,7 @@
 #include "jrx_internal.hpp"
 #include "jrx_kernels.hpp"
 #include "jrx_material.hpp"
+#include "edge_stencils3d.hpp"
 #include "vep3_plan.hpp"
 
 namespace {
@@ -215,25 +216,7 @@ __global__ __launch_bounds__(256) void k_vep3_phase_avg(double *__restrict__ Kc,
     }
 }
 
-// Stencil tables of StressKernels.jl:604-668 for the edge families T = 0 (yz), 1 (xz), 2 (xy): entries pick the
-// clamped index {0: n-1, 1: n, 2: n+1} per direction, in the reference's order of summation.  constexpr functions so that the
-// unrolled loops fold every table entry into the address arithmetic.
-__host__ __device__ constexpr int cen3(int t, int q, int d)
-{
-    constexpr int T[3][4][3] = {
-        {{1, 0, 0}, {1, 1, 0}, {1, 0, 1}, {1, 1, 1}},
-        {{0, 1, 0}, {1, 1, 0}, {0, 1, 1}, {1, 1, 1}},
-        {{0, 0, 1}, {1, 0, 1}, {0, 1, 1}, {1, 1, 1}}};
-    return T[t][q][d];
-}
-__host__ __device__ constexpr int oth3(int t, int s, int q, int d)
-{
-    constexpr int T[3][3][4][3] = {
-        {{{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, {{1, 0, 1}, {2, 0, 1}, {1, 1, 1}, {2, 1, 1}}, {{1, 1, 0}, {2, 1, 0}, {1, 1, 1}, {2, 1, 1}}},
-        {{{0, 1, 1}, {1, 1, 1}, {1, 2, 1}, {0, 2, 1}}, {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, {{1, 1, 0}, {1, 2, 0}, {1, 1, 1}, {1, 2, 1}}},
-        {{{0, 1, 1}, {1, 1, 1}, {0, 1, 2}, {1, 1, 2}}, {{1, 0, 1}, {1, 1, 1}, {1, 0, 2}, {1, 1, 2}}, {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}}};
-    return T[t][s][q][d];
-}
+// The stencil tables cen3 / oth3 of StressKernels.jl:604-668 are edge_stencils3d.hpp's.
 
 // return mapping of one edge node of family T (StressKernels.jl:724-779 and the two sibling blocks), in two steps so that the z-marching
 // kernel can reduce its operands to the trial stress early: edge_mat (phase-ratio material values of the node), then vep3_edge_plastic on
