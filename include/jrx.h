@@ -364,6 +364,19 @@ typedef struct jrx_vep2d_fields {
     double *phase_c, *phase_v;                     /* phase_ratios.center / .vertex */
     const double *T;                               /* args.T at the cell centres (ni) for the density laws; may be NULL (T = 0) */
     double *dexx, *deyy, *divU;                    /* strain_increment variant: Δε.xx, Δε.yy, stokes.∇U (ni); may be NULL otherwise */
+    /* ---- appended with the thermal stresses; a zero-initialised tail gives the isothermal pressure equation ----
+     * args.ΔT: compute_P! of the multiphase driver gains the thermal-expansion source α ΔT / dt (PressureKernels.jl:64-85,129-152,197-206; handed over
+     * by Stokes2D.jl:663-676): rhs = (-∇V + (α_c * (ΔT * _dt))) + (Q * _dt), with α_c = fn_ratio(get_thermal_expansion, rheology, phase_ratio[I]) -- the phase-ratio
+     * sum with the early-return and skip rules of the density average; α of a phase is its `alpha` for the density kinds PT_Density and T_Density and 0 for
+     * ConstantDensity and Compressible_Density [GeoParams form, assumed]; rho_kind and alpha are read whether or not has_density is set (ρg may stay the caller's).  For ratios that
+     * sum to one this is the plain phase-ratio sum of PressureKernels.jl:147.  ΔT is read at the cell's own [i, j] (PressureKernels.jl:149): cell-centred (ni), or
+     * thermal.ΔT itself (ni .+ 2) with p->dT_ghosted = 1, then still unshifted.  NULL: the instantiations and the bits of the isothermal driver.
+     * Read by jrx_stokes2d_vep_solve (all its forms) and jrx_vep2d_compute_P only: the single-phase driver hands compute_P! no args (Stokes2D.jl:420), the ΔT
+     * methods of the variational drivers are commented out in the reference, and the DYREL drivers refuse ΔT by the members of their own struct. */
+    const double *dT;
+    /* args.melt_fraction: a no-op without ΔT, as in the reference (PressureKernels.jl:108-127).  Together with ΔT the reference takes α(ϕ) from GeoParams in a
+     * form nothing under it states: refused with JRX_ERR_ARG before anything is launched. */
+    const double *melt_fraction;
 } jrx_vep2d_fields;
 
 typedef struct jrx_vep2d_params {
@@ -380,6 +393,7 @@ typedef struct jrx_vep2d_params {
     int32_t strain_increment;                      /* kwarg strain_increment (jrx_stokes2d_vep_solve only; Stokes2D.jl:588,659-734, StressKernels.jl:1147-1302): strains
                                                     * from the displacement increments U = V dt, Δε form of the stress update; U and its BCs are refreshed every iteration */
     const double *inv_spacing[6];                  /* non-uniform Geometry: as in jrx_stokes2d_params (all NULL: uniform); not with strain_increment */
+    int32_t dT_ghosted;                            /* f->dT = args.ΔT is thermal.ΔT (nx+2, ny+2), read at the cell's own [i, j]; 0: cell-centred (ni) */
 } jrx_vep2d_params;
 
 jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_rheology *rh, const jrx_vep2d_params *p,
@@ -388,12 +402,18 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
  * single-phase visco-elasto-plastic driver built on compute_τ_nonlinear! and center2vertex! (test/test_WENO5.jl:226-291).  The rheology is
  * phase 0 of the table (creep law, ConstantElasticity, optional DruckerPrager_regularised, density); phase_c / phase_v are not read.
  * f->T = args.T: cell-centred (ni), or thermal.T (ni.+2) with p->T_ghosted = 1 -- then read at [i, j] by the density and at [i+1, j+1]
- * by the viscosity, as the reference's two argument helpers do. */
+ * by the viscosity, as the reference's two argument helpers do.  f->dT and f->melt_fraction are not read: this driver hands compute_P! no args
+ * (Stokes2D.jl:420). */
 jrx_status jrx_stokes2d_nonlinear_solve(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_rheology *rh, const jrx_vep2d_params *p,
                                         jrx_solve_result *res);
 /* update_stresses_center_vertex_ps! alone (θ, λ, λv are caller arrays of extents ni, ni, ni.+1) -- for parity tests */
 jrx_status jrx_vep2d_update_stresses(jrx_handle *h, const jrx_vep2d_fields *f, const double *theta, double *lambda, double *lambda_v,
                                      const jrx_rheology *rh, const jrx_vep2d_params *p);
+/* the phase averages (K, G, and with f->dT the thermal source α_c * (ΔT * _dt)) and one evaluation of compute_∇V! + compute_P! (phase form, thermal form with
+ * f->dT: PressureKernels.jl:87-106,129-152) + compute_strain_rate! on the caller's arrays -- for parity tests.  θ (ni) is the pressure compute_P! updates in
+ * place; ητ is taken as the driver's first iteration takes it (compute_maxloc! of f->eta).  Writes θ, ∇V, RP, ε.xx, ε.yy, ε.xy and nothing else;
+ * reads f->Q, f->P0, V, η, the centre phase ratios.  f->dT with f->melt_fraction is refused as in the solve. */
+jrx_status jrx_vep2d_compute_P(jrx_handle *h, const jrx_vep2d_fields *f, double *theta, const jrx_rheology *rh, const jrx_vep2d_params *p);
 /* compute_τ_nonlinear! 2D alone: single phase (multiphase = 0; StressKernels.jl:266-307, uses rheology phase 0) or phases at
  * the cell centres (multiphase = 1; :310-351) with _compute_τ_nonlinear! (rheology/StressUpdate.jl:2-57).  Centre-only
  * visco-elasto-plastic update: writes τ.xx, τ.yy, τ.xy_c, τ.II, η_vep, ε_pl.xx, ε_pl.yy, ε_pl.xy[i,j], λ and θ (caller
@@ -473,6 +493,11 @@ typedef struct jrx_vep3d_fields {
     double *omega_yz, *omega_xz, *omega_xy;               /* optional: vorticity on the edges */
     const double *phase_c, *phase_yz, *phase_xz, *phase_xy;
     const double *T;                                      /* args.T at the cell centres (ni); may be NULL (T = 0) */
+    /* ---- appended with the thermal stresses; a zero-initialised tail gives the isothermal pressure equation ----
+     * args.ΔT and args.melt_fraction as in jrx_vep2d_fields (compute_P! of Stokes3D.jl:518-531, PressureKernels.jl:129-152,197-206): ΔT at the cell's own
+     * [i, j, k], of extent ni or -- p->dT_ghosted = 1 -- ni .+ 2.  Read by jrx_stokes3d_vep_solve (fused, three-kernel and multi-rank paths) and jrx_vep3d_compute_P. */
+    const double *dT;
+    const double *melt_fraction;
 } jrx_vep3d_fields;
 
 typedef struct jrx_vep3d_params {
@@ -487,6 +512,7 @@ typedef struct jrx_vep3d_params {
     int32_t T_ghosted;             /* f->T = args.T is thermal.T (ni .+ 2), as the miniapps pass it (RisingBlob3D/Blob3D.jl:355): update_ρg! reads it at the cell's own
                                     * [i, j, k], unshifted (getindex_NamedTuple(args, I...), BuoyancyForces.jl:52); 0: cell-centred (ni) */
     int32_t b_width[3];            /* kwargs.b_width (Stokes3D.jl:460): boundary-slab widths of the hidden update_halo!(V) (multi-rank runs; <= 0: 4) */
+    int32_t dT_ghosted;            /* f->dT = args.ΔT is thermal.ΔT (ni .+ 2), read at the cell's own [i, j, k]; 0: cell-centred (ni) */
 } jrx_vep3d_params;
 
 jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_rheology *rh, const jrx_vep3d_params *p,
@@ -495,6 +521,8 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
  * Every update reads the stresses of the previous call (the reference's single launch races on neighbouring values). */
 jrx_status jrx_vep3d_update_stresses(jrx_handle *h, const jrx_vep3d_fields *f, const double *theta, double *lambda, double *const lambda_v[3],
                                      const jrx_rheology *rh, const jrx_vep3d_params *p);
+/* jrx_vep2d_compute_P one dimension up: writes θ (ni), ∇V, RP and the six components of ε; nothing else */
+jrx_status jrx_vep3d_compute_P(jrx_handle *h, const jrx_vep3d_fields *f, double *theta, const jrx_rheology *rh, const jrx_vep3d_params *p);
 /* compute_viscosity! 3D (εII form; ..._tauII: update_viscosity_τII!) for the table rheology: η <- ν·η_phase + (1-ν)·η, clamped to the cutoff; creep laws that
  * read fields: T, P at the cell, invariant of @strain / @stress with the edge components gathered (Viscosity.jl:455-503) */
 jrx_status jrx_vep3d_compute_viscosity(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_rheology *rh, const jrx_vep3d_params *p, double nu);

@@ -96,7 +96,8 @@ ThermalPhaseFields = _ptr_struct("ThermalPhaseFields", TPH_NAMES)
 
 VEP_NAMES = ["P", "P0", "divV", "Q", "Vx", "Vy", "Ux", "Uy", "exx", "eyy", "exy", "exy_c", "eplxx", "eplyy", "eplxy", "eplxy_c",
              "dexy_c", "dexy", "txx", "tyy", "txy", "txy_c", "tII", "toxx", "toyy", "toxy", "toxy_c", "eta", "eta_v", "eta_vep",
-             "EII_pl", "evol_pl", "EVol_pl", "fx", "fy", "RP", "Rx", "Ry", "omega_xy", "phase_c", "phase_v", "T", "dexx", "deyy", "divU"]
+             "EII_pl", "evol_pl", "EVol_pl", "fx", "fy", "RP", "Rx", "Ry", "omega_xy", "phase_c", "phase_v", "T", "dexx", "deyy", "divU",
+             "dT", "melt_fraction"]      # args.ΔT / args.melt_fraction of the multiphase driver's compute_P! (NULL: isothermal)
 VEP2DFields = _ptr_struct("VEP2DFields", VEP_NAMES)
 RockRatio2D = _ptr_struct("RockRatio2D", ["center", "vertex", "Vx", "Vy"])      # jrx_rock_ratio2d
 RockRatio3D = _ptr_struct("RockRatio3D", ["center", "vertex", "Vx", "Vy", "Vz", "yz", "xz", "xy"])      # jrx_rock_ratio3d
@@ -129,7 +130,7 @@ class VEP2DParams(C.Structure):
                 ("free_slip", C.c_uint32), ("no_slip", C.c_uint32), ("periodic", C.c_uint32),
                 ("lambda_relaxation", C.c_double), ("viscosity_relaxation", C.c_double), ("cutoff_lo", C.c_double), ("cutoff_hi", C.c_double),
                 ("verbose", C.c_int32), ("free_surface", C.c_int32), ("displacement_bcs", C.c_int32), ("T_ghosted", C.c_int32), ("strain_increment", C.c_int32),
-                ("inv_spacing", C.c_void_p * 6)]
+                ("inv_spacing", C.c_void_p * 6), ("dT_ghosted", C.c_int32)]
 
 
 VEP3_NAMES = ["P", "P0", "divV", "Q", "Vx", "Vy", "Vz", "Ux", "Uy", "Uz",
@@ -139,7 +140,7 @@ VEP3_NAMES = ["P", "P0", "divV", "Q", "Vx", "Vy", "Vz", "Ux", "Uy", "Uz",
               "txx", "tyy", "tzz", "tyz", "txz", "txy", "tyz_c", "txz_c", "txy_c", "tII",
               "toxx", "toyy", "tozz", "toyz", "toxz", "toxy", "toyz_c", "toxz_c", "toxy_c",
               "eta", "eta_vep", "EII_pl", "evol_pl", "EVol_pl", "fx", "fy", "fz", "RP", "Rx", "Ry", "Rz",
-              "omega_yz", "omega_xz", "omega_xy", "phase_c", "phase_yz", "phase_xz", "phase_xy", "T"]
+              "omega_yz", "omega_xz", "omega_xy", "phase_c", "phase_yz", "phase_xz", "phase_xy", "T", "dT", "melt_fraction"]
 VEP3DFields = _ptr_struct("VEP3DFields", VEP3_NAMES)
 
 
@@ -150,7 +151,7 @@ class VEP3DParams(C.Structure):
                 ("eps_rel", C.c_double), ("eps_abs", C.c_double), ("iterMax", C.c_int64), ("nout", C.c_int64),
                 ("free_slip", C.c_uint32), ("no_slip", C.c_uint32), ("periodic", C.c_uint32),
                 ("lambda_relaxation", C.c_double), ("viscosity_relaxation", C.c_double), ("cutoff_lo", C.c_double), ("cutoff_hi", C.c_double),
-                ("verbose", C.c_int32), ("displacement_bcs", C.c_int32), ("T_ghosted", C.c_int32), ("b_width", C.c_int32 * 3)]
+                ("verbose", C.c_int32), ("displacement_bcs", C.c_int32), ("T_ghosted", C.c_int32), ("b_width", C.c_int32 * 3), ("dT_ghosted", C.c_int32)]
 
 
 class DYREL2DParams(C.Structure):      # jrx_dyrel2d_params

@@ -25,6 +25,24 @@ __device__ __forceinline__ double mat_density_ratio(const jrx_rheology &rh, cons
     }
     return x;
 }
+// get_thermal_expansion of a phase: the α of its density law (PT_Density, T_Density), 0 for the laws without one [GeoParams form, assumed; include/jrx.h]
+__device__ __forceinline__ double mat_thermal_expansion(const jrx_rheology &rh, int q)
+{
+    return (rh.rho_kind[q] == 1 || rh.rho_kind[q] == 2) ? rh.alpha[q] : 0.0;
+}
+// fn_ratio(get_thermal_expansion, rheology, ratio) with the rules of mat_density_ratio (zero ratios skipped, a ratio of one returns that phase's value alone).  The early return is this
+// project's choice: PressureKernels.jl:147 calls the three-argument fn_ratio (src/phases/phases.jl:6-15), which only skips zero ratios.  The two differ only when a ratio of exactly 1
+// follows a non-zero ratio, i.e. never for ratios that sum to one.
+__device__ __forceinline__ double mat_thermal_expansion_ratio(const jrx_rheology &rh, const double *r)
+{
+    double x = 0.0;
+    for (int q = 0; q < rh.nphase; q++) {
+        const double rq = r[q];
+        if (rq == 1.0) return mat_thermal_expansion(rh, q) * rq;
+        x += (rq == 0.0) ? 0.0 : mat_thermal_expansion(rh, q) * rq;
+    }
+    return x;
+}
 static inline bool mat_density_is_constant(const jrx_rheology *rh)
 {
     for (int q = 0; q < rh->nphase; q++)

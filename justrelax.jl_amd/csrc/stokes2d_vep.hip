@@ -26,6 +26,7 @@ struct VepArgs {
     jrx_rheology rh;
     const double *theta, *etatau, *Kc, *Gc;
     const double *eta_lin_c, *eta_lin_v;                // linear laws: phase-averaged η at centres / vertices, computed once per solve (nullptr: from the ratios per call)
+    const double *src;                                  // args.ΔT: the thermal source α_c * (ΔT * _dt) of compute_P! at the centres, constant over a solve (k_phase_avg); read by the TH forms of the pre kernels only
     double *lam, *lamv;
     double *txx_out = nullptr, *tyy_out = nullptr;      // where the centre half writes τxx, τyy (nullptr: in place)
     Sp2 sp;                                             // non-uniform grid: inverse spacing arrays (all NULL: _dx, _dy)
@@ -34,6 +35,7 @@ struct VepArgs {
     bool soft;            // some phase has a softening law (EII_pl is then read by the yield function)
     bool si;              // strain_increment variant
     bool tg;              // args.T is the ghosted thermal.T (nx+2, ny+2): densities read it at the cell's own [i, j], unshifted (BuoyancyForces.jl:52)
+    bool dtg;             // args.ΔT is the ghosted thermal.ΔT (nx+2, ny+2): compute_P! reads it at the cell's own [i, j], unshifted (PressureKernels.jl:149)
     bool vfields;         // some phase's creep law reads T, P or the invariant (visc_kind != 0)
     bool vtau;            // the viscosity is taken from the stress (update_viscosity_τII!, the in-loop form) rather than from the strain rate (compute_viscosity!)
     bool obs = true;      // the outputs nothing inside the PT loop reads -- ∇V, RP, ε_pl (3), ε_vol_pl, τII, η_vep -- are stored; the solve loop clears it on iterations whose
@@ -54,7 +56,8 @@ __device__ __forceinline__ double sinv_stag(double xx, double yy, double a, doub
 // ML: compute_maxloc!(ητ, η) of the own cell first (clamped 3 x 3 window, same comparison order as k_maxloc) and store it: saves the
 // separate launch of the launch-bound 2D loop
 // RHO: update_ρg! of the own cell (args.T, args.P = stokes.P; phase-ratio density times the scalar gravity, into the last component of ρg)
-template <bool ML, bool RHO = false>
+// TH: the thermal form of _compute_P! (PressureKernels.jl:197-206): rhs = (-∇V + (α * (ΔT * _dt))) + (Q * _dt), the middle term read from a.src
+template <bool ML, bool RHO = false, bool TH = false>
 __global__ __launch_bounds__(256) void k_vep_pre(const VepArgs a, double *__restrict__ theta)
 {
     const int nx = a.nx, ny = a.ny;
@@ -72,7 +75,7 @@ __global__ __launch_bounds__(256) void k_vep_pre(const VepArgs a, double *__rest
         if (a.obs) a.f.divV[c] = divV;
         const double _Kdt = 1.0 / (a.Kc[c] * a.dt), _Gdt = 1.0 / (a.Gc[c] * a.dt), _dt = 1.0 / a.dt;
         const double P = theta[c], P0 = a.f.P0[c];
-        const double rhs = -divV + (a.f.Q[c] * _dt);
+        const double rhs = TH ? (-divV + a.src[c]) + (a.f.Q[c] * _dt) : -divV + (a.f.Q[c] * _dt);
         if (a.obs) a.f.RP[c] = fma(-(P - P0), _Kdt, rhs);
         double et;
         if (ML) {
@@ -129,8 +132,8 @@ __global__ __launch_bounds__(256) void k_vep_strain_inc(const VepArgs a)
 }
 // compute_stress_increment(τ, τ_o, η, Δε, _G, dτ_r, dt) -- StressKernels.jl:18-21
 // k_vep_pre<ML = true> for uniform grids and constant densities with every operand requested up front (option "fused2d_batch"): the control-flow form issues its 24 loads in five
-// dependent groups (the 3 x 3 window of η compares as it loads, every `if (a.obs)` ends a basic block); same arithmetic, expression for expression.  OBS: a.obs as a constant.
-template <bool OBS>
+// dependent groups (the 3 x 3 window of η compares as it loads, every `if (a.obs)` ends a basic block); same arithmetic, expression for expression.  OBS: a.obs as a constant.  TH: as in k_vep_pre.
+template <bool OBS, bool TH = false>
 __global__ __launch_bounds__(256) void k_vep_pre_b(const VepArgs a, double *__restrict__ theta)
 {
     const int nx = a.nx, ny = a.ny;
@@ -146,6 +149,7 @@ __global__ __launch_bounds__(256) void k_vep_pre_b(const VepArgs a, double *__re
     const double x00 = Vx[qx], x01 = Vx[qx + (nx + 1)], x11 = Vx[qx + (nx + 1) + (i < nx ? 1 : 0)];
     const double y00 = Vy[qy], y10 = Vy[qy + 1], y11 = Vy[qy + 1 + (j < ny ? nx + 2 : 0)];
     const double Kc = a.Kc[c], Gc = a.Gc[c], P = theta[c], P0 = a.f.P0[c], Q = a.f.Q[c];
+    const double S = TH ? a.src[c] : 0.0;
     double w[9];
 #pragma unroll
     for (int q = 0; q < 3; q++) {
@@ -160,7 +164,7 @@ __global__ __launch_bounds__(256) void k_vep_pre_b(const VepArgs a, double *__re
         const double divV = dxi + dyi;
         if (OBS) a.f.divV[c] = divV;
         const double _Kdt = 1.0 / (Kc * a.dt), _Gdt = 1.0 / (Gc * a.dt), _dt = 1.0 / a.dt;
-        const double rhs = -divV + (Q * _dt);
+        const double rhs = TH ? (-divV + S) + (Q * _dt) : -divV + (Q * _dt);
         if (OBS) a.f.RP[c] = fma(-(P - P0), _Kdt, rhs);
         double et = -INFINITY;
 #pragma unroll
@@ -567,8 +571,9 @@ __global__ __launch_bounds__(256) void k_vep_visc_velocity_b(const VepArgs a, co
 }
 
 // rho: also compute_ρg!(ρg, phase_ratios, rheology, args) (Stokes2D.jl:646)
+// src: args.ΔT is given -- the thermal source of compute_P!, α_c * (ΔT * _dt) with α_c = fn_ratio(get_thermal_expansion, ...) and ΔT at the cell's own [i, j] (PressureKernels.jl:147-149,201)
 __global__ __launch_bounds__(256) void k_phase_avg(double *__restrict__ Kc, double *__restrict__ Gc, const VepArgs a, const bool rho, double *__restrict__ elc = nullptr,
-                                                   double *__restrict__ elv = nullptr)
+                                                   double *__restrict__ elv = nullptr, double *__restrict__ src = nullptr)
 {
     const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (elv && t < (i64)(a.nx + 1) * (a.ny + 1)) elv[t] = phase_viscosity(a.rh, a.f.phase_v + a.rh.nphase * t);
@@ -577,6 +582,10 @@ __global__ __launch_bounds__(256) void k_phase_avg(double *__restrict__ Kc, doub
     Kc[t] = ratio_avg(a.rh.Kb, a.f.phase_c + a.rh.nphase * t, a.rh.nphase);
     Gc[t] = ratio_avg(a.rh.G, a.f.phase_c + a.rh.nphase * t, a.rh.nphase);
     if (rho) a.f.fy[t] = mat_density_ratio(a.rh, a.f.phase_c + a.rh.nphase * t, !a.f.T ? 0.0 : (a.tg ? a.f.T[(t % a.nx) + (i64)(a.nx + 2) * (t / a.nx)] : a.f.T[t]), a.f.P[t]) * a.rh.gravity;
+    if (src) {
+        const double dT = a.dtg ? a.f.dT[(t % a.nx) + (i64)(a.nx + 2) * (t / a.nx)] : a.f.dT[t], _dt = 1.0 / a.dt;
+        src[t] = mat_thermal_expansion_ratio(a.rh, a.f.phase_c + a.rh.nphase * t) * (dT * _dt);
+    }
 }
 
 // Single-phase driver (Stokes2D.jl:345-557): compute_ρg!/update_ρg!(ρg[2], rheology, args) and compute_viscosity!/compute_viscosity_τII!
@@ -701,10 +710,37 @@ VepArgs make_vep(const jrx_vep2d_fields *f, const jrx_rheology *rh, const jrx_ve
     a.soft = mat_has_softening(rh);
     a.si = p->strain_increment != 0;
     a.tg = p->T_ghosted != 0;
+    a.dtg = p->dT_ghosted != 0;
     a.vfields = mat_viscosity_reads_fields(rh); a.vtau = true;
     a.obs = true;
     a.sp = Sp2{p->inv_spacing[0], p->inv_spacing[1], p->inv_spacing[2], p->inv_spacing[3], p->inv_spacing[4], p->inv_spacing[5]};
     return a;
+}
+
+// args.ΔT with args.melt_fraction: the reference then takes α(ϕ) from GeoParams (PressureKernels.jl:154-176) in a form nothing under it states
+jrx_status check_vep_thermal(jrx_handle *h, const jrx_vep2d_fields *f)
+{
+    if (f->dT && f->melt_fraction)
+        return jrx_fail(h, JRX_ERR_ARG, "compute_P!: args.melt_fraction together with args.ΔT (the melt-dependent thermal expansion α(ϕ)) is not built");
+    return JRX_OK;
+}
+
+// the pre kernel of the multiphase driver.  ml: compute_maxloc! folded in (ranks with neighbours exchange ητ instead); rho: update_ρg!; batch: the form that requests every operand
+// up front (ml, no rho, uniform grids); a.src != nullptr: the thermal forms (args.ΔT).  Without it the instantiations are those of the isothermal driver.
+void launch_vep_pre(hipStream_t s, unsigned gv, const VepArgs &a, double *theta, bool ml, bool rho, bool batch)
+{
+    const std::true_type yes{};
+    const std::false_type no{};
+    auto go = [&](auto TH_) {
+        constexpr bool TH = decltype(TH_)::value;
+        if (!ml && rho) hipLaunchKernelGGL((k_vep_pre<false, true, TH>), dim3(gv), dim3(256), 0, s, a, theta);
+        else if (!ml) hipLaunchKernelGGL((k_vep_pre<false, false, TH>), dim3(gv), dim3(256), 0, s, a, theta);
+        else if (rho) hipLaunchKernelGGL((k_vep_pre<true, true, TH>), dim3(gv), dim3(256), 0, s, a, theta);
+        else if (batch && a.obs) hipLaunchKernelGGL((k_vep_pre_b<true, TH>), dim3(gv), dim3(256), 0, s, a, theta);
+        else if (batch) hipLaunchKernelGGL((k_vep_pre_b<false, TH>), dim3(gv), dim3(256), 0, s, a, theta);
+        else hipLaunchKernelGGL((k_vep_pre<true, false, TH>), dim3(gv), dim3(256), 0, s, a, theta);      // compute_maxloc! folded in
+    };
+    if (a.src) go(yes); else go(no);
 }
 
 // compute_viscosity! (tau = false: the invariant from the strain rate) / update_viscosity_τII! (tau = true: from the stress) as entry points of their own
@@ -764,6 +800,26 @@ jrx_status jrx_vep2d_update_stresses(jrx_handle *h, const jrx_vep2d_fields *f, c
     hipLaunchKernelGGL(k_vep_vertex, dim3(gv), dim3(256), 0, h->stream, a);
     JRX_LAUNCH_CHECK(h);
     hipLaunchKernelGGL(k_vep_centre, dim3(gc), dim3(256), 0, h->stream, a);
+    JRX_LAUNCH_CHECK(h);
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_vep2d_compute_P(jrx_handle *h, const jrx_vep2d_fields *f, double *theta, const jrx_rheology *rh, const jrx_vep2d_params *p)
+{
+    JRX_TRY(check_vep(h, f, rh, p));
+    JRX_TRY(check_vep_thermal(h, f));
+    if (!theta) return jrx_fail(h, JRX_ERR_ARG, "θ is NULL");
+    const size_t n = (size_t)p->nx * p->ny, nv = (size_t)(p->nx + 1) * (p->ny + 1);
+    JRX_TRY(jrx_ensure_etatau(h, 4 * n));
+    double *etatau = h->etatau, *Kc = etatau + n, *Gc = Kc + n, *src = f->dT ? Gc + n : nullptr;
+    VepArgs a = make_vep(f, rh, p);
+    a.theta = theta; a.etatau = etatau; a.Kc = Kc; a.Gc = Gc;
+    const unsigned gv = (unsigned)((nv + 255) / 256), gc = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(k_phase_avg, dim3(gc), dim3(256), 0, h->stream, Kc, Gc, a, false, (double *)nullptr, (double *)nullptr, src);
+    JRX_LAUNCH_CHECK(h);
+    a.src = src;
+    launch_vep_pre(h->stream, gv, a, theta, true, false, h->fused2d_batch && !p->inv_spacing[0]);      // the form the driver takes for constant densities
     JRX_LAUNCH_CHECK(h);
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
@@ -849,6 +905,7 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
                                   jrx_solve_result *res)
 {
     JRX_TRY(check_vep(h, f, rh, p));
+    JRX_TRY(check_vep_thermal(h, f));
     if (!res) return jrx_fail(h, JRX_ERR_ARG, "null result");
     if (p->nout < 1) return jrx_fail(h, JRX_ERR_ARG, "nout must be >= 1");
     const bool comm = jrx_comm_active(h);
@@ -856,13 +913,14 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
     const int64_t nn[3] = {nx, ny, 1};
     const size_t n = (size_t)nx * ny, nv = (size_t)(nx + 1) * (ny + 1);
     hipStream_t s = h->stream;
-    // library scratch: ητ, θ, λ, K, G (centre), λv (vertex) and the second set of τxx, τyy, carved out of one allocation
-    JRX_TRY(jrx_ensure_etatau(h, 8 * n + 2 * nv));
+    // library scratch: ητ, θ, λ, K, G (centre), λv (vertex) and the second set of τxx, τyy, carved out of one allocation; with args.ΔT the thermal source of compute_P! behind them
+    JRX_TRY(jrx_ensure_etatau(h, (f->dT ? 9 : 8) * n + 2 * nv));
     double *etatau = h->etatau, *theta = etatau + n, *lam = theta + n, *Kc = lam + n, *Gc = Kc + n, *lamv = Gc + n;
     VepArgs a = make_vep(f, rh, p);
     a.theta = theta; a.etatau = etatau; a.Kc = Kc; a.Gc = Gc; a.lam = lam; a.lamv = lamv;
     a.txx_out = lamv + nv; a.tyy_out = a.txx_out + n;
     double *eta_lin_c = a.tyy_out + n, *eta_lin_v = eta_lin_c + n;
+    double *const src = f->dT ? eta_lin_v + nv : nullptr;
     jrx_stokes2d_fields g = view2d(f);
     jrx_stokes2d_params q;
     memset(&q, 0, sizeof(q));
@@ -882,8 +940,9 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
     // linear laws: η of a cell / vertex depends on its phase ratios only -- averaged once per solve, compute_viscosity! then reads one array instead of the ratios
     const bool lin = !a.vfields;
     hipLaunchKernelGGL(k_phase_avg, dim3(lin && f->eta_v ? gv : gc), dim3(256), 0, s, Kc, Gc, a, rh->has_density != 0, lin ? eta_lin_c : (double *)nullptr,
-                       lin && f->eta_v ? eta_lin_v : (double *)nullptr);
+                       lin && f->eta_v ? eta_lin_v : (double *)nullptr, src);
     JRX_LAUNCH_CHECK(h);
+    a.src = src;
     if (lin) { a.eta_lin_c = eta_lin_c; a.eta_lin_v = f->eta_v ? eta_lin_v : nullptr; }
     const bool upd_rho = rh->has_density && !mat_density_is_constant(rh);       // update_ρg!: a no-op for constant densities
     const bool ubc = p->displacement_bcs != 0;
@@ -934,9 +993,7 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
                         aa.obs = h->vep_store_all;          // a run of unobserved iterations
                         Args2 bb = b;
                         for (int q = 0; q < GIT; q++) {
-                            if (upd_rho) hipLaunchKernelGGL((k_vep_pre<true, true>), dim3(gv), dim3(256), 0, s, aa, theta);
-                            else if (batch_pre) { if (aa.obs) hipLaunchKernelGGL(k_vep_pre_b<true>, dim3(gv), dim3(256), 0, s, aa, theta); else hipLaunchKernelGGL(k_vep_pre_b<false>, dim3(gv), dim3(256), 0, s, aa, theta); }
-                            else hipLaunchKernelGGL(k_vep_pre<true>, dim3(gv), dim3(256), 0, s, aa, theta);
+                            launch_vep_pre(s, gv, aa, theta, true, upd_rho, batch_pre);
                             if (aa.soft) hipLaunchKernelGGL(k_vep_stress2d<true>, dim3(gv), dim3(256), 0, s, aa);
                             else switch (h->vep3_np_const ? aa.rh.nphase : 0) {
                             case 1: hipLaunchKernelGGL((k_vep_stress2d<false, false, 1>), dim3(gv), dim3(256), 0, s, aa); break;
@@ -977,11 +1034,8 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
             double *arrs[1] = {etatau};
             const int64_t ext[1][3] = {{nx, ny, 1}};
             JRX_TRY(jrx_halo_exchange(h, s, 1, arrs, ext, nn));
-            if (upd_rho) hipLaunchKernelGGL((k_vep_pre<false, true>), dim3(gv), dim3(256), 0, s, a, theta);
-            else hipLaunchKernelGGL(k_vep_pre<false>, dim3(gv), dim3(256), 0, s, a, theta);
-        } else if (upd_rho) hipLaunchKernelGGL((k_vep_pre<true, true>), dim3(gv), dim3(256), 0, s, a, theta);
-        else if (batch_pre) { if (a.obs) hipLaunchKernelGGL(k_vep_pre_b<true>, dim3(gv), dim3(256), 0, s, a, theta); else hipLaunchKernelGGL(k_vep_pre_b<false>, dim3(gv), dim3(256), 0, s, a, theta); }
-        else hipLaunchKernelGGL(k_vep_pre<true>, dim3(gv), dim3(256), 0, s, a, theta);      // compute_maxloc! folded in
+            launch_vep_pre(s, gv, a, theta, false, upd_rho, false);
+        } else launch_vep_pre(s, gv, a, theta, true, upd_rho, batch_pre);
         JRX_LAUNCH_CHECK(h);
         if (a.si) {
             hipLaunchKernelGGL(k_vep_strain_inc, dim3(gv), dim3(256), 0, s, a);

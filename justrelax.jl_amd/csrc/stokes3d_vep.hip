@@ -25,6 +25,7 @@ struct Vep3Args {
     jrx_vep3d_fields f;
     jrx_rheology rh;
     const double *etatau, *Kc, *Gc;
+    const double *src = nullptr;       // args.ΔT: the thermal source α_c * (ΔT * _dt) of compute_P! (constant over a solve), precomputed by k_vep3_phase_avg; read by the TH forms of the pre kernels only
     const double *eta_lin = nullptr;   // linear laws: the phase average of η (constant over a solve), precomputed by k_vep3_phase_avg; nullptr: computed per call
     double *theta, *lam;
     double *lamv[3], *tnew[3];
@@ -34,6 +35,7 @@ struct Vep3Args {
     bool soft;            // some phase has a softening law: the yield function then reads EII_pl
     bool nt;              // outputs with non-temporal stores
     bool tg;              // args.T is the ghosted thermal.T (ni .+ 2): densities read it at the cell's own [i, j, k], unshifted
+    bool dtg;             // args.ΔT is the ghosted thermal.ΔT (ni .+ 2): compute_P! reads it at the cell's own [i, j, k], unshifted (PressureKernels.jl:149)
     bool obs;             // the outputs nothing inside the PT loop reads -- ∇V, RP, ε_pl (6), ε_vol_pl, η_vep, τII (update_viscosity_τII! takes its invariant from the stress arrays) -- are stored; the solve loop clears it on iterations whose
                           // results cannot be observed (not a norm check, not the last one): the next iteration overwrites them anyway (11 of 29 written passes)
 };
@@ -78,7 +80,8 @@ struct Vep3Args {
 // RHO: update_ρg! of the own cell (phase-ratio density at args.T, args.P = stokes.P, times the scalar gravity, into ρg_z)
 // A thread walks KZ planes of its (i, j) column (blockIdx.y = z chunk): the 3 x 3 x 3 maximum is then the maximum of three 3 x 3 plane maxima, two of
 // which are carried from the previous planes -- 9 loads of η per cell instead of 27 (max is order-independent: same result).
-template <bool ML, bool RHO = false, int KZ = 8>
+// TH: the thermal form of _compute_P! (PressureKernels.jl:197-206): rhs = (-∇V + (α * (ΔT * _dt))) + (Q * _dt), the middle term read from a.src
+template <bool ML, bool RHO = false, int KZ = 8, bool TH = false>
 __global__ __launch_bounds__(256) void k_vep3_pre(const Vep3Args a)
 {
     const int nx = a.nx, ny = a.ny, nz = a.nz;
@@ -125,7 +128,7 @@ __global__ __launch_bounds__(256) void k_vep3_pre(const Vep3Args a)
             if (a.obs) VST(a, a.f.divV[c], divV);
             const double _Kdt = 1.0 / (a.Kc[c] * a.dt), _Gdt = 1.0 / (a.Gc[c] * a.dt), _dt = 1.0 / a.dt;
             const double P = a.theta[c], P0 = a.f.P0[c];
-            const double rhs = -divV + (a.f.Q[c] * _dt);
+            const double rhs = TH ? (-divV + a.src[c]) + (a.f.Q[c] * _dt) : -divV + (a.f.Q[c] * _dt);
             if (a.obs) VST(a, a.f.RP[c], fma(-(P - P0), _Kdt, rhs));
             double et;
             if (ML) {
@@ -201,7 +204,9 @@ __global__ __launch_bounds__(256) void k_vep3_visc(const Vep3Args a, double nu)
 }
 
 // rho: also compute_ρg!(ρg, phase_ratios, rheology, args) (Stokes3D.jl:505)
-__global__ __launch_bounds__(256) void k_vep3_phase_avg(double *__restrict__ Kc, double *__restrict__ Gc, const Vep3Args a, const bool rho, double *__restrict__ eta_lin = nullptr)
+// src: args.ΔT is given -- the thermal source of compute_P!, α_c * (ΔT * _dt) with α_c = fn_ratio(get_thermal_expansion, ...) and ΔT at the cell's own [i, j, k] (PressureKernels.jl:147-149,201)
+__global__ __launch_bounds__(256) void k_vep3_phase_avg(double *__restrict__ Kc, double *__restrict__ Gc, const Vep3Args a, const bool rho, double *__restrict__ eta_lin = nullptr,
+                                                        double *__restrict__ src = nullptr)
 {
     const i64 c = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= (i64)a.nx * a.ny * a.nz) return;
@@ -213,6 +218,11 @@ __global__ __launch_bounds__(256) void k_vep3_phase_avg(double *__restrict__ Kc,
         const int k = (int)(c / ((i64)a.nx * a.ny)), j = (int)((c - (i64)k * a.nx * a.ny) / a.nx), i = (int)(c - (i64)k * a.nx * a.ny - (i64)j * a.nx);
         const double T = !a.f.T ? 0.0 : (a.tg ? a.f.T[i + (i64)(a.nx + 2) * (j + (i64)(a.ny + 2) * k)] : a.f.T[c]);
         a.f.fz[c] = mat_density_ratio(a.rh, r, T, a.f.P[c]) * a.rh.gravity;
+    }
+    if (src) {
+        const int k = (int)(c / ((i64)a.nx * a.ny)), j = (int)((c - (i64)k * a.nx * a.ny) / a.nx), i = (int)(c - (i64)k * a.nx * a.ny - (i64)j * a.nx);
+        const double dT = a.dtg ? a.f.dT[i + (i64)(a.nx + 2) * (j + (i64)(a.ny + 2) * k)] : a.f.dT[c], _dt = 1.0 / a.dt;
+        src[c] = mat_thermal_expansion_ratio(a.rh, r) * (dT * _dt);
     }
 }
 
@@ -827,7 +837,8 @@ __global__ __launch_bounds__(256) void k_vep3_centre(const Vep3Args a)
 // scheduler, which works one block at a time, can no longer issue the plane's loads as one batch -- seven dependent memory round trips per plane instead of two)
 // ML = false (ranks with neighbours): ητ arrives in a.etatau -- compute_maxloc! of the relaxed η and its update_halo! run on the halo stream beside the edge pass -- instead of being taken
 // from the 3 x 3 x 3 window of η here
-template <bool SOFT, bool RHO, int NP = 0, bool OBS = true, bool ML = true>
+// TH: the thermal form of _compute_P!, as in k_vep3_pre: one more centre operand (a.src), requested behind the plane's batch
+template <bool SOFT, bool RHO, int NP = 0, bool OBS = true, bool ML = true, bool TH = false>
 __global__ __launch_bounds__(256, 3) void k_vep3_prec(const Vep3Args a, double *__restrict__ eta_out, const int KZ, const int tile_ntx = 0)
 {
     const int nx = a.nx, ny = a.ny, nz = a.nz, np = NP > 0 ? NP : a.rh.nphase;
@@ -935,6 +946,7 @@ __global__ __launch_bounds__(256, 3) void k_vep3_prec(const Vep3Args a, double *
         for (int s = 0; s < 6; s++) { tij[s] = LB(tc[s], oc); toij[s] = LB(toc[s], oc); }
         const double EII_ = SOFT ? LB(a.f.EII_pl, oc) : 0.0;
         __builtin_amdgcn_sched_barrier(0);      // (the scheduler, minimising register pressure, would sink every load to its first use again)
+        const double S_ = TH ? LB(a.src, oc) : 0.0;      // behind the batch: two more registers at its peak would spill at three and four phases
         // ---- compute_∇V!, compute_P!, compute_strain_rate! (k_vep3_pre)
         const double dxi = (-vx_a + vx_b) * _dx;
         const double dyi = (-vy_a + vy_b) * _dy;
@@ -942,7 +954,8 @@ __global__ __launch_bounds__(256, 3) void k_vep3_prec(const Vep3Args a, double *
         const double divV = dxi + dyi + dzi;
         if (OBS) SW(a.f.divV, oc) = divV;
         const double _Kdt = 1.0 / (Kc_ * a.dt), _Gdt0 = 1.0 / (Gc_ * a.dt);
-        const double rhs = -divV + (Q_ * _dt);
+        const double rhs = TH ? (-divV + S_) + (Q_ * _dt) : -divV + (Q_ * _dt);
+        if (TH && RHO) __builtin_amdgcn_sched_barrier(0);      // density-updating form: the source and Q end here, before the density law asks for its registers (8 B less scratch; the other forms spill more with it)
         if (OBS) SW(a.f.RP, oc) = fma(-(P - P0), _Kdt, rhs);
         double et = et_in;
         if (ML) {
@@ -1141,6 +1154,7 @@ Vep3Args make_vep3(const jrx_vep3d_fields *f, const jrx_rheology *rh, const jrx_
     a.nx = (int)p->nx; a.ny = (int)p->ny; a.nz = (int)p->nz;
     a.soft = mat_has_softening(rh);
     a.tg = p->T_ghosted != 0;
+    a.dtg = p->dT_ghosted != 0;
     a.nt = false;
     a.obs = true;
     return a;
@@ -1219,17 +1233,21 @@ jrx_status launch_vep3_stress(jrx_handle *h, hipStream_t s, const Vep3Args &a, c
 }
 
 // k_vep3_pre (∇V, θ, RP, ε; ML: compute_maxloc! folded in -- ranks with neighbours exchange ητ instead; RHO: update_ρg!), prekz planes per thread.  The depth is a template
-// argument: the forms with neighbours or densities are built for 8 planes only
+// argument: the forms with neighbours or densities are built for 8 planes only.  a.src != nullptr: the thermal forms (args.ΔT); without it the instantiations of the isothermal driver
 void launch_vep3_pre(hipStream_t s, const Vep3Args &a, bool ml, bool rho, int prekz)
 {
     const unsigned gx = (unsigned)(((i64)(a.nx + 1) * (a.ny + 1) + 255) / 256);
     const dim3 g8(gx, (unsigned)((a.nz + 1 + 7) / 8));
-    if (!ml && rho) hipLaunchKernelGGL((k_vep3_pre<false, true, 8>), g8, dim3(256), 0, s, a);
-    else if (!ml) hipLaunchKernelGGL((k_vep3_pre<false, false, 8>), g8, dim3(256), 0, s, a);
-    else if (rho) hipLaunchKernelGGL((k_vep3_pre<true, true, 8>), g8, dim3(256), 0, s, a);
-    else dispatch_const<1, 2, 4, 8, 16, 32>(vep3_pre_depth(prekz), [&](auto KZ) {
-        hipLaunchKernelGGL((k_vep3_pre<true, false, decltype(KZ)::value>), dim3(gx, (unsigned)((a.nz + decltype(KZ)::value) / decltype(KZ)::value)), dim3(256), 0, s, a);
-    });
+    auto go = [&](auto TH_) {
+        constexpr bool TH = decltype(TH_)::value;
+        if (!ml && rho) hipLaunchKernelGGL((k_vep3_pre<false, true, 8, TH>), g8, dim3(256), 0, s, a);
+        else if (!ml) hipLaunchKernelGGL((k_vep3_pre<false, false, 8, TH>), g8, dim3(256), 0, s, a);
+        else if (rho) hipLaunchKernelGGL((k_vep3_pre<true, true, 8, TH>), g8, dim3(256), 0, s, a);
+        else dispatch_const<1, 2, 4, 8, 16, 32>(vep3_pre_depth(prekz), [&](auto KZ) {
+            hipLaunchKernelGGL((k_vep3_pre<true, false, decltype(KZ)::value, TH>), dim3(gx, (unsigned)((a.nz + decltype(KZ)::value) / decltype(KZ)::value)), dim3(256), 0, s, a);
+        });
+    };
+    if (a.src) go(std::true_type{}); else go(std::false_type{});
 }
 
 // k_vep3_prec (pre + viscosity relaxation + centre pass): ML as for k_vep3_pre, RHO update_ρg!, OBS from a.obs, the phase count a constant where the instantiation exists:
@@ -1237,9 +1255,16 @@ void launch_vep3_pre(hipStream_t s, const Vep3Args &a, bool ml, bool rho, int pr
 jrx_status launch_vep3_prec(jrx_handle *h, hipStream_t s, const Vep3Args &a, double *eta_out, const Vep3PrecPlan &pl, bool ml, bool rho)
 {
     const dim3 g(pl.gx, pl.gy);
-    const int np = (h->vep3_np_const && !rho && a.rh.nphase <= 4) ? a.rh.nphase : 0;
-    auto launch = [&](auto ML, auto RHO, auto NP, int tntx) {
-        if (a.obs) hipLaunchKernelGGL((k_vep3_prec<false, decltype(RHO)::value, decltype(NP)::value, true, decltype(ML)::value>), g, dim3(256), 0, s, a, eta_out, pl.kz, tntx);
+    int np = (h->vep3_np_const && !rho && a.rh.nphase <= 4) ? a.rh.nphase : 0;
+    // thermal form, four phases, unobserved, without neighbours: the constant-count instantiation spills 20 B per lane where its isothermal twin spills nothing; the run-time loops
+    // (166 VGPRs, no scratch) compute the same bits (tests/test_gpu_vep3d.py pins the two against each other)
+    if (a.src && ml && !a.obs && np == 4) np = 0;
+    auto launch = [&](auto ML, auto RHO, auto NP, int tntx) {      // a.src != nullptr: the thermal forms (args.ΔT); without it the instantiations of the isothermal driver
+        if (a.src) {
+            if (a.obs) hipLaunchKernelGGL((k_vep3_prec<false, decltype(RHO)::value, decltype(NP)::value, true, decltype(ML)::value, true>), g, dim3(256), 0, s, a, eta_out, pl.kz, tntx);
+            else if constexpr (!(decltype(ML)::value && decltype(NP)::value == 4))      // (four phases take NP = 0 here, see above: that instantiation is not built)
+                hipLaunchKernelGGL((k_vep3_prec<false, decltype(RHO)::value, decltype(NP)::value, false, decltype(ML)::value, true>), g, dim3(256), 0, s, a, eta_out, pl.kz, tntx);
+        } else if (a.obs) hipLaunchKernelGGL((k_vep3_prec<false, decltype(RHO)::value, decltype(NP)::value, true, decltype(ML)::value>), g, dim3(256), 0, s, a, eta_out, pl.kz, tntx);
         else hipLaunchKernelGGL((k_vep3_prec<false, decltype(RHO)::value, decltype(NP)::value, false, decltype(ML)::value>), g, dim3(256), 0, s, a, eta_out, pl.kz, tntx);
     };
     const std::true_type yes{};
@@ -1323,9 +1348,38 @@ jrx_status apply_vep3_bc(jrx_handle *h, hipStream_t s, Vep3Bc bc, const jrx_vep3
     return JRX_OK;
 }
 
+// args.ΔT with args.melt_fraction: the reference then takes α(ϕ) from GeoParams (PressureKernels.jl:154-176) in a form nothing under it states
+jrx_status check_vep3_thermal(jrx_handle *h, const jrx_vep3d_fields *f)
+{
+    if (f->dT && f->melt_fraction)
+        return jrx_fail(h, JRX_ERR_ARG, "compute_P!: args.melt_fraction together with args.ΔT (the melt-dependent thermal expansion α(ϕ)) is not built");
+    return JRX_OK;
+}
+
 }   // namespace
 
 extern "C" {
+
+jrx_status jrx_vep3d_compute_P(jrx_handle *h, const jrx_vep3d_fields *f, double *theta, const jrx_rheology *rh, const jrx_vep3d_params *p)
+{
+    JRX_TRY(check_vep3(h, f, rh, p));
+    JRX_TRY(check_vep3_thermal(h, f));
+    if (!theta) return jrx_fail(h, JRX_ERR_ARG, "θ is NULL");
+    const int nx = (int)p->nx, ny = (int)p->ny, nz = (int)p->nz;
+    const size_t n = (size_t)nx * ny * nz;
+    JRX_TRY(jrx_ensure_etatau(h, 4 * n));
+    double *etatau = h->etatau, *Kc = etatau + n, *Gc = Kc + n, *src = f->dT ? Gc + n : nullptr;
+    Vep3Args a = make_vep3(f, rh, p);
+    a.nt = h->vep3_nt;
+    a.theta = theta; a.etatau = etatau; a.Kc = Kc; a.Gc = Gc;
+    hipLaunchKernelGGL(k_vep3_phase_avg, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, Kc, Gc, a, false, (double *)nullptr, src);
+    JRX_LAUNCH_CHECK(h);
+    a.src = src;
+    launch_vep3_pre(h->stream, a, true, false, vep3_plan_prekz(nx, ny, nz, h->vep3_prekz));      // the depth the one-rank driver takes
+    JRX_LAUNCH_CHECK(h);
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
 
 jrx_status jrx_vep3d_update_stresses(jrx_handle *h, const jrx_vep3d_fields *f, const double *theta, double *lambda, double *const lambda_v[3],
                                      const jrx_rheology *rh, const jrx_vep3d_params *p)
@@ -1420,14 +1474,16 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
                                   jrx_solve_result *res)
 {
     JRX_TRY(check_vep3(h, f, rh, p));
+    JRX_TRY(check_vep3_thermal(h, f));
     if (!res) return jrx_fail(h, JRX_ERR_ARG, "null result");
     if (p->nout < 1) return jrx_fail(h, JRX_ERR_ARG, "nout must be >= 1");
     const int nx = (int)p->nx, ny = (int)p->ny, nz = (int)p->nz;
     const size_t n = (size_t)nx * ny * nz;
     const EdgeN ne = edge_counts(p->nx, p->ny, p->nz);
     hipStream_t s = h->stream;
-    // library scratch: ητ, θ, λ, K, G, a second ητ, the phase-averaged η of the linear laws (centres), λv and the new edge stresses (edges), carved out of one allocation
-    JRX_TRY(jrx_ensure_etatau(h, 11 * n + 2 * (size_t)(ne.yz + ne.xz + ne.xy)));
+    // library scratch: ητ, θ, λ, K, G, a second ητ, the phase-averaged η of the linear laws (centres), λv and the new edge stresses (edges), carved out of one allocation;
+    // with args.ΔT the thermal source of compute_P! behind them
+    JRX_TRY(jrx_ensure_etatau(h, (f->dT ? 12 : 11) * n + 2 * (size_t)(ne.yz + ne.xz + ne.xy)));
     double *etatau = h->etatau, *theta = etatau + n, *lam = theta + n, *Kc = lam + n, *Gc = Kc + n, *etatau_next = Gc + n;
     Vep3Args a = make_vep3(f, rh, p);
     a.nt = h->vep3_nt;
@@ -1436,6 +1492,7 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
     a.lamv[0] = eta_lin + n; a.lamv[1] = a.lamv[0] + ne.yz; a.lamv[2] = a.lamv[1] + ne.xz;
     a.tnew[0] = a.lamv[2] + ne.xy; a.tnew[1] = a.tnew[0] + ne.yz; a.tnew[2] = a.tnew[1] + ne.xz;
     double *const cset = a.tnew[2] + ne.xy;      // second set of τxx, τyy, τzz, then a second η (see `fuse` below)
+    double *const src = f->dT ? cset + 4 * n : nullptr;
     const bool comm = jrx_comm_active(h);
     Vep3EdgePlan eplan;      // the launch plan (vep3_plan.hpp), once per solve; k_vep3_pre is built for 8 planes only where ητ is exchanged
     JRX_TRY(plan_vep3_edges(h, a, true, &eplan));
@@ -1455,7 +1512,8 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
     JRX_HIP(h, hipMemsetAsync(lam, 0, n * sizeof(double), s));
     JRX_HIP(h, hipMemsetAsync(a.lamv[0], 0, (size_t)(ne.yz + ne.xz + ne.xy) * sizeof(double), s));
     const bool lin = !mat_viscosity_reads_fields(rh);       // η of the laws depends on the phase ratios only: average it once per solve (update_viscosity_τII! then reads one array instead of the ratios)
-    hipLaunchKernelGGL(k_vep3_phase_avg, dim3(gc), dim3(256), 0, s, Kc, Gc, a, rh->has_density != 0, lin ? eta_lin : (double *)nullptr);
+    hipLaunchKernelGGL(k_vep3_phase_avg, dim3(gc), dim3(256), 0, s, Kc, Gc, a, rh->has_density != 0, lin ? eta_lin : (double *)nullptr, src);
+    a.src = src;
     if (lin) a.eta_lin = eta_lin;
     launch_vep3_visc(s, gc, a, 1.0, false);                                                          // compute_viscosity! :507 (εII form)
     JRX_LAUNCH_CHECK(h);

@@ -242,7 +242,27 @@ def _args_T(args):
     return args.get("T") if isinstance(args, dict) else getattr(args, "T", None)
 
 
-def vep_fields2d(stokes, ρg, phase_ratios, args=None, allow_ghosted_T=False, strain_increment=False) -> _lib.VEP2DFields:
+def _args_get(args, key):
+    if args is None:
+        return None
+    return args.get(key) if isinstance(args, dict) else getattr(args, key, None)
+
+
+def _ghosted_ΔT_flag(stokes, args):
+    """dT_ghosted of the params: args.ΔT of the reference's `args` (PressureKernels.jl:64-85) is cell-centred (ni, SinkingBlock2D_WENO5.jl:196; 0) or thermal.ΔT itself
+    (ni .+ 2, test_thermalstresses.jl:321; 1) -- compute_P! reads either at the cell's own index.  Any other extent raises."""
+    ΔT = _args_get(args, "ΔT")
+    ni = tuple(stokes._ni)
+    if ΔT is None or tuple(ΔT.shape) == ni:
+        return 0
+    if tuple(ΔT.shape) != tuple(n + 2 for n in ni):
+        raise ValueError(f"args.ΔT must be ni {ni} or ni .+ 2 (thermal.ΔT), got {tuple(ΔT.shape)}")
+    return 1
+
+
+def vep_fields2d(stokes, ρg, phase_ratios, args=None, allow_ghosted_T=False, strain_increment=False, thermal_stress=False) -> _lib.VEP2DFields:
+    """thermal_stress: args.ΔT and args.melt_fraction go into the struct (its extent is checked; the caller sets p.dT_ghosted = _ghosted_ΔT_flag(stokes, args)) -- the
+    multiphase driver and compute_P_ only.  The single-phase driver's compute_P! takes no args (Stokes2D.jl:420), the variational and DYREL drivers do not read them."""
     s = stokes
     vals = dict(P=s.P, P0=s.P0, divV=s.divV, Q=s.Q, Vx=s.V.Vx, Vy=s.V.Vy, Ux=s.U.Ux, Uy=s.U.Uy,
                 exx=s.ε.xx, eyy=s.ε.yy, exy=s.ε.xy, exy_c=s.ε.xy_c,
@@ -256,6 +276,9 @@ def vep_fields2d(stokes, ρg, phase_ratios, args=None, allow_ghosted_T=False, st
         vals.update(dexx=s.Δε.xx, deyy=s.Δε.yy, divU=getattr(s, "∇U"))      # "∇" is not a Python identifier character
     if vals["T"] is not None and tuple(vals["T"].shape) != tuple(s._ni) and not allow_ghosted_T:
         raise ValueError(f"args.T must be cell-centred {tuple(s._ni)} (thermal.Tc), got {tuple(vals['T'].shape)}")
+    if thermal_stress:
+        _ghosted_ΔT_flag(s, args)
+        vals.update(dT=_args_get(args, "ΔT"), melt_fraction=_args_get(args, "melt_fraction"))
     f = _lib.VEP2DFields()
     for n in _lib.VEP_NAMES:
         setattr(f, n, ptr(vals.get(n)))
@@ -293,7 +316,8 @@ def _solve_vep2d(stokes, pt_stokes, grid, flow_bcs, ρg, phase_ratios, rheology,
             raise NotImplementedError("the reference's 3D VEP driver has no strain_increment variant (Stokes3D.jl:447-668)")
         return _solve_vep3d(stokes, pt_stokes, grid, flow_bcs, ρg, phase_ratios, rheology, args, dt, kw, h)
     p = vep_params2d(stokes, pt_stokes, grid, flow_bcs, dt, **kw)
-    f = vep_fields2d(stokes, ρg, phase_ratios, args, allow_ghosted_T=True, strain_increment=bool(p.strain_increment))
+    f = vep_fields2d(stokes, ρg, phase_ratios, args, allow_ghosted_T=True, strain_increment=bool(p.strain_increment), thermal_stress=True)
+    p.dT_ghosted = _ghosted_ΔT_flag(stokes, args)
     T = _args_T(args)
     if T is not None and tuple(T.shape) != tuple(stokes._ni):      # args.T = thermal.T (ghosted): update_ρg! reads it at [i, j], as the reference does
         if tuple(T.shape) != tuple(n + 2 for n in stokes._ni):
@@ -331,7 +355,8 @@ def _solve_nonlinear2d(stokes, pt_stokes, grid, flow_bcs, ρg, rheology, args, d
     return hist.result(2)
 
 
-def vep_fields3d(stokes, ρg, phase_ratios, args=None) -> _lib.VEP3DFields:
+def vep_fields3d(stokes, ρg, phase_ratios, args=None, thermal_stress=False) -> _lib.VEP3DFields:
+    """thermal_stress: as in vep_fields2d"""
     s = stokes
     vals = dict(P=s.P, P0=s.P0, divV=s.divV, Q=s.Q, Vx=s.V.Vx, Vy=s.V.Vy, Vz=s.V.Vz, Ux=s.U.Ux, Uy=s.U.Uy, Uz=s.U.Uz,
                 eta=s.viscosity.η, eta_vep=s.viscosity.η_vep, EII_pl=s.EII_pl, evol_pl=s.ε_vol_pl, EVol_pl=s.EVol_pl,
@@ -345,6 +370,9 @@ def vep_fields3d(stokes, ρg, phase_ratios, args=None) -> _lib.VEP3DFields:
             vals[pre + c + "_c"] = getattr(T, c + "_c")
     for c in ("yz", "xz", "xy"):
         vals["de" + c], vals["de" + c + "_c"] = getattr(s.Δε, c), getattr(s.Δε, c + "_c")
+    if thermal_stress:
+        _ghosted_ΔT_flag(s, args)
+        vals.update(dT=_args_get(args, "ΔT"), melt_fraction=_args_get(args, "melt_fraction"))
     f = _lib.VEP3DFields()
     for n in _lib.VEP3_NAMES:
         setattr(f, n, ptr(vals.get(n)))
@@ -377,7 +405,8 @@ def vep_params3d(stokes, pt, grid, flow_bcs, dt, *, iterMax=10.0e3, nout=500, ve
 def _solve_vep3d(stokes, pt_stokes, grid, flow_bcs, ρg, phase_ratios, rheology, args, dt, kw, h):
     """solve!(stokes, pt_stokes, grid, flow_bcs, ρg, phase_ratios, rheology, args, dt, igg; kwargs) in 3D -- Stokes3D.jl:447-668"""
     p = vep_params3d(stokes, pt_stokes, grid, flow_bcs, dt, **kw)
-    f = vep_fields3d(stokes, ρg, phase_ratios, args)
+    f = vep_fields3d(stokes, ρg, phase_ratios, args, thermal_stress=True)
+    p.dT_ghosted = _ghosted_ΔT_flag(stokes, args)
     T = _args_T(args)
     if T is not None and tuple(T.shape) != tuple(stokes._ni):      # args.T = thermal.T (ghosted), as the miniapps pass it: update_ρg! reads it at [i, j, k]
         if tuple(T.shape) != tuple(n + 2 for n in stokes._ni):
@@ -388,6 +417,23 @@ def _solve_vep3d(stokes, pt_stokes, grid, flow_bcs, ρg, phase_ratios, rheology,
     torch.cuda.current_stream(stokes.P.device).synchronize()
     h.call("jrx_stokes3d_vep_solve", C.byref(f), C.byref(rh), C.byref(p), C.byref(hist.c))
     return hist.result(3)
+
+
+def compute_P_(stokes, θ, pt_stokes, grid_or_di, phase_ratios, rheology, args, dt, *, handle=None):
+    """compute_∇V! + compute_P!(θ, P0, RP, ∇V, Q, ητ, rheology, phase_ratios, dt, r, θ_dτ, args) + compute_strain_rate! of the multiphase drivers, once, on
+    the caller's arrays (PressureKernels.jl:47-206; with args.ΔT the thermal form).  ητ = compute_maxloc!(η), as in the driver's first iteration."""
+    _require_gpu(stokes)
+    h = handle or _lib.default_handle(stokes.P.device.index)
+    grid = _as_grid(stokes, grid_or_di)
+    zero = (stokes.P,) * len(stokes._ni)      # ρg is not read
+    if len(stokes._ni) == 3:
+        p, f, name = vep_params3d(stokes, pt_stokes, grid, None, dt), vep_fields3d(stokes, zero, phase_ratios, args, thermal_stress=True), "jrx_vep3d_compute_P"
+    else:
+        p, f, name = vep_params2d(stokes, pt_stokes, grid, None, dt), vep_fields2d(stokes, zero, phase_ratios, args, allow_ghosted_T=True, thermal_stress=True), "jrx_vep2d_compute_P"
+    p.dT_ghosted = _ghosted_ΔT_flag(stokes, args)
+    rh = rheology_table(rheology)
+    torch.cuda.current_stream(stokes.P.device).synchronize()
+    h.call(name, C.byref(f), C.c_void_p(ptr(θ)), C.byref(rh), C.byref(p))
 
 
 def compute_τ_nonlinear_(stokes, θ, λ, rheology, dt, pt_stokes, *, phase_ratios=None, handle=None):
