@@ -132,6 +132,8 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   "stat_weno3d_calls" / "stat_weno3d_fused" = the same for jrx_weno5_advection3d (the 2D pair counts 2D calls only),
  *   "stat_phase_ratios_calls" / "stat_phase_ratios_fused" = jrx_update_phase_ratios2d / 3d calls that launched / those that ran the one-launch form,
  *   "stat_rotate_stress_calls" = jrx_rotate_stress2d / 3d calls that launched,
+ *   "stat_rock_fraction_calls" / "stat_topography_advect_calls" / "stat_topography_phase_calls" = jrx_compute_rock_fraction2d / jrx_advect_topography2d /
+ *   jrx_update_phases_topography2d calls that launched,
  *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* and jrx_dyrel3d_* entry points -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
@@ -905,6 +907,66 @@ jrx_status jrx_rotate_stress2d(jrx_handle *h, double *const tau_o[6], const doub
                                int64_t ny, const double _di[2], double dt, int32_t method, int32_t advection);
 jrx_status jrx_rotate_stress3d(jrx_handle *h, double *const tau_o[9], const double *const tau[9], const double *const omega[3], const double *const V[3],
                                int64_t nx, int64_t ny, int64_t nz, const double _di[3], double dt, int32_t method, int32_t advection);
+
+/* ------------------------------------------------------------------ a moving free surface in 2D: topography field, rock fractions from it
+ * The variational drivers take a RockRatio; jrx_update_rock_ratio derives one from the air phase's ratios, so the surface sits where the advected air field
+ * happens to be smeared.  These three operators track the surface itself: a height field h at the nx + 1 vertex abscissae (Python: Topography(backend, nx),
+ * members h and h_old), the rock fractions from it, its advection and the phase correction.  NO reference text exists to restate: the reference's free-surface
+ * miniapps (miniapps/DYREL2D/volcano/Caldera2D.jl:175-195,439-449 and the Subduction2D_VS* set) call JustPIC's marker chain -- fill_chain_from_vertices!,
+ * semilagrangian_advection_markerchain!, compute_rock_fraction!(ϕ, chain, xvi, di) -- which is not in the reference tree, and update_phases_given_markerchain!
+ * (src/phases/topography_correction.jl:64-90, with its closest_phase) works on particles.  What is built is defined here, to the rounding.
+ *
+ * Scope: 2D, uniform grid, one block.  fp64, no fma anywhere (the library builds with -ffp-contract=off): every product and sum is rounded once, left to right as
+ * written, so tests/_topography.py (the same text in NumPy) agrees bit for bit.  Indices 0-based, x fastest; ni = (nx, ny), y0 the grid's origin in y, _dx, _dy the
+ * inverse spacings.  The surface is the polyline through (x_v[i], h[i]).
+ *   clamp(x, lo, hi) = x >= lo ? (x <= hi ? x : hi) : lo      (comparisons; a NaN becomes lo)
+ *   s[i] = (h[i] - y0) * _dy                                    heights in cell units
+ *   m[i] = 0.5 * (s[i] + s[i+1])                                midpoint of segment i
+ *   Φ(g) = 0 for g <= 0;  (0.5 * g) * g for 0 < g < H;  H * g - (0.5 * H) * H for g >= H
+ *   P(ga, gb, w, H): one linear piece with end heights ga, gb above the bottom of a volume of width w and height H (cell units):
+ *       ga == gb:  w * clamp(ga, 0, H);      otherwise:  (w * (Φ(gb) - Φ(ga))) / (gb - ga)
+ *   Volumes centred on a vertex row j:  b = max(j - 0.5, 0), t = min(j + 0.5, ny), H = t - b  (clipped to the domain, normalised by what remains).
+ *
+ * 1. compute_rock_fraction!(ϕ::RockRatio, topo, grid) -- jrx_compute_rock_fraction2d.  Writes all four 2D members of ϕ, each the fraction of the member's
+ *    control volume below the polyline:
+ *      center[i,j] (nx, ny)        P(s[i]-j, s[i+1]-j, 1, 1)
+ *      Vy[i,j]     (nx, ny+1)      P(s[i]-b, s[i+1]-b, 1, H) / H
+ *      Vx[i,j]     (nx+1, ny)      ( left half P(m[i-1]-j, s[i]-j, 0.5, 1) if i > 0, + right half P(s[i]-j, m[i]-j, 0.5, 1) if i < nx, added in that order ) / W
+ *      vertex[i,j] (nx+1, ny+1)    the two halves of Vx with b, H of Vy, divided by (W * H)
+ *    W = the width present, 1 or 0.5.  Every value is finally passed through clamp(., 0, 1): a guarantee for the masks of the solver (isvalid is `> 0`); no input
+ *    has been found for which the quotient leaves [0, 1].  One launch, a thread per node of the ni .+ 1 box writes every member that node owns; the only loads are
+ *    h[i-1], h[i], h[i+1].  Nothing else in ϕ is read.
+ *    Against jrx_update_rock_ratio on binary phase fields with the air above a face-aligned surface: center is bit-identical.  That operator interpolates ratios and this one
+ *    integrates areas, so the other members need not agree; on that flat surface they do (largest difference measured over vertex, Vx, Vy: 0 -- the interpolated
+ *    ratio of the face row is 0.5, the area fraction of its volume; tests/test_topography_restatement.py prints it).  Under a sloped or mid-cell surface the two
+ *    routes answer different questions and no agreement is claimed.
+ * 2. advect_topography!(topo, V, grid, dt) -- jrx_advect_topography2d.  V = (Vx (nx+1, ny+2), Vy (nx+2, ny+1)) as stokes.V, with ghost layers.  The call copies
+ *    h to h_old, then writes every h[i] from h_old (s_old its heights in cell units):
+ *      vertex velocities (as for the stress rotation above):  vxv(i,j) = 0.5 * (Vx[i,j] + Vx[i,j+1]),  vyv(i,j) = 0.5 * (Vy[i,j] + Vy[i+1,j])
+ *      surface velocity at the arrival point:  σ = clamp(s_old[i], 0, ny), j0 = min(floor(σ), ny - 1), t = σ - j0,  v = (1 - t) * v(i,j0) + t * v(i,j0+1) for vx, vy
+ *      departure point:  ξ = clamp(i - (vx * dt) * _dx, 0, nx), i0 = min(floor(ξ), nx - 1), r = ξ - i0
+ *      new height:  h[i] = ((1 - r) * h_old[i0] + r * h_old[i0+1]) + vy * dt
+ *    First order, unconditionally stable; dt comes from compute_dt undivided (the two Courant numbers need not sum below 1 as for the upwind step above).
+ *    The step has no limit of its own, but a time loop with a free surface has one: compute_dt is 0.9 d / max|V| and the velocities shrink as the surface
+ *    flattens, so the Courant step outgrows the relaxation time 4 π η / (ρ g λ) of the longest wavelength and the explicit update then overshoots
+ *    (examples/free_surface_relaxation2d.py passes a quarter of that time as the dt_diff of compute_dt).
+ * 3. update_phases_given_topography!(phases, topo, grid, air_phase) -- jrx_update_phases_topography2d.  phases: the N cell-centred (nx, ny) phase fields that
+ *    update_phase_ratios_2D! takes, 1 <= N <= JRX_MAXPHASE, a HOST array of DEVICE pointers; air_phase is 1-based.  A thread per column marches j = 0 .. ny - 1
+ *    and carries rock proportions p_k (k over the non-air indices; before any cell with rock: 1 on the lowest non-air index, 0 elsewhere).  In each cell, with
+ *    c_k the fields' values, f = center[i,j] of operator 1 (computed in the kernel) and R = the sum of the non-air c_k in index order:
+ *      if R > 0:  p_k = c_k / R  (else the carried set stays);
+ *      if c_air == 1 - f the cell is left untouched;  otherwise  c_k = f * p_k  for the non-air k and  c_air = 1 - f.
+ *    Air below the surface becomes the nearest rock below it, rock above the surface becomes air (the grid counterpart of closest_phase).
+ *
+ * All three are synchronous.  JRX_ERR_ARG (4) with a text naming the cause, nothing launched and no counter moved: a NULL member, an extent < 1, air_phase
+ * outside 1..N, N outside 1..JRX_MAXPHASE, overlapping outputs (or an output that overlaps an input), 2^31 or more entries in the ni .+ 2 box that holds every
+ * array (32-bit offsets), a non-finite dt, _dx, _dy or y0. */
+jrx_status jrx_compute_rock_fraction2d(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, const double *topo_h, int64_t nx, int64_t ny,
+                                       double y0, double _dy);
+jrx_status jrx_advect_topography2d(jrx_handle *h, double *topo_h, double *topo_h_old, const double *Vx, const double *Vy, int64_t nx, int64_t ny, double y0,
+                                   double _dx, double _dy, double dt);
+jrx_status jrx_update_phases_topography2d(jrx_handle *h, double *const *phases, int32_t nphase, const double *topo_h, int64_t nx, int64_t ny, double y0,
+                                          double _dy, int32_t air_phase);
 
 /* ------------------------------------------------------------------ timing hooks for bench.py */
 /* Runs `iters` PT iterations of the 3D loop body back to back (no norm checks) and reports device times

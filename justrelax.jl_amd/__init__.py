@@ -6,8 +6,8 @@ The directory name contains a dot, so import it through `__graft_entry__.load_pa
 
 Layout: csrc/ (hand-written HIP kernels for gfx950 + the C ABI declared in include/jrx.h),
 arrays.py / backend.py / grid.py (host-side mirror of the reference's types and traits),
-stokes.py / thermal.py / halo.py / gridops.py / advection.py / variational.py / dyrel.py / phases.py / stress_rotation.py (the operator API: solve_, heatdiffusion_PT_, flow_bcs_,
-velocity2vertex_, WENO_advection_, solve_VariationalStokes_, solve_DYREL_, update_phase_ratios_2D_, rotate_stress_, ...),
+stokes.py / thermal.py / halo.py / gridops.py / advection.py / variational.py / dyrel.py / phases.py / stress_rotation.py / topography.py (the operator API: solve_, heatdiffusion_PT_, flow_bcs_,
+velocity2vertex_, WENO_advection_, solve_VariationalStokes_, solve_DYREL_, update_phase_ratios_2D_, rotate_stress_, compute_rock_fraction_, ...),
 miniapps/ (synthetic-input builders restating the reference's benchmark scripts).
 Julia's `f!` is spelled `f_` here.
 """
@@ -19,7 +19,7 @@ from .arrays import (DisplacementBoundaryConditions, PhaseRatios, PrincipalStres
                      trim_library_arrays, use_library_arrays)
 from .grid import (IGG, Geometry, finalize_global_grid, init_global_grid, legacy_uniform_grid,  # noqa: F401
                    nx_g, ny_g, nz_g)
-from .convert import Array_, PTArray_, checkpointing_npz, copy_, load_checkpoint_npz  # noqa: F401
+from .convert import Array_, PTArray_, checkpointing_npz, copy_, load_checkpoint_extra_npz, load_checkpoint_npz  # noqa: F401
 from .vtk import pack_velocity, save_vtk  # noqa: F401
 from . import miniapps  # noqa: F401
 
@@ -27,9 +27,9 @@ from . import miniapps  # noqa: F401
 def __getattr__(name):
     # the operator API is imported lazily: it loads the HIP shared library and fails loudly if absent
     import importlib
-    if name.startswith("_") or name in ("stokes", "thermal", "halo", "checks", "build", "arrays", "grid", "backend", "convert", "gridops", "advection", "variational", "dyrel", "phases", "stress_rotation"):
+    if name.startswith("_") or name in ("stokes", "thermal", "halo", "checks", "build", "arrays", "grid", "backend", "convert", "gridops", "advection", "variational", "dyrel", "phases", "stress_rotation", "topography"):
         raise AttributeError(name)
-    for sub in ("stokes", "thermal", "halo", "gridops", "advection", "variational", "dyrel", "phases", "stress_rotation"):
+    for sub in ("stokes", "thermal", "halo", "gridops", "advection", "variational", "dyrel", "phases", "stress_rotation", "topography"):
         mod = importlib.import_module(f"{__name__}.{sub}")
         if hasattr(mod, name):
             return getattr(mod, name)

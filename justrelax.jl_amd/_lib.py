@@ -234,6 +234,10 @@ def load(check_symbols: bool = False):
         # jrx_rotate_stress2d / 3d: handle, tau_o[], tau[] (host arrays of device pointers), ω (2D: one pointer; 3D: an array of three), V[], the extents, _di[], dt, method, advection
         L.jrx_rotate_stress2d.argtypes = [C.c_void_p, _vpp, _vpp, C.c_void_p, _vpp] + [C.c_int64] * 2 + [_dp, C.c_double, C.c_int32, C.c_int32]
         L.jrx_rotate_stress3d.argtypes = [C.c_void_p, _vpp, _vpp, _vpp, _vpp] + [C.c_int64] * 3 + [_dp, C.c_double, C.c_int32, C.c_int32]
+        # the free-surface operators: the four members of ϕ, h, the extents, y0, _dy | h, h_old, Vx, Vy, the extents, y0, _dx, _dy, dt | a host array of device pointers, N, h, the extents, y0, _dy, air_phase
+        L.jrx_compute_rock_fraction2d.argtypes = [C.c_void_p] * 6 + [C.c_int64] * 2 + [C.c_double] * 2
+        L.jrx_advect_topography2d.argtypes = [C.c_void_p] * 5 + [C.c_int64] * 2 + [C.c_double] * 4
+        L.jrx_update_phases_topography2d.argtypes = [C.c_void_p, _vpp, C.c_int32, C.c_void_p] + [C.c_int64] * 2 + [C.c_double] * 2 + [C.c_int32]
         _lib = L
     if check_symbols:
         missing = [s for s in declared_symbols() if not hasattr(_lib, s)]

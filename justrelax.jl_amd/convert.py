@@ -56,7 +56,7 @@ def copy_(x):
         return t
     if isinstance(x, np.ndarray):
         return x.copy(order="F")
-    if isinstance(x, (StokesArrays, ThermalArrays)):
+    if isinstance(x, (StokesArrays, ThermalArrays)) or type(x).__name__ == "Topography":
         y = type(x)(_backend_of(x), x._ni)
         _assign(y, x, lambda dst, src: dst.copy_(src))
         return y
@@ -88,6 +88,8 @@ def PTArray_(backend_tag, x, kind=None):
         return from_numpy(x, dev)
     if isinstance(x, torch.Tensor):
         return copy_(x).to(dev) if x.device != dev else copy_(x)
+    if kind is None and hasattr(x, "h_old"):
+        from .topography import Topography as kind          # imported here: the operator modules load the HIP library
     kind = kind or (ThermalArrays if hasattr(x, "Told") else StokesArrays)
     y = kind(backend_tag, x._ni)
     _assign(y, x, lambda dst, src: dst.copy_(from_numpy(src, dev) if isinstance(src, np.ndarray) else src))
@@ -129,6 +131,10 @@ def checkpointing_npz(dst, stokes, thermal=None, time=0.0, timestep=0.0, igg=Non
         if isinstance(v, (tuple, list)):
             for q, a in enumerate(v):
                 items[f"extra/{k}/{q}"] = Array_(a)
+        elif hasattr(v, "_ni") and hasattr(v, "__dict__"):          # a container (e.g. a Topography): its arrays under extra/<k>/, read back by load_checkpoint_extra_npz
+            hv = Array_(v)
+            items[f"extra/{k}/_ni"] = np.asarray(hv._ni, dtype=np.int64)
+            _flatten(f"extra/{k}", hv, items)
         else:
             items[f"extra/{k}"] = Array_(v) if isinstance(v, (torch.Tensor, np.ndarray)) else np.asarray(v)
     with tempfile.TemporaryDirectory() as tmp:
@@ -163,3 +169,10 @@ def load_checkpoint_npz(file_path, igg=None):
     with np.load(checkpoint_name(file_path, igg)) as z:
         items = {k: z[k] for k in z.files}
     return _unflatten(items, "stokes"), _unflatten(items, "thermal"), float(items["time"]), float(items["timestep"])
+
+
+def load_checkpoint_extra_npz(file_path, name, igg=None):
+    """the container written as the keyword `name` of checkpointing_npz (e.g. topo = a Topography), as a host tree for PTArray_; None if the file has none"""
+    with np.load(checkpoint_name(file_path, igg)) as z:
+        items = {k: z[k] for k in z.files}
+    return _unflatten(items, f"extra/{name}")

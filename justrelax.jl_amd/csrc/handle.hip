@@ -123,6 +123,8 @@ int find_opt(jrx_handle *h, const char *key, bool tuning, OptRef *out)
         {"stat_principal_calls", 2, &h->stat_principal_calls},
         {"stat_phase_ratios_calls", 2, &h->stat_phase_ratios_calls}, {"stat_phase_ratios_fused", 2, &h->stat_phase_ratios_fused},
         {"stat_rotate_stress_calls", 2, &h->stat_rotate_stress_calls},
+        {"stat_rock_fraction_calls", 2, &h->stat_rock_fraction_calls}, {"stat_topography_advect_calls", 2, &h->stat_topography_advect_calls},
+        {"stat_topography_phase_calls", 2, &h->stat_topography_phase_calls},
         {"stat_dyrel_launches", 2, &h->stat_dyrel_launches},
     };
     const OptRef tun[] = {
