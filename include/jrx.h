@@ -133,7 +133,7 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   "stat_phase_ratios_calls" / "stat_phase_ratios_fused" = jrx_update_phase_ratios2d / 3d calls that launched / those that ran the one-launch form,
  *   "stat_rotate_stress_calls" = jrx_rotate_stress2d / 3d calls that launched,
  *   "stat_rock_fraction_calls" / "stat_topography_advect_calls" / "stat_topography_phase_calls" = jrx_compute_rock_fraction2d / jrx_advect_topography2d /
- *   jrx_update_phases_topography2d calls that launched,
+ *   jrx_update_phases_topography2d calls that launched (their 3D forms jrx_compute_rock_fraction3d / jrx_advect_topography3d / jrx_update_phases_topography3d count in the same three),
  *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* and jrx_dyrel3d_* entry points -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
@@ -967,6 +967,71 @@ jrx_status jrx_advect_topography2d(jrx_handle *h, double *topo_h, double *topo_h
                                    double _dx, double _dy, double dt);
 jrx_status jrx_update_phases_topography2d(jrx_handle *h, double *const *phases, int32_t nphase, const double *topo_h, int64_t nx, int64_t ny, double y0,
                                           double _dy, int32_t air_phase);
+
+/* ------------------------------------------------------------------ a moving free surface in 3D: topography h(x, y), rock fractions from it
+ * The 3D forms of the three operators above, for the eight-member RockRatio of the 3D variational driver (Python: Topography(backend, (nx, ny)), h and h_old of
+ * shape (nx+1, ny+1)).  As in 2D there is no reference text to restate (JustPIC's marker chain is not in the reference tree); what is built is defined here, to
+ * the rounding.  Scope: 3D, uniform grid, one block.  fp64, no fma: every product and sum is rounded once, left to right as written, so tests/_topography3d.py
+ * (the same text in NumPy) agrees bit for bit.  Indices 0-based, x fastest; ni = (nx, ny, nz), z the vertical, z0 the grid's origin in z, _dx, _dy, _dz the
+ * inverse spacings; clamp as above.
+ *
+ * The surface.  Heights h[i,j] at the (nx+1) x (ny+1) vertex positions; s[i,j] = (h[i,j] - z0) * _dz in cell units; every cell (i,j) has the centre value
+ *   c[i,j] = 0.25 * ((s[i,j] + s[i+1,j]) + (s[i,j+1] + s[i+1,j+1]))
+ * and is split into the four triangles corner-corner-centre, the surface linear on each: no diagonal bias, and on a surface constant along y the 2D polyline.
+ * A QUADRANT is the quarter of cell (i,j) at one of its corners: two half-triangles of area 1/8 with the vertex values (A, mx, c) and (A, my, c), A the corner's
+ * height, X and Y the heights of the cell's neighbouring corners along x and y, mx = 0.5 * (A + X), my = 0.5 * (A + Y).
+ * The mean over a triangle of clamp(g, 0, H), g linear with the vertex values g1, g2, g3 sorted to a <= b <= c (three comparisons):
+ *   Ψ(a,b,c) = 0                                                    if c <= 0
+ *            = ((a + b) + c) / 3                                     if a >= 0
+ *            = ((c * c) * c) / ((3 * (c - a)) * (c - b))              if b <= 0
+ *            = ((a + b) + c) / 3 + (((-a) * (-a)) * (-a)) / ((3 * (b - a)) * (c - a))      otherwise
+ *   T(g1,g2,g3,H) = H if a >= H;  0 if c <= 0;  otherwise Ψ(a, b, c) - Ψ(a - H, b - H, c - H)
+ * The two shortcuts of T are part of the definition: a fully covered volume is exactly 1, and a kernel may skip the arithmetic without changing a bit.
+ * A quadrant's volume inside the z range [b, b + H]:
+ *   q = 0.125 * T(A - b, mx - b, c - b, H) + 0.125 * T(A - b, my - b, c - b, H)
+ *
+ * 1. compute_rock_fraction!(ϕ::RockRatio{3}, topo, grid) -- jrx_compute_rock_fraction3d.  Writes all eight members of ϕ, each the fraction of the member's
+ *    control volume below the surface.  Four footprints, built from quadrants named by the vertex they touch and the direction (+-x, +-y); their volumes are
+ *    added in the order listed, starting from 0; a quadrant whose cell is outside the domain is skipped:
+ *      cell (i,j):                 (i,j,+,+), (i+1,j,-,+), (i,j+1,+,-), (i+1,j+1,-,-)                                   area 1
+ *      x-face (i,j), i = 0..nx:    (i,j,-,+), (i,j+1,-,-) if i > 0; then (i,j,+,+), (i,j+1,+,-) if i < nx                area 1 or 0.5
+ *      y-face (i,j), j = 0..ny:    (i,j,+,-), (i+1,j,-,-) if j > 0; then (i,j,+,+), (i+1,j,-,+) if j < ny                area 1 or 0.5
+ *      vertex (i,j):               (-,-), (+,-), (-,+), (+,+) of the vertex, those that exist                          area 0.25 * their number
+ *    Two z ranges:  cell row k: b = k, H = 1;   vertex row k: b = max(k - 0.5, 0), t = min(k + 0.5, nz), H = t - b.
+ *      center (nx, ny, nz)      cell, cell row        Vz (nx, ny, nz+1)        cell, vertex row
+ *      Vx (nx+1, ny, nz)        x-face, cell row      xz (nx+1, ny, nz+1)      x-face, vertex row
+ *      Vy (nx, ny+1, nz)        y-face, cell row      yz (nx, ny+1, nz+1)      y-face, vertex row
+ *      xy (nx+1, ny+1, nz)      vertex, cell row      vertex (nx+1, ny+1, nz+1) vertex, vertex row
+ *    On a surface constant along y the y-face members equal their cell partners bit for bit on interior rows (the same volumes in the same order); the vertex
+ *    footprint adds the volumes of the x-face in another order, and a footprint clipped at a face of the domain has half of them, so those pairs (and every
+ *    pair after x and y are exchanged) agree only to the rounding of the sum.
+ *    The value is clamp(sum / (area * H), 0, 1): as in 2D a guarantee for the masks of the solver (the sum itself is good to a few 1e-16).  One launch; the only loads are the nine heights around (i,j); nothing
+ *    else in ϕ is read.  A thread owns a node (i,j) of the (nx+1, ny+1) vertex positions and a chunk of vertex rows k (tuning key "rock_fraction3d_rows",
+ *    include/jrx_tuning.h); a row whose z range lies below the smallest (above the largest) of the nine heights is 1 (0) by the shortcuts, the others are evaluated.
+ * 2. advect_topography!(topo, V, grid, dt) -- jrx_advect_topography3d.  V = stokes.V with ghost layers: Vx (nx+1, ny+2, nz+2), Vy (nx+2, ny+1, nz+2),
+ *    Vz (nx+2, ny+2, nz+1).  The call copies h to h_old, then writes every h[i,j] from h_old (s_old its heights in cell units).  Vertex velocities, paired so
+ *    that a plane-strain state reproduces the bits of the 2D operator:
+ *      vxv(i,j,k) = 0.25 * ((Vx[i,j,k] + Vx[i,j,k+1]) + (Vx[i,j+1,k] + Vx[i,j+1,k+1]))
+ *      vyv(i,j,k) = 0.25 * ((Vy[i,j,k] + Vy[i,j,k+1]) + (Vy[i+1,j,k] + Vy[i+1,j,k+1]))
+ *      vzv(i,j,k) = 0.25 * ((Vz[i,j,k] + Vz[i+1,j,k]) + (Vz[i,j+1,k] + Vz[i+1,j+1,k]))
+ *      at the surface:  σ = clamp(s_old[i,j], 0, nz), k0 = min(floor(σ), nz - 1), t = σ - k0,  v = (1 - t) * v(i,j,k0) + t * v(i,j,k0+1) for vx, vy, vz
+ *      departure point: ξ = clamp(i - (vx * dt) * _dx, 0, nx), i0 = min(floor(ξ), nx - 1), r = ξ - i0;  η = clamp(j - (vy * dt) * _dy, 0, ny), j0 = min(floor(η), ny - 1), q = η - j0
+ *      h[i,j] = ((1 - q) * ((1 - r) * h_old[i0,j0] + r * h_old[i0+1,j0]) + q * ((1 - r) * h_old[i0,j0+1] + r * h_old[i0+1,j0+1])) + vz * dt
+ *    First order, stable at any dt.  The 2D remark about the relaxation time applies unchanged, and weighs more: the 3D variational driver has no free-surface
+ *    stabilisation (examples/free_surface_relaxation3d.py passes a quarter of that time as the dt_diff of compute_dt).
+ * 3. update_phases_given_topography!(phases, topo, grid, air_phase) -- jrx_update_phases_topography3d.  phases: the N cell-centred (nx, ny, nz) fields that
+ *    update_phase_ratios_3D! takes, 1 <= N <= JRX_MAXPHASE, a HOST array of DEVICE pointers; air_phase is 1-based.  A thread per column (i,j) marches
+ *    k = 0 .. nz - 1 by exactly the 2D rule, with f = center[i,j,k] of operator 1 computed in the kernel.
+ *
+ * All three are synchronous and count in the 2D operators' counters.  JRX_ERR_ARG (4) with a text naming the cause, nothing launched and no counter moved: a NULL
+ * member, an extent < 1, air_phase outside 1..N, N outside 1..JRX_MAXPHASE, overlapping outputs (or an output that overlaps an input), 2^31 or more entries in the
+ * ni .+ 2 box, a non-finite dt, spacing or z0. */
+jrx_status jrx_compute_rock_fraction3d(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, double *Vz, double *yz, double *xz, double *xy,
+                                       const double *topo_h, int64_t nx, int64_t ny, int64_t nz, double z0, double _dz);
+jrx_status jrx_advect_topography3d(jrx_handle *h, double *topo_h, double *topo_h_old, const double *Vx, const double *Vy, const double *Vz, int64_t nx, int64_t ny,
+                                   int64_t nz, double z0, double _dx, double _dy, double _dz, double dt);
+jrx_status jrx_update_phases_topography3d(jrx_handle *h, double *const *phases, int32_t nphase, const double *topo_h, int64_t nx, int64_t ny, int64_t nz, double z0,
+                                          double _dz, int32_t air_phase);
 
 /* ------------------------------------------------------------------ timing hooks for bench.py */
 /* Runs `iters` PT iterations of the 3D loop body back to back (no norm checks) and reports device times

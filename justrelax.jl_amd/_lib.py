@@ -238,6 +238,10 @@ def load(check_symbols: bool = False):
         L.jrx_compute_rock_fraction2d.argtypes = [C.c_void_p] * 6 + [C.c_int64] * 2 + [C.c_double] * 2
         L.jrx_advect_topography2d.argtypes = [C.c_void_p] * 5 + [C.c_int64] * 2 + [C.c_double] * 4
         L.jrx_update_phases_topography2d.argtypes = [C.c_void_p, _vpp, C.c_int32, C.c_void_p] + [C.c_int64] * 2 + [C.c_double] * 2 + [C.c_int32]
+        # their 3D forms: the eight members of ϕ, h, the extents, z0, _dz | h, h_old, Vx, Vy, Vz, the extents, z0, _dx, _dy, _dz, dt | as in 2D with one more extent
+        L.jrx_compute_rock_fraction3d.argtypes = [C.c_void_p] * 10 + [C.c_int64] * 3 + [C.c_double] * 2
+        L.jrx_advect_topography3d.argtypes = [C.c_void_p] * 6 + [C.c_int64] * 3 + [C.c_double] * 5
+        L.jrx_update_phases_topography3d.argtypes = [C.c_void_p, _vpp, C.c_int32, C.c_void_p] + [C.c_int64] * 3 + [C.c_double] * 2 + [C.c_int32]
         _lib = L
     if check_symbols:
         missing = [s for s in declared_symbols() if not hasattr(_lib, s)]

@@ -111,6 +111,7 @@ struct jrx_handle {
     int64_t stat_phase_ratios_calls = 0, stat_phase_ratios_fused = 0;   // jrx_update_phase_ratios2d / 3d calls that launched / those that ran the one-launch form
     int64_t stat_rotate_stress_calls = 0;   // jrx_rotate_stress2d / 3d calls that launched
     int64_t stat_rock_fraction_calls = 0, stat_topography_advect_calls = 0, stat_topography_phase_calls = 0;   // jrx_compute_rock_fraction2d / jrx_advect_topography2d / jrx_update_phases_topography2d calls that launched
+    int rock_fraction3d_rows = 0;        // tuning: vertex rows k a thread of k_rock_fraction3d marches (0: the built-in depth; 1: a thread per node; bit-identical)
     int64_t stat_principal_calls = 0;    // jrx_principal_stresses2d / 3d calls that launched
     int64_t stat_dyrel_launches = 0;     // kernels launched by the jrx_dyrel2d_* / jrx_dyrel3d_* entry points (dyrel2d.hip, dyrel3d.hip)
     // ---- read-only counters (jrx_get_option "stat_*"): launches of the fused kernels since jrx_create, so that tests and the bench can

@@ -13,12 +13,19 @@
 // only loads are h[i - 1], h[i], h[i + 1], so the stores are the whole traffic.  k_advect_topography2d: a thread per vertex abscissa.
 // k_phases_topography2d<N>: a thread per column marches j = 0 .. ny - 1 and carries the rock proportions of the last cell that had rock; the lanes of a wave
 // read and write consecutive x.  Addressing: 32-bit element offsets (every array below 2^31 entries, checked).
+//
+// 3D (the second half of the file; tests/_topography3d.py is the same text in NumPy): the surface h(x, y) at the (nx + 1, ny + 1) vertex positions, linear on the
+// four triangles corner-corner-centre of every cell.  k_rock_fraction3d: ONE launch, a thread per node (i, j) and per chunk of vertex rows k (64 x 4 nodes, 4 rows
+// by measurement) writes the eight members that node owns; its only loads are the nine heights around (i, j); rows the surface does not cross are 1 or 0 by the
+// shortcuts of the definition without evaluating a triangle.  k_advect_topography3d: a thread per vertex.  k_phases_topography3d<N>: a thread per column (i, j)
+// marches k by the 2D rule.
 #include "jrx_internal.hpp"
 
 namespace {
 
 constexpr int kTpTX = 64, kTpTY = 4;                  // tile of nodes of k_rock_fraction2d
 constexpr int kTpCols = 64;                           // columns per block of the 1D kernels
+constexpr int kTpRows3 = 4;                           // vertex rows a thread of k_rock_fraction3d marches (tuning "rock_fraction3d_rows"; measured, profiles/topography3d_bench.txt)
 
 // clamp by comparisons: a NaN becomes lo (so that an index derived from it stays inside its array)
 __device__ __forceinline__ double tp_clamp(double x, double lo, double hi) { return x >= lo ? (x <= hi ? x : hi) : lo; }
@@ -138,6 +145,213 @@ __global__ __launch_bounds__(kTpCols) void k_phases_topography2d(const PhArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ 3D: the surface h(x, y) at the (nx + 1, ny + 1) vertex positions
+// Every cell is split into the four triangles corner-corner-centre (include/jrx.h); a quadrant is the quarter of a cell at one of its corners, two half-triangles
+// of area 1/8 with the vertex values (A, mx, c) and (A, my, c).
+
+// Ψ(a, b, c): the mean of max(g, 0) over a triangle, g linear with the sorted vertex values a <= b <= c
+__device__ __forceinline__ double tp_psi(double a, double b, double c)
+{
+    if (c <= 0.0) return 0.0;
+    if (a >= 0.0) return ((a + b) + c) / 3.0;
+    if (b <= 0.0) return ((c * c) * c) / ((3.0 * (c - a)) * (c - b));
+    const double na = -a;
+    return ((a + b) + c) / 3.0 + ((na * na) * na) / ((3.0 * (b - a)) * (c - a));
+}
+
+// T(g1, g2, g3, H): the mean over a triangle of clamp(g, 0, H)
+__device__ __forceinline__ double tp_tri(double g1, double g2, double g3, double H)
+{
+    const bool w1 = g2 < g1;
+    const double lo = w1 ? g2 : g1, hi = w1 ? g1 : g2;
+    const bool w2 = g3 < hi;
+    const double c = w2 ? hi : g3, m = w2 ? g3 : hi;
+    const bool w3 = m < lo;
+    const double a = w3 ? m : lo, b = w3 ? lo : m;
+    if (a >= H) return H;
+    if (c <= 0.0) return 0.0;
+    return tp_psi(a, b, c) - tp_psi(a - H, b - H, c - H);
+}
+
+// the volume of the quadrant at the corner A (X, Y: the cell's neighbouring corners along x and y, c: its centre value) inside the z range [b, b + H]
+__device__ __forceinline__ double tp_quad(double A, double X, double Y, double c, double b, double H)
+{
+    const double mx = 0.5 * (A + X), my = 0.5 * (A + Y), ga = A - b, gc = c - b;
+    return 0.125 * tp_tri(ga, mx - b, gc, H) + 0.125 * tp_tri(ga, my - b, gc, H);
+}
+
+__device__ __forceinline__ double tp_centre4(double s00, double s10, double s01, double s11) { return 0.25 * ((s00 + s10) + (s01 + s11)); }
+
+// center[i, j, k] from the four corners of cell (i, j) and its centre value; lo, hi: the smallest and the largest corner.  Midpoints and centre lie between the
+// corners and x - b is monotone in x, so lo - b >= 1 (hi - b <= 0) says that every triangle takes its first (second) shortcut: the sum is then exactly 1 (0)
+__device__ __forceinline__ double tp_center3(double s00, double s10, double s01, double s11, double c, double lo, double hi, double b)
+{
+    if (lo - b >= 1.0) return 1.0;
+    if (hi - b <= 0.0) return 0.0;
+    double v = 0.0;
+    v = v + tp_quad(s00, s10, s01, c, b, 1.0);
+    v = v + tp_quad(s10, s00, s11, c, b, 1.0);
+    v = v + tp_quad(s01, s11, s00, c, b, 1.0);
+    v = v + tp_quad(s11, s01, s10, c, b, 1.0);
+    return tp_clamp(v, 0.0, 1.0);
+}
+
+__device__ __forceinline__ double tp_min(double a, double b) { return b < a ? b : a; }
+__device__ __forceinline__ double tp_max(double a, double b) { return b > a ? b : a; }
+
+struct Rf3Args {
+    const double *h;
+    double *center, *vertex, *Vx, *Vy, *Vz, *yz, *xz, *xy;
+    double z0, idz;
+    int nx, ny, nz, nbx, nby, rows;      // rows: vertex rows k a thread marches
+};
+
+// A thread per node (i, j) of the (nx + 1, ny + 1) vertex positions and per chunk of `rows` vertex rows k writes the eight members that node owns: the cell
+// row k (center, Vx, Vy, xy) and the vertex row k (Vz, xz, yz, vertex).  The nine heights around (i, j) are its only loads.  A row whose z range lies below the
+// smallest (above the largest) of them is all 1 (0) by the shortcuts of T, to the bit; only the rows the surface crosses evaluate the nine quadrants.
+__global__ __launch_bounds__(256) void k_rock_fraction3d(const Rf3Args a)
+{
+    const int nx = a.nx, ny = a.ny, nz = a.nz;
+    int blk = (int)blockIdx.x;
+    const int bx = blk % a.nbx;
+    blk /= a.nbx;
+    const int by = blk % a.nby, bz = blk / a.nby;
+    const int i = bx * kTpTX + (int)threadIdx.x, j = by * kTpTY + (int)threadIdx.y;
+    if (i > nx || j > ny) return;
+    const bool hasl = i > 0, hasr = i < nx, hasd = j > 0, hasu = j < ny;
+    const int im = hasl ? i - 1 : i, ip = hasr ? i + 1 : i, jm = hasd ? j - 1 : j, jp = hasu ? j + 1 : j, sx = nx + 1;      // a missing neighbour: the node itself (unused)
+    const double z0 = a.z0, idz = a.idz;
+    const double smm = (a.h[jm * sx + im] - z0) * idz, s0m = (a.h[jm * sx + i] - z0) * idz, spm = (a.h[jm * sx + ip] - z0) * idz;
+    const double sm0 = (a.h[j * sx + im] - z0) * idz, s00 = (a.h[j * sx + i] - z0) * idz, sp0 = (a.h[j * sx + ip] - z0) * idz;
+    const double smp = (a.h[jp * sx + im] - z0) * idz, s0p = (a.h[jp * sx + i] - z0) * idz, spp = (a.h[jp * sx + ip] - z0) * idz;
+    const double cmm = tp_centre4(smm, s0m, sm0, s00), cpm = tp_centre4(s0m, spm, s00, sp0), cmp = tp_centre4(sm0, s00, smp, s0p), cpp = tp_centre4(s00, sp0, s0p, spp);
+    const double lo = tp_min(tp_min(tp_min(tp_min(smm, s0m), tp_min(spm, sm0)), tp_min(tp_min(s00, sp0), tp_min(smp, s0p))), spp);
+    const double hi = tp_max(tp_max(tp_max(tp_max(smm, s0m), tp_max(spm, sm0)), tp_max(tp_max(s00, sp0), tp_max(smp, s0p))), spp);
+    const double Wx = hasl && hasr ? 1.0 : 0.5, Wy = hasd && hasu ? 1.0 : 0.5;
+    const double Wv = 0.25 * (double)((int)(hasl && hasd) + (int)(hasr && hasd) + (int)(hasl && hasu) + (int)(hasr && hasu));
+    const int k0 = bz * a.rows, k1 = k0 + a.rows < nz + 1 ? k0 + a.rows : nz + 1;
+    for (int k = k0; k < k1; k++) {
+#pragma unroll 1
+        for (int r = k < nz ? 0 : 1; r < 2; r++) {      // r = 0: the cell row k, r = 1: the vertex row k
+            const double kd = (double)k;
+            const double bv = kd - 0.5 > 0.0 ? kd - 0.5 : 0.0, tv = kd + 0.5 < (double)nz ? kd + 0.5 : (double)nz;
+            const double b = r ? bv : kd, H = r ? tv - bv : 1.0;
+            double vc, vx, vy, vv;
+            if (lo - b >= H) vc = vx = vy = vv = 1.0;
+            else if (hi - b <= 0.0) vc = vx = vy = vv = 0.0;
+            else {
+                const double q1 = tp_quad(s00, sp0, s0p, cpp, b, H), q2 = tp_quad(sp0, s00, spp, cpp, b, H), q3 = tp_quad(s0p, spp, s00, cpp, b, H);
+                const double q4 = tp_quad(spp, s0p, sp0, cpp, b, H), q5 = tp_quad(s00, sm0, s0p, cmp, b, H), q6 = tp_quad(s0p, smp, s00, cmp, b, H);
+                const double q7 = tp_quad(s00, sp0, s0m, cpm, b, H), q8 = tp_quad(sp0, s00, spm, cpm, b, H), q9 = tp_quad(s00, sm0, s0m, cmm, b, H);
+                double t = 0.0;
+                t = t + q1, t = t + q2, t = t + q3, t = t + q4;
+                vc = tp_clamp(t / (1.0 * H), 0.0, 1.0);
+                t = 0.0;
+                if (hasl) t = t + q5, t = t + q6;
+                if (hasr) t = t + q1, t = t + q3;
+                vx = tp_clamp(t / (Wx * H), 0.0, 1.0);
+                t = 0.0;
+                if (hasd) t = t + q7, t = t + q8;
+                if (hasu) t = t + q1, t = t + q2;
+                vy = tp_clamp(t / (Wy * H), 0.0, 1.0);
+                t = 0.0;
+                if (hasl && hasd) t = t + q9;
+                if (hasr && hasd) t = t + q7;
+                if (hasl && hasu) t = t + q5;
+                if (hasr && hasu) t = t + q1;
+                vv = tp_clamp(t / (Wv * H), 0.0, 1.0);
+            }
+            double *const pc = r ? a.Vz : a.center, *const px = r ? a.xz : a.Vx, *const py = r ? a.yz : a.Vy, *const pv = r ? a.vertex : a.xy;
+            if (hasr && hasu) pc[(k * ny + j) * nx + i] = vc;
+            if (hasu) px[(k * ny + j) * (nx + 1) + i] = vx;
+            if (hasr) py[(k * (ny + 1) + j) * nx + i] = vy;
+            pv[(k * (ny + 1) + j) * (nx + 1) + i] = vv;
+        }
+    }
+}
+
+struct Adv3Args {
+    double *h;
+    const double *h_old, *Vx, *Vy, *Vz;      // Vx (nx + 1, ny + 2, nz + 2), Vy (nx + 2, ny + 1, nz + 2), Vz (nx + 2, ny + 2, nz + 1)
+    double z0, idx, idy, idz, dt;
+    int nx, ny, nz, nbx;
+};
+
+__global__ __launch_bounds__(256) void k_advect_topography3d(const Adv3Args a)
+{
+    const int nx = a.nx, ny = a.ny, nz = a.nz;
+    const int i = ((int)blockIdx.x % a.nbx) * kTpTX + (int)threadIdx.x, j = ((int)blockIdx.x / a.nbx) * kTpTY + (int)threadIdx.y;
+    if (i > nx || j > ny) return;
+    const int sx = nx + 1;
+    const double sig = tp_clamp((a.h_old[j * sx + i] - a.z0) * a.idz, 0.0, (double)nz);
+    int k0 = (int)floor(sig);
+    k0 = k0 < nz - 1 ? k0 : nz - 1;
+    const double t = sig - (double)k0;
+    double v[3][2];
+#pragma unroll
+    for (int l = 0; l < 2; l++) {
+        const int k = k0 + l;
+        const double *px = a.Vx + (k * (ny + 2) + j) * (nx + 1) + i, *py = a.Vy + (k * (ny + 1) + j) * (nx + 2) + i, *pz = a.Vz + (k * (ny + 2) + j) * (nx + 2) + i;
+        const int px_k = (ny + 2) * (nx + 1), py_k = (ny + 1) * (nx + 2);
+        v[0][l] = 0.25 * ((px[0] + px[px_k]) + (px[nx + 1] + px[nx + 1 + px_k]));          // vxv(i, j, k): Vx[i, j .. j + 1, k .. k + 1]
+        v[1][l] = 0.25 * ((py[0] + py[py_k]) + (py[1] + py[1 + py_k]));                    // vyv(i, j, k): Vy[i .. i + 1, j, k .. k + 1]
+        v[2][l] = 0.25 * ((pz[0] + pz[1]) + (pz[nx + 2] + pz[nx + 3]));                    // vzv(i, j, k): Vz[i .. i + 1, j .. j + 1, k]
+    }
+    const double vx = (1.0 - t) * v[0][0] + t * v[0][1], vy = (1.0 - t) * v[1][0] + t * v[1][1], vz = (1.0 - t) * v[2][0] + t * v[2][1];
+    const double xi = tp_clamp((double)i - (vx * a.dt) * a.idx, 0.0, (double)nx), eta = tp_clamp((double)j - (vy * a.dt) * a.idy, 0.0, (double)ny);
+    int i0 = (int)floor(xi), j0 = (int)floor(eta);
+    i0 = i0 < nx - 1 ? i0 : nx - 1;
+    j0 = j0 < ny - 1 ? j0 : ny - 1;
+    const double r = xi - (double)i0, q = eta - (double)j0;
+    const double *ho = a.h_old + j0 * sx + i0;
+    const double lo = (1.0 - r) * ho[0] + r * ho[1], hi = (1.0 - r) * ho[sx] + r * ho[sx + 1];
+    a.h[j * sx + i] = ((1.0 - q) * lo + q * hi) + vz * a.dt;
+}
+
+struct Ph3Args {
+    double *c[JRX_MAXPHASE];
+    const double *h;
+    double z0, idz;
+    int nx, ny, nz, nbx, air;      // air: 0-based
+};
+
+template <int N>
+__global__ __launch_bounds__(256) void k_phases_topography3d(const Ph3Args a)
+{
+    const int nx = a.nx, ny = a.ny, nz = a.nz, air = a.air;
+    const int i = ((int)blockIdx.x % a.nbx) * kTpTX + (int)threadIdx.x, j = ((int)blockIdx.x / a.nbx) * kTpTY + (int)threadIdx.y;
+    if (i >= nx || j >= ny) return;
+    const double *hp = a.h + j * (nx + 1) + i;
+    const double s00 = (hp[0] - a.z0) * a.idz, s10 = (hp[1] - a.z0) * a.idz, s01 = (hp[nx + 1] - a.z0) * a.idz, s11 = (hp[nx + 2] - a.z0) * a.idz;
+    const double cc = tp_centre4(s00, s10, s01, s11);
+    const double lo = tp_min(tp_min(s00, s10), tp_min(s01, s11)), hi = tp_max(tp_max(s00, s10), tp_max(s01, s11));
+    const int first = air == 0 ? 1 : 0;                               // the lowest non-air index (N == 1: none, and no rock field is touched)
+    double p[N], c[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) p[k] = k == first ? 1.0 : 0.0;
+#pragma unroll 1
+    for (int kz = 0; kz < nz; kz++) {
+        const int lin = (kz * ny + j) * nx + i;
+        const double f = tp_center3(s00, s10, s01, s11, cc, lo, hi, (double)kz);
+        double R = 0.0, ca = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            c[k] = a.c[k][lin];
+            if (k == air) ca = c[k];
+            else R = R + c[k];
+        }
+        if (R > 0.0) {
+#pragma unroll
+            for (int k = 0; k < N; k++)
+                if (k != air) p[k] = c[k] / R;
+        }
+        const double airv = 1.0 - f;
+        if (ca == airv) continue;
+#pragma unroll
+        for (int k = 0; k < N; k++) a.c[k][lin] = k == air ? airv : f * p[k];
+    }
+}
+
 bool tp_overlaps(const void *a, i64 na, const void *b, i64 nb)
 {
     const char *pa = (const char *)a, *pb = (const char *)b;
@@ -149,6 +363,15 @@ jrx_status tp_extents(jrx_handle *h, const char *fn, int64_t nx, int64_t ny)
 {
     if (nx < 1 || ny < 1) return jrx_fail(h, JRX_ERR_ARG, "%s: extents %lld x %lld (each must be >= 1)", fn, (long long)nx, (long long)ny);
     if ((double)(nx + 2) * (double)(ny + 2) >= 2147483648.0) return jrx_fail(h, JRX_ERR_ARG, "%s: the ni .+ 2 box has 2^31 or more entries (32-bit offsets)", fn);
+    return JRX_OK;
+}
+
+jrx_status tp_extents3(jrx_handle *h, const char *fn, int64_t nx, int64_t ny, int64_t nz)
+{
+    if (nx < 1 || ny < 1 || nz < 1)
+        return jrx_fail(h, JRX_ERR_ARG, "%s: extents %lld x %lld x %lld (each must be >= 1)", fn, (long long)nx, (long long)ny, (long long)nz);
+    if ((double)(nx + 2) * (double)(ny + 2) * (double)(nz + 2) >= 2147483648.0)
+        return jrx_fail(h, JRX_ERR_ARG, "%s: the ni .+ 2 box has 2^31 or more entries (32-bit offsets)", fn);
     return JRX_OK;
 }
 
@@ -238,6 +461,101 @@ jrx_status jrx_update_phases_topography2d(jrx_handle *h, double *const *phases, 
     h->stat_topography_phase_calls++;
     dispatch_const<1, 2, 3, 4, 5, 6, 7, 8>((int)nphase, [&](auto NN) {
         hipLaunchKernelGGL((k_phases_topography2d<NN()>), dim3((unsigned)((nx + kTpCols - 1) / kTpCols)), dim3(kTpCols), 0, h->stream, a);
+    });
+    JRX_LAUNCH_CHECK(h);
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_compute_rock_fraction3d(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, double *Vz, double *yz, double *xz, double *xy,
+                                       const double *topo_h, int64_t nx, int64_t ny, int64_t nz, double z0, double _dz)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "compute_rock_fraction!";
+    double *const out[8] = {center, vertex, Vx, Vy, Vz, yz, xz, xy};
+    static const char *const names[8] = {"center", "vertex", "Vx", "Vy", "Vz", "yz", "xz", "xy"};
+    for (int m = 0; m < 8; m++)
+        if (!out[m]) return jrx_fail(h, JRX_ERR_ARG, "%s: ϕ.%s is NULL", fn, names[m]);
+    if (!topo_h) return jrx_fail(h, JRX_ERR_ARG, "%s: topo.h is NULL", fn);
+    JRX_TRY(tp_extents3(h, fn, nx, ny, nz));
+    if (!std::isfinite(z0) || !std::isfinite(_dz)) return jrx_fail(h, JRX_ERR_ARG, "%s: z0 = %g, _dz = %g (both must be finite)", fn, z0, _dz);
+    const i64 cnt[8] = {nx * ny * nz,       (nx + 1) * (ny + 1) * (nz + 1), (nx + 1) * ny * nz,       nx * (ny + 1) * nz,
+                        nx * ny * (nz + 1), nx * (ny + 1) * (nz + 1),       (nx + 1) * ny * (nz + 1), (nx + 1) * (ny + 1) * nz};
+    for (int m = 0; m < 8; m++) {
+        if (tp_overlaps(out[m], cnt[m], topo_h, (nx + 1) * (ny + 1))) return jrx_fail(h, JRX_ERR_ARG, "%s: output ϕ.%s overlaps topo.h", fn, names[m]);
+        for (int q = m + 1; q < 8; q++)
+            if (tp_overlaps(out[m], cnt[m], out[q], cnt[q])) return jrx_fail(h, JRX_ERR_ARG, "%s: outputs ϕ.%s and ϕ.%s overlap", fn, names[m], names[q]);
+    }
+    JRX_TRY(jrx_check_device(h));
+    int rows = h->rock_fraction3d_rows > 0 ? h->rock_fraction3d_rows : kTpRows3;
+    if (rows > nz + 1) rows = (int)(nz + 1);      // a deeper march is the whole column; keeps k0 + rows inside an int
+    Rf3Args a = {topo_h, center, vertex, Vx, Vy, Vz, yz, xz, xy, z0, _dz, (int)nx, (int)ny, (int)nz, (int)((nx + 1 + kTpTX - 1) / kTpTX), (int)((ny + 1 + kTpTY - 1) / kTpTY), rows};
+    const int64_t nb = (int64_t)a.nbx * a.nby * ((nz + 1 + rows - 1) / rows);      // below 2^31: no more blocks than nodes of the ni .+ 1 box
+    h->stat_rock_fraction_calls++;
+    hipLaunchKernelGGL(k_rock_fraction3d, dim3((unsigned)nb), dim3(kTpTX, kTpTY), 0, h->stream, a);
+    JRX_LAUNCH_CHECK(h);
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_advect_topography3d(jrx_handle *h, double *topo_h, double *topo_h_old, const double *Vx, const double *Vy, const double *Vz, int64_t nx, int64_t ny,
+                                   int64_t nz, double z0, double _dx, double _dy, double _dz, double dt)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "advect_topography!";
+    if (!topo_h) return jrx_fail(h, JRX_ERR_ARG, "%s: topo.h is NULL", fn);
+    if (!topo_h_old) return jrx_fail(h, JRX_ERR_ARG, "%s: topo.h_old is NULL", fn);
+    if (!Vx) return jrx_fail(h, JRX_ERR_ARG, "%s: V.Vx is NULL", fn);
+    if (!Vy) return jrx_fail(h, JRX_ERR_ARG, "%s: V.Vy is NULL", fn);
+    if (!Vz) return jrx_fail(h, JRX_ERR_ARG, "%s: V.Vz is NULL", fn);
+    JRX_TRY(tp_extents3(h, fn, nx, ny, nz));
+    if (!std::isfinite(dt) || !std::isfinite(_dx) || !std::isfinite(_dy) || !std::isfinite(_dz) || !std::isfinite(z0))
+        return jrx_fail(h, JRX_ERR_ARG, "%s: dt = %g, _dx = %g, _dy = %g, _dz = %g, z0 = %g (all must be finite)", fn, dt, _dx, _dy, _dz, z0);
+    const i64 nh = (nx + 1) * (ny + 1);
+    const void *const in[4] = {topo_h_old, Vx, Vy, Vz};
+    static const char *const names[4] = {"topo.h_old", "V.Vx", "V.Vy", "V.Vz"};
+    const i64 cnt[4] = {nh, (nx + 1) * (ny + 2) * (nz + 2), (nx + 2) * (ny + 1) * (nz + 2), (nx + 2) * (ny + 2) * (nz + 1)};
+    for (int m = 0; m < 4; m++)
+        if (tp_overlaps(topo_h, nh, in[m], cnt[m])) return jrx_fail(h, JRX_ERR_ARG, "%s: output topo.h overlaps %s", fn, names[m]);
+    for (int m = 1; m < 4; m++)
+        if (tp_overlaps(topo_h_old, nh, in[m], cnt[m])) return jrx_fail(h, JRX_ERR_ARG, "%s: output topo.h_old overlaps %s", fn, names[m]);
+    JRX_TRY(jrx_check_device(h));
+    h->stat_topography_advect_calls++;
+    JRX_HIP(h, hipMemcpyAsync(topo_h_old, topo_h, (size_t)nh * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    Adv3Args a = {topo_h, topo_h_old, Vx, Vy, Vz, z0, _dx, _dy, _dz, dt, (int)nx, (int)ny, (int)nz, (int)((nx + 1 + kTpTX - 1) / kTpTX)};
+    hipLaunchKernelGGL(k_advect_topography3d, dim3((unsigned)((int64_t)a.nbx * ((ny + 1 + kTpTY - 1) / kTpTY))), dim3(kTpTX, kTpTY), 0, h->stream, a);
+    JRX_LAUNCH_CHECK(h);
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_update_phases_topography3d(jrx_handle *h, double *const *phases, int32_t nphase, const double *topo_h, int64_t nx, int64_t ny, int64_t nz, double z0,
+                                          double _dz, int32_t air_phase)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "update_phases_given_topography!";
+    if (!phases) return jrx_fail(h, JRX_ERR_ARG, "%s: phases is NULL", fn);
+    if (nphase < 1 || nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d phase fields (1 .. %d are built)", fn, (int)nphase, JRX_MAXPHASE);
+    if (air_phase < 1 || air_phase > nphase) return jrx_fail(h, JRX_ERR_ARG, "%s: air_phase %d outside 1 .. %d", fn, (int)air_phase, (int)nphase);
+    for (int k = 0; k < nphase; k++)
+        if (!phases[k]) return jrx_fail(h, JRX_ERR_ARG, "%s: phase field %d is NULL", fn, k + 1);
+    if (!topo_h) return jrx_fail(h, JRX_ERR_ARG, "%s: topo.h is NULL", fn);
+    JRX_TRY(tp_extents3(h, fn, nx, ny, nz));
+    if (!std::isfinite(z0) || !std::isfinite(_dz)) return jrx_fail(h, JRX_ERR_ARG, "%s: z0 = %g, _dz = %g (both must be finite)", fn, z0, _dz);
+    const i64 nc = nx * ny * nz;
+    for (int k = 0; k < nphase; k++) {
+        if (tp_overlaps(phases[k], nc, topo_h, (nx + 1) * (ny + 1))) return jrx_fail(h, JRX_ERR_ARG, "%s: phase field %d overlaps topo.h", fn, k + 1);
+        for (int q = k + 1; q < nphase; q++)
+            if (tp_overlaps(phases[k], nc, phases[q], nc)) return jrx_fail(h, JRX_ERR_ARG, "%s: phase fields %d and %d overlap", fn, k + 1, q + 1);
+    }
+    JRX_TRY(jrx_check_device(h));
+    Ph3Args a = {};
+    for (int k = 0; k < nphase; k++) a.c[k] = phases[k];
+    a.h = topo_h, a.z0 = z0, a.idz = _dz, a.nx = (int)nx, a.ny = (int)ny, a.nz = (int)nz, a.nbx = (int)((nx + kTpTX - 1) / kTpTX), a.air = (int)air_phase - 1;
+    const unsigned nb = (unsigned)((int64_t)a.nbx * ((ny + kTpTY - 1) / kTpTY));
+    h->stat_topography_phase_calls++;
+    dispatch_const<1, 2, 3, 4, 5, 6, 7, 8>((int)nphase, [&](auto NN) {
+        hipLaunchKernelGGL((k_phases_topography3d<NN()>), dim3(nb), dim3(kTpTX, kTpTY), 0, h->stream, a);
     });
     JRX_LAUNCH_CHECK(h);
     JRX_HIP(h, hipStreamSynchronize(h->stream));
