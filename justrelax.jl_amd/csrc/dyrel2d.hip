@@ -1,10 +1,11 @@
 // dyrel2d.hip -- 2D DYREL (self-tuned dynamic relaxation inside Powell-Hestenes pressure iterations) for gfx950: kernels, per-kernel entry points, driver.
 //
-// Reference being replaced (PTsolvers/JustRelax.jl): src/DYREL/solver.jl:44-294 (_solve_DYREL!), :359-365 (compute_λminV!), constructors.jl:178-190 (DYREL!),
-// :230-254 (compute_bulk_viscosity_and_penalty!), pressure_kernels.jl:112 (_compute_RP!, the plain form of _RP_cell :118-121), velocity_kernels.jl:154-240
-// (compute_∇V_strain_rate_RP!), :326-349 (compute_PH_residual_V!), :625-658 (compute_dV!, update_cV!), :660-727 (damped_update_V, compute_DR_residual_update_V!),
-// stress_kernels.jl:100-307 (compute_stress_viscosity_DRYEL!, compute_local_stress, _compute_local_stress), Gershgorin.jl:1-155 (Gershgorin_Stokes2D_SchurComplement!),
-// :171-247 (update_α_β!, update_dτV_α_β!).
+// Reference being replaced (PTsolvers/JustRelax.jl): src/DYREL/solver.jl:44-294 (_solve_DYREL!; here its prologue :86-117, the loop is dyrel_common.hpp's),
+// pressure_kernels.jl:112 (_compute_RP!, the plain form of _RP_cell :118-121), velocity_kernels.jl:154-240 (compute_∇V_strain_rate_RP!), :326-349
+// (compute_PH_residual_V!), :660-727 (damped_update_V, compute_DR_residual_update_V!), stress_kernels.jl:100-307 (compute_stress_viscosity_DRYEL!,
+// compute_local_stress, _compute_local_stress), Gershgorin.jl:1-155 (Gershgorin_Stokes2D_SchurComplement!).
+// Shared with dyrel3d.hip: the sums, the check-time kernels, DYREL! and the solve loop (dyrel_common.hpp), its error bookkeeping (dyrel_conv.hpp), the local law
+// (dyrel_local.hpp).
 //
 // One inner iteration is three launches, as the reference fuses it: k_dy_strain_rp -> k_dy_stress -> k_dy_update.
 // Hazards of the stress kernel (the reference's ordering is stress, halo, viscosity): every array it writes -- τ (xx, yy, xy_c, xx_v, yy_v, xy), ε_pl, ε_vol_pl,
@@ -15,12 +16,9 @@
 // The per-phase laws (cohesion and friction softening, creep viscosity, the phase average of the viscosity, fn_ratio) are jrx_material.hpp's.  Its phase-weighted
 // plasticity helpers (plastic_params, yield_F, plastic_grad) average the PARAMETERS over the phases of a node; DYREL's compute_local_stress evaluates the whole
 // return mapping per phase and averages the RESULTS, so those three do not apply: the yield function and the flow direction of one phase are formed here from
-// the same per-phase laws.  32-bit element offsets (the extents are checked against 2^31).  fma only in update_α_β (the reference's @muladd).
+// the same per-phase laws.  32-bit element offsets (the extents are checked against 2^31).
 // Not built here: 3D (dyrel3d.hip), more than one rank, non-uniform spacing, a RockRatio, the thermal / melt-fraction forms of _RP_cell.
-#include <initializer_list>
-#include "jrx_internal.hpp"
-#include "jrx_kernels.hpp"
-#include "jrx_material.hpp"
+#include "dyrel_common.hpp"
 #include "dyrel_local.hpp"
 #include "stokes2d_kernels.hpp"
 
@@ -233,126 +231,6 @@ __global__ __launch_bounds__(256) void k_dy_gershgorin(const DyArgs a)
 #undef VE
 }
 
-// _update_dτV_α_β! (Gershgorin.jl:229-247; DTAU) / _update_α_β! (:182-198): the reference's @muladd is the two fma here
-template <bool DTAU>
-__global__ __launch_bounds__(256) void k_dy_dtau(const jrx_dyrel2d_fields d, const double CFL, const int nxn, const int nyn)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        if (t >= (c ? nyn : nxn)) continue;
-        double *dtau = c ? d.dtauVy : d.dtauVx, *beta = c ? d.betaVy : d.betaVx, *alpha = c ? d.alphaVy : d.alphaVx;
-        const double *cV = c ? d.cVy : d.cVx, *lmax = c ? d.lmaxVy : d.lmaxVx;
-        double x = dtau[t];
-        if (DTAU) { x = 2 / sqrt(lmax[t]) * CFL; dtau[t] = x; }
-        const double cv = cV[t], den = fma(cv, x, 2.0);
-        beta[t] = 2 * x / den;
-        alpha[t] = fma(-cv, x, 2.0) / den;
-    }
-}
-
-// compute_bulk_viscosity_and_penalty! (constructors.jl:237-254); eta_mean = mean(η[.!isinf.(η)]) is sums[0] / sums[1] of k_dy_eta_sum
-__global__ __launch_bounds__(256) void k_dy_bulk(const DyArgs a, const double *__restrict__ sums, const double gamma_fact)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= a.nx * a.ny) return;
-    const double eta_mean = sums[0] / sums[1];
-    const double Kbdt = ratio_avg(a.rh.Kb, a.f.phase_c + a.rh.nphase * t, a.rh.nphase) * a.dt;
-    a.d.etab[t] = Kbdt;
-    const double e = a.f.eta[t];
-    const double g_num = gamma_fact * (isinf(e) ? eta_mean : e);
-    const double g_phy = isinf(Kbdt) ? g_num : Kbdt;
-    a.d.gamma_eff[t] = g_phy * g_num / (g_phy + g_num);
-}
-
-// fixed-order two-stage sums: wave shuffle -> the four waves of a block -> one partial row of 8 per block -> k_dy_sum_final in one block
-__device__ __forceinline__ void dy_block_store(const double s[8], const int ns, double *__restrict__ partials)
-{
-    __shared__ double sm[8][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c = 0; c < ns; c++) {
-        const double w = wave_sum(s[c]);
-        if (lane == 0) sm[c][wave] = w;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < 8) {
-        const int c = threadIdx.x;
-        partials[blockIdx.x * 8 + c] = c < ns ? (sm[c][0] + sm[c][1]) + (sm[c][2] + sm[c][3]) : 0.0;
-    }
-}
-__global__ __launch_bounds__(256) void k_dy_sum_final(const double *__restrict__ partials, const int nblocks, double *__restrict__ out)
-{
-    __shared__ double sm[8][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < 8; c++) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < nblocks; b += blockDim.x) s += partials[b * 8 + c];
-        s = wave_sum(s);
-        if (lane == 0) sm[c][wave] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        const int c = threadIdx.x;
-        out[c] = (sm[c][0] + sm[c][1]) + (sm[c][2] + sm[c][3]);
-    }
-}
-// Σ η and the count over the finite entries
-__global__ __launch_bounds__(256) void k_dy_eta_sum(const double *__restrict__ eta, const int n, double *__restrict__ partials)
-{
-    double s[8] = {};
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
-        const double e = eta[t];
-        if (!isinf(e)) { s[0] += e; s[1] += 1.0; }
-    }
-    dy_block_store(s, 2, partials);
-}
-// the Powell-Hestenes norms (solver.jl:151-152): Σ Rx², Σ Ry², Σ RP² over the whole arrays
-__global__ __launch_bounds__(256) void k_dy_ph_sums(const double *__restrict__ Rx, const double *__restrict__ Ry, const double *__restrict__ RP, const int nx,
-                                                    const int ny, double *__restrict__ partials)
-{
-    double s[8] = {};
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < nx * ny; t += gridDim.x * blockDim.x) {
-        if (t < (nx - 1) * ny) { const double v = Rx[t]; s[0] += v * v; }
-        if (t < nx * (ny - 1)) { const double v = Ry[t]; s[1] += v * v; }
-        const double v = RP[t];
-        s[2] += v * v;
-    }
-    dy_block_store(s, 3, partials);
-}
-// the residual check of the inner loop (solver.jl:231,251, :359-365): compute_dV!, then Σ (D R)² per component, Σ dV (R - R0) and Σ dV² per component
-__global__ __launch_bounds__(256) void k_dy_check_sums(const jrx_dyrel2d_fields d, const double *__restrict__ Rx, const double *__restrict__ Ry, const int nxn,
-                                                       const int nyn, double *__restrict__ partials)
-{
-    double s[8] = {};
-    const int n = nxn > nyn ? nxn : nyn;
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
-        if (t < nxn) {
-            const double R = Rx[t], DR = d.Dx[t] * R, dV = d.dVxdtau[t] * d.betaVx[t] * d.dtauVx[t];
-            d.dVx[t] = dV;
-            s[0] += DR * DR; s[2] += dV * (R - d.Rx0[t]); s[4] += dV * dV;
-        }
-        if (t < nyn) {
-            const double R = Ry[t], DR = d.Dy[t] * R, dV = d.dVydtau[t] * d.betaVy[t] * d.dtauVy[t];
-            d.dVy[t] = dV;
-            s[1] += DR * DR; s[3] += dV * (R - d.Ry0[t]); s[5] += dV * dV;
-        }
-    }
-    dy_block_store(s, 6, partials);
-}
-// update_cV! (velocity_kernels.jl:642-654)
-__global__ __launch_bounds__(256) void k_dy_fill2(double *__restrict__ a0, const int n0, double *__restrict__ a1, const int n1, const double v)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n0) a0[t] = v;
-    if (t < n1) a1[t] = v;
-}
-// @. P += γ_eff * RP (solver.jl:264)
-__global__ __launch_bounds__(256) void k_dy_add_P(double *__restrict__ P, const double *__restrict__ gam, const double *__restrict__ RP, const int n)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n) P[t] = P[t] + gam[t] * RP[t];
-}
 // the epilogue (solver.jl:269-286): P += ΔPψ, compute_∇V!, compute_vorticity!, shear2center! of ε, ε_pl, Δε, accumulate_tensor!, accumulate_vol!
 __global__ __launch_bounds__(256) void k_dy_epilogue(const DyArgs a)
 {
@@ -406,109 +284,122 @@ jrx_status dy_check(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_dyrel2d_
     return JRX_OK;
 }
 
-DyArgs dy_make(const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rheology *rh, const jrx_vep2d_params *p)
-{
+// the launches of this file's kernels on the handle's stream: what the entry points below call, and the launch object of dy_solve (dyrel_common.hpp)
+struct Dy2 {
+    typedef DyArgs Args;
+    static constexpr int ND = 2, MAXBLK = 1024;      // partial rows of 8: half of kMaxRedBlocks rows of 4
+    jrx_handle *h;
+    hipStream_t s;
     DyArgs a;
-    memset(&a, 0, sizeof(a));
-    a.f = *f; a.d = *d;
-    if (rh) a.rh = *rh;
-    a._dx = p->_dx; a._dy = p->_dy; a.dt = p->dt;
-    a.nx = (int)p->nx; a.ny = (int)p->ny;
-    a.fs = p->free_slip; a.ns = p->no_slip;
-    a.tg = p->T_ghosted != 0;
-    a.rel = 1.0; a.nu = 1.0e-2; a.cut_lo = -INFINITY; a.cut_hi = INFINITY;
-    return a;
-}
-DyMom dy_mom(const DyArgs &a, const double *th)
-{
-    return DyMom{a.f.P, th, a.f.txx, a.f.tyy, a.f.txy, a.f.fx, a.f.fy, a._dx, a._dy, a.nx, a.ny};
-}
-DyUpd dy_upd(const DyArgs &a)
-{
-    const jrx_dyrel2d_fields &d = a.d;
-    return DyUpd{a.f.Rx, a.f.Ry, a.f.Vx, a.f.Vy, d.dVxdtau, d.dVydtau, d.Dx, d.Dy, d.alphaVx, d.alphaVy, d.betaVx, d.betaVy, d.dtauVx, d.dtauVy, a.fs, a.ns};
-}
-bool dy_has(std::initializer_list<const void *> req)
-{
-    for (const void *q : req)
-        if (!q) return false;
-    return true;
-}
-#define DY_REQ(h, what, ...) \
-    if (!dy_has({__VA_ARGS__})) return jrx_fail(h, JRX_ERR_ARG, "%s: a required field pointer is NULL", what)
-#define DY_LAUNCH(h) \
-    do { (h)->stat_dyrel_launches++; JRX_LAUNCH_CHECK(h); } while (0)
+    double dofs[2], pdof;      // velocity_dofs(Val(2)), pressure_dof (solver.jl:349-357)
+    bool bcs_applied = false;      // flow_bcs! has run in full on V since the solve began
 
-inline unsigned dy_gv(const DyArgs &a) { return (unsigned)(((a.nx + 1) * (a.ny + 1) + 255) / 256); }
-inline unsigned dy_gc(const DyArgs &a) { return (unsigned)((a.nx * a.ny + 255) / 256); }
-inline int dy_nblk(const DyArgs &a) { const unsigned g = (dy_gc(a) + 7) / 8; return (int)(g < 1 ? 1 : (g > 1024 ? 1024 : g)); }      // partial rows of 8: half of kMaxRedBlocks rows of 4
-
-jrx_status dy_strain_rp(jrx_handle *h, hipStream_t s, const DyArgs &a, bool strain)
-{
-    if (strain) hipLaunchKernelGGL(k_dy_strain_rp<true>, dim3(dy_gv(a)), dim3(256), 0, s, a.f.exx, a.f.eyy, a.f.exy, (const double *)a.f.Vx, (const double *)a.f.Vy,
-                                   a.f.RP, (const double *)a.f.P, (const double *)a.f.P0, (const double *)a.f.Q, (const double *)a.d.etab, a._dx, a._dy, a.dt, a.nx, a.ny);
-    else hipLaunchKernelGGL(k_dy_strain_rp<false>, dim3(dy_gv(a)), dim3(256), 0, s, a.f.exx, a.f.eyy, a.f.exy, (const double *)a.f.Vx, (const double *)a.f.Vy,
-                            a.f.RP, (const double *)a.f.P, (const double *)a.f.P0, (const double *)a.f.Q, (const double *)a.d.etab, a._dx, a._dy, a.dt, a.nx, a.ny);
-    DY_LAUNCH(h);
-    return JRX_OK;
-}
-jrx_status dy_stress(jrx_handle *h, hipStream_t s, const DyArgs &a, bool lin)
-{
-    const bool soft = mat_has_softening(&a.rh);
-    if (soft) {
-        if (lin) hipLaunchKernelGGL((k_dy_stress<true, true>), dim3(dy_gv(a)), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_dy_stress<true, false>), dim3(dy_gv(a)), dim3(256), 0, s, a);
-    } else {
-        if (lin) hipLaunchKernelGGL((k_dy_stress<false, true>), dim3(dy_gv(a)), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_dy_stress<false, false>), dim3(dy_gv(a)), dim3(256), 0, s, a);
+    Dy2(jrx_handle *h_, const jrx_vep2d_fields *f, const jrx_dyrel2d_fields *d, const jrx_rheology *rh, const jrx_vep2d_params *p) : h(h_), s(h_->stream)
+    {
+        memset(&a, 0, sizeof(a));
+        a.f = *f; a.d = *d;
+        if (rh) a.rh = *rh;
+        a._dx = p->_dx; a._dy = p->_dy; a.dt = p->dt;
+        a.nx = (int)p->nx; a.ny = (int)p->ny;
+        a.fs = p->free_slip; a.ns = p->no_slip;
+        a.tg = p->T_ghosted != 0;
+        a.rel = 1.0; a.nu = 1.0e-2; a.cut_lo = -INFINITY; a.cut_hi = INFINITY;
+        dofs[0] = (double)((p->nxg - 2) * (p->nyg - 1)); dofs[1] = (double)((p->nxg - 1) * (p->nyg - 2));
+        pdof = (double)(p->nxg * p->nyg);
     }
-    DY_LAUNCH(h);
-    return JRX_OK;
-}
-jrx_status dy_gershgorin(jrx_handle *h, hipStream_t s, const DyArgs &a)
-{
-    hipLaunchKernelGGL(k_dy_gershgorin, dim3(dy_gc(a)), dim3(256), 0, s, a);
-    DY_LAUNCH(h);
-    return JRX_OK;
-}
-jrx_status dy_dtau(jrx_handle *h, hipStream_t s, const DyArgs &a, double CFL, bool from_lmax)
-{
-    const int nxn = (a.nx - 1) * a.ny, nyn = a.nx * (a.ny - 1);
-    const unsigned g = (unsigned)(((nxn > nyn ? nxn : nyn) + 255) / 256);
-    if (from_lmax) hipLaunchKernelGGL(k_dy_dtau<true>, dim3(g), dim3(256), 0, s, a.d, CFL, nxn, nyn);
-    else hipLaunchKernelGGL(k_dy_dtau<false>, dim3(g), dim3(256), 0, s, a.d, CFL, nxn, nyn);
-    DY_LAUNCH(h);
-    return JRX_OK;
-}
-jrx_status dy_bulk(jrx_handle *h, hipStream_t s, const DyArgs &a, double gamma_fact)
-{
-    const int nb = dy_nblk(a);
-    hipLaunchKernelGGL(k_dy_eta_sum, dim3(nb), dim3(256), 0, s, (const double *)a.f.eta, a.nx * a.ny, h->d_partials);
-    DY_LAUNCH(h);
-    hipLaunchKernelGGL(k_dy_sum_final, dim3(1), dim3(256), 0, s, (const double *)h->d_partials, nb, h->d_sums);
-    DY_LAUNCH(h);
-    hipLaunchKernelGGL(k_dy_bulk, dim3(dy_gc(a)), dim3(256), 0, s, a, (const double *)h->d_sums, gamma_fact);
-    DY_LAUNCH(h);
-    return JRX_OK;
-}
-// DYREL! (constructors.jl:178-190)
-jrx_status dy_init(jrx_handle *h, hipStream_t s, const DyArgs &a, double CFL, double gamma_fact)
-{
-    JRX_TRY(dy_bulk(h, s, a, gamma_fact));
-    JRX_TRY(dy_gershgorin(h, s, a));
-    return dy_dtau(h, s, a, CFL, true);
-}
-// the sums of one reduction kernel, read on the host: the one synchronisation of a check
-jrx_status dy_read_sums(jrx_handle *h, hipStream_t s, int nb, int count)
-{
-    hipLaunchKernelGGL(k_dy_sum_final, dim3(1), dim3(256), 0, s, (const double *)h->d_partials, nb, h->d_sums);
-    DY_LAUNCH(h);
-    JRX_HIP(h, hipMemcpyAsync(h->h_sums, h->d_sums, count * sizeof(double), hipMemcpyDeviceToHost, s));
-    JRX_HIP(h, hipStreamSynchronize(s));
-    return JRX_OK;
-}
+    int cells() const { return a.nx * a.ny; }
+    dim3 gv() const { return dim3(dy_g1((a.nx + 1) * (a.ny + 1))); }
+    dim3 gc() const { return dim3(dy_g1(cells())); }
+    DyMom mom(const double *th) const { return DyMom{a.f.P, th, a.f.txx, a.f.tyy, a.f.txy, a.f.fx, a.f.fy, a._dx, a._dy, a.nx, a.ny}; }
+    DyUpd upd() const
+    {
+        const jrx_dyrel2d_fields &d = a.d;
+        return DyUpd{a.f.Rx, a.f.Ry, a.f.Vx, a.f.Vy, d.dVxdtau, d.dVydtau, d.Dx, d.Dy, d.alphaVx, d.alphaVy, d.betaVx, d.betaVy, d.dtauVx, d.dtauVy, a.fs, a.ns};
+    }
+    DyDof<2> dof() const
+    {
+        const jrx_dyrel2d_fields &d = a.d;
+        const int nxn = (a.nx - 1) * a.ny, nyn = a.nx * (a.ny - 1);
+        return DyDof<2>{{a.f.Rx, a.f.Ry}, {d.Rx0, d.Ry0}, {d.Dx, d.Dy}, {d.lmaxVx, d.lmaxVy}, {d.dVxdtau, d.dVydtau}, {d.dtauVx, d.dtauVy}, {d.dVx, d.dVy},
+                        {d.betaVx, d.betaVy}, {d.cVx, d.cVy}, {d.alphaVx, d.alphaVy}, {nxn, nyn}, nxn > nyn ? nxn : nyn};
+    }
 
-#define DY_FIELDS_STRESS(f, d)                                                                                                                                   \
+    jrx_status strain_rp(bool strain) const
+    {
+        if (strain) hipLaunchKernelGGL(k_dy_strain_rp<true>, gv(), dim3(256), 0, s, a.f.exx, a.f.eyy, a.f.exy, (const double *)a.f.Vx, (const double *)a.f.Vy,
+                                       a.f.RP, (const double *)a.f.P, (const double *)a.f.P0, (const double *)a.f.Q, (const double *)a.d.etab, a._dx, a._dy, a.dt, a.nx, a.ny);
+        else hipLaunchKernelGGL(k_dy_strain_rp<false>, gv(), dim3(256), 0, s, a.f.exx, a.f.eyy, a.f.exy, (const double *)a.f.Vx, (const double *)a.f.Vy,
+                                a.f.RP, (const double *)a.f.P, (const double *)a.f.P0, (const double *)a.f.Q, (const double *)a.d.etab, a._dx, a._dy, a.dt, a.nx, a.ny);
+        DY_LAUNCH(h);
+        return JRX_OK;
+    }
+    jrx_status stress(bool lin) const
+    {
+        const bool soft = mat_has_softening(&a.rh);
+        if (soft) {
+            if (lin) hipLaunchKernelGGL((k_dy_stress<true, true>), gv(), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((k_dy_stress<true, false>), gv(), dim3(256), 0, s, a);
+        } else {
+            if (lin) hipLaunchKernelGGL((k_dy_stress<false, true>), gv(), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((k_dy_stress<false, false>), gv(), dim3(256), 0, s, a);
+        }
+        DY_LAUNCH(h);
+        return JRX_OK;
+    }
+    jrx_status ph_residual() const
+    {
+        hipLaunchKernelGGL(k_dy_ph_residual, gc(), dim3(256), 0, s, mom(a.d.dPpsi), a.f.Rx, a.f.Ry);
+        DY_LAUNCH(h);
+        return JRX_OK;
+    }
+    jrx_status copy_old_residual() const
+    {
+        const DyDof<2> q = dof();
+        hipLaunchKernelGGL(k_copy6, dim3(256), dim3(256), 0, s, q.R0[0], (const double *)q.R[0], (i64)q.n[0], q.R0[1], (const double *)q.R[1], (i64)q.n[1],
+                           (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr,
+                           (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0);
+        DY_LAUNCH(h);
+        return JRX_OK;
+    }
+    // BCF: flow_bcs! in full the first time; afterwards the update kernel refreshes the ghosts of the nodes it moves
+    jrx_status update(bool BCF) const
+    {
+        if (BCF) hipLaunchKernelGGL(k_dy_update<true>, gc(), dim3(256), 0, s, mom(a.d.P_num), upd());
+        else hipLaunchKernelGGL(k_dy_update<false>, gc(), dim3(256), 0, s, mom(a.d.P_num), upd());
+        DY_LAUNCH(h);
+        return JRX_OK;
+    }
+    jrx_status update_V(bool, bool)
+    {
+        JRX_TRY(update(bcs_applied));
+        if (!bcs_applied) { JRX_TRY(jrx2d_bcs(h, s, a.f.Vx, a.f.Vy, a.nx, a.ny, a.fs, a.ns, 0)); bcs_applied = true; }
+        return JRX_OK;
+    }
+    jrx_status gershgorin() const
+    {
+        hipLaunchKernelGGL(k_dy_gershgorin, gc(), dim3(256), 0, s, a);
+        DY_LAUNCH(h);
+        return JRX_OK;
+    }
+    jrx_status rhog() const      // ρg[end] = ρg y
+    {
+        const int64_t nn[3] = {a.nx, a.ny, 1}, tdim[3] = {a.tg ? a.nx + 2 : a.nx, a.tg ? a.ny + 2 : a.ny, 1};
+        return jrx_compute_rhog(h, a.f.fy, &a.rh, a.f.phase_c, a.f.T, a.f.P, nn, tdim, 2);
+    }
+    jrx_status epilogue() const
+    {
+        const i64 n = cells(), nv = (i64)(a.nx + 1) * (a.ny + 1);
+        hipLaunchKernelGGL(k_dy_epilogue, gv(), dim3(256), 0, s, a);
+        DY_LAUNCH(h);
+        hipLaunchKernelGGL(k_copy6, dim3(256), dim3(256), 0, s, a.f.toxx, (const double *)a.f.txx, n, a.f.toyy, (const double *)a.f.tyy, n, a.f.toxy,
+                           (const double *)a.f.txy, nv, a.f.toxy_c, (const double *)a.f.txy_c, n, a.d.toxx_v, (const double *)a.d.txx_v, nv, a.d.toyy_v,
+                           (const double *)a.d.tyy_v, nv);
+        DY_LAUNCH(h);
+        return JRX_OK;
+    }
+};
+
+#define DY_FIELDS_STRESS(f, d)                                                                                                                                  \
     (f)->P, (f)->exx, (f)->eyy, (f)->exy, (f)->eplxx, (f)->eplyy, (f)->eplxy, (f)->txx, (f)->tyy, (f)->txy, (f)->txy_c, (f)->tII, (f)->toxx, (f)->toyy, (f)->toxy,  \
         (f)->toxy_c, (f)->eta, (f)->eta_v, (f)->eta_vep, (f)->EII_pl, (f)->evol_pl, (f)->RP, (f)->phase_c, (f)->phase_v, (d)->txx_v, (d)->tyy_v, (d)->toxx_v,       \
         (d)->toyy_v, (d)->lambda, (d)->lambda_v, (d)->dPpsi, (d)->P_num, (d)->gamma_eff
@@ -525,8 +416,7 @@ jrx_status jrx_dyrel2d_strain_rate_RP(jrx_handle *h, const jrx_vep2d_fields *f, 
 {
     JRX_TRY(dy_check(h, f, d, nullptr, nullptr, p));
     DY_REQ(h, "compute_∇V_strain_rate_RP!", f->exx, f->eyy, f->exy, f->Vx, f->Vy, f->RP, f->P, f->P0, f->Q, d->etab);
-    const DyArgs a = dy_make(f, d, nullptr, p);
-    JRX_TRY(dy_strain_rp(h, h->stream, a, do_strain_rate != 0));
+    JRX_TRY(Dy2(h, f, d, nullptr, p).strain_rp(do_strain_rate != 0));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -537,9 +427,9 @@ jrx_status jrx_dyrel2d_stress_viscosity(jrx_handle *h, const jrx_vep2d_fields *f
     JRX_TRY(dy_check(h, f, d, nullptr, rh, p));
     if (!rh || !dp) return jrx_fail(h, JRX_ERR_ARG, "DYREL: null argument");
     DY_REQ(h, "compute_stress_viscosity_DRYEL!", DY_FIELDS_STRESS(f, d));
-    DyArgs a = dy_make(f, d, rh, p);
-    a.rel = lambda_relaxation; a.nu = dp->viscosity_relaxation; a.cut_lo = dp->cutoff_lo; a.cut_hi = dp->cutoff_hi;
-    JRX_TRY(dy_stress(h, h->stream, a, dp->linear_viscosity != 0));
+    Dy2 o(h, f, d, rh, p);
+    o.a.rel = lambda_relaxation; o.a.nu = dp->viscosity_relaxation; o.a.cut_lo = dp->cutoff_lo; o.a.cut_hi = dp->cutoff_hi;
+    JRX_TRY(o.stress(dp->linear_viscosity != 0));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -548,9 +438,7 @@ jrx_status jrx_dyrel2d_PH_residual(jrx_handle *h, const jrx_vep2d_fields *f, con
 {
     JRX_TRY(dy_check(h, f, d, nullptr, nullptr, p));
     DY_REQ(h, "compute_PH_residual_V!", DY_FIELDS_MOM(f), d->dPpsi);
-    const DyArgs a = dy_make(f, d, nullptr, p);
-    hipLaunchKernelGGL(k_dy_ph_residual, dim3(dy_gc(a)), dim3(256), 0, h->stream, dy_mom(a, d->dPpsi), f->Rx, f->Ry);
-    DY_LAUNCH(h);
+    JRX_TRY(Dy2(h, f, d, nullptr, p).ph_residual());
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -560,9 +448,7 @@ jrx_status jrx_dyrel2d_DR_residual_update_V(jrx_handle *h, const jrx_vep2d_field
     JRX_TRY(dy_check(h, f, d, nullptr, nullptr, p));
     DY_REQ(h, "compute_DR_residual_update_V!", DY_FIELDS_MOM(f), f->Vx, f->Vy, d->P_num, d->Dx, d->Dy, d->dVxdtau, d->dVydtau, d->alphaVx, d->alphaVy, d->betaVx,
            d->betaVy, d->dtauVx, d->dtauVy);
-    const DyArgs a = dy_make(f, d, nullptr, p);
-    hipLaunchKernelGGL(k_dy_update<false>, dim3(dy_gc(a)), dim3(256), 0, h->stream, dy_mom(a, d->P_num), dy_upd(a));
-    DY_LAUNCH(h);
+    JRX_TRY(Dy2(h, f, d, nullptr, p).update(false));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -572,8 +458,7 @@ jrx_status jrx_dyrel2d_gershgorin(jrx_handle *h, const jrx_vep2d_fields *f, cons
     JRX_TRY(dy_check(h, f, d, nullptr, rh, p));
     if (!rh) return jrx_fail(h, JRX_ERR_ARG, "DYREL: null argument");
     DY_REQ(h, "Gershgorin_Stokes2D_SchurComplement!", f->eta, f->eta_v, f->phase_c, f->phase_v, d->gamma_eff, d->Dx, d->Dy, d->lmaxVx, d->lmaxVy);
-    const DyArgs a = dy_make(f, d, rh, p);
-    JRX_TRY(dy_gershgorin(h, h->stream, a));
+    JRX_TRY(Dy2(h, f, d, rh, p).gershgorin());
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -584,8 +469,7 @@ jrx_status jrx_dyrel2d_update_dtauV_alpha_beta(jrx_handle *h, const jrx_dyrel2d_
     memset(&none, 0, sizeof(none));
     JRX_TRY(dy_check(h, &none, d, nullptr, nullptr, p));
     DY_REQ(h, "update_dτV_α_β!", d->dtauVx, d->dtauVy, d->betaVx, d->betaVy, d->alphaVx, d->alphaVy, d->cVx, d->cVy, d->lmaxVx, d->lmaxVy);
-    const DyArgs a = dy_make(&none, d, nullptr, p);
-    JRX_TRY(dy_dtau(h, h->stream, a, CFL, from_lambda_max != 0));
+    JRX_TRY(dy_dtau(Dy2(h, &none, d, nullptr, p), CFL, from_lambda_max != 0));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -596,8 +480,7 @@ jrx_status jrx_dyrel2d_bulk_viscosity_and_penalty(jrx_handle *h, const jrx_vep2d
     JRX_TRY(dy_check(h, f, d, nullptr, rh, p));
     if (!rh) return jrx_fail(h, JRX_ERR_ARG, "DYREL: null argument");
     DY_REQ(h, "compute_bulk_viscosity_and_penalty!", f->eta, f->phase_c, d->etab, d->gamma_eff);
-    const DyArgs a = dy_make(f, d, rh, p);
-    JRX_TRY(dy_bulk(h, h->stream, a, gamma_fact));
+    JRX_TRY(dy_bulk(Dy2(h, f, d, rh, p), gamma_fact));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -608,8 +491,7 @@ jrx_status jrx_dyrel2d_init(jrx_handle *h, const jrx_vep2d_fields *f, const jrx_
     JRX_TRY(dy_check(h, f, d, phi, rh, p));
     if (!rh || !dp) return jrx_fail(h, JRX_ERR_ARG, "DYREL: null argument");
     DY_REQ(h, "DYREL!", f->eta, f->eta_v, f->phase_c, f->phase_v, d->gamma_eff, d->etab, DY_FIELDS_DAMP(d));
-    const DyArgs a = dy_make(f, d, rh, p);
-    JRX_TRY(dy_init(h, h->stream, a, dp->CFL, dp->gamma_fact));
+    JRX_TRY(dy_init(Dy2(h, f, d, rh, p), dp->CFL, dp->gamma_fact));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -622,14 +504,10 @@ jrx_status jrx_dyrel2d_solve(jrx_handle *h, const jrx_vep2d_fields *f, const jrx
     if (dp->nout < 1) return jrx_fail(h, JRX_ERR_ARG, "nout must be >= 1");
     DY_REQ(h, "solve_DYREL!", DY_FIELDS_STRESS(f, d), DY_FIELDS_MOM(f), DY_FIELDS_DAMP(d), f->P0, f->divV, f->Q, f->Vx, f->Vy, f->eplxy_c, f->EVol_pl, d->etab);
     if (mat_viscosity_reads_invariant(rh) && !f->exy_c) return jrx_fail(h, JRX_ERR_ARG, "a power-law creep needs ε.xy_c for compute_viscosity!");
-    hipStream_t s = h->stream;
-    DyArgs a = dy_make(f, d, rh, p);
-    a.nu = dp->viscosity_relaxation; a.cut_lo = dp->cutoff_lo; a.cut_hi = dp->cutoff_hi;
-    const int nx = a.nx, ny = a.ny;
-    const size_t n = (size_t)nx * ny, nv = (size_t)(nx + 1) * (ny + 1), nxn = (size_t)(nx - 1) * ny, nyn = (size_t)nx * (ny - 1);
-    const bool lin = dp->linear_viscosity != 0;
-    const int nb = dy_nblk(a);
-    const double EPS = 2.220446049250313e-16;
+    Dy2 o(h, f, d, rh, p);
+    o.a.nu = dp->viscosity_relaxation; o.a.cut_lo = dp->cutoff_lo; o.a.cut_hi = dp->cutoff_hi;
+    hipStream_t s = o.s;
+    const size_t n = (size_t)o.cells(), nv = (size_t)(o.a.nx + 1) * (o.a.ny + 1);
 
     // solver.jl:86-95: P0 <- P, @tensor_center(ε_pl) = 0, λ = λv = 0
     JRX_HIP(h, hipMemcpyAsync(f->P0, f->P, n * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -639,113 +517,12 @@ jrx_status jrx_dyrel2d_solve(jrx_handle *h, const jrx_vep2d_fields *f, const jrx
     JRX_HIP(h, hipMemsetAsync(d->lambda, 0, n * sizeof(double), s));
     JRX_HIP(h, hipMemsetAsync(d->lambda_v, 0, nv * sizeof(double), s));
     JRX_HIP(h, hipEventRecord(h->ev[6], s));
-    {   // :117-119: compute_viscosity! (relaxation 1, the strain-rate invariant), compute_ρg!(ρg[end], ...), DYREL!
+    {   // :117: compute_viscosity! (relaxation 1, the strain-rate invariant)
         jrx_vep2d_params pv = *p;
         pv.cutoff_lo = dp->cutoff_lo; pv.cutoff_hi = dp->cutoff_hi;
         JRX_TRY(jrx_vep2d_compute_viscosity(h, f, rh, &pv, 1.0));
     }
-    const int64_t nn[3] = {nx, ny, 1}, tdim[3] = {a.tg ? nx + 2 : nx, a.tg ? ny + 2 : ny, 1};
-    if (rh->has_density) JRX_TRY(jrx_compute_rhog(h, f->fy, rh, f->phase_c, f->T, f->P, nn, tdim, 2));
-    JRX_TRY(dy_init(h, s, a, dp->CFL, dp->gamma_fact));
-    const bool rho_loop = rh->has_density && !mat_density_is_constant(rh);
-
-    double err = 2 * dp->eps, err_min = INFINITY, errV0[2] = {1.0, 1.0}, errPt0 = 1.0, errV00 = 1.0, errPt = 1.0, rel_drop = dp->rel_drop;
-    int64_t iter = 0, cont = 0, itPH_done = 0;
-    bool bcs_applied = false;
-    jrx_status bad = JRX_OK;
-    for (int64_t itPH = 1; itPH <= 1000; itPH++) {
-        itPH_done = itPH;
-        if (rho_loop) JRX_TRY(jrx_compute_rhog(h, f->fy, rh, f->phase_c, f->T, f->P, nn, tdim, 2));      // update_ρg! :124
-        JRX_TRY(dy_strain_rp(h, s, a, true));
-        a.rel = dp->lambda_relaxation_PH;
-        JRX_TRY(dy_stress(h, s, a, lin));
-        hipLaunchKernelGGL(k_dy_ph_residual, dim3(dy_gc(a)), dim3(256), 0, s, dy_mom(a, d->dPpsi), f->Rx, f->Ry);
-        DY_LAUNCH(h);
-        hipLaunchKernelGGL(k_dy_ph_sums, dim3(nb), dim3(256), 0, s, (const double *)f->Rx, (const double *)f->Ry, (const double *)f->RP, nx, ny, h->d_partials);
-        DY_LAUNCH(h);
-        JRX_TRY(dy_read_sums(h, s, nb, 3));      // the host read of this Powell-Hestenes iteration
-        const double errV[2] = {sqrt(h->h_sums[0]) / sqrt((double)((p->nxg - 2) * (p->nyg - 1))), sqrt(h->h_sums[1]) / sqrt((double)((p->nxg - 1) * (p->nyg - 2)))};
-        errPt = sqrt(h->h_sums[2]) / sqrt((double)(p->nxg * p->nyg));
-        if (itPH == 1) { errV0[0] = errV[0] + EPS; errV0[1] = errV[1] + EPS; errPt0 = errPt + EPS; }
-        if (itPH == 2) errPt0 = errPt + EPS;
-        const double e0 = fmin(errV[0] / errV0[0], errV[0]), e1 = fmin(errV[1] / errV0[1], errV[1]), e2 = fmin(errPt / errPt0, errPt);
-        err = fmax(e0, fmax(e1, e2));
-        if (std::isnan(e0) || std::isnan(e1) || std::isnan(e2)) err = NAN;
-        if (dp->verbose_PH)
-            printf("itPH = %02lld iter = %06lld iter/nx = %03lld, err = %1.3e - norm[R1=%1.3e %1.3e, R2=%1.3e %1.3e, Rp=%1.3e %1.3e] \n", (long long)itPH, (long long)iter,
-                   (long long)(iter / nx), err, errV[0], errV[0] / errV0[0], errV[1], errV[1] / errV0[1], errPt, errPt / errPt0);
-        if (std::isnan(err)) { bad = jrx_fail(h, JRX_ERR_NAN, "NaN detected in outer loop"); break; }
-        if (err > 1.0e10) { bad = jrx_fail(h, JRX_ERR_NAN, "Kaboom! Error > 1e10 in outer loop"); break; }
-        if (err < dp->eps) break;
-        if (err > err_min * 1.05) rel_drop = fmax(rel_drop * 0.1, 1.0e-3);
-        if (err_min > err) err_min = err;
-        const double eps_vel = err * rel_drop;
-        int64_t itPT = 0;
-        a.rel = dp->lambda_relaxation_DR;
-        while (err > eps_vel && itPT <= dp->iterMax) {
-            itPT++; iter++;
-            const bool check = iter % dp->nout == 0;
-            if (check) {      // pseudo-old residuals :191
-                hipLaunchKernelGGL(k_copy6, dim3(256), dim3(256), 0, s, d->Rx0, (const double *)f->Rx, (i64)nxn, d->Ry0, (const double *)f->Ry, (i64)nyn,
-                                   (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr,
-                                   (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0);
-                DY_LAUNCH(h);
-            }
-            JRX_TRY(dy_strain_rp(h, s, a, true));
-            JRX_TRY(dy_stress(h, s, a, lin));
-            // flow_bcs! in full the first time; afterwards the update kernel refreshes the ghosts of the nodes it moves
-            if (bcs_applied) hipLaunchKernelGGL(k_dy_update<true>, dim3(dy_gc(a)), dim3(256), 0, s, dy_mom(a, d->P_num), dy_upd(a));
-            else hipLaunchKernelGGL(k_dy_update<false>, dim3(dy_gc(a)), dim3(256), 0, s, dy_mom(a, d->P_num), dy_upd(a));
-            DY_LAUNCH(h);
-            if (!bcs_applied) { JRX_TRY(jrx2d_bcs(h, s, f->Vx, f->Vy, nx, ny, p->free_slip, p->no_slip, 0)); bcs_applied = true; }
-            if (check) {
-                hipLaunchKernelGGL(k_dy_check_sums, dim3(nb), dim3(256), 0, s, a.d, (const double *)f->Rx, (const double *)f->Ry, (int)nxn, (int)nyn, h->d_partials);
-                DY_LAUNCH(h);
-                JRX_TRY(dy_read_sums(h, s, nb, 6));      // the host read of these nout iterations
-                const double *S = h->h_sums;
-                const double eV0 = sqrt(S[0]) / sqrt((double)((p->nxg - 2) * (p->nyg - 1))), eV1 = sqrt(S[1]) / sqrt((double)((p->nxg - 1) * (p->nyg - 2)));
-                if (iter == dp->nout) errV00 = fmax(eV0, eV1) + EPS;
-                err = fmax(eV0 / errV00, eV1 / errV00);
-                if (std::isnan(eV0) || std::isnan(eV1)) err = NAN;
-                if (cont < res->cap) {
-                    if (res->err_evo_tot) res->err_evo_tot[cont] = err;
-                    if (res->err_evo_V) res->err_evo_V[cont] = err;
-                    if (res->err_evo_P) res->err_evo_P[cont] = errPt / errPt0;
-                    if (res->err_evo_it) res->err_evo_it[cont] = (double)iter;
-                }
-                cont++;
-                if (std::isnan(err)) { bad = jrx_fail(h, JRX_ERR_NAN, "NaN detected in inner loop"); break; }
-                if (dp->verbose_DR) printf("it = %lld, iter = %lld, err = %1.3e \n", (long long)itPT, (long long)iter, err);
-                const double lmin = fabs(S[2] + S[3]) / (S[4] + S[5]);      // compute_λminV! :359-365
-                const double cV = 2 * sqrt(lmin) * dp->c_fact;
-                hipLaunchKernelGGL(k_dy_fill2, dim3((unsigned)(((nxn > nyn ? nxn : nyn) + 255) / 256)), dim3(256), 0, s, d->cVx, (int)nxn, d->cVy, (int)nyn, cV);
-                DY_LAUNCH(h);
-                JRX_TRY(dy_gershgorin(h, s, a));
-                JRX_TRY(dy_dtau(h, s, a, dp->CFL, true));
-            }
-        }
-        if (bad != JRX_OK) break;
-        JRX_TRY(dy_strain_rp(h, s, a, false));      // update pressure :263-264
-        hipLaunchKernelGGL(k_dy_add_P, dim3(dy_gc(a)), dim3(256), 0, s, f->P, (const double *)d->gamma_eff, (const double *)f->RP, (int)n);
-        DY_LAUNCH(h);
-        if (iter > dp->total_iterMax) break;
-    }
-    JRX_HIP(h, hipEventRecord(h->ev[7], s));
-    if (bad == JRX_OK) {      // epilogue :269-290
-        hipLaunchKernelGGL(k_dy_epilogue, dim3(dy_gv(a)), dim3(256), 0, s, a);
-        DY_LAUNCH(h);
-        hipLaunchKernelGGL(k_copy6, dim3(256), dim3(256), 0, s, f->toxx, (const double *)f->txx, (i64)n, f->toyy, (const double *)f->tyy, (i64)n, f->toxy,
-                           (const double *)f->txy, (i64)nv, f->toxy_c, (const double *)f->txy_c, (i64)n, d->toxx_v, (const double *)d->txx_v, (i64)nv, d->toyy_v,
-                           (const double *)d->tyy_v, (i64)nv);
-        DY_LAUNCH(h);
-    }
-    JRX_HIP(h, hipStreamSynchronize(s));
-    float ms = 0.f;
-    JRX_HIP(h, hipEventElapsedTime(&ms, h->ev[6], h->ev[7]));
-    res->iter = iter; res->itPH = itPH_done;
-    res->nchecks = cont < res->cap ? cont : res->cap;
-    res->time_s = ms * 1e-3;
-    return bad;
+    return dy_solve(o, dp, res);
 }
 
 }   // extern "C"

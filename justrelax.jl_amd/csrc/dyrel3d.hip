@@ -1,9 +1,9 @@
 // dyrel3d.hip -- 3D DYREL (self-tuned dynamic relaxation inside Powell-Hestenes pressure iterations) for gfx950: kernels, per-kernel entry points, driver.
 //
-// Reference (PTsolvers/JustRelax.jl).  Restated: src/DYREL/constructors.jl:61-111 (the 3D allocator), :178-190 (DYREL!), :230-254 (compute_bulk_viscosity_and_penalty!),
-// solver.jl:44-294 (_solve_DYREL!), :329-365 (dyrel_fields(Val(3)), velocity_dofs, pressure_dof, compute_λminV!), velocity_kernels.jl:242-322
-// (compute_∇V_strain_rate_RP! 3D), :441-477 (compute_PH_residual_V! 3D), :625-663 (compute_dV!, update_cV!, damped_update_V), :729-828 (compute_DR_residual_update_V! 3D),
-// Gershgorin.jl:171-310 (update_α_β!, update_dτV_α_β!), stress_kernels.jl:224-315 (the local law, dyrel_local.hpp).
+// Reference (PTsolvers/JustRelax.jl).  Restated: src/DYREL/constructors.jl:61-111 (the 3D allocator), solver.jl:44-294 (_solve_DYREL!; here its prologue :86-117,
+// the loop is dyrel_common.hpp's), :329-357 (dyrel_fields(Val(3)), velocity_dofs, pressure_dof), velocity_kernels.jl:242-322 (compute_∇V_strain_rate_RP! 3D), :441-477
+// (compute_PH_residual_V! 3D), :660-663 (damped_update_V), :729-828 (compute_DR_residual_update_V! 3D), stress_kernels.jl:224-315 (the local law, dyrel_local.hpp).
+// Shared with dyrel2d.hip: the sums, the check-time kernels, DYREL! and the solve loop (dyrel_common.hpp), its error bookkeeping (dyrel_conv.hpp).
 // No reference text (the reference cannot run a 3D solve): the stress kernel and the eigenvalue bound; their forms are stated in include/jrx.h and below.
 //
 // Departures.  (1) The reference's 3D momentum residuals take d_yi / d_zi / d_xi of the shear stresses from MiniKernels.jl:53-55, which read A[i+1, j+1, k+1]: one plane
@@ -14,11 +14,8 @@
 // An inner iteration: k_dy3_strain_rp -> k_dy3_stress (edges) -> k_dy3_stress (centres) -> k_dy3_update -> flow_bcs!.  The stress kernel is two launches: the centre
 // half rewrites η (unless linear_viscosity), which the edge half of the neighbouring nodes reads through harm_clamped; edges first, then centres, so every edge sees
 // the η of the previous refresh whatever the schedule.  Everything else the stress kernel writes is read by the same launch at the thread's own index only; the
-// edges average τ_o, ε, P, EII_pl, which it never writes.  32-bit element offsets (the extents are checked against 2^31).  fma only in update_α_β (the reference's @muladd).
-#include <initializer_list>
-#include "jrx_internal.hpp"
-#include "jrx_kernels.hpp"
-#include "jrx_material.hpp"
+// edges average τ_o, ε, P, EII_pl, which it never writes.  32-bit element offsets (the extents are checked against 2^31).
+#include "dyrel_common.hpp"
 #include "dyrel_local.hpp"
 #include "edge_stencils3d.hpp"
 
@@ -281,125 +278,6 @@ __global__ __launch_bounds__(256) void k_dy3_gershgorin(const Dy3Args a)
 #undef VEC
 }
 
-// _update_dτV_α_β! (Gershgorin.jl:229-247, 290-310; DTAU) / _update_α_β! (:182-198): the reference's @muladd is the two fma here
-struct Dy3Damp { double *dtau[3], *beta[3], *alpha[3]; const double *cV[3], *lmax[3]; int n[3]; };
-template <bool DTAU>
-__global__ __launch_bounds__(256) void k_dy3_dtau(const Dy3Damp d, const double CFL)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        if (t >= d.n[c]) continue;
-        double x = d.dtau[c][t];
-        if (DTAU) { x = 2 / sqrt(d.lmax[c][t]) * CFL; d.dtau[c][t] = x; }
-        const double cv = d.cV[c][t], den = fma(cv, x, 2.0);
-        d.beta[c][t] = 2 * x / den;
-        d.alpha[c][t] = fma(-cv, x, 2.0) / den;
-    }
-}
-
-// compute_bulk_viscosity_and_penalty! (constructors.jl:237-254); eta_mean = mean(η[.!isinf.(η)]) is sums[0] / sums[1] of k_dy3_eta_sum
-__global__ __launch_bounds__(256) void k_dy3_bulk(const Dy3Args a, const double *__restrict__ sums, const double gamma_fact)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= a.nx * a.ny * a.nz) return;
-    const double eta_mean = sums[0] / sums[1];
-    const double Kbdt = ratio_avg(a.rh.Kb, a.f.phase_c + a.rh.nphase * t, a.rh.nphase) * a.dt;
-    a.d.etab[t] = Kbdt;
-    const double e = a.f.eta[t];
-    const double g_num = gamma_fact * (isinf(e) ? eta_mean : e);
-    const double g_phy = isinf(Kbdt) ? g_num : Kbdt;
-    a.d.gamma_eff[t] = g_phy * g_num / (g_phy + g_num);
-}
-
-// fixed-order two-stage sums, no atomics: wave shuffle -> the four waves of a block -> one partial row of DY3_NS per block -> k_dy3_sum_final in one block
-constexpr int DY3_NS = 12;
-__device__ __forceinline__ void dy3_block_store(const double s[DY3_NS], const int ns, double *__restrict__ partials)
-{
-    __shared__ double sm[DY3_NS][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c = 0; c < ns; c++) {
-        const double w = wave_sum(s[c]);
-        if (lane == 0) sm[c][wave] = w;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < DY3_NS) {
-        const int c = threadIdx.x;
-        partials[blockIdx.x * DY3_NS + c] = c < ns ? (sm[c][0] + sm[c][1]) + (sm[c][2] + sm[c][3]) : 0.0;
-    }
-}
-__global__ __launch_bounds__(256) void k_dy3_sum_final(const double *__restrict__ partials, const int nblocks, double *__restrict__ out)
-{
-    __shared__ double sm[DY3_NS][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < DY3_NS; c++) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < nblocks; b += blockDim.x) s += partials[b * DY3_NS + c];
-        s = wave_sum(s);
-        if (lane == 0) sm[c][wave] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < DY3_NS) {
-        const int c = threadIdx.x;
-        out[c] = (sm[c][0] + sm[c][1]) + (sm[c][2] + sm[c][3]);
-    }
-}
-// Σ η and the count over the finite entries
-__global__ __launch_bounds__(256) void k_dy3_eta_sum(const double *__restrict__ eta, const int n, double *__restrict__ partials)
-{
-    double s[DY3_NS] = {};
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
-        const double e = eta[t];
-        if (!isinf(e)) { s[0] += e; s[1] += 1.0; }
-    }
-    dy3_block_store(s, 2, partials);
-}
-// the Powell-Hestenes norms (solver.jl:151-152): Σ Rx², Σ Ry², Σ Rz², Σ RP² over the whole arrays
-__global__ __launch_bounds__(256) void k_dy3_ph_sums(const double *__restrict__ Rx, const double *__restrict__ Ry, const double *__restrict__ Rz, const double *__restrict__ RP,
-                                                     const int nxn, const int nyn, const int nzn, const int n, double *__restrict__ partials)
-{
-    double s[DY3_NS] = {};
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
-        if (t < nxn) { const double v = Rx[t]; s[0] += v * v; }
-        if (t < nyn) { const double v = Ry[t]; s[1] += v * v; }
-        if (t < nzn) { const double v = Rz[t]; s[2] += v * v; }
-        const double v = RP[t];
-        s[3] += v * v;
-    }
-    dy3_block_store(s, 4, partials);
-}
-// the residual check of the inner loop (solver.jl:231,251, :359-365): compute_dV!, then per component Σ (D R)², Σ dV (R - R0), Σ dV²
-struct Dy3Chk { double *dV[3]; const double *R[3], *R0[3], *D[3], *dVdtau[3], *be[3], *dtau[3]; int n[3]; };
-__global__ __launch_bounds__(256) void k_dy3_check_sums(const Dy3Chk d, const int nmax, double *__restrict__ partials)
-{
-    double s[DY3_NS] = {};
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < nmax; t += gridDim.x * blockDim.x) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            if (t >= d.n[c]) continue;
-            const double R = d.R[c][t], DR = d.D[c][t] * R, dV = d.dVdtau[c][t] * d.be[c][t] * d.dtau[c][t];
-            d.dV[c][t] = dV;
-            s[c] += DR * DR; s[3 + c] += dV * (R - d.R0[c][t]); s[6 + c] += dV * dV;
-        }
-    }
-    dy3_block_store(s, 9, partials);
-}
-// update_cV! (velocity_kernels.jl:642-654)
-__global__ __launch_bounds__(256) void k_dy3_fill3(double *__restrict__ a0, const int n0, double *__restrict__ a1, const int n1, double *__restrict__ a2, const int n2,
-                                                   const double v)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n0) a0[t] = v;
-    if (t < n1) a1[t] = v;
-    if (t < n2) a2[t] = v;
-}
-// @. P += γ_eff * RP (solver.jl:264)
-__global__ __launch_bounds__(256) void k_dy3_add_P(double *__restrict__ P, const double *__restrict__ gam, const double *__restrict__ RP, const int n)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n) P[t] = P[t] + gam[t] * RP[t];
-}
 // the epilogue (solver.jl:269-286): P += ΔPψ, compute_∇V!, compute_vorticity! 3D, shear2center! of ε, ε_pl, Δε, accumulate_tensor!, accumulate_vol!; one thread per
 // node of ni .+ 1.  P, EII_pl and EVol_pl are updated in place at the thread's own cell; everything a neighbour reads (V, the edge arrays) is not written
 __global__ __launch_bounds__(256) void k_dy3_epilogue(const Dy3Args a)
@@ -465,126 +343,131 @@ jrx_status dy3_check(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_dyrel3d
     return JRX_OK;
 }
 
-Dy3Args dy3_make(const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_rheology *rh, const jrx_vep3d_params *p)
-{
+// the launches of this file's kernels on the handle's stream: what the entry points below call, and the launch object of dy_solve (dyrel_common.hpp)
+struct Dy3 {
+    typedef Dy3Args Args;
+    static constexpr int ND = 3, MAXBLK = 512;      // partial rows of 12: 512 rows fit kMaxRedBlocks rows of 4
+    jrx_handle *h;
+    hipStream_t s;
     Dy3Args a;
-    memset(&a, 0, sizeof(a));
-    a.f = *f; a.d = *d;
-    if (rh) a.rh = *rh;
-    a._dx = p->_dx; a._dy = p->_dy; a._dz = p->_dz; a.dt = p->dt;
-    a.nx = (int)p->nx; a.ny = (int)p->ny; a.nz = (int)p->nz;
-    a.fs = p->free_slip; a.ns = p->no_slip;
-    a.tg = p->T_ghosted != 0;
-    a.rel = 1.0; a.nu = 1.0e-2; a.cut_lo = -INFINITY; a.cut_hi = INFINITY;
-    return a;
-}
-Dy3Mom dy3_mom(const Dy3Args &a, const double *th)
-{
-    return Dy3Mom{a.f.P, th, a.f.txx, a.f.tyy, a.f.tzz, a.f.tyz, a.f.txz, a.f.txy, a.f.fx, a.f.fy, a.f.fz, a._dx, a._dy, a._dz, a.nx, a.ny, a.nz};
-}
-Dy3Upd dy3_upd(const Dy3Args &a)
-{
-    const jrx_dyrel3d_fields &d = a.d;
-    return Dy3Upd{{a.f.Rx, a.f.Ry, a.f.Rz}, {a.f.Vx, a.f.Vy, a.f.Vz}, {d.dVxdtau, d.dVydtau, d.dVzdtau}, {d.Dx, d.Dy, d.Dz}, {d.alphaVx, d.alphaVy, d.alphaVz},
-                  {d.betaVx, d.betaVy, d.betaVz}, {d.dtauVx, d.dtauVy, d.dtauVz}};
-}
-struct Dy3N { int c, x, y, z, max; };
-Dy3N dy3_counts(const Dy3Args &a)
-{
-    Dy3N n{a.nx * a.ny * a.nz, (a.nx - 1) * a.ny * a.nz, a.nx * (a.ny - 1) * a.nz, a.nx * a.ny * (a.nz - 1), 0};
-    n.max = n.x > n.y ? n.x : n.y;
-    n.max = n.z > n.max ? n.z : n.max;
-    return n;
-}
-bool dy3_has(std::initializer_list<const void *> req)
-{
-    for (const void *q : req)
-        if (!q) return false;
-    return true;
-}
-#define DY3_REQ(h, what, ...) \
-    if (!dy3_has({__VA_ARGS__})) return jrx_fail(h, JRX_ERR_ARG, "%s: a required field pointer is NULL", what)
-#define DY3_LAUNCH(h) \
-    do { (h)->stat_dyrel_launches++; JRX_LAUNCH_CHECK(h); } while (0)
+    double dofs[3], pdof;      // velocity_dofs(Val(3)), pressure_dof (solver.jl:349-357)
+    bool bcs_applied = false;      // flow_bcs! has run in the reference's pass order on V since the solve began
 
-inline dim3 dy3_gv(const Dy3Args &a) { return DY3_GRID(a.nx + 1, a.ny + 1, a.nz + 1); }
-inline dim3 dy3_gc(const Dy3Args &a) { return DY3_GRID(a.nx, a.ny, a.nz); }
-inline unsigned dy3_g1(int n) { return (unsigned)((n + 255) / 256); }
-inline int dy3_nblk(const Dy3Args &a) { const unsigned g = (dy3_g1(a.nx * a.ny * a.nz) + 7) / 8; return (int)(g < 1 ? 1 : (g > 512 ? 512 : g)); }      // partial rows of 12: 512 rows fit kMaxRedBlocks rows of 4
-static_assert(512 * DY3_NS <= kMaxRedBlocks * 4, "the reduction scratch holds the partial rows");
+    Dy3(jrx_handle *h_, const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_rheology *rh, const jrx_vep3d_params *p) : h(h_), s(h_->stream)
+    {
+        memset(&a, 0, sizeof(a));
+        a.f = *f; a.d = *d;
+        if (rh) a.rh = *rh;
+        a._dx = p->_dx; a._dy = p->_dy; a._dz = p->_dz; a.dt = p->dt;
+        a.nx = (int)p->nx; a.ny = (int)p->ny; a.nz = (int)p->nz;
+        a.fs = p->free_slip; a.ns = p->no_slip;
+        a.tg = p->T_ghosted != 0;
+        a.rel = 1.0; a.nu = 1.0e-2; a.cut_lo = -INFINITY; a.cut_hi = INFINITY;
+        dofs[0] = (double)((p->nxg - 2) * (p->nyg - 1) * (p->nzg - 1)); dofs[1] = (double)((p->nxg - 1) * (p->nyg - 2) * (p->nzg - 1));
+        dofs[2] = (double)((p->nxg - 1) * (p->nyg - 1) * (p->nzg - 2));
+        pdof = (double)(p->nxg * p->nyg * p->nzg);
+    }
+    int cells() const { return a.nx * a.ny * a.nz; }
+    dim3 gv() const { return DY3_GRID(a.nx + 1, a.ny + 1, a.nz + 1); }
+    dim3 gc() const { return DY3_GRID(a.nx, a.ny, a.nz); }
+    Dy3Mom mom(const double *th) const
+    {
+        return Dy3Mom{a.f.P, th, a.f.txx, a.f.tyy, a.f.tzz, a.f.tyz, a.f.txz, a.f.txy, a.f.fx, a.f.fy, a.f.fz, a._dx, a._dy, a._dz, a.nx, a.ny, a.nz};
+    }
+    Dy3Upd upd() const
+    {
+        const jrx_dyrel3d_fields &d = a.d;
+        return Dy3Upd{{a.f.Rx, a.f.Ry, a.f.Rz}, {a.f.Vx, a.f.Vy, a.f.Vz}, {d.dVxdtau, d.dVydtau, d.dVzdtau}, {d.Dx, d.Dy, d.Dz}, {d.alphaVx, d.alphaVy, d.alphaVz},
+                      {d.betaVx, d.betaVy, d.betaVz}, {d.dtauVx, d.dtauVy, d.dtauVz}};
+    }
+    DyDof<3> dof() const
+    {
+        const jrx_dyrel3d_fields &d = a.d;
+        const int nxn = (a.nx - 1) * a.ny * a.nz, nyn = a.nx * (a.ny - 1) * a.nz, nzn = a.nx * a.ny * (a.nz - 1), nxy = nxn > nyn ? nxn : nyn;
+        return DyDof<3>{{a.f.Rx, a.f.Ry, a.f.Rz}, {d.Rx0, d.Ry0, d.Rz0}, {d.Dx, d.Dy, d.Dz}, {d.lmaxVx, d.lmaxVy, d.lmaxVz}, {d.dVxdtau, d.dVydtau, d.dVzdtau},
+                        {d.dtauVx, d.dtauVy, d.dtauVz}, {d.dVx, d.dVy, d.dVz}, {d.betaVx, d.betaVy, d.betaVz}, {d.cVx, d.cVy, d.cVz}, {d.alphaVx, d.alphaVy, d.alphaVz},
+                        {nxn, nyn, nzn}, nzn > nxy ? nzn : nxy};
+    }
 
-jrx_status dy3_strain_rp(jrx_handle *h, hipStream_t s, const Dy3Args &a, bool strain)
-{
-    const jrx_vep3d_fields &f = a.f;
-    if (strain) hipLaunchKernelGGL(k_dy3_strain_rp<true>, dy3_gv(a), dim3(256), 0, s, f.exx, f.eyy, f.ezz, f.eyz, f.exz, f.exy, (const double *)f.Vx, (const double *)f.Vy,
-                                   (const double *)f.Vz, f.RP, (const double *)f.P, (const double *)f.P0, (const double *)f.Q, (const double *)a.d.etab, a._dx, a._dy, a._dz,
-                                   a.dt, a.nx, a.ny, a.nz);
-    else hipLaunchKernelGGL(k_dy3_strain_rp<false>, dy3_gv(a), dim3(256), 0, s, f.exx, f.eyy, f.ezz, f.eyz, f.exz, f.exy, (const double *)f.Vx, (const double *)f.Vy,
-                            (const double *)f.Vz, f.RP, (const double *)f.P, (const double *)f.P0, (const double *)f.Q, (const double *)a.d.etab, a._dx, a._dy, a._dz, a.dt,
-                            a.nx, a.ny, a.nz);
-    DY3_LAUNCH(h);
-    return JRX_OK;
-}
-template <bool SOFT, bool LIN>
-jrx_status dy3_stress_t(jrx_handle *h, hipStream_t s, const Dy3Args &a)
-{
-    hipLaunchKernelGGL((k_dy3_stress<SOFT, LIN, 7>), dy3_gv(a), dim3(256), 0, s, a);
-    DY3_LAUNCH(h);
-    hipLaunchKernelGGL((k_dy3_stress<SOFT, LIN, 8>), dy3_gc(a), dim3(256), 0, s, a);
-    DY3_LAUNCH(h);
-    return JRX_OK;
-}
-jrx_status dy3_stress(jrx_handle *h, hipStream_t s, const Dy3Args &a, bool lin)
-{
-    if (mat_has_softening(&a.rh)) return lin ? dy3_stress_t<true, true>(h, s, a) : dy3_stress_t<true, false>(h, s, a);
-    return lin ? dy3_stress_t<false, true>(h, s, a) : dy3_stress_t<false, false>(h, s, a);
-}
-jrx_status dy3_gershgorin(jrx_handle *h, hipStream_t s, const Dy3Args &a)
-{
-    hipLaunchKernelGGL(k_dy3_gershgorin, dy3_gc(a), dim3(256), 0, s, a);
-    DY3_LAUNCH(h);
-    return JRX_OK;
-}
-jrx_status dy3_dtau(jrx_handle *h, hipStream_t s, const Dy3Args &a, double CFL, bool from_lmax)
-{
-    const jrx_dyrel3d_fields &d = a.d;
-    const Dy3N n = dy3_counts(a);
-    const Dy3Damp q{{d.dtauVx, d.dtauVy, d.dtauVz}, {d.betaVx, d.betaVy, d.betaVz}, {d.alphaVx, d.alphaVy, d.alphaVz}, {d.cVx, d.cVy, d.cVz}, {d.lmaxVx, d.lmaxVy, d.lmaxVz},
-                    {n.x, n.y, n.z}};
-    if (from_lmax) hipLaunchKernelGGL(k_dy3_dtau<true>, dim3(dy3_g1(n.max)), dim3(256), 0, s, q, CFL);
-    else hipLaunchKernelGGL(k_dy3_dtau<false>, dim3(dy3_g1(n.max)), dim3(256), 0, s, q, CFL);
-    DY3_LAUNCH(h);
-    return JRX_OK;
-}
-jrx_status dy3_bulk(jrx_handle *h, hipStream_t s, const Dy3Args &a, double gamma_fact)
-{
-    const int nb = dy3_nblk(a), n = a.nx * a.ny * a.nz;
-    hipLaunchKernelGGL(k_dy3_eta_sum, dim3(nb), dim3(256), 0, s, (const double *)a.f.eta, n, h->d_partials);
-    DY3_LAUNCH(h);
-    hipLaunchKernelGGL(k_dy3_sum_final, dim3(1), dim3(256), 0, s, (const double *)h->d_partials, nb, h->d_sums);
-    DY3_LAUNCH(h);
-    hipLaunchKernelGGL(k_dy3_bulk, dim3(dy3_g1(n)), dim3(256), 0, s, a, (const double *)h->d_sums, gamma_fact);
-    DY3_LAUNCH(h);
-    return JRX_OK;
-}
-// DYREL! (constructors.jl:178-190)
-jrx_status dy3_init(jrx_handle *h, hipStream_t s, const Dy3Args &a, double CFL, double gamma_fact)
-{
-    JRX_TRY(dy3_bulk(h, s, a, gamma_fact));
-    JRX_TRY(dy3_gershgorin(h, s, a));
-    return dy3_dtau(h, s, a, CFL, true);
-}
-// the sums of one reduction kernel, read on the host: the one synchronisation of a check
-jrx_status dy3_read_sums(jrx_handle *h, hipStream_t s, int nb, int count)
-{
-    hipLaunchKernelGGL(k_dy3_sum_final, dim3(1), dim3(256), 0, s, (const double *)h->d_partials, nb, h->d_sums);
-    DY3_LAUNCH(h);
-    JRX_HIP(h, hipMemcpyAsync(h->h_sums, h->d_sums, count * sizeof(double), hipMemcpyDeviceToHost, s));
-    JRX_HIP(h, hipStreamSynchronize(s));
-    return JRX_OK;
-}
+    jrx_status strain_rp(bool strain) const
+    {
+        const jrx_vep3d_fields &f = a.f;
+        if (strain) hipLaunchKernelGGL(k_dy3_strain_rp<true>, gv(), dim3(256), 0, s, f.exx, f.eyy, f.ezz, f.eyz, f.exz, f.exy, (const double *)f.Vx, (const double *)f.Vy,
+                                       (const double *)f.Vz, f.RP, (const double *)f.P, (const double *)f.P0, (const double *)f.Q, (const double *)a.d.etab, a._dx, a._dy, a._dz,
+                                       a.dt, a.nx, a.ny, a.nz);
+        else hipLaunchKernelGGL(k_dy3_strain_rp<false>, gv(), dim3(256), 0, s, f.exx, f.eyy, f.ezz, f.eyz, f.exz, f.exy, (const double *)f.Vx, (const double *)f.Vy,
+                                (const double *)f.Vz, f.RP, (const double *)f.P, (const double *)f.P0, (const double *)f.Q, (const double *)a.d.etab, a._dx, a._dy, a._dz, a.dt,
+                                a.nx, a.ny, a.nz);
+        DY_LAUNCH(h);
+        return JRX_OK;
+    }
+    template <bool SOFT, bool LIN>
+    jrx_status stress_t() const
+    {
+        hipLaunchKernelGGL((k_dy3_stress<SOFT, LIN, 7>), gv(), dim3(256), 0, s, a);
+        DY_LAUNCH(h);
+        hipLaunchKernelGGL((k_dy3_stress<SOFT, LIN, 8>), gc(), dim3(256), 0, s, a);
+        DY_LAUNCH(h);
+        return JRX_OK;
+    }
+    jrx_status stress(bool lin) const
+    {
+        if (mat_has_softening(&a.rh)) return lin ? stress_t<true, true>() : stress_t<true, false>();
+        return lin ? stress_t<false, true>() : stress_t<false, false>();
+    }
+    jrx_status ph_residual() const
+    {
+        hipLaunchKernelGGL(k_dy3_ph_residual, gc(), dim3(256), 0, s, mom(a.d.dPpsi), a.f.Rx, a.f.Ry, a.f.Rz);
+        DY_LAUNCH(h);
+        return JRX_OK;
+    }
+    jrx_status copy_old_residual() const
+    {
+        const DyDof<3> q = dof();
+        hipLaunchKernelGGL(k_copy6, dim3(256), dim3(256), 0, s, q.R0[0], (const double *)q.R[0], (i64)q.n[0], q.R0[1], (const double *)q.R[1], (i64)q.n[1], q.R0[2],
+                           (const double *)q.R[2], (i64)q.n[2], (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0,
+                           (double *)nullptr, (const double *)nullptr, (i64)0);
+        DY_LAUNCH(h);
+        return JRX_OK;
+    }
+    jrx_status update() const
+    {
+        hipLaunchKernelGGL(k_dy3_update, gc(), dim3(256), 0, s, mom(a.d.P_num), upd());
+        DY_LAUNCH(h);
+        return JRX_OK;
+    }
+    // flow_bcs!: in the reference's pass order the first time and wherever the velocities can be observed (a check, the last iteration of a velocity solve);
+    // in between, all faces in one launch, which agrees on every entry a stencil reads
+    jrx_status update_V(bool check, bool last)
+    {
+        JRX_TRY(update());
+        if (!bcs_applied || check || last) JRX_TRY(jrx3d_bcs(h, s, a.f.Vx, a.f.Vy, a.f.Vz, a.nx, a.ny, a.nz, a.fs, a.ns, 0));
+        else JRX_TRY(jrx3d_bcs_faces(h, s, a.f.Vx, a.f.Vy, a.f.Vz, a.nx, a.ny, a.nz, a.fs, a.ns));
+        bcs_applied = true;
+        return JRX_OK;
+    }
+    jrx_status gershgorin() const
+    {
+        hipLaunchKernelGGL(k_dy3_gershgorin, gc(), dim3(256), 0, s, a);
+        DY_LAUNCH(h);
+        return JRX_OK;
+    }
+    jrx_status rhog() const      // ρg[end] = ρg z
+    {
+        const int64_t nn[3] = {a.nx, a.ny, a.nz}, tdim[3] = {a.tg ? a.nx + 2 : a.nx, a.tg ? a.ny + 2 : a.ny, a.tg ? a.nz + 2 : a.nz};
+        return jrx_compute_rhog(h, a.f.fz, &a.rh, a.f.phase_c, a.f.T, a.f.P, nn, tdim, 3);
+    }
+    jrx_status epilogue() const      // copy_stress_vertices!(Val(3)) has nothing to copy: no vertex-normal stresses are kept in 3D
+    {
+        hipLaunchKernelGGL(k_dy3_epilogue, gv(), dim3(256), 0, s, a);
+        DY_LAUNCH(h);
+        JRX_TRY((jrx3d_copy_old_stresses<256>(h, s, &a.f, a.nx, a.ny, a.nz)));
+        h->stat_dyrel_launches += 2;
+        return JRX_OK;
+    }
+};
 
-#define DY3_FIELDS_STRESS(f, d)                                                                                                                                     \
+#define DY3_FIELDS_STRESS(f, d)                                                                                                                                    \
     (f)->P, (f)->exx, (f)->eyy, (f)->ezz, (f)->eyz, (f)->exz, (f)->exy, (f)->eplxx, (f)->eplyy, (f)->eplzz, (f)->eplyz, (f)->eplxz, (f)->eplxy, (f)->txx, (f)->tyy,    \
         (f)->tzz, (f)->tyz, (f)->txz, (f)->txy, (f)->tyz_c, (f)->txz_c, (f)->txy_c, (f)->tII, (f)->toxx, (f)->toyy, (f)->tozz, (f)->toyz, (f)->toxz, (f)->toxy,       \
         (f)->toyz_c, (f)->toxz_c, (f)->toxy_c, (f)->eta, (f)->eta_vep, (f)->EII_pl, (f)->evol_pl, (f)->RP, (f)->phase_c, (f)->phase_yz, (f)->phase_xz, (f)->phase_xy, \
@@ -601,9 +484,8 @@ extern "C" {
 jrx_status jrx_dyrel3d_strain_rate_RP(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_vep3d_params *p, int32_t do_strain_rate)
 {
     JRX_TRY(dy3_check(h, f, d, nullptr, nullptr, p));
-    DY3_REQ(h, "compute_∇V_strain_rate_RP! 3D", f->exx, f->eyy, f->ezz, f->eyz, f->exz, f->exy, f->Vx, f->Vy, f->Vz, f->RP, f->P, f->P0, f->Q, d->etab);
-    const Dy3Args a = dy3_make(f, d, nullptr, p);
-    JRX_TRY(dy3_strain_rp(h, h->stream, a, do_strain_rate != 0));
+    DY_REQ(h, "compute_∇V_strain_rate_RP! 3D", f->exx, f->eyy, f->ezz, f->eyz, f->exz, f->exy, f->Vx, f->Vy, f->Vz, f->RP, f->P, f->P0, f->Q, d->etab);
+    JRX_TRY(Dy3(h, f, d, nullptr, p).strain_rp(do_strain_rate != 0));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -613,10 +495,10 @@ jrx_status jrx_dyrel3d_stress_viscosity(jrx_handle *h, const jrx_vep3d_fields *f
 {
     JRX_TRY(dy3_check(h, f, d, nullptr, rh, p));
     if (!rh || !dp) return jrx_fail(h, JRX_ERR_ARG, "DYREL 3D: null argument");
-    DY3_REQ(h, "compute_stress_viscosity_DRYEL! 3D", DY3_FIELDS_STRESS(f, d));
-    Dy3Args a = dy3_make(f, d, rh, p);
-    a.rel = lambda_relaxation; a.nu = dp->viscosity_relaxation; a.cut_lo = dp->cutoff_lo; a.cut_hi = dp->cutoff_hi;
-    JRX_TRY(dy3_stress(h, h->stream, a, dp->linear_viscosity != 0));
+    DY_REQ(h, "compute_stress_viscosity_DRYEL! 3D", DY3_FIELDS_STRESS(f, d));
+    Dy3 o(h, f, d, rh, p);
+    o.a.rel = lambda_relaxation; o.a.nu = dp->viscosity_relaxation; o.a.cut_lo = dp->cutoff_lo; o.a.cut_hi = dp->cutoff_hi;
+    JRX_TRY(o.stress(dp->linear_viscosity != 0));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -624,10 +506,8 @@ jrx_status jrx_dyrel3d_stress_viscosity(jrx_handle *h, const jrx_vep3d_fields *f
 jrx_status jrx_dyrel3d_PH_residual(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_vep3d_params *p)
 {
     JRX_TRY(dy3_check(h, f, d, nullptr, nullptr, p));
-    DY3_REQ(h, "compute_PH_residual_V! 3D", DY3_FIELDS_MOM(f), d->dPpsi);
-    const Dy3Args a = dy3_make(f, d, nullptr, p);
-    hipLaunchKernelGGL(k_dy3_ph_residual, dy3_gc(a), dim3(256), 0, h->stream, dy3_mom(a, d->dPpsi), f->Rx, f->Ry, f->Rz);
-    DY3_LAUNCH(h);
+    DY_REQ(h, "compute_PH_residual_V! 3D", DY3_FIELDS_MOM(f), d->dPpsi);
+    JRX_TRY(Dy3(h, f, d, nullptr, p).ph_residual());
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -635,11 +515,9 @@ jrx_status jrx_dyrel3d_PH_residual(jrx_handle *h, const jrx_vep3d_fields *f, con
 jrx_status jrx_dyrel3d_DR_residual_update_V(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_vep3d_params *p)
 {
     JRX_TRY(dy3_check(h, f, d, nullptr, nullptr, p));
-    DY3_REQ(h, "compute_DR_residual_update_V! 3D", DY3_FIELDS_MOM(f), f->Vx, f->Vy, f->Vz, d->P_num, d->Dx, d->Dy, d->Dz, d->dVxdtau, d->dVydtau, d->dVzdtau, d->alphaVx,
-            d->alphaVy, d->alphaVz, d->betaVx, d->betaVy, d->betaVz, d->dtauVx, d->dtauVy, d->dtauVz);
-    const Dy3Args a = dy3_make(f, d, nullptr, p);
-    hipLaunchKernelGGL(k_dy3_update, dy3_gc(a), dim3(256), 0, h->stream, dy3_mom(a, d->P_num), dy3_upd(a));
-    DY3_LAUNCH(h);
+    DY_REQ(h, "compute_DR_residual_update_V! 3D", DY3_FIELDS_MOM(f), f->Vx, f->Vy, f->Vz, d->P_num, d->Dx, d->Dy, d->Dz, d->dVxdtau, d->dVydtau, d->dVzdtau, d->alphaVx,
+           d->alphaVy, d->alphaVz, d->betaVx, d->betaVy, d->betaVz, d->dtauVx, d->dtauVy, d->dtauVz);
+    JRX_TRY(Dy3(h, f, d, nullptr, p).update());
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -648,9 +526,8 @@ jrx_status jrx_dyrel3d_gershgorin(jrx_handle *h, const jrx_vep3d_fields *f, cons
 {
     JRX_TRY(dy3_check(h, f, d, nullptr, rh, p));
     if (!rh) return jrx_fail(h, JRX_ERR_ARG, "DYREL 3D: null argument");
-    DY3_REQ(h, "the 3D Gershgorin estimate", f->eta, f->phase_c, f->phase_yz, f->phase_xz, f->phase_xy, d->gamma_eff, d->Dx, d->Dy, d->Dz, d->lmaxVx, d->lmaxVy, d->lmaxVz);
-    const Dy3Args a = dy3_make(f, d, rh, p);
-    JRX_TRY(dy3_gershgorin(h, h->stream, a));
+    DY_REQ(h, "the 3D Gershgorin estimate", f->eta, f->phase_c, f->phase_yz, f->phase_xz, f->phase_xy, d->gamma_eff, d->Dx, d->Dy, d->Dz, d->lmaxVx, d->lmaxVy, d->lmaxVz);
+    JRX_TRY(Dy3(h, f, d, rh, p).gershgorin());
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -660,10 +537,9 @@ jrx_status jrx_dyrel3d_update_dtauV_alpha_beta(jrx_handle *h, const jrx_dyrel3d_
     jrx_vep3d_fields none;
     memset(&none, 0, sizeof(none));
     JRX_TRY(dy3_check(h, &none, d, nullptr, nullptr, p));
-    DY3_REQ(h, "update_dτV_α_β! 3D", d->dtauVx, d->dtauVy, d->dtauVz, d->betaVx, d->betaVy, d->betaVz, d->alphaVx, d->alphaVy, d->alphaVz, d->cVx, d->cVy, d->cVz, d->lmaxVx,
-            d->lmaxVy, d->lmaxVz);
-    const Dy3Args a = dy3_make(&none, d, nullptr, p);
-    JRX_TRY(dy3_dtau(h, h->stream, a, CFL, from_lambda_max != 0));
+    DY_REQ(h, "update_dτV_α_β! 3D", d->dtauVx, d->dtauVy, d->dtauVz, d->betaVx, d->betaVy, d->betaVz, d->alphaVx, d->alphaVy, d->alphaVz, d->cVx, d->cVy, d->cVz, d->lmaxVx,
+           d->lmaxVy, d->lmaxVz);
+    JRX_TRY(dy_dtau(Dy3(h, &none, d, nullptr, p), CFL, from_lambda_max != 0));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -673,9 +549,8 @@ jrx_status jrx_dyrel3d_bulk_viscosity_and_penalty(jrx_handle *h, const jrx_vep3d
 {
     JRX_TRY(dy3_check(h, f, d, nullptr, rh, p));
     if (!rh) return jrx_fail(h, JRX_ERR_ARG, "DYREL 3D: null argument");
-    DY3_REQ(h, "compute_bulk_viscosity_and_penalty! 3D", f->eta, f->phase_c, d->etab, d->gamma_eff);
-    const Dy3Args a = dy3_make(f, d, rh, p);
-    JRX_TRY(dy3_bulk(h, h->stream, a, gamma_fact));
+    DY_REQ(h, "compute_bulk_viscosity_and_penalty! 3D", f->eta, f->phase_c, d->etab, d->gamma_eff);
+    JRX_TRY(dy_bulk(Dy3(h, f, d, rh, p), gamma_fact));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -685,9 +560,8 @@ jrx_status jrx_dyrel3d_init(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_
 {
     JRX_TRY(dy3_check(h, f, d, phi, rh, p));
     if (!rh || !dp) return jrx_fail(h, JRX_ERR_ARG, "DYREL 3D: null argument");
-    DY3_REQ(h, "DYREL! 3D", f->eta, f->phase_c, f->phase_yz, f->phase_xz, f->phase_xy, d->gamma_eff, d->etab, DY3_FIELDS_DAMP(d));
-    const Dy3Args a = dy3_make(f, d, rh, p);
-    JRX_TRY(dy3_init(h, h->stream, a, dp->CFL, dp->gamma_fact));
+    DY_REQ(h, "DYREL! 3D", f->eta, f->phase_c, f->phase_yz, f->phase_xz, f->phase_xy, d->gamma_eff, d->etab, DY3_FIELDS_DAMP(d));
+    JRX_TRY(dy_init(Dy3(h, f, d, rh, p), dp->CFL, dp->gamma_fact));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
@@ -698,23 +572,14 @@ jrx_status jrx_dyrel3d_solve(jrx_handle *h, const jrx_vep3d_fields *f, const jrx
     JRX_TRY(dy3_check(h, f, d, phi, rh, p));
     if (!rh || !dp || !res) return jrx_fail(h, JRX_ERR_ARG, "DYREL 3D: null argument");
     if (dp->nout < 1) return jrx_fail(h, JRX_ERR_ARG, "nout must be >= 1");
-    DY3_REQ(h, "solve_DYREL! 3D", DY3_FIELDS_STRESS(f, d), DY3_FIELDS_MOM(f), DY3_FIELDS_DAMP(d), f->P0, f->divV, f->Q, f->Vx, f->Vy, f->Vz, f->eplyz_c, f->eplxz_c,
-            f->eplxy_c, f->EVol_pl, d->etab);
+    DY_REQ(h, "solve_DYREL! 3D", DY3_FIELDS_STRESS(f, d), DY3_FIELDS_MOM(f), DY3_FIELDS_DAMP(d), f->P0, f->divV, f->Q, f->Vx, f->Vy, f->Vz, f->eplyz_c, f->eplxz_c,
+           f->eplxy_c, f->EVol_pl, d->etab);
     if (mat_viscosity_reads_invariant(rh) && !(f->eyz_c && f->exz_c && f->exy_c)) return jrx_fail(h, JRX_ERR_ARG, "a power-law creep needs the centre shear strain rates for compute_viscosity!");
-    hipStream_t s = h->stream;
-    Dy3Args a = dy3_make(f, d, rh, p);
-    a.nu = dp->viscosity_relaxation; a.cut_lo = dp->cutoff_lo; a.cut_hi = dp->cutoff_hi;
-    const int nx = a.nx, ny = a.ny, nz = a.nz;
-    const Dy3N cnt = dy3_counts(a);
-    const size_t n = (size_t)cnt.c;
-    const EdgeN ne = edge_counts(nx, ny, nz);
-    const bool lin = dp->linear_viscosity != 0;
-    const int nb = dy3_nblk(a);
-    const double EPS = 2.220446049250313e-16;
-    // velocity_dofs(Val(3)), pressure_dof (solver.jl:349-357)
-    const double dofs[3] = {(double)((p->nxg - 2) * (p->nyg - 1) * (p->nzg - 1)), (double)((p->nxg - 1) * (p->nyg - 2) * (p->nzg - 1)),
-                            (double)((p->nxg - 1) * (p->nyg - 1) * (p->nzg - 2))};
-    const double pdof = (double)(p->nxg * p->nyg * p->nzg);
+    Dy3 o(h, f, d, rh, p);
+    o.a.nu = dp->viscosity_relaxation; o.a.cut_lo = dp->cutoff_lo; o.a.cut_hi = dp->cutoff_hi;
+    hipStream_t s = o.s;
+    const size_t n = (size_t)o.cells();
+    const EdgeN ne = edge_counts(o.a.nx, o.a.ny, o.a.nz);
 
     // solver.jl:86-95: P0 <- P, @tensor_center(ε_pl) = 0, λ = λv = 0
     JRX_HIP(h, hipMemcpyAsync(f->P0, f->P, n * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -723,119 +588,12 @@ jrx_status jrx_dyrel3d_solve(jrx_handle *h, const jrx_vep3d_fields *f, const jrx
     JRX_HIP(h, hipMemsetAsync(d->lambda_xz, 0, (size_t)ne.xz * sizeof(double), s));
     JRX_HIP(h, hipMemsetAsync(d->lambda_xy, 0, (size_t)ne.xy * sizeof(double), s));
     JRX_HIP(h, hipEventRecord(h->ev[6], s));
-    {   // :117-119: compute_viscosity! (relaxation 1, the strain-rate invariant), compute_ρg!(ρg[end], ...), DYREL!
+    {   // :117: compute_viscosity! (relaxation 1, the strain-rate invariant)
         jrx_vep3d_params pv = *p;
         pv.cutoff_lo = dp->cutoff_lo; pv.cutoff_hi = dp->cutoff_hi;
         JRX_TRY(jrx_vep3d_compute_viscosity(h, f, rh, &pv, 1.0));
     }
-    const int64_t nn[3] = {nx, ny, nz}, tdim[3] = {a.tg ? nx + 2 : nx, a.tg ? ny + 2 : ny, a.tg ? nz + 2 : nz};
-    if (rh->has_density) JRX_TRY(jrx_compute_rhog(h, f->fz, rh, f->phase_c, f->T, f->P, nn, tdim, 3));
-    JRX_TRY(dy3_init(h, s, a, dp->CFL, dp->gamma_fact));
-    const bool rho_loop = rh->has_density && !mat_density_is_constant(rh);
-
-    double err = 2 * dp->eps, err_min = INFINITY, errV0[3] = {1.0, 1.0, 1.0}, errPt0 = 1.0, errV00 = 1.0, errPt = 1.0, rel_drop = dp->rel_drop;
-    int64_t iter = 0, cont = 0, itPH_done = 0;
-    bool bcs_applied = false;
-    jrx_status bad = JRX_OK;
-    const Dy3Chk chk{{d->dVx, d->dVy, d->dVz}, {f->Rx, f->Ry, f->Rz}, {d->Rx0, d->Ry0, d->Rz0}, {d->Dx, d->Dy, d->Dz}, {d->dVxdtau, d->dVydtau, d->dVzdtau},
-                     {d->betaVx, d->betaVy, d->betaVz}, {d->dtauVx, d->dtauVy, d->dtauVz}, {cnt.x, cnt.y, cnt.z}};
-    for (int64_t itPH = 1; itPH <= 1000; itPH++) {
-        itPH_done = itPH;
-        if (rho_loop) JRX_TRY(jrx_compute_rhog(h, f->fz, rh, f->phase_c, f->T, f->P, nn, tdim, 3));      // update_ρg! :124
-        JRX_TRY(dy3_strain_rp(h, s, a, true));
-        a.rel = dp->lambda_relaxation_PH;
-        JRX_TRY(dy3_stress(h, s, a, lin));
-        hipLaunchKernelGGL(k_dy3_ph_residual, dy3_gc(a), dim3(256), 0, s, dy3_mom(a, d->dPpsi), f->Rx, f->Ry, f->Rz);
-        DY3_LAUNCH(h);
-        hipLaunchKernelGGL(k_dy3_ph_sums, dim3(nb), dim3(256), 0, s, (const double *)f->Rx, (const double *)f->Ry, (const double *)f->Rz, (const double *)f->RP, cnt.x, cnt.y,
-                           cnt.z, cnt.c, h->d_partials);
-        DY3_LAUNCH(h);
-        JRX_TRY(dy3_read_sums(h, s, nb, 4));      // the host read of this Powell-Hestenes iteration
-        double errV[3], e[4];
-        for (int c = 0; c < 3; c++) errV[c] = sqrt(h->h_sums[c]) / sqrt(dofs[c]);
-        errPt = sqrt(h->h_sums[3]) / sqrt(pdof);
-        if (itPH == 1) { for (int c = 0; c < 3; c++) errV0[c] = errV[c] + EPS; errPt0 = errPt + EPS; }
-        if (itPH == 2) errPt0 = errPt + EPS;
-        for (int c = 0; c < 3; c++) e[c] = fmin(errV[c] / errV0[c], errV[c]);
-        e[3] = fmin(errPt / errPt0, errPt);
-        err = fmax(fmax(e[0], e[1]), fmax(e[2], e[3]));
-        if (std::isnan(e[0]) || std::isnan(e[1]) || std::isnan(e[2]) || std::isnan(e[3])) err = NAN;
-        if (dp->verbose_PH)
-            printf("itPH = %02lld iter = %06lld iter/nx = %03lld, err = %1.3e - norm[R1=%1.3e %1.3e, R2=%1.3e %1.3e, R3=%1.3e %1.3e, Rp=%1.3e %1.3e] \n", (long long)itPH,
-                   (long long)iter, (long long)(iter / nx), err, errV[0], errV[0] / errV0[0], errV[1], errV[1] / errV0[1], errV[2], errV[2] / errV0[2], errPt, errPt / errPt0);
-        if (std::isnan(err)) { bad = jrx_fail(h, JRX_ERR_NAN, "NaN detected in outer loop"); break; }
-        if (err > 1.0e10) { bad = jrx_fail(h, JRX_ERR_NAN, "Kaboom! Error > 1e10 in outer loop"); break; }
-        if (err < dp->eps) break;
-        if (err > err_min * 1.05) rel_drop = fmax(rel_drop * 0.1, 1.0e-3);
-        if (err_min > err) err_min = err;
-        const double eps_vel = err * rel_drop;
-        int64_t itPT = 0;
-        a.rel = dp->lambda_relaxation_DR;
-        while (err > eps_vel && itPT <= dp->iterMax) {
-            itPT++; iter++;
-            const bool check = iter % dp->nout == 0;
-            if (check) {      // pseudo-old residuals :191
-                hipLaunchKernelGGL(k_copy6, dim3(256), dim3(256), 0, s, d->Rx0, (const double *)f->Rx, (i64)cnt.x, d->Ry0, (const double *)f->Ry, (i64)cnt.y, d->Rz0,
-                                   (const double *)f->Rz, (i64)cnt.z, (double *)nullptr, (const double *)nullptr, (i64)0, (double *)nullptr, (const double *)nullptr, (i64)0,
-                                   (double *)nullptr, (const double *)nullptr, (i64)0);
-                DY3_LAUNCH(h);
-            }
-            JRX_TRY(dy3_strain_rp(h, s, a, true));
-            JRX_TRY(dy3_stress(h, s, a, lin));
-            hipLaunchKernelGGL(k_dy3_update, dy3_gc(a), dim3(256), 0, s, dy3_mom(a, d->P_num), dy3_upd(a));
-            DY3_LAUNCH(h);
-            // flow_bcs!: in the reference's pass order the first time and wherever the velocities can be observed (a check, the last iteration of a velocity solve);
-            // in between, all faces in one launch, which agrees on every entry a stencil reads
-            if (!bcs_applied || check || itPT > dp->iterMax) JRX_TRY(jrx3d_bcs(h, s, f->Vx, f->Vy, f->Vz, nx, ny, nz, p->free_slip, p->no_slip, 0));
-            else JRX_TRY(jrx3d_bcs_faces(h, s, f->Vx, f->Vy, f->Vz, nx, ny, nz, p->free_slip, p->no_slip));
-            bcs_applied = true;
-            if (check) {
-                hipLaunchKernelGGL(k_dy3_check_sums, dim3(nb), dim3(256), 0, s, chk, cnt.max, h->d_partials);
-                DY3_LAUNCH(h);
-                JRX_TRY(dy3_read_sums(h, s, nb, 9));      // the host read of these nout iterations
-                const double *S = h->h_sums;
-                double eV[3];
-                for (int c = 0; c < 3; c++) eV[c] = sqrt(S[c]) / sqrt(dofs[c]);
-                if (iter == dp->nout) errV00 = fmax(fmax(eV[0], eV[1]), eV[2]) + EPS;
-                err = fmax(fmax(eV[0] / errV00, eV[1] / errV00), eV[2] / errV00);
-                if (std::isnan(eV[0]) || std::isnan(eV[1]) || std::isnan(eV[2])) err = NAN;
-                if (cont < res->cap) {
-                    if (res->err_evo_tot) res->err_evo_tot[cont] = err;
-                    if (res->err_evo_V) res->err_evo_V[cont] = err;
-                    if (res->err_evo_P) res->err_evo_P[cont] = errPt / errPt0;
-                    if (res->err_evo_it) res->err_evo_it[cont] = (double)iter;
-                }
-                cont++;
-                if (std::isnan(err)) { bad = jrx_fail(h, JRX_ERR_NAN, "NaN detected in inner loop"); break; }
-                if (dp->verbose_DR) printf("it = %lld, iter = %lld, err = %1.3e \n", (long long)itPT, (long long)iter, err);
-                const double lmin = fabs((S[3] + S[4]) + S[5]) / ((S[6] + S[7]) + S[8]);      // compute_λminV! :359-365
-                const double cV = 2 * sqrt(lmin) * dp->c_fact;
-                hipLaunchKernelGGL(k_dy3_fill3, dim3(dy3_g1(cnt.max)), dim3(256), 0, s, d->cVx, cnt.x, d->cVy, cnt.y, d->cVz, cnt.z, cV);
-                DY3_LAUNCH(h);
-                JRX_TRY(dy3_gershgorin(h, s, a));
-                JRX_TRY(dy3_dtau(h, s, a, dp->CFL, true));
-            }
-        }
-        if (bad != JRX_OK) break;
-        JRX_TRY(dy3_strain_rp(h, s, a, false));      // update pressure :263-264
-        hipLaunchKernelGGL(k_dy3_add_P, dim3(dy3_g1(cnt.c)), dim3(256), 0, s, f->P, (const double *)d->gamma_eff, (const double *)f->RP, cnt.c);
-        DY3_LAUNCH(h);
-        if (iter > dp->total_iterMax) break;
-    }
-    JRX_HIP(h, hipEventRecord(h->ev[7], s));
-    if (bad == JRX_OK) {      // epilogue :269-290; copy_stress_vertices!(Val(3)) has nothing to copy: no vertex-normal stresses are kept in 3D
-        hipLaunchKernelGGL(k_dy3_epilogue, dy3_gv(a), dim3(256), 0, s, a);
-        DY3_LAUNCH(h);
-        JRX_TRY((jrx3d_copy_old_stresses<256>(h, s, f, nx, ny, nz)));
-        h->stat_dyrel_launches += 2;
-    }
-    JRX_HIP(h, hipStreamSynchronize(s));
-    float ms = 0.f;
-    JRX_HIP(h, hipEventElapsedTime(&ms, h->ev[6], h->ev[7]));
-    res->iter = iter; res->itPH = itPH_done;
-    res->nchecks = cont < res->cap ? cont : res->cap;
-    res->time_s = ms * 1e-3;
-    return bad;
+    return dy_solve(o, dp, res);
 }
 
 }   // extern "C"
