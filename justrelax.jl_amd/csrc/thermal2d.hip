@@ -5,9 +5,7 @@
 // Cp, rho = rho0*(1 - alpha*(T - T0)) -- the PT_Density form of the un-vendored GeoParams.jl is an
 // assumption), kernels DiffusionPT_kernels.jl:327-440,519-601,603-673 and
 // thermal_bcs! (BoundaryConditions.jl:39-53; constant_value.jl:1-13; free_slip.jl:72-84; periodic.jl:1-13).
-#include "jrx_internal.hpp"
-#include "jrx_kernels.hpp"
-#include "jrx_thermal_phases.hpp"
+#include "thermal_common.hpp"
 
 namespace {
 
@@ -275,11 +273,6 @@ __global__ __launch_bounds__(256) void k_tbc2d(double *__restrict__ T, int nx, i
 }
 #undef TT_
 
-__global__ __launch_bounds__(256) void k_sub(double *__restrict__ d, const double *__restrict__ a, const double *__restrict__ b, i64 n)
-{
-    for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (i64)gridDim.x * blockDim.x) d[t] = a[t] - b[t];
-}
-
 // update_pt_thermal_arrays! (DiffusionPT_coefficients.jl:105-136) over ni of a 2D or 3D grid (nz = 1 in 2D): T read at Idx .+ 1
 __global__ __launch_bounds__(256) void k_pt_thermal_arrays(double *__restrict__ th, double *__restrict__ dr, const double *__restrict__ T, int nx, int ny, int nz,
                                                            int ndim, double _dt, const TPh ph)
@@ -333,36 +326,14 @@ jrx_status checkT(jrx_handle *h, const jrx_thermal2d_fields *t, const jrx_therma
 jrx_status launch_tbcs(jrx_handle *h, hipStream_t s, double *T, const jrx_thermal2d_params *p)
 {
     const int nx = (int)p->nx, ny = (int)p->ny;
-    const unsigned gy = (unsigned)((nx + 2 + 255) / 256), gx = (unsigned)((ny + 2 + 255) / 256);
-    auto any = [](const int32_t *m) { return m[0] | m[1] | m[2] | m[3]; };
-    // each reference kernel does rows (bot/top) then columns (left/right) per thread: rows first, then columns
-    if (any(p->constant_value_on)) {
-        if (p->constant_value_on[TB] | p->constant_value_on[TT]) {
-            hipLaunchKernelGGL(k_tbc2d, dim3(gy), dim3(256), 0, s, T, nx, ny, 0, 1, p->constant_value_on[TB], p->constant_value_on[TT], p->constant_value[TB], p->constant_value[TT]);
-            JRX_LAUNCH_CHECK(h);
-        }
-        if (p->constant_value_on[TL] | p->constant_value_on[TR]) {
-            hipLaunchKernelGGL(k_tbc2d, dim3(gx), dim3(256), 0, s, T, nx, ny, 0, 0, p->constant_value_on[TL], p->constant_value_on[TR], p->constant_value[TL], p->constant_value[TR]);
-            JRX_LAUNCH_CHECK(h);
-        }
-    }
-    if (any(p->no_flux)) {
-        if (p->no_flux[TB] | p->no_flux[TT]) {
-            hipLaunchKernelGGL(k_tbc2d, dim3(gy), dim3(256), 0, s, T, nx, ny, 1, 1, p->no_flux[TB], p->no_flux[TT], 0.0, 0.0);
-            JRX_LAUNCH_CHECK(h);
-        }
-        if (p->no_flux[TL] | p->no_flux[TR]) {
-            hipLaunchKernelGGL(k_tbc2d, dim3(gx), dim3(256), 0, s, T, nx, ny, 1, 0, p->no_flux[TL], p->no_flux[TR], 0.0, 0.0);
-            JRX_LAUNCH_CHECK(h);
-        }
-    }
-    if (any(p->periodic)) {
-        if (p->periodic[TB] | p->periodic[TT]) {
-            hipLaunchKernelGGL(k_tbc2d, dim3(gy), dim3(256), 0, s, T, nx, ny, 2, 1, p->periodic[TB], p->periodic[TT], 0.0, 0.0);
-            JRX_LAUNCH_CHECK(h);
-        }
-        if (p->periodic[TL] | p->periodic[TR]) {
-            hipLaunchKernelGGL(k_tbc2d, dim3(gx), dim3(256), 0, s, T, nx, ny, 2, 0, p->periodic[TL], p->periodic[TR], 0.0, 0.0);
+    // per BC type: rows (bot/top), then columns (left/right) -- each reference kernel does rows then columns per thread
+    const int lo[2] = {TB, TL}, hi[2] = {TT, TR}, len[2] = {nx + 2, ny + 2};
+    for (int step = 0; step < 3; step++) {
+        const int32_t *on = step == 0 ? p->constant_value_on : (step == 1 ? p->no_flux : p->periodic);
+        for (int q = 0; q < 2; q++) {
+            if (!(on[lo[q]] | on[hi[q]])) continue;
+            hipLaunchKernelGGL(k_tbc2d, dim3((unsigned)((len[q] + 255) / 256)), dim3(256), 0, s, T, nx, ny, step, q == 0 ? 1 : 0, on[lo[q]], on[hi[q]],
+                               step == 0 ? p->constant_value[lo[q]] : 0.0, step == 0 ? p->constant_value[hi[q]] : 0.0);
             JRX_LAUNCH_CHECK(h);
         }
     }
@@ -441,173 +412,93 @@ jrx_status jrx_thermal2d_check_res(jrx_handle *h, const jrx_thermal2d_fields *t,
 }   // extern "C"
 
 namespace {
+// The launches of the 2D loop (heat_solve, thermal_common.hpp).  The array and single-rheology forms fuse on a uniform grid of one rank without a periodic face; the second set
+// is the handle's tscratch2.  The forms that keep the two kernels (phase ratios, adiabatic term, Dirichlet cells) replay compute_flux! + update_T! pairs as graphs, in place.
 template <class PHT>
-jrx_status heat2d(jrx_handle *h, const jrx_thermal2d_fields *t, const jrx_thermal2d_params *p, const PHT &ph,
-                  int64_t *iter_count, double *norm_ResT, int64_t cap, int64_t *nnorms)
-{
-    constexpr bool PH = is_tph<PHT>::value;
-    if (p->nout < 1) return jrx_fail(h, JRX_ERR_ARG, "nout must be >= 1");
-    const int nx = (int)p->nx, ny = (int)p->ny;
-    const i64 nT = (i64)(nx + 2) * (ny + 2), n = (i64)nx * ny;
-    hipStream_t s = h->stream;
-    const double sq = 1.0 / sqrt((double)n);
-    JRX_HIP(h, hipMemcpyAsync(t->Told, t->T, (size_t)nT * sizeof(double), hipMemcpyDeviceToDevice, s));   // @copy thermal.Told thermal.T
-    int64_t iter = 0, cnt = 0;
-    double err = 2 * p->eps;
-    bool pt_fresh = false;
+struct Heat2 {
+    static constexpr bool PH = is_tph<PHT>::value;
+    static constexpr int SUB_BLOCKS = 256;
+    jrx_handle *h;
+    const PHT &ph;
     TArgs a;
-    a.t = *t; a.p = *p;
-    // iterations nobody observes: one fused launch, ping-pong between the caller's (T, qT) and a library-owned set (option thermal_fused)
-    const bool any_periodic = p->periodic[0] | p->periodic[1] | p->periodic[2] | p->periodic[3];
-    const bool fusable = !PH && !t->adiabatic && !t->dirichlet_mask && !p->inv_spacing[0] && h->thermal_fused && h->scratch_sets && !any_periodic && !jrx_comm_active(h) && nx >= 2 && ny >= 2;
-    const TSet2 user = {t->T, t->qTx, t->qTy};
-    TSet2 cur = user, oth = user;
-    if (fusable) {
+    const int nx, ny, n[3];
+    TSet2 set[2];
+    bool any_periodic, fusable;
+
+    Heat2(jrx_handle *h_, const jrx_thermal2d_fields *t, const jrx_thermal2d_params *p, const PHT &ph_) : h(h_), ph(ph_), nx((int)p->nx), ny((int)p->ny), n{nx, ny, 1}
+    {
+        a.t = *t; a.p = *p;
+        set[0] = set[1] = TSet2{t->T, t->qTx, t->qTy};
+        any_periodic = p->periodic[0] | p->periodic[1] | p->periodic[2] | p->periodic[3];
+        fusable = !PH && !t->adiabatic && !t->dirichlet_mask && !p->inv_spacing[0] && h->thermal_fused && h->scratch_sets && !any_periodic && !jrx_comm_active(h) && nx >= 2 && ny >= 2;
+    }
+    i64 nodes() const { return (i64)(nx + 2) * (ny + 2); }
+    size_t entries(int q) const { return q == 0 ? (size_t)nodes() : (q == 1 ? (size_t)(nx + 1) * ny : (size_t)nx * (ny + 1)); }      // of T, qTx, qTy
+    void point(int c) { a.t.T = set[c].T; a.t.qTx = set[c].qx; a.t.qTy = set[c].qy; }
+    jrx_status second_set()
+    {
         if (!(h->tscratch2[0] && h->tscratch2_dims[0] == nx && h->tscratch2_dims[1] == ny)) {
             for (int q = 0; q < 3; q++) { if (h->tscratch2[q]) JRX_HIP(h, hipFree(h->tscratch2[q])); h->tscratch2[q] = nullptr; }
             h->tscratch2_dims[0] = h->tscratch2_dims[1] = 0;
-            const size_t sz[3] = {(size_t)nT, (size_t)(nx + 1) * ny, (size_t)nx * (ny + 1)};
-            for (int q = 0; q < 3; q++) JRX_HIP(h, hipMalloc(&h->tscratch2[q], sz[q] * sizeof(double)));
+            for (int q = 0; q < 3; q++) JRX_HIP(h, hipMalloc(&h->tscratch2[q], entries(q) * sizeof(double)));
             h->tscratch2_dims[0] = nx; h->tscratch2_dims[1] = ny;
         }
-        oth = TSet2{h->tscratch2[0], h->tscratch2[1], h->tscratch2[2]};
-        JRX_HIP(h, hipMemcpyAsync(oth.T, t->T, (size_t)nT * sizeof(double), hipMemcpyDeviceToDevice, s));    // ghosts no BC rewrites
+        set[1] = TSet2{h->tscratch2[0], h->tscratch2[1], h->tscratch2[2]};
+        JRX_HIP(h, hipMemcpyAsync(set[1].T, set[0].T, entries(0) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));    // ghosts no BC rewrites
+        return JRX_OK;
     }
-    const int FTX = nx > 128 ? 256 : (nx > 64 ? 128 : 64), ntx = (nx + FTX - 1) / FTX;
-    jrx_thermal2d_fields tc = *t;
-    auto fused_launch = [&](const TArgs &aa, const TSet2 &dst) {
-        if (FTX == 256) hipLaunchKernelGGL(k_thermal2d_fused<256>, dim3((unsigned)(ntx * ny)), dim3(256), 0, s, aa, dst, ntx);
-        else if (FTX == 128) hipLaunchKernelGGL(k_thermal2d_fused<128>, dim3((unsigned)(ntx * ny)), dim3(128), 0, s, aa, dst, ntx);
-        else hipLaunchKernelGGL(k_thermal2d_fused<64>, dim3((unsigned)(ntx * ny)), dim3(64), 0, s, aa, dst, ntx);
-    };
-    // Runs of unobserved fused iterations replay as a captured graph of GIT iterations (an even count: the ping-pong sets end where they started): on these
-    // launch-bound grids the gap between dependent launches is shorter inside a graph (scripts/graph_probe.hip: 4.6 vs 5.7 - 6.1 us per pair of short kernels).
-    // One graph per parity of the current set, built on first use, destroyed at the end; option "loop_graphs" = 0 keeps plain launches.
-    constexpr int GIT = 32;
-    GraphExecs gexec;        // released on every exit path
-    bool graphs = fusable && h->loop_graphs;
-    // the forms that keep the two kernels (phase ratios, adiabatic term, Dirichlet cells) replay compute_flux! + update_T! pairs the same way, in place
-    bool graphs2 = !fusable && h->loop_graphs && !any_periodic && !jrx_comm_active(h) && nx >= 2 && ny >= 2 && n <= 200000;
-    auto destroy_graphs = [&]() { gexec.reset(); };
-    while (err > p->eps && iter < p->iterMax) {
-        if (graphs) {
-            const int64_t nxt = std::min<int64_t>(((iter / p->nout) + 1) * p->nout, p->iterMax);      // 1-based number of the next observed iteration
-            int64_t run = nxt - 1 - iter;                                                              // unobserved iterations from here
-            if (run >= GIT) {
-                const int par = cur.T == user.T ? 0 : 1;
-                if (!gexec[par]) {
-                    hipGraph_t g = nullptr;
-                    bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                    if (ok) {
-                        TSet2 c = cur, o = oth;
-                        for (int q = 0; q < GIT; q++) {
-                            TArgs aa = a;
-                            aa.t.T = c.T; aa.t.qTx = c.qx; aa.t.qTy = c.qy;
-                            fused_launch(aa, o);
-                            const TSet2 tmp = c; c = o; o = tmp;
-                        }
-                        ok = hipStreamEndCapture(s, &g) == hipSuccess && g != nullptr;
-                    }
-                    if (ok) ok = hipGraphInstantiate(&gexec[par], g, nullptr, nullptr, 0) == hipSuccess;
-                    if (g) (void)hipGraphDestroy(g);
-                    if (!ok) { (void)hipGetLastError(); gexec[par] = nullptr; graphs = false; }
-                }
-                if (gexec[par]) {
-                    while (run >= GIT) {
-                        JRX_HIP(h, hipGraphLaunch(gexec[par], s));
-                        iter += GIT; run -= GIT;
-                        h->stat_thermal_fused += GIT; h->stat_graph_replays++;
-                    }
-                    continue;
-                }
-            }
-        }
-        if (graphs2 && (!PH || pt_fresh)) {
-            const int64_t nxt = std::min<int64_t>(((iter / p->nout) + 1) * p->nout, p->iterMax);
-            int64_t run = nxt - 1 - iter;
-            if (run >= GIT) {
-                if (!gexec[0]) {
-                    hipGraph_t g = nullptr;
-                    bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                    if (ok) {
-                        TArgs aa = a;
-                        aa.t.T = cur.T; aa.t.qTx = cur.qx; aa.t.qTy = cur.qy; aa.wpt = PH;
-                        for (int q = 0; q < GIT; q++) {
-                            hipLaunchKernelGGL(k_flux2d<PHT>, dim3((unsigned)(((i64)(nx + 1) * (ny + 1) + 255) / 256)), dim3(256), 0, s, aa, ph);
-                            hipLaunchKernelGGL((k_updateT2d<false, true, PHT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, aa, ph);
-                        }
-                        ok = hipStreamEndCapture(s, &g) == hipSuccess && g != nullptr;
-                    }
-                    if (ok) ok = hipGraphInstantiate(&gexec[0], g, nullptr, nullptr, 0) == hipSuccess;
-                    if (g) (void)hipGraphDestroy(g);
-                    if (!ok) { (void)hipGetLastError(); gexec[0] = nullptr; graphs2 = false; }
-                }
-                if (gexec[0]) {
-                    while (run >= GIT) {
-                        JRX_HIP(h, hipGraphLaunch(gexec[0], s));
-                        iter += GIT; run -= GIT;
-                        h->stat_graph_replays++;
-                    }
-                    continue;
-                }
-            }
-        }
-        const bool observed = ((iter + 1) % p->nout == 0) || (iter + 1 >= p->iterMax);
-        a.t.T = cur.T; a.t.qTx = cur.qx; a.t.qTy = cur.qy;
-        if constexpr (PH) {      // update_pt_thermal_arrays!(pt_thermal, phase, rheology, args, _dt) -- DiffusionPT_solver.jl:233-234
-            // on unobserved iterations update_T! writes the coefficients of the next iteration itself (same values: they depend on the cell's own new T
-            // only); observed iterations leave pt_thermal as the reference does, and the stand-alone kernel runs before the following iteration
-            if (!pt_fresh) JRX_TRY(jrx_enqueue_pt_thermal_arrays(h, s, t->thetar_dtau, t->dtau_rho, cur.T, nx, ny, 1, 2, 1.0 / p->dt, ph));
-            pt_fresh = !observed;
-        }
-        if (fusable && !observed) {
-            fused_launch(a, oth);
-            h->stat_thermal_fused++;
-            JRX_LAUNCH_CHECK(h);
-            const TSet2 tmp = cur; cur = oth; oth = tmp;
-        } else {
-            tc.T = cur.T; tc.qTx = cur.qx; tc.qTy = cur.qy;
-            JRX_TRY(enqueue_titer(h, &tc, p, ph, true, PH && pt_fresh));
-        }
-        iter++;
-        if (iter % p->nout == 0) {
-            hipLaunchKernelGGL((k_updateT2d<true, false, PHT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, ph);
-            JRX_LAUNCH_CHECK(h);
-            RedArr Z = {nullptr, {0, 0, 0}, 0}, A3 = {t->ResT, {nx, ny, 1}, 0};
-            int nb = (int)((n + 2047) / 2048);
-            nb = nb < 1 ? 1 : (nb > kMaxRedBlocks ? kMaxRedBlocks : nb);
-            hipLaunchKernelGGL(k_sumsq_partial, dim3(nb), dim3(256), 0, s, Z, Z, Z, A3, h->d_partials);
-            JRX_LAUNCH_CHECK(h);
-            hipLaunchKernelGGL(k_sumsq_final, dim3(1), dim3(256), 0, s, h->d_partials, nb, h->d_sums);
-            JRX_LAUNCH_CHECK(h);
-            JRX_HIP(h, hipMemcpyAsync(h->h_sums, h->d_sums, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-            JRX_HIP(h, hipStreamSynchronize(s));
-            err = sqrt(h->h_sums[3]) * sq;          // norm(ResT) * _sq_len_RT : local norm, no reduction across ranks (:131)
-            // The reference stops each rank on its own local norm (no MPI reduction at :131); with an exchange in every iteration ranks that
-            // cross ϵ at different checks would then wait for each other for ever.  Deviation: with more than one rank the loop test uses the
-            // maximum of the local norms, so that all ranks leave together; the reported norm_ResT stays the local one.
-            double err_stop = err;
-            if (jrx_comm_active(h)) JRX_TRY(jrx_allreduce_host(h, &err_stop, 1, 1));
-            if (cnt < cap) {
-                if (norm_ResT) norm_ResT[cnt] = err;
-                if (iter_count) iter_count[cnt] = iter;
-            }
-            cnt++;
-            if (p->verbose && jrx_comm_rank(h) == 0) printf("iter = %lld, err = %1.3e \n", (long long)iter, err);
-            err = err_stop;
-        }
+    jrx_status fused(int c)
+    {
+        point(c);
+        const int FTX = nx > 128 ? 256 : (nx > 64 ? 128 : 64), ntx = (nx + FTX - 1) / FTX;
+        dispatch_const<256, 128, 64>(FTX, [&](auto TX) {
+            hipLaunchKernelGGL(k_thermal2d_fused<decltype(TX)::value>, dim3((unsigned)(ntx * ny)), dim3(FTX), 0, h->stream, a, set[c ^ 1], ntx);
+        });
+        JRX_LAUNCH_CHECK(h);
+        return JRX_OK;
     }
-    destroy_graphs();
-    if (cur.T != user.T) {      // leave the results in the caller's arrays
-        JRX_HIP(h, hipMemcpyAsync(user.T, cur.T, (size_t)nT * sizeof(double), hipMemcpyDeviceToDevice, s));
-        JRX_HIP(h, hipMemcpyAsync(user.qx, cur.qx, (size_t)(nx + 1) * ny * sizeof(double), hipMemcpyDeviceToDevice, s));
-        JRX_HIP(h, hipMemcpyAsync(user.qy, cur.qy, (size_t)nx * (ny + 1) * sizeof(double), hipMemcpyDeviceToDevice, s));
+    jrx_status two_kernels(int c, bool, bool wpt)
+    {
+        point(c);
+        return enqueue_titer(h, &a.t, &a.p, ph, true, wpt);
     }
-    hipLaunchKernelGGL(k_sub, dim3(256), dim3(256), 0, s, t->dT, (const double *)t->T, (const double *)t->Told, nT);   // update_ΔT!
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(s));
-    if (nnorms) *nnorms = cnt < cap ? cnt : cap;
-    return JRX_OK;
+    jrx_status residual(int c)
+    {
+        point(c);
+        hipLaunchKernelGGL((k_updateT2d<true, false, PHT>), dim3((unsigned)(((i64)nx * ny + 255) / 256)), dim3(256), 0, h->stream, a, ph);
+        JRX_LAUNCH_CHECK(h);
+        return JRX_OK;
+    }
+    jrx_status refresh_pt(int c)
+    {
+        if constexpr (PH) return jrx_enqueue_pt_thermal_arrays(h, h->stream, a.t.thetar_dtau, a.t.dtau_rho, set[c].T, nx, ny, 1, 2, 1.0 / a.p.dt, ph);
+        else return JRX_OK;
+    }
+    jrx_status copy_back()
+    {
+        double *const dst[3] = {set[0].T, set[0].qx, set[0].qy}, *const src[3] = {set[1].T, set[1].qx, set[1].qy};
+        for (int q = 0; q < 3; q++) JRX_HIP(h, hipMemcpyAsync(dst[q], src[q], entries(q) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        return JRX_OK;
+    }
+    bool graphable() const { return fusable || (!any_periodic && !jrx_comm_active(h) && nx >= 2 && ny >= 2 && (i64)nx * ny <= 200000); }
+    jrx_status graph_iteration(int c)
+    {
+        if (fusable) return fused(c);
+        point(c);
+        TArgs aa = a;
+        aa.wpt = PH;
+        hipLaunchKernelGGL(k_flux2d<PHT>, dim3((unsigned)(((i64)(nx + 1) * (ny + 1) + 255) / 256)), dim3(256), 0, h->stream, aa, ph);
+        JRX_LAUNCH_CHECK(h);
+        hipLaunchKernelGGL((k_updateT2d<false, true, PHT>), dim3((unsigned)(((i64)nx * ny + 255) / 256)), dim3(256), 0, h->stream, aa, ph);
+        JRX_LAUNCH_CHECK(h);
+        return JRX_OK;
+    }
+};
+template <class PHT>
+jrx_status heat2d(jrx_handle *h, const jrx_thermal2d_fields *t, const jrx_thermal2d_params *p, const PHT &ph, int64_t *iter_count, double *norm_ResT, int64_t cap, int64_t *nnorms)
+{
+    Heat2<PHT> o(h, t, p, ph);
+    return heat_solve(o, iter_count, norm_ResT, cap, nnorms);
 }
 }   // namespace
 
@@ -630,14 +521,15 @@ jrx_status jrx_heatdiffusion_PT2d_phases(jrx_handle *h, const jrx_thermal2d_fiel
     JRX_TRY(checkT(h, t, &q));
     JRX_TRY(tph_check(h, ph, pf, false));
     q.rheology_form = 2;
+    jrx_status st = JRX_OK;
+    // option "thermal_np_const" (default): the instantiations with the phase count as a constant
+    if (dispatch_const<1, 2, 3, 4>(h->thermal_np_const ? ph->nphase : 0, [&](auto N) {
+            TPhN<decltype(N)::value> y;
+            y.m = *ph; y.f = *pf;
+            st = heat2d(h, t, &q, y, iter_count, norm_ResT, cap, nnorms);
+        })) return st;
     TPh x;
     x.m = *ph; x.f = *pf;
-    switch (h->thermal_np_const ? ph->nphase : 0) {       // option "thermal_np_const" (default): the instantiations with the phase count as a constant
-#define TPN(N_) case N_: { TPhN<N_> y; y.m = *ph; y.f = *pf; return heat2d(h, t, &q, y, iter_count, norm_ResT, cap, nnorms); }
-    TPN(1) TPN(2) TPN(3) TPN(4)
-#undef TPN
-    default: break;
-    }
     return heat2d(h, t, &q, x, iter_count, norm_ResT, cap, nnorms);
 }
 

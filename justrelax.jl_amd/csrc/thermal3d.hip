@@ -5,9 +5,7 @@
 // DiffusionPT_kernels.jl:6-61 (compute_flux! 3D), :160-199 (update_T! 3D), :250-282 (check_res! 3D), :670-673 (update_ΔT!)
 // and thermal_bcs! 3D (BoundaryConditions.jl:46-54; constant_value.jl:15-33; free_slip.jl:86-103; periodic.jl:42-60).
 // 3D thermal face names: bot <-> k = 1, top <-> k = end.  HBM-bound fp64 stencils (20 array passes per iteration).
-#include "jrx_internal.hpp"
-#include "jrx_kernels.hpp"
-#include "jrx_thermal_phases.hpp"
+#include "thermal_common.hpp"
 
 namespace {
 
@@ -726,11 +724,6 @@ __global__ __launch_bounds__(256) void k_tbc3d(double *__restrict__ T, int nx, i
 #undef T3_
 #undef CC_
 
-__global__ __launch_bounds__(256) void k_sub3(double *__restrict__ d, const double *__restrict__ a, const double *__restrict__ b, i64 n)
-{
-    for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (i64)gridDim.x * blockDim.x) d[t] = a[t] - b[t];
-}
-
 jrx_status checkT3(jrx_handle *h, const jrx_thermal3d_fields *t, const jrx_thermal3d_params *p)
 {
     if (!h) return JRX_ERR_ARG;
@@ -764,20 +757,6 @@ jrx_status launch_tbcs3(jrx_handle *h, hipStream_t s, double *T, const jrx_therm
             JRX_LAUNCH_CHECK(h);
         }
     }
-    return JRX_OK;
-}
-
-static jrx_status ensure_tscratch(jrx_handle *h, int nx, int ny, int nz)
-{
-    if (h->tscratch[0] && h->tscratch_dims[0] == nx && h->tscratch_dims[1] == ny && h->tscratch_dims[2] == nz) return JRX_OK;
-    for (int q = 0; q < 4; q++) {
-        if (h->tscratch[q]) JRX_TRY(jrx_dev_free(h, h->tscratch[q]));
-        h->tscratch[q] = nullptr;
-    }
-    h->tscratch_dims[0] = h->tscratch_dims[1] = h->tscratch_dims[2] = 0;
-    const size_t n[4] = {(size_t)(nx + 2) * (ny + 2) * (nz + 2), (size_t)(nx + 1) * ny * nz, (size_t)nx * (ny + 1) * nz, (size_t)nx * ny * (nz + 1)};
-    for (int q = 0; q < 4; q++) JRX_TRY(jrx_dev_alloc(h, n[q] * sizeof(double), (void **)&h->tscratch[q], 1));
-    h->tscratch_dims[0] = nx; h->tscratch_dims[1] = ny; h->tscratch_dims[2] = nz;
     return JRX_OK;
 }
 
@@ -848,189 +827,128 @@ jrx_status jrx_thermal3d_check_res(jrx_handle *h, const jrx_thermal3d_fields *t,
 }   // extern "C"
 
 namespace {
+// The launches of the 3D loop (heat_solve, thermal_common.hpp).  The array and single-rheology forms fuse on one rank without a periodic face (option "thermal_fused" = 0: always
+// the two kernels); the phase-ratio form fuses, too, where the phase count is a template constant (k_thermal3d_fused_ph; the default tile plan only): θr_dτ then ping-pongs with
+// T and the fluxes, through the handle's ητ scratch.  The second set is the handle's tscratch, from the field pool.  Only fused runs of small grids replay as graphs.
 template <class PHT>
-jrx_status heat3d(jrx_handle *h, const jrx_thermal3d_fields *t, const jrx_thermal3d_params *p, const PHT &ph, int64_t *iter_count, double *norm_ResT,
-                  int64_t cap, int64_t *nnorms)
-{
-    constexpr bool PH = is_tph<PHT>::value;
-    if (p->nout < 1) return jrx_fail(h, JRX_ERR_ARG, "nout must be >= 1");
-    const int nx = (int)p->nx, ny = (int)p->ny, nz = (int)p->nz;
-    const i64 nT = (i64)(nx + 2) * (ny + 2) * (nz + 2), n = (i64)nx * ny * nz;
-    hipStream_t s = h->stream;
-    const double sq = 1.0 / sqrt((double)n);
-    JRX_HIP(h, hipMemcpyAsync(t->Told, t->T, (size_t)nT * sizeof(double), hipMemcpyDeviceToDevice, s));   // @copy thermal.Told thermal.T
-    int64_t iter = 0, cnt = 0;
-    double err = 2 * p->eps;
-    bool pt_fresh = false;
+struct Heat3 {
+    static constexpr bool PH = is_tph<PHT>::value;
+    static constexpr int NPHC = tph_np<PHT>::value, SUB_BLOCKS = 1024;
+    jrx_handle *h;
+    const PHT &ph;
     T3Args a;
-    a.t = *t; a.p = *p;
-    a.nt = h->thermal_nt;
-    // Iterations nobody observes run as one fused launch that ping-pongs (T, qT) between the caller's arrays and a library-owned set
-    // (option "thermal_fused" = 0: always the two kernels); observed ones (check / last) run the two kernels in place on the current set.
-    bool any_periodic = false;
-    for (int q = 0; q < 6; q++) any_periodic |= p->periodic[q] != 0;
-    // the phase-ratio form fuses, too, where the phase count is a template constant (k_thermal3d_fused_ph; its default tile shape only): θr_dτ then ping-pongs with T and the fluxes
-    constexpr int NPHC = tph_np<PHT>::value;
-    const bool fusable = (!PH || (NPHC > 0 && h->thermal_cfg == 0 && h->thermal_xg == 8 && h->thermal_fused_ph)) && !t->adiabatic && !t->dirichlet_mask && h->thermal_fused &&
-                         h->scratch_sets && !any_periodic && !jrx_comm_active(h);
-    const TSet user = {t->T, t->qTx, t->qTy, t->qTz};
-    TSet cur = user, oth = user;
-    double *const th_user = const_cast<double *>(t->thetar_dtau);
-    double *th_cur = th_user, *th_oth = th_user;
-    if (fusable) {
-        JRX_TRY(ensure_tscratch(h, nx, ny, nz));
-        oth = TSet{h->tscratch[0], h->tscratch[1], h->tscratch[2], h->tscratch[3]};
-        // ghosts that no BC rewrites (prescribed values) must exist in both sets
-        JRX_HIP(h, hipMemcpyAsync(oth.T, t->T, (size_t)nT * sizeof(double), hipMemcpyDeviceToDevice, s));
-        if (PH) { JRX_TRY(jrx_ensure_etatau(h, (size_t)n)); th_oth = h->etatau; }
+    const int nx, ny, nz, n[3];
+    const heat_plan::Tile3 tile;
+    TSet set[2];
+    double *th[2];
+    bool fusable;
+
+    Heat3(jrx_handle *h_, const jrx_thermal3d_fields *t, const jrx_thermal3d_params *p, const PHT &ph_)
+        : h(h_), ph(ph_), nx((int)p->nx), ny((int)p->ny), nz((int)p->nz), n{nx, ny, nz}, tile(heat_plan::tile3d(nx, ny, nz, h_->thermal_cfg, h_->thermal_xg))
+    {
+        a.t = *t; a.p = *p;
+        a.nt = h->thermal_nt;
+        set[0] = set[1] = TSet{t->T, t->qTx, t->qTy, t->qTz};
+        th[0] = th[1] = const_cast<double *>(t->thetar_dtau);
+        bool any_periodic = false;
+        for (int q = 0; q < 6; q++) any_periodic |= p->periodic[q] != 0;
+        fusable = (!PH || (NPHC > 0 && h->thermal_cfg == 0 && h->thermal_xg == 8 && h->thermal_fused_ph)) && !t->adiabatic && !t->dirichlet_mask && h->thermal_fused &&
+                  h->scratch_sets && !any_periodic && !jrx_comm_active(h);
     }
-    // tile = TX cells of R rows, KZ planes deep; option "thermal_cfg" = R*10000 + (TX/64)*100 + KZ overrides (tuning)
-    const int cfg = h->thermal_cfg;
-    const int FR = cfg ? cfg / 10000 : 1, FTX = cfg ? ((cfg / 100) % 100) * 64 : (nx > 128 ? 256 : (nx > 64 ? 128 : 64));
-    // planes per block: 4, halved while the launch has fewer than 4096 waves -- a block marches its planes one after the other, and a small grid in 4-plane chunks leaves most of the
-    // chip idle (64^3: 1024 single-wave blocks): 16^3 74.7 k -> 175 k it/s, 32^3 72.4 k -> 159 k, 48^3 64.3 k -> 112 k, 64^3 52.5 k -> 101 k with one plane per block; from 96^3 on
-    // 4 planes are the better depth again (35.5 k against 33.2 k) (profiles/r03_small_grids_graphs.txt)
-    int FKZ = cfg ? cfg % 100 : 4;
-    const int FXG = h->thermal_xg;
-    // (the shallower chunks are instantiated for the default XCD band width only: with the tuning switch "thermal_xg" != 8 the depth stays 4)
-    if (!cfg && FXG == 8)
-        while (FKZ > 1 && (i64)((nx + FTX - 1) / FTX) * (FTX / 64) * ny * ((nz + FKZ - 1) / FKZ) < 4096) FKZ /= 2;
-    const int ntx = (nx + FTX - 1) / FTX, nty = (ny + FR - 1) / FR, ntz = (nz + FKZ - 1) / FKZ;
-    // launch_fused: one unobserved iteration from set c into set o (the caller swaps)
-    auto launch_fused = [&](const TSet &c, const TSet &o, double *thc = nullptr, double *tho = nullptr) -> jrx_status {
-        T3Args b = a;
-        b.t.T = c.T; b.t.qTx = c.qx; b.t.qTy = c.qy; b.t.qTz = c.qz;
+    i64 nodes() const { return (i64)(nx + 2) * (ny + 2) * (nz + 2); }
+    size_t entries(int q) const      // of T, qTx, qTy, qTz
+    {
+        return q == 0 ? (size_t)nodes() : (q == 1 ? (size_t)(nx + 1) * ny * nz : (q == 2 ? (size_t)nx * (ny + 1) * nz : (size_t)nx * ny * (nz + 1)));
+    }
+    void point(int c)
+    {
+        a.t.T = set[c].T; a.t.qTx = set[c].qx; a.t.qTy = set[c].qy; a.t.qTz = set[c].qz;
+        a.t.thetar_dtau = th[c];
+    }
+    jrx_status second_set()
+    {
+        if (!(h->tscratch[0] && h->tscratch_dims[0] == nx && h->tscratch_dims[1] == ny && h->tscratch_dims[2] == nz)) {
+            for (int q = 0; q < 4; q++) {
+                if (h->tscratch[q]) JRX_TRY(jrx_dev_free(h, h->tscratch[q]));
+                h->tscratch[q] = nullptr;
+            }
+            h->tscratch_dims[0] = h->tscratch_dims[1] = h->tscratch_dims[2] = 0;
+            for (int q = 0; q < 4; q++) JRX_TRY(jrx_dev_alloc(h, entries(q) * sizeof(double), (void **)&h->tscratch[q], 1));
+            h->tscratch_dims[0] = nx; h->tscratch_dims[1] = ny; h->tscratch_dims[2] = nz;
+        }
+        set[1] = TSet{h->tscratch[0], h->tscratch[1], h->tscratch[2], h->tscratch[3]};
+        // ghosts that no BC rewrites (prescribed values) must exist in both sets
+        JRX_HIP(h, hipMemcpyAsync(set[1].T, set[0].T, entries(0) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        if (PH) { JRX_TRY(jrx_ensure_etatau(h, (size_t)nx * ny * nz)); th[1] = h->etatau; }
+        return JRX_OK;
+    }
+    jrx_status fused(int c)
+    {
+        point(c);
+        hipStream_t s = h->stream;
+        const TSet &o = set[c ^ 1];
+        const int FTX = tile.TX, FKZ = tile.KZ, FR = tile.R, FXG = h->thermal_xg, ntx = tile.ntx, nty = tile.nty;
+        const unsigned nblk = (unsigned)(ntx * nty * tile.ntz);
+        bool launched = false;
         if constexpr (NPHC > 0) {
-            b.t.thetar_dtau = thc;
-            const TSetP op = {o.T, o.qx, o.qy, o.qz, tho};
-            bool ok = true;
-#define THP(TX_, KZ_) if (FTX == TX_ && FKZ == KZ_) hipLaunchKernelGGL((k_thermal3d_fused_ph<TX_, KZ_, 8, NPHC>), dim3((unsigned)(ntx * nty * ntz)), dim3(TX_), 0, s, b, op, ph, ntx, nty); else
-            THP(256, 4) THP(128, 4) THP(64, 4) THP(256, 2) THP(128, 2) THP(64, 2) THP(256, 1) THP(128, 1) THP(64, 1) ok = false;
+            const TSetP op = {o.T, o.qx, o.qy, o.qz, th[c ^ 1]};
+#define THP(TX_, KZ_) if (FTX == TX_ && FKZ == KZ_) { hipLaunchKernelGGL((k_thermal3d_fused_ph<TX_, KZ_, 8, NPHC>), dim3(nblk), dim3(TX_), 0, s, a, op, ph, ntx, nty); launched = true; }
+            HEAT3_FUSED_PH_SHAPES(THP)
 #undef THP
-            if (!ok) return jrx_fail(h, JRX_ERR_ARG, "internal: no fused phase-ratio instantiation for this tile shape");
-            h->stat_thermal_fused++;
+            if (!launched) return jrx_fail(h, JRX_ERR_ARG, "internal: no fused phase-ratio instantiation for this tile shape");
             JRX_LAUNCH_CHECK(h);
             return JRX_OK;
         }
-#define THL(TX_, KZ_, R_, XG_)                                                                                                      \
-    if (FTX == TX_ && FKZ == KZ_ && FR == R_ && FXG == XG_) {                                                                       \
-        hipLaunchKernelGGL((k_thermal3d_fused<TX_, KZ_, XG_, R_>), dim3((unsigned)(ntx * nty * ntz)), dim3(TX_), 0, s, b, o, ntx, nty); \
-        launched = true; h->stat_thermal_fused++;                                                                                                         \
-    }
-        bool launched = false;
         if (h->thermal_tile == 4 || h->thermal_tile == 8) {        // round 6: 64 x TY tiles, y neighbours through LDS (k_thermal3d_fused_t)
             const int TYv = h->thermal_tile, ntx_t = (nx + 63) / 64, nty_t = (ny + TYv - 1) / TYv, ntz_t = (nz + 3) / 4;
             const unsigned nb = (unsigned)(ntx_t * nty_t * ntz_t);
-            const int xg = h->thermal_xg == 8 ? (TYv == 4 ? 2 : 1) : h->thermal_xg;      // default band: 8 rows per XCD, as the row-segment form has
-#define THT(TY_, XG_) if (TYv == TY_ && xg == XG_) { hipLaunchKernelGGL((k_thermal3d_fused_t<TY_, 4, XG_>), dim3(nb), dim3(64 * TY_), 0, s, b, o, ntx_t, nty_t); launched = true; }
+            const int xg = FXG == 8 ? (TYv == 4 ? 2 : 1) : FXG;      // default band: 8 rows per XCD, as the row-segment form has
+#define THT(TY_, XG_) if (TYv == TY_ && xg == XG_) { hipLaunchKernelGGL((k_thermal3d_fused_t<TY_, 4, XG_>), dim3(nb), dim3(64 * TY_), 0, s, a, o, ntx_t, nty_t); launched = true; }
             THT(4, 1) THT(4, 2) THT(4, 4) THT(8, 1) THT(8, 2) THT(8, 4)
 #undef THT
-            if (launched) { h->stat_thermal_fused++; JRX_LAUNCH_CHECK(h); return JRX_OK; }
+            if (launched) { JRX_LAUNCH_CHECK(h); return JRX_OK; }
         }
-        // measured at 256^3 (profiles/r01_thermal3d_fused_sweep.txt): one row per thread 2289 it/s, two rows 1526, four rows 1301
-        THL(256, 4, 1, 8) THL(128, 4, 1, 8) THL(64, 4, 1, 8) THL(256, 8, 1, 8) THL(256, 4, 2, 8)
-        THL(256, 4, 1, 1) THL(256, 4, 1, 2) THL(256, 4, 1, 4) THL(256, 2, 1, 1) THL(256, 2, 1, 2) THL(256, 8, 1, 1) THL(128, 4, 1, 1) THL(64, 4, 1, 1)
-        THL(64, 2, 1, 8) THL(64, 1, 1, 8) THL(128, 2, 1, 8) THL(128, 1, 1, 8) THL(256, 2, 1, 8) THL(256, 1, 1, 8)
-        if (!launched) return jrx_fail(h, JRX_ERR_ARG, "JRX_TH_CFG: no such configuration");
+#define THL(TX_, KZ_, R_, XG_) if (FTX == TX_ && FKZ == KZ_ && FR == R_ && FXG == XG_) { hipLaunchKernelGGL((k_thermal3d_fused<TX_, KZ_, XG_, R_>), dim3(nblk), dim3(TX_), 0, s, a, o, ntx, nty); launched = true; }
+        HEAT3_FUSED_SHAPES(THL)
 #undef THL
+        if (!launched) return jrx_fail(h, JRX_ERR_ARG, "JRX_TH_CFG: no such configuration");
         JRX_LAUNCH_CHECK(h);
         return JRX_OK;
-    };
-    // small grids: runs of unobserved one-launch iterations replay as captured graphs of GIT iterations (an even count: the ping-pong sets end where they
-    // began; one graph per parity), as the 2D loop does (option "loop_graphs"; profiles/r03_small_grids_graphs.txt)
-    constexpr int GIT = 32;
-    GraphExecs gexec;
-    bool graphs = h->loop_graphs && fusable && (double)n <= kGraphCells3D;
-    while (err > p->eps && iter < p->iterMax) {
-        if (graphs) {
-            // observed iterations (1-based number it1 = iter + 1): the multiples of nout and every it1 >= iterMax
-            int64_t nxt = ((iter / p->nout) + 1) * p->nout;
-            if (nxt > p->iterMax) nxt = p->iterMax;
-            int64_t run = nxt - 1 - iter;
-            if (run >= GIT) {
-                const int par = cur.T == user.T ? 0 : 1;
-                if (!gexec[par]) {
-                    JRX_TRY(jrx_capture_graph(s, &gexec[par], [&]() -> jrx_status {
-                        TSet c = cur, o = oth;
-                        double *tc_ = th_cur, *to_ = th_oth;
-                        for (int q = 0; q < GIT; q++) {
-                            JRX_TRY(launch_fused(c, o, tc_, to_));
-                            const TSet tmp = c; c = o; o = tmp;
-                            double *tt_ = tc_; tc_ = to_; to_ = tt_;
-                        }
-                        return JRX_OK;
-                    }));
-                    if (!gexec[par]) graphs = false;
-                    else h->stat_thermal_fused -= GIT;          // the capture counted launches that have not run
-                }
-                if (gexec[par]) {
-                    while (run >= GIT) {
-                        JRX_HIP(h, hipGraphLaunch(gexec[par], s));
-                        iter += GIT; run -= GIT;
-                        h->stat_thermal_fused += GIT; h->stat_graph_replays++;
-                    }
-                    continue;
-                }
-            }
-        }
-        // qT*2 is observable after the loop as well (the arrays belong to the caller): written on check iterations and on the last one
-        const bool q2 = ((iter + 1) % p->nout == 0) || (iter + 1 >= p->iterMax);
-        a.t.T = cur.T; a.t.qTx = cur.qx; a.t.qTy = cur.qy; a.t.qTz = cur.qz;
-        a.t.thetar_dtau = th_cur;
-        if constexpr (PH) {    // update_pt_thermal_arrays!(pt_thermal, phase, rheology, args, _dt) -- DiffusionPT_solver.jl:233-234
-            // on unobserved iterations update_T! writes the coefficients of the next iteration itself (same values: they depend on the cell's own new T
-            // only); observed iterations leave pt_thermal as the reference does, and the stand-alone kernel runs before the following iteration
-            if (!pt_fresh) JRX_TRY(jrx_enqueue_pt_thermal_arrays(h, s, th_cur, const_cast<double *>(t->dtau_rho), cur.T, nx, ny, nz, 3, 1.0 / p->dt, ph));
-            pt_fresh = !q2;
-            a.wpt = pt_fresh;
-        }
-        if (fusable && !q2) {
-            JRX_TRY(launch_fused(cur, oth, th_cur, th_oth));
-            const TSet tmp = cur; cur = oth; oth = tmp;
-            if (PH) { double *tt_ = th_cur; th_cur = th_oth; th_oth = tt_; }
-        } else {
-            JRX_TRY(enqueue_titer3(h, &a.t, p, ph, q2, true, a.wpt));
-        }
-        iter++;
-        if (iter % p->nout == 0) {
-            hipLaunchKernelGGL((k_updateT3d<true, false, PHT>), GRID_IJK(nx, ny, nz), dim3(256), 0, s, a, ph);
-            JRX_LAUNCH_CHECK(h);
-            RedArr Z = {nullptr, {0, 0, 0}, 0}, A3 = {t->ResT, {nx, ny, nz}, 0};
-            int nb = (int)((n + 2047) / 2048);
-            nb = nb < 1 ? 1 : (nb > kMaxRedBlocks ? kMaxRedBlocks : nb);
-            hipLaunchKernelGGL(k_sumsq_partial, dim3(nb), dim3(256), 0, s, Z, Z, Z, A3, h->d_partials);
-            JRX_LAUNCH_CHECK(h);
-            hipLaunchKernelGGL(k_sumsq_final, dim3(1), dim3(256), 0, s, h->d_partials, nb, h->d_sums);
-            JRX_LAUNCH_CHECK(h);
-            JRX_HIP(h, hipMemcpyAsync(h->h_sums, h->d_sums, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-            JRX_HIP(h, hipStreamSynchronize(s));
-            err = sqrt(h->h_sums[3]) * sq;          // norm(ResT) * _sq_len_RT (local norm, DiffusionPT_solver.jl:131)
-            // The reference stops each rank on its own local norm (no MPI reduction at :131); with an exchange in every iteration ranks that
-            // cross ϵ at different checks would then wait for each other for ever.  Deviation: with more than one rank the loop test uses the
-            // maximum of the local norms, so that all ranks leave together; the reported norm_ResT stays the local one.
-            double err_stop = err;
-            if (jrx_comm_active(h)) JRX_TRY(jrx_allreduce_host(h, &err_stop, 1, 1));
-            if (cnt < cap) {
-                if (norm_ResT) norm_ResT[cnt] = err;
-                if (iter_count) iter_count[cnt] = iter;
-            }
-            cnt++;
-            if (p->verbose && jrx_comm_rank(h) == 0) printf("iter = %lld, err = %1.3e \n", (long long)iter, err);
-            err = err_stop;
-        }
     }
-    if (th_cur != th_user) JRX_HIP(h, hipMemcpyAsync(th_user, th_cur, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));      // ... and the PT coefficients of the phase-ratio form
-    if (cur.T != user.T) {      // leave the results in the caller's arrays
-        JRX_HIP(h, hipMemcpyAsync(user.T, cur.T, (size_t)nT * sizeof(double), hipMemcpyDeviceToDevice, s));
-        JRX_HIP(h, hipMemcpyAsync(user.qx, cur.qx, (size_t)(nx + 1) * ny * nz * sizeof(double), hipMemcpyDeviceToDevice, s));
-        JRX_HIP(h, hipMemcpyAsync(user.qy, cur.qy, (size_t)nx * (ny + 1) * nz * sizeof(double), hipMemcpyDeviceToDevice, s));
-        JRX_HIP(h, hipMemcpyAsync(user.qz, cur.qz, (size_t)nx * ny * (nz + 1) * sizeof(double), hipMemcpyDeviceToDevice, s));
+    // qT*2 is observable after the loop as well (the arrays belong to the caller): written on check iterations and on the last one
+    jrx_status two_kernels(int c, bool observed, bool wpt)
+    {
+        point(c);
+        return enqueue_titer3(h, &a.t, &a.p, ph, observed, true, wpt);
     }
-    hipLaunchKernelGGL(k_sub3, dim3(1024), dim3(256), 0, s, t->dT, (const double *)t->T, (const double *)t->Told, nT);   // update_ΔT!
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(s));
-    if (nnorms) *nnorms = cnt < cap ? cnt : cap;
-    return JRX_OK;
+    jrx_status residual(int c)
+    {
+        point(c);
+        hipLaunchKernelGGL((k_updateT3d<true, false, PHT>), GRID_IJK(nx, ny, nz), dim3(256), 0, h->stream, a, ph);
+        JRX_LAUNCH_CHECK(h);
+        return JRX_OK;
+    }
+    jrx_status refresh_pt(int c)
+    {
+        if constexpr (PH) return jrx_enqueue_pt_thermal_arrays(h, h->stream, th[c], const_cast<double *>(a.t.dtau_rho), set[c].T, nx, ny, nz, 3, 1.0 / a.p.dt, ph);
+        else return JRX_OK;
+    }
+    jrx_status copy_back()
+    {
+        if (th[1] != th[0]) JRX_HIP(h, hipMemcpyAsync(th[0], th[1], (size_t)nx * ny * nz * sizeof(double), hipMemcpyDeviceToDevice, h->stream));      // the PT coefficients of the phase-ratio form
+        double *const dst[4] = {set[0].T, set[0].qx, set[0].qy, set[0].qz}, *const src[4] = {set[1].T, set[1].qx, set[1].qy, set[1].qz};
+        for (int q = 0; q < 4; q++) JRX_HIP(h, hipMemcpyAsync(dst[q], src[q], entries(q) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        return JRX_OK;
+    }
+    // small grids only (kGraphCells3D), as the other 3D loops; two-kernel runs are not graphed
+    bool graphable() const { return fusable && (double)nx * ny * nz <= kGraphCells3D; }
+    jrx_status graph_iteration(int c) { return fused(c); }
+};
+template <class PHT>
+jrx_status heat3d(jrx_handle *h, const jrx_thermal3d_fields *t, const jrx_thermal3d_params *p, const PHT &ph, int64_t *iter_count, double *norm_ResT, int64_t cap, int64_t *nnorms)
+{
+    Heat3<PHT> o(h, t, p, ph);
+    return heat_solve(o, iter_count, norm_ResT, cap, nnorms);
 }
 }   // namespace
 
@@ -1053,15 +971,15 @@ jrx_status jrx_heatdiffusion_PT3d_phases(jrx_handle *h, const jrx_thermal3d_fiel
     JRX_TRY(checkT3(h, t, &q));
     JRX_TRY(tph_check(h, ph, pf, true));
     q.rheology_form = 2;
+    jrx_status st = JRX_OK;
+    // option "thermal_np_const" (default): the instantiations with the phase count as a constant
+    if (dispatch_const<1, 2, 3, 4>(h->thermal_np_const ? ph->nphase : 0, [&](auto N) {
+            TPhN<decltype(N)::value> y;
+            y.m = *ph; y.f = *pf;
+            st = heat3d(h, t, &q, y, iter_count, norm_ResT, cap, nnorms);
+        })) return st;
     TPh x;
     x.m = *ph; x.f = *pf;
-    // option "thermal_np_const" (default): the instantiations with the phase count as a constant
-    switch (h->thermal_np_const ? ph->nphase : 0) {
-#define TPN(N_) case N_: { TPhN<N_> y; y.m = *ph; y.f = *pf; return heat3d(h, t, &q, y, iter_count, norm_ResT, cap, nnorms); }
-    TPN(1) TPN(2) TPN(3) TPN(4)
-#undef TPN
-    default: break;
-    }
     return heat3d(h, t, &q, x, iter_count, norm_ResT, cap, nnorms);
 }
 

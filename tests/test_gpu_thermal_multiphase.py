@@ -313,3 +313,40 @@ def test_phase_count_constant_kernels_equal_the_run_time_loops(jr, dim, ni):
     assert outs[0][0] == outs[1][0] == [20, 40, 60] and outs[0][1] == outs[1][1]
     for a, b in zip(outs[0][2], outs[1][2]):
         assert np.array_equal(a, b, equal_nan=True)
+
+
+@pytest.mark.parametrize("cadence", [(99, 33), (102, 34)])
+@pytest.mark.parametrize("ni", [(20, 14, 12), (65, 3, 3)])
+def test_fused_3d_phase_form_in_graphs_equals_plain_launches_and_the_two_kernels(jr, ni, cadence):
+    """the one-launch 3D phase-ratio iteration (k_thermal3d_fused_ph: θr_dτ swaps with T and the fluxes) inside captured graphs of 32 iterations, as plain launches and
+    against the two kernels: (99, 33) runs of 32 = one graph each, an even number of swaps (the observed iteration works on the caller's arrays); (102, 34) runs of
+    33 = one graph and one launch, an odd number (θr_dτ and the set are copied back).  Every field, the PT coefficients and the norm history bit for bit; the launch
+    counters show the branch taken"""
+    from justrelax_jl_amd import _lib
+    h = _lib.default_handle()
+    iterMax, nout = cadence
+    unobserved = iterMax - iterMax // nout
+    paths = [dict(thermal_fused=1, loop_graphs=1), dict(thermal_fused=1, loop_graphs=0), dict(thermal_fused=0, loop_graphs=0)]
+    saved = {k: h.get_option(k) for k in paths[0]}
+    outs = []
+    try:
+        for opts in paths:
+            for k, v in opts.items():
+                h.set_option(k, v)
+            s = jr.miniapps.diffusion3d_multiphase(ni, iterMax=iterMax, nout=nout)
+            _randomise(s, 14)
+            thermal, pt, pr, args = _device_setup(jr, s, eps=1e-30)
+            f0, g0 = h.get_option("stat_thermal_fused"), h.get_option("stat_graph_replays")
+            r = jr.heatdiffusion_PT_(thermal, pt, s.flow_bcs, s.extra["rheology"], args, s.dt, s.grid, kwargs=dict(phase=pr, iterMax=iterMax, nout=nout, verbose=False))
+            counters = (h.get_option("stat_thermal_fused") - f0, h.get_option("stat_graph_replays") - g0)
+            assert counters == (unobserved * opts["thermal_fused"], 3 * opts["thermal_fused"] * opts["loop_graphs"]), (opts, counters)
+            fields = [thermal.T, thermal.Told, thermal.ΔT, thermal.qTx, thermal.qTy, thermal.qTz, thermal.qTx2, thermal.qTy2, thermal.qTz2, thermal.ResT, pt.θr_dτ, pt.dτ_ρ]
+            outs.append((list(r.iter_count), list(r.norm_ResT), [jr.to_numpy(t) for t in fields]))
+    finally:
+        for k, v in saved.items():
+            h.set_option(k, v)
+    assert outs[0][0] == list(range(nout, iterMax + 1, nout))
+    for o in outs[1:]:
+        assert o[0] == outs[0][0] and o[1] == outs[0][1]
+        for a, b in zip(outs[0][2], o[2]):
+            assert np.array_equal(a, b)
