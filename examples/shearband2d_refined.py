@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The refined shear band of miniapps/benchmarks/stokes2D/shear_band/ShearBand2D_refined.jl through the native backend: the multiphase visco-elasto-plastic
 2D solve! on a grid whose vertices are refined towards the inclusion in x (Geometry(xvi...)), time steps with the stress history carried as the script does
-(tensor_invariant!, τ -> τ_o is done inside solve!), and a .vtr file per step.
+(tensor_invariant!, τ -> τ_o is done inside solve!), the pure-shear velocities set by pureshear_bc!, and a .vtr file per step.
     python examples/shearband2d_refined.py [n=64] [steps=5] [outdir=shearband2d_refined_out]"""
 import sys
 from pathlib import Path
@@ -28,6 +28,9 @@ def main(n=64, steps=5, outdir="shearband2d_refined_out"):
     s = jr.miniapps.shearband2d(n, iterMax=50_000, nout=1000, xvi=(refined(n), np.linspace(0.0, 1.0, n + 1)))
     s.kwargs.update(verbose=False)
     st, pr, ρg = _upload(jr, s)
+    # pureshear_bc!(stokes, xci, xvi, εbg, backend): the pure-shear velocities on the device, from the refined vertices (the ghost rows keep the builder's
+    # free-slip values)
+    jr.pureshear_bc_(st, s.grid.xci, s.grid.xvi, s.extra["εbg"], jr.AMDGPUBackend)
     t = 0.0
     for it in range(1, steps + 1):
         r = jr.solve_(st, s.pt, s.grid, s.flow_bcs, ρg, pr, s.extra["phases"], None, s.dt, None, kwargs=s.kwargs)

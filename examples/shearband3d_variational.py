@@ -19,6 +19,10 @@ def main(n=32, steps=3, air_layers=3):
     s = jr.miniapps.shearband3d_variational(n, air_layers, iterMax=20_000, nout=500)
     s.kwargs.update(verbose=False)
     st, pr, ρg = _upload(jr, s)
+    # pureshear_bc!(stokes, xci, xvi, εbg, backend) sets Vx = εbg x, Vy = εbg y, Vz = -εbg z on the device.  This shear band is plane strain in x-z
+    # (test/test_shearband3D_MPI.jl:149-150 sets Vx and Vz only), so Vy goes back to zero
+    jr.pureshear_bc_(st, s.grid.xci, s.grid.xvi, s.extra["εbg"], jr.AMDGPUBackend)
+    st.V.Vy.zero_()
     air = s.kwargs["air_phase"]
     ϕ = jr.RockRatio(jr.AMDGPUBackend, s.ni)
     jr.update_rock_ratio_(ϕ, pr, air)

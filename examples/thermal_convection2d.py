@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Thermo-mechanical time loop of test/test_WENO5.jl:216-282 (thermal_convection2D, circular perturbation) through the native backend, without the particle /
 WENO advection of temperature unless asked for: per step solve! (single MaterialParams: update_ρg! and the Arrhenius viscosity relaxation run inside),
-compute_dt, compute_shear_heating!, heatdiffusion_PT! (rheology form), velocity2vertex!, one .vtr file.  With weno = True (opt-in; off by default) every step
+compute_dt, subgrid_characteristic_time! (its minimum is printed beside dt), compute_shear_heating!, heatdiffusion_PT! (rheology form), velocity2vertex!, one .vtr file.  With weno = True (opt-in; off by default) every step
 ends with the reference's advection block (test_WENO5.jl:262-266): center2vertex! of the interior of T, velocity2vertex!, WENO_advection! (Z, weno built
 for ni .+ 1), vertex2center! into the interior of the ghosted T.
     python examples/thermal_convection2d.py [n=64] [steps=3] [outdir=thermal_convection2d_out] [weno=0]"""
@@ -39,6 +39,11 @@ def main(n=64, steps=3, outdir="thermal_convection2d_out", weno=False, record=No
     K, ρCp = jr.fzeros(s.ni, dev, 3.0), jr.fzeros(s.ni, dev, 1.2e3 * 3.1e3)
     pt_thermal = jr.PTThermalCoeffs(jr.AMDGPUBackend, K, ρCp, s.dt, di, li, CFL=1.0e-3 / np.sqrt(2.1), ϵ=1.0e-5)
     dt, t, yr = s.dt, 0.0, 3600 * 24 * 365.25
+    # subgrid_characteristic_time!: the diffusion time of a cell, ρCp / (2 K Σ 1/dx²), for the one material of this run (all ratios 1)
+    one_phase = jr.PhaseRatios(jr.AMDGPUBackend, 1, s.ni)
+    one_phase.center.fill_(1.0)
+    thermal_table = [dict(k=3.0, Cp=1.2e3, density=dict(kind="PT", rho0=3.1e3, alpha=1.5e-5, T0=0.0))]
+    dt0 = jr.fzeros(s.ni, dev)
     if weno:
         w = jr.WENO5(jr.AMDGPUBackend, 2, tuple(k + 1 for k in s.ni))      # test_WENO5.jl: WENO5(backend_JR, Val(2), ni .+ 1)
         T_WENO = jr.fzeros(tuple(k + 1 for k in s.ni), dev)
@@ -46,6 +51,8 @@ def main(n=64, steps=3, outdir="thermal_convection2d_out", weno=False, record=No
         args = dict(T=thermal.T, P=st.P)
         r = jr.solve_(st, s.pt, s.grid, s.flow_bcs, ρg, stokes_rheology, args, dt, None, kwargs=s.kwargs)
         dt = jr.compute_dt_(st, di, dt_diff)
+        jr.subgrid_characteristic_time_(dt0, one_phase, thermal_table, thermal, st, di)
+        print(f"step {it}: dt = {dt / yr:.4e} yr (compute_dt)  min subgrid dt₀ = {float(dt0.min()) / yr:.4e} yr", flush=True)
         jr.compute_shear_heating_(thermal, st, stokes_rheology, dt)
         rt = jr.heatdiffusion_PT_(thermal, pt_thermal, s.extra["thermal_bc"], thermal_rheology, None, dt, s.grid, kwargs=dict(iterMax=10_000, nout=100, verbose=False))
         t += dt

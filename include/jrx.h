@@ -134,7 +134,8 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   "stat_rotate_stress_calls" = jrx_rotate_stress2d / 3d calls that launched,
  *   "stat_rock_fraction_calls" / "stat_topography_advect_calls" / "stat_topography_phase_calls" = jrx_compute_rock_fraction2d / jrx_advect_topography2d /
  *   jrx_update_phases_topography2d calls that launched (their 3D forms jrx_compute_rock_fraction3d / jrx_advect_topography3d / jrx_update_phases_topography3d count in the same three),
- *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* and jrx_dyrel3d_* entry points -- so that a caller
+ *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* and jrx_dyrel3d_* entry points,
+ *   "stat_stepops_launches" = kernels launched by jrx_pureshear_bc2d / 3d, jrx_free_surface_bcs2d / 3d, jrx_subgrid_characteristic_time and jrx_compute_melt_fraction -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
 /* the caller has written to an operand array (tau_o, P0, Q, K, G, eta, rho g) since the last driver call: a cached verdict of the operand pass ("operand_cache") is dropped */
@@ -1180,6 +1181,64 @@ jrx_status jrx_dyrel3d_update_dtauV_alpha_beta(jrx_handle *h, const jrx_dyrel3d_
 /* compute_bulk_viscosity_and_penalty! (constructors.jl:230-254): ηb, γ_eff; the mean of the finite η is reduced on the device */
 jrx_status jrx_dyrel3d_bulk_viscosity_and_penalty(jrx_handle *h, const jrx_vep3d_fields *f, const jrx_dyrel3d_fields *d, const jrx_rheology *rh,
                                                   const jrx_vep3d_params *p, double gamma_fact);
+
+/* ------------------------------------------------------------------ per-step operators: pureshear_bc!, free_surface_bcs!, subgrid_characteristic_time!,
+ * compute_melt_fraction!
+ * What a time loop calls once per step around the solves.  Each is ONE launch, synchronous.  JRX_ERR_ARG (4) with a text naming the cause, nothing launched
+ * and nothing written: a NULL pointer that is not optional, an extent < 1, a phase count outside 1..JRX_MAXPHASE, an array of 2^31 or more entries, a spacing
+ * or dt that is not positive and finite, and what each operator lists.  Counter "stat_stepops_launches" (jrx_get_option): the kernels these six entry points
+ * launched.
+ *
+ * pureshear_bc!(stokes, xci, xvi, εbg, backend) -- src/boundaryconditions/pure_shear.jl:1-33.  xv, yv[, zv]: device arrays of the nx+1, ny+1[, nz+1] vertex
+ * coordinates (so a non-uniform Geometry works: no spacing enters); xci gives the reference only the extents, which are nx, ny[, nz] here.
+ *   2D: Vx[:, 2:end-1] = εbg xv[i], Vy[2:end-1, :] = -εbg yv[j].
+ *   3D: Vx[:, 2:end-1, 2:end-1] = εbg xv[i], Vy[2:end-1, :, 2:end-1] = εbg yv[j], Vz[2:end-1, 2:end-1, :] = -εbg zv[k].
+ * The ghost rows, columns and planes are not touched.  The multiply is the only rounding.
+ * NOT FOLLOWED in 3D: the reference's text iterates `y in xv` for Vy and `y in xc` for Vz (pure_shear.jl:23,28): Vy takes the x vertices, and the array
+ * comprehensions fit size(Vy), size(Vz) only when nx == ny.  The form with yv is built; where nx == ny and xv == yv both give the same bits. */
+jrx_status jrx_pureshear_bc2d(jrx_handle *h, double *Vx, double *Vy, const double *xv, const double *yv, double eps_bg, int64_t nx, int64_t ny);
+jrx_status jrx_pureshear_bc3d(jrx_handle *h, double *Vx, double *Vy, double *Vz, const double *xv, const double *yv, const double *zv, double eps_bg,
+                              int64_t nx, int64_t ny, int64_t nz);
+/* free_surface_bcs!(stokes, flow_bcs, η, rheology, phase_ratios, dt, di...) -- src/boundaryconditions/free_surface.jl:1-99 (kernels FreeSurface_Vy! :38-68,
+ * :70-99).  free_surface = flow_bcs.free_surface: 0 returns JRX_OK at once, nothing is launched.  phase_c: phase_ratios.center (nphase, ni...); of rh only
+ * nphase and G are read: G = fn_ratio(get_shear_modulus, rheology, ratios of the top cell), the plain weighted sum (src/phases/phases.jl:6-15).
+ *   2D, i = 1..nx, ν = 1e-2:  Vy[i+1, end] = ν (Vy[i+1, end-1] + 3/2 (P[i,end] / (2 η[i,end]) + (τ_o.yy[i,end] + P0[i,end]) / (2 G dt)
+ *                                              + inv(3) (Vx[i+1, end-1] - Vx[i, end-1]) inv(dx)) dy) + (1 - ν) Vy[i+1, end]
+ *   3D, (i, j) = (1..nx, 1..ny):  Vz[i+1, j+1, end] = Vz[i+1, j+1, end-1] + 3/2 (P / (2 η) + (τ_o.yy + P0) / (2 G dt)
+ *                                              + inv(3) ((Vx[i+1, j+1, end-1] - Vx[i, j+1, end-1]) inv(dx) + (Vy[i+1, j+1, end-1] - Vy[i+1, j, end-1]) inv(dy))) dz
+ *     with P, η, τ_o.yy, P0 at [i, j, end].
+ * Grouping and operation order are the reference's, without fma.  Only Vy[2:end-1, end] (2D) / Vz[2:end-1, 2:end-1, end] (3D) is written.
+ * KEPT QUIRK: the 3D form reads τ_o.yy, not τ_o.zz (free_surface.jl:28,76,91), as the reference does; tau_o_yy is that array.
+ * Spacings: dx, dy[, dz] are used as the kernel uses them (inv(dx), ... dy).  2D: dx_i / dy_j, when not NULL, are the reference's spacing arrays _di_vx[1]
+ * (nx entries, read at [i]) and _di_vy[2] (ny entries, read at [end]) -- members [0] and [1] of jrx_stokes2d_params.inv_spacing -- and replace the scalars;
+ * the values are used as handed over (the reference's only, commented-out 2D call hands it the _di arrays: Stokes2D.jl:782).  3D: scalars only. */
+jrx_status jrx_free_surface_bcs2d(jrx_handle *h, const double *Vx, double *Vy, const double *P, const double *P0, const double *tau_o_yy, const double *eta,
+                                  const double *phase_c, const jrx_rheology *rh, double dt, double dx, double dy, const double *dx_i, const double *dy_j,
+                                  int64_t nx, int64_t ny, int32_t free_surface);
+jrx_status jrx_free_surface_bcs3d(jrx_handle *h, const double *Vx, const double *Vy, double *Vz, const double *P, const double *P0, const double *tau_o_yy,
+                                  const double *eta, const double *phase_c, const jrx_rheology *rh, double dt, double dx, double dy, double dz, int64_t nx,
+                                  int64_t ny, int64_t nz, int32_t free_surface);
+/* subgrid_characteristic_time!(subgrid_arrays, particles, dt₀, phases, rheology, thermal, stokes[, di]) -- src/particles/subgrid_diffusion.jl:36-50 (the kernel;
+ * its first two arguments are not read by it):  dt0[I] = ρCp / (2 K Σ_d inv(dx_d)^2), ρCp = compute_ρCp and K = compute_conductivity of the thermal phase table
+ * averaged over the centre ratios of the cell (fn_ratio with args: a ratio of exactly 1 returns that phase alone, phases.jl:17-30), P = stokes.P[I],
+ * T = thermal.T[I .+ 1].  T is the ghosted (ni .+ 2) array: I .+ 1 is the cell's OWN centre node in this layout (ghost layer at index 0), the same node
+ * jrx_update_pt_thermal_arrays reads.  n = {nx, ny, nz} (nz = 1 in 2D), di = {dx, dy[, dz]}: uniform spacings.  Of ph, max_lxyz and Vpdtau are not read. */
+jrx_status jrx_subgrid_characteristic_time(jrx_handle *h, double *dt0, const double *phase_c, const jrx_thermal_phases *ph, const double *T, const double *P,
+                                           const int64_t n[3], int32_t ndim, const double di[3]);
+/* compute_melt_fraction!(ϕ, [phase_ratios,] rheology, args) -- src/rheology/Melting.jl:10-35.  The melting laws of the phases as a table: kind 0 = no law
+ * (ϕ = 0), kind 1 = MeltingParam_Caricchi: ϕ = 1 / (1 + exp((a - (T - c)) / b)), T in kelvin, defaults a = 800, b = 23, c = 273.15.  GeoParams is not part of
+ * the reference tree; kind 1 is the one law whose form the reference's own test pins (test/test_rheology.jl:228-253: 0.95 < ϕ < 1 at 1373.15 K, ~3e-10 at
+ * 573.15 K), so any other kind is refused by name ("melting") rather than written from memory. */
+typedef struct jrx_melting {
+    int32_t nphase;
+    int32_t kind[JRX_MAXPHASE];
+    double a[JRX_MAXPHASE], b[JRX_MAXPHASE], c[JRX_MAXPHASE];
+} jrx_melting;
+/* phase_c NULL: the single-material form, ϕ[I] = compute_meltfraction(phase 0, args[I]); otherwise fn_ratio over phase_ratios.center with the ratio == 1
+ * shortcut (phases.jl:17-30).  args.T / args.P: T, P are arrays of the extent of ϕ read at the cell's own index (getindex_NamedTuple), or NULL, and then the
+ * scalars T_scalar / P_scalar apply.  Neither law above reads P.  n = {nx, ny, nz} (nz = 1 in 2D). */
+jrx_status jrx_compute_melt_fraction(jrx_handle *h, double *phi, const double *phase_c, const jrx_melting *m, const double *T, double T_scalar, const double *P,
+                                     double P_scalar, const int64_t n[3], int32_t ndim);
 
 #ifdef __cplusplus
 }

@@ -90,6 +90,10 @@ class ThermalPhases(C.Structure):
                [(k, C.c_double * 8) for k in ("rho0", "alpha", "beta", "T0", "P0")] + [("max_lxyz", C.c_double), ("Vpdtau", C.c_double)]
 
 
+class Melting(C.Structure):      # jrx_melting
+    _fields_ = [("nphase", C.c_int32), ("kind", C.c_int32 * 8)] + [(k, C.c_double * 8) for k in ("a", "b", "c")]
+
+
 TPH_NAMES = ["P", "phase_c", "phase_qx", "phase_qy", "phase_qz"]
 ThermalPhaseFields = _ptr_struct("ThermalPhaseFields", TPH_NAMES)
 
