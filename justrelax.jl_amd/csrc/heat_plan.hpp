@@ -2,20 +2,17 @@
 // thermal_common.hpp) and the tile of the 3D one-launch kernels (thermal3d.hip).  No HIP header: g++ alone compiles it (tests/host/heat_plan_harness.cpp).
 #pragma once
 #include <cstdint>
+#include "pt_replay.hpp"
 
 namespace heat_plan {
 
 // Observed iterations (1-based): the multiples of nout (a residual check follows them) and the last one, iterMax.  Runs of unobserved iterations replay in
 // whole graphs of kGraphIters (an even count: the ping-pong sets end where they began), the rest as single launches.
 constexpr int kGraphIters = 32;
-// the 1-based number of the next observed iteration when `iter` (< iterMax) are done
-inline int64_t next_observed(int64_t iter, int64_t nout, int64_t iterMax)
-{
-    const int64_t nxt = (iter / nout + 1) * nout;
-    return nxt < iterMax ? nxt : iterMax;
-}
-inline int64_t unobserved_run(int64_t iter, int64_t nout, int64_t iterMax) { return next_observed(iter, nout, iterMax) - 1 - iter; }
-inline bool observes_next(int64_t iter, int64_t nout, int64_t iterMax) { return next_observed(iter, nout, iterMax) == iter + 1; }
+// the window itself is pt_replay's, with iterMax as the last iteration the loop can run
+inline int64_t next_observed(int64_t iter, int64_t nout, int64_t iterMax) { return pt_replay::next_observed(iter, nout, iterMax); }
+inline int64_t unobserved_run(int64_t iter, int64_t nout, int64_t iterMax) { return pt_replay::unobserved_run(iter, nout, iterMax); }
+inline bool observes_next(int64_t iter, int64_t nout, int64_t iterMax) { return pt_replay::observes_next(iter, nout, iterMax); }
 
 // Tile of k_thermal3d_fused: TX cells of R rows, KZ planes deep; ntx x nty x ntz tiles.  The tuning switch "thermal_cfg" = R*10000 + (TX/64)*100 + KZ overrides the default:
 // TX by nx, one row, 4 planes, halved while the launch has fewer than 4096 waves -- a block marches its planes one after the other, and a small grid in 4-plane chunks leaves

@@ -10,6 +10,7 @@
 #include <type_traits>
 #include "jrx.h"
 #include "pt_log.hpp"
+#include "pt_replay.hpp"
 
 struct jrx_comm_state;   // halo.hip
 struct jrx_field_pool;   // fieldpool.hip

@@ -603,48 +603,38 @@ jrx_status jrx_stokes2d_solve(jrx_handle *h, const jrx_stokes2d_fields *f, const
     constexpr int GIT = 32;
     GraphExecs gexec;        // released on every exit path
     bool graphs = h->loop_graphs && fusable;
-    auto capture = [&](hipGraphExec_t *out, auto &&body) -> bool {
-        hipGraph_t g = nullptr;
-        bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
-        if (ok) { body(); ok = hipStreamEndCapture(s, &g) == hipSuccess && g != nullptr; }
-        if (ok) ok = hipGraphInstantiate(out, g, nullptr, nullptr, 0) == hipSuccess;
-        if (g) (void)hipGraphDestroy(g);
-        if (!ok) { (void)hipGetLastError(); *out = nullptr; }
-        return ok;
+    // one fused step: the launch from the current set c into the other one, which becomes the current set
+    auto fused_step = [&](jrx_stokes2d_fields &c, bool &c_is_user) {
+        const Out6_2d dst = c_is_user ? setS : setU;
+        launch_fused2d(s, make_args2(&c, h->etatau, p), dst);
+        c.P = dst.P; c.txx = dst.txx; c.tyy = dst.tyy; c.txy = dst.txy; c.Vx = dst.Vx; c.Vy = dst.Vy;
+        c_is_user = !c_is_user;
     };
     while (keep_going(iter)) {
-        if (graphs && iter >= 2) {
-            // observed iterations: the multiples of nout and iteration iterMax + 1 (Stokes2D.jl:265,312); between them err does not change, so keep_going holds
-            int64_t nxt = ((iter / p->nout) + 1) * p->nout;
-            if (nxt > p->iterMax + 1) nxt = p->iterMax + 1;
-            int64_t run = nxt - 1 - iter;                     // unobserved iterations from here
-            if (fusable) {
-                int64_t frun = run - 1;                       // the last unobserved iteration before an observed one is not fused with it
-                if (stress_done && frun >= GIT) {
-                    const int par = cur_is_user ? 0 : 1;
-                    if (!gexec[par]) {
-                        const bool ok = capture(&gexec[par], [&]() {
-                            jrx_stokes2d_fields c = cur;
-                            bool cu = cur_is_user;
-                            for (int q = 0; q < GIT; q++) {
-                                const Args2 aa = make_args2(&c, h->etatau, p);
-                                const Out6_2d dst = cu ? setS : setU;
-                                launch_fused2d(s, aa, dst);
-                                c.P = dst.P; c.txx = dst.txx; c.tyy = dst.tyy; c.txy = dst.txy; c.Vx = dst.Vx; c.Vy = dst.Vy;
-                                cu = !cu;
-                            }
-                        });
-                        if (!ok) graphs = false;
+        if (graphs && iter >= 2 && stress_done) {
+            // observed iterations: the multiples of nout and iteration iterMax + 1 (Stokes2D.jl:265,312); between them err does not change, so keep_going holds.
+            // The last unobserved iteration before an observed one is not fused with it: held back
+            int64_t frun = pt_replay::unobserved_run(iter, p->nout, p->iterMax + 1, 1);
+            if (frun >= GIT) {
+                const int par = cur_is_user ? 0 : 1;
+                if (!gexec[par]) {
+                    JRX_TRY(jrx_capture_graph(s, &gexec[par], [&]() -> jrx_status {
+                        jrx_stokes2d_fields c = cur;
+                        bool cu = cur_is_user;
+                        for (int q = 0; q < GIT; q++) fused_step(c, cu);
+                        return JRX_OK;
+                    }));
+                    if (!gexec[par]) graphs = false;
+                }
+                if (gexec[par]) {
+                    while (frun >= GIT) {
+                        JRX_HIP(h, hipGraphLaunch(gexec[par], s));
+                        iter += GIT; frun -= GIT;
+                        h->stat_fused2d += GIT;
+                        if (batch2) h->stat_fused2d_b += GIT;
+                        h->stat_graph_replays++;
                     }
-                    if (gexec[par]) {
-                        while (frun >= GIT) {
-                            JRX_HIP(h, hipGraphLaunch(gexec[par], s));
-                            iter += GIT; frun -= GIT;
-                            h->stat_fused2d += GIT;
-                            if (batch2) h->stat_fused2d_b += GIT;
-                        }
-                        continue;
-                    }
+                    continue;
                 }
             }
         }
@@ -658,13 +648,10 @@ jrx_status jrx_stokes2d_solve(jrx_handle *h, const jrx_stokes2d_fields *f, const
                 hipLaunchKernelGGL(k_stress2d<false>, dim3((unsigned)((nvt + 255) / 256)), dim3(256), 0, s, a);
                 JRX_LAUNCH_CHECK(h);
             }
-            const Out6_2d dst = cur_is_user ? setS : setU;
-            launch_fused2d(s, a, dst);
+            fused_step(cur, cur_is_user);
             h->stat_fused2d++;
             if (batch2) h->stat_fused2d_b++;
             JRX_LAUNCH_CHECK(h);
-            cur.P = dst.P; cur.txx = dst.txx; cur.tyy = dst.tyy; cur.txy = dst.txy; cur.Vx = dst.Vx; cur.Vy = dst.Vy;
-            cur_is_user = !cur_is_user;
             stress_done = true; ghosts_stale = true;
         } else {
             if (ghosts_stale && diag) {

@@ -766,6 +766,48 @@ jrx_stokes2d_fields view2d(const jrx_vep2d_fields *f)
     return g;
 }
 
+// update_stresses_center_vertex_ps!: vertex and centre halves in one launch.  Softening laws and the strain_increment form take the general kernel, otherwise the phase
+// count is a constant up to four (option vep3_np_const; more phases: 0, the run-time count)
+void launch_vep_stress2d(jrx_handle *h, hipStream_t s, unsigned gv, const VepArgs &a)
+{
+    const std::true_type yes{};
+    const std::false_type no{};
+    const std::integral_constant<int, 0> np0{};
+    auto go = [&](auto SOFT, auto SI, auto NP) { hipLaunchKernelGGL((k_vep_stress2d<SOFT(), SI(), NP()>), dim3(gv), dim3(256), 0, s, a); };
+    if (a.si && a.soft) go(yes, yes, np0);
+    else if (a.si) go(no, yes, np0);
+    else if (a.soft) go(yes, no, np0);
+    else dispatch_const<0, 1, 2, 3, 4>(h->vep3_np_const && a.rh.nphase <= 4 ? a.rh.nphase : 0, [&](auto NP) { go(no, no, NP); });
+}
+
+// What one PT iteration of the multiphase solve loop works on: the arguments of the VEP kernels (a), of the velocity kernels (b) and the view the norms take (g), which all
+// name the current (τxx, τyy).  The stress kernel writes the other set (a.txx_out, a.tyy_out) and adopting its output is a swap, so the captured graphs of an even number of
+// iterations, which run on a copy, end where they began.
+struct Vep2Iter {
+    VepArgs a;
+    Args2 b;
+    jrx_stokes2d_fields g;
+    const jrx_vep2d_fields *f;       // the caller's arrays
+
+    void adopt_stresses()
+    {
+        { double *t_ = a.f.txx; a.f.txx = a.txx_out; a.txx_out = t_; }
+        { double *t_ = a.f.tyy; a.f.tyy = a.tyy_out; a.tyy_out = t_; }
+        b.f.txx = g.txx = a.f.txx; b.f.tyy = g.tyy = a.f.tyy;
+    }
+    bool odd() const { return a.f.txx != f->txx; }      // an odd number of iterations so far
+    // an odd number of swaps: leave τxx, τyy in the caller's arrays, and the arguments pointing at them
+    jrx_status restore(jrx_handle *h, hipStream_t s)
+    {
+        if (!odd()) return JRX_OK;
+        const size_t n = (size_t)a.nx * a.ny;
+        JRX_HIP(h, hipMemcpyAsync(f->txx, a.f.txx, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        JRX_HIP(h, hipMemcpyAsync(f->tyy, a.f.tyy, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        adopt_stresses();
+        return JRX_OK;
+    }
+};
+
 }   // namespace
 
 extern "C" {
@@ -916,18 +958,23 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
     // library scratch: ητ, θ, λ, K, G (centre), λv (vertex) and the second set of τxx, τyy, carved out of one allocation; with args.ΔT the thermal source of compute_P! behind them
     JRX_TRY(jrx_ensure_etatau(h, (f->dT ? 9 : 8) * n + 2 * nv));
     double *etatau = h->etatau, *theta = etatau + n, *lam = theta + n, *Kc = lam + n, *Gc = Kc + n, *lamv = Gc + n;
-    VepArgs a = make_vep(f, rh, p);
+    Vep2Iter st;
+    st.f = f;
+    VepArgs &a = st.a;
+    Args2 &b = st.b;
+    jrx_stokes2d_fields &g = st.g;
+    a = make_vep(f, rh, p);
     a.theta = theta; a.etatau = etatau; a.Kc = Kc; a.Gc = Gc; a.lam = lam; a.lamv = lamv;
     a.txx_out = lamv + nv; a.tyy_out = a.txx_out + n;
     double *eta_lin_c = a.tyy_out + n, *eta_lin_v = eta_lin_c + n;
     double *const src = f->dT ? eta_lin_v + nv : nullptr;
-    jrx_stokes2d_fields g = view2d(f);
+    g = view2d(f);
     jrx_stokes2d_params q;
     memset(&q, 0, sizeof(q));
     q.nx = nx; q.ny = ny; q.nxg = p->nxg; q.nyg = p->nyg; q._dx = p->_dx; q._dy = p->_dy; q.dt = p->dt; q.r = p->r;
     q.theta_dtau = p->theta_dtau; q.eta_dtau = p->eta_dtau; q.free_slip = p->free_slip; q.no_slip = p->no_slip; q.periodic = p->periodic;
     for (int d = 0; d < 6; d++) q.inv_spacing[d] = p->inv_spacing[d];
-    Args2 b = make_args2(&g, etatau, &q);
+    b = make_args2(&g, etatau, &q);
     const unsigned gv = (unsigned)((nv + 255) / 256), gc = (unsigned)((n + 255) / 256);
 
     JRX_HIP(h, hipMemcpyAsync(f->P0, f->P, n * sizeof(double), hipMemcpyDeviceToDevice, s));        // @copy stokes.P0 stokes.P
@@ -960,73 +1007,15 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
     PtLog log(res);
     int64_t iter = 0;
     auto done = [&]() { return log.rel() < p->eps_rel || log.err() < p->eps_abs; };
-    // an odd number of swaps: leave τxx, τyy in the caller's arrays, and the arguments pointing at them
-    auto restore = [&]() -> jrx_status {
-        if (a.f.txx != f->txx) {
-            JRX_HIP(h, hipMemcpyAsync(f->txx, a.f.txx, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-            JRX_HIP(h, hipMemcpyAsync(f->tyy, a.f.tyy, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-            a.f.txx = f->txx; a.f.tyy = f->tyy; b.f.txx = f->txx; b.f.tyy = f->tyy; g.txx = f->txx; g.tyy = f->tyy;
-        }
-        return JRX_OK;
-    };
+    auto is_check = [&](int64_t i1) { return (i1 % p->nout == 0) && i1 > 1; };
+    // can the loop stop after iteration i1: a check follows it, it is the last allowed one, or the loop has already converged
+    auto can_stop = [&](int64_t i1) { return is_check(i1) || i1 > p->iterMax || (p->iterMin < i1 && done()); };
     JRX_HIP(h, hipEventRecord(h->ev[6], s));
-    // Runs of unobserved iterations replay as a captured graph of GIT iterations (three launches each: at the sizes where the loop is launch-bound -- 17 - 18 us
-    // per iteration up to 256^2 -- the gap between dependent launches is shorter inside a graph).  An even count, so that the (τxx, τyy) sets end where they
-    // started.  Only in the plain steady state: one rank, no periodic face, velocity boundary conditions, strain-rate form.  Option "loop_graphs" = 0: plain launches.
-    constexpr int GIT = 32;
-    GraphExecs gexec;        // released on every exit path
-    bool graphs = h->loop_graphs && !comm && !ubc && !a.si && p->periodic == 0 && (i64)(nx + 1) * (ny + 1) <= 200000;
-    while (iter <= p->iterMax) {
-        if (p->iterMin < iter && done()) break;          // Stokes2D.jl:650-651
-        if (graphs && iter >= 1 && !done()) {
-            // observed iterations (checks: multiples of nout; the last one: iterMax + 1) end a run; err does not change inside one
-            int64_t nxt = ((iter / p->nout) + 1) * p->nout;
-            if (nxt > p->iterMax + 1) nxt = p->iterMax + 1;
-            int64_t run = nxt - 1 - iter;
-            if (run >= GIT) {
-                const int par = a.f.txx == f->txx ? 0 : 1;
-                if (!gexec[par]) {
-                    hipGraph_t gr = nullptr;
-                    bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                    if (ok) {
-                        VepArgs aa = a;
-                        aa.obs = h->vep_store_all;          // a run of unobserved iterations
-                        Args2 bb = b;
-                        for (int q = 0; q < GIT; q++) {
-                            launch_vep_pre(s, gv, aa, theta, true, upd_rho, batch_pre);
-                            if (aa.soft) hipLaunchKernelGGL(k_vep_stress2d<true>, dim3(gv), dim3(256), 0, s, aa);
-                            else switch (h->vep3_np_const ? aa.rh.nphase : 0) {
-                            case 1: hipLaunchKernelGGL((k_vep_stress2d<false, false, 1>), dim3(gv), dim3(256), 0, s, aa); break;
-                            case 2: hipLaunchKernelGGL((k_vep_stress2d<false, false, 2>), dim3(gv), dim3(256), 0, s, aa); break;
-                            case 3: hipLaunchKernelGGL((k_vep_stress2d<false, false, 3>), dim3(gv), dim3(256), 0, s, aa); break;
-                            case 4: hipLaunchKernelGGL((k_vep_stress2d<false, false, 4>), dim3(gv), dim3(256), 0, s, aa); break;
-                            default: hipLaunchKernelGGL(k_vep_stress2d<false>, dim3(gv), dim3(256), 0, s, aa);
-                            }
-                            { double *t_ = aa.f.txx; aa.f.txx = aa.txx_out; aa.txx_out = t_; }
-                            { double *t_ = aa.f.tyy; aa.f.tyy = aa.tyy_out; aa.tyy_out = t_; }
-                            bb.f.txx = aa.f.txx; bb.f.tyy = aa.f.tyy;
-                            if (batch_vv) hipLaunchKernelGGL(k_vep_visc_velocity_b<true>, dim3(gv), dim3(256), 0, s, aa, bb);
-                            else hipLaunchKernelGGL(k_vep_visc_velocity<true>, dim3(gv), dim3(256), 0, s, aa, bb);
-                        }
-                        ok = hipStreamEndCapture(s, &gr) == hipSuccess && gr != nullptr;
-                    }
-                    if (ok) ok = hipGraphInstantiate(&gexec[par], gr, nullptr, nullptr, 0) == hipSuccess;
-                    if (gr) (void)hipGraphDestroy(gr);
-                    if (!ok) { (void)hipGetLastError(); gexec[par] = nullptr; graphs = false; }
-                }
-                if (gexec[par]) {
-                    while (run >= GIT) {
-                        JRX_HIP(h, hipGraphLaunch(gexec[par], s));
-                        iter += GIT; run -= GIT;
-                    }
-                    continue;
-                }
-            }
-        }
-        {   // can the loop stop after the iteration launched now (a check, the last allowed one, or already converged)?  Only then are its output-only arrays stored
-            const int64_t it1 = iter + 1;
-            a.obs = ((it1 % p->nout == 0) && it1 > 1) || it1 > p->iterMax || (p->iterMin < it1 && done()) || h->vep_store_all;
-        }
+    // One iteration, enqueued on s, when `iter` are done (the steps marked `comm` only on ranks with neighbours).  diag: a check follows, or the loop can end here -- only
+    // then are the output-only arrays stored, is U = V dt observable and does flow_bcs! run as launches of its own
+    auto enqueue_iteration = [&](Vep2Iter &it, int64_t iter, bool diag) -> jrx_status {
+        VepArgs &A = it.a;
+        A.obs = diag || h->vep_store_all;
         if (comm) {
             hipLaunchKernelGGL(k_maxloc, dim3(gc, 1), dim3(256), 0, s, etatau, (const double *)f->eta, nx, ny, 1);
             JRX_LAUNCH_CHECK(h);
@@ -1034,29 +1023,16 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
             double *arrs[1] = {etatau};
             const int64_t ext[1][3] = {{nx, ny, 1}};
             JRX_TRY(jrx_halo_exchange(h, s, 1, arrs, ext, nn));
-            launch_vep_pre(s, gv, a, theta, false, upd_rho, false);
-        } else launch_vep_pre(s, gv, a, theta, true, upd_rho, batch_pre);
+            launch_vep_pre(s, gv, A, theta, false, upd_rho, false);
+        } else launch_vep_pre(s, gv, A, theta, true, upd_rho, batch_pre);
         JRX_LAUNCH_CHECK(h);
-        if (a.si) {
-            hipLaunchKernelGGL(k_vep_strain_inc, dim3(gv), dim3(256), 0, s, a);
+        if (A.si) {
+            hipLaunchKernelGGL(k_vep_strain_inc, dim3(gv), dim3(256), 0, s, A);
             JRX_LAUNCH_CHECK(h);
         }
-        // update_stresses_center_vertex_ps!: vertex and centre halves in one launch; the new τxx, τyy go to the other set, then swap
-        if (a.si) {
-            if (a.soft) hipLaunchKernelGGL((k_vep_stress2d<true, true>), dim3(gv), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_vep_stress2d<false, true>), dim3(gv), dim3(256), 0, s, a);
-        } else if (a.soft) hipLaunchKernelGGL(k_vep_stress2d<true>, dim3(gv), dim3(256), 0, s, a);
-        else switch (h->vep3_np_const ? a.rh.nphase : 0) {
-        case 1: hipLaunchKernelGGL((k_vep_stress2d<false, false, 1>), dim3(gv), dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((k_vep_stress2d<false, false, 2>), dim3(gv), dim3(256), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((k_vep_stress2d<false, false, 3>), dim3(gv), dim3(256), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((k_vep_stress2d<false, false, 4>), dim3(gv), dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL(k_vep_stress2d<false>, dim3(gv), dim3(256), 0, s, a);
-        }
+        launch_vep_stress2d(h, s, gv, A);      // the new τxx, τyy go to the other set, then swap
         JRX_LAUNCH_CHECK(h);
-        { double *t_ = a.f.txx; a.f.txx = a.txx_out; a.txx_out = t_; }
-        { double *t_ = a.f.tyy; a.f.tyy = a.tyy_out; a.tyy_out = t_; }
-        b.f.txx = a.f.txx; b.f.tyy = a.f.tyy; g.txx = a.f.txx; g.tyy = a.f.tyy;
+        it.adopt_stresses();
         if (comm) {   // update_halo!(stokes.τ.xy) (Stokes2D.jl:757)
             double *arrs[1] = {f->txy};
             const int64_t ext[1][3] = {{nx + 1, ny + 1, 1}};
@@ -1064,37 +1040,62 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
         }
         // flow_bcs! applied in full by iteration 1: refresh ghosts in-kernel (never with DisplacementBoundaryConditions: flow_bcs! then acts on U)
         // (nor with strain_increment: U = V dt must copy the ghosts of V as the previous flow_bcs! left them)
-        const bool bcf = iter >= 1 && p->periodic == 0 && !comm && !ubc && !a.si;
-        bool used_bcf = false;
-        {
-            const bool next_check = ((iter + 1) % p->nout == 0) && iter + 1 > 1;
-            const bool next_last = next_check || iter + 1 > p->iterMax || (p->iterMin < iter + 1 && done());
-            used_bcf = bcf && !next_last;
-            // compute_viscosity! + compute_V! (free-surface form with dt*free_surface = 0) in one launch
-            if (batch_vv && used_bcf) hipLaunchKernelGGL(k_vep_visc_velocity_b<true>, dim3(gv), dim3(256), 0, s, a, b);
-            else if (batch_vv) hipLaunchKernelGGL(k_vep_visc_velocity_b<false>, dim3(gv), dim3(256), 0, s, a, b);
-            else if (used_bcf) hipLaunchKernelGGL(k_vep_visc_velocity<true>, dim3(gv), dim3(256), 0, s, a, b);
-            else hipLaunchKernelGGL(k_vep_visc_velocity<false>, dim3(gv), dim3(256), 0, s, a, b);
-        }
+        const bool used_bcf = iter >= 1 && p->periodic == 0 && !comm && !ubc && !A.si && !diag;
+        // compute_viscosity! + compute_V! (free-surface form with dt*free_surface = 0) in one launch
+        if (batch_vv && used_bcf) hipLaunchKernelGGL(k_vep_visc_velocity_b<true>, dim3(gv), dim3(256), 0, s, A, it.b);
+        else if (batch_vv) hipLaunchKernelGGL(k_vep_visc_velocity_b<false>, dim3(gv), dim3(256), 0, s, A, it.b);
+        else if (used_bcf) hipLaunchKernelGGL(k_vep_visc_velocity<true>, dim3(gv), dim3(256), 0, s, A, it.b);
+        else hipLaunchKernelGGL(k_vep_visc_velocity<false>, dim3(gv), dim3(256), 0, s, A, it.b);
         JRX_LAUNCH_CHECK(h);
-        iter += 1;
-        const bool check = (iter % p->nout == 0) && iter > 1;
-        // the loop can stop after this iteration if it is a check, the last allowed one, or already converged
-        const bool last = check || iter > p->iterMax || (p->iterMin < iter && done());
-        if (last || a.si) {   // U = V*dt is only observable after an iteration the loop can stop at -- or every iteration when the strains are taken from U
+        if (diag || A.si) {   // U = V*dt is only observable after an iteration the loop can stop at -- or every iteration when the strains are taken from U
             hipLaunchKernelGGL(k_scale3, dim3(256), dim3(256), 0, s, f->Ux, (const double *)f->Vx, (i64)(nx + 1) * (ny + 2), f->Uy,
                                (const double *)f->Vy, (i64)(nx + 2) * (ny + 1), (double *)nullptr, (const double *)nullptr, (i64)0, p->dt);
             JRX_LAUNCH_CHECK(h);
         }
         if (ubc) {    // flow_bcs!(stokes, ::DisplacementBoundaryConditions) acts on U = V dt, which the next iteration overwrites: only the last one is observable
-            if (last || a.si) JRX_TRY(jrx2d_bcs(h, s, f->Ux, f->Uy, nx, ny, p->free_slip, p->no_slip, p->periodic));
+            if (diag || A.si) JRX_TRY(jrx2d_bcs(h, s, f->Ux, f->Uy, nx, ny, p->free_slip, p->no_slip, p->periodic));
         } else if (!used_bcf) JRX_TRY(jrx2d_bcs(h, s, f->Vx, f->Vy, nx, ny, p->free_slip, p->no_slip, p->periodic));
         if (comm) {   // update_halo!(@velocity(stokes)...) (Stokes2D.jl:784)
             double *arrs[2] = {f->Vx, f->Vy};
             const int64_t ext[2][3] = {{nx + 1, ny + 2, 1}, {nx + 2, ny + 1, 1}};
             JRX_TRY(jrx_halo_exchange(h, s, 2, arrs, ext, nn));
         }
-        if (check) {
+        return JRX_OK;
+    };
+    // Runs of unobserved iterations replay as a captured graph of GIT iterations (three launches each: at the sizes where the loop is launch-bound -- 17 - 18 us
+    // per iteration up to 256^2 -- the gap between dependent launches is shorter inside a graph).  An even count, so that the (τxx, τyy) sets end where they
+    // started; one graph per parity.  Only in the plain steady state: one rank, no periodic face, velocity boundary conditions, strain-rate form.  Option "loop_graphs" = 0: plain launches.
+    constexpr int GIT = 32;
+    GraphExecs gexec;        // released on every exit path
+    bool graphs = h->loop_graphs && !comm && !ubc && !a.si && p->periodic == 0 && (i64)(nx + 1) * (ny + 1) <= 200000;
+    while (iter <= p->iterMax) {
+        if (p->iterMin < iter && done()) break;          // Stokes2D.jl:650-651
+        if (graphs && iter >= 1 && !done()) {
+            // observed iterations (checks: multiples of nout; the last one: iterMax + 1) end a run; err does not change inside one
+            int64_t run = pt_replay::unobserved_run(iter, p->nout, p->iterMax + 1);
+            if (run >= GIT) {
+                const int par = st.odd() ? 1 : 0;
+                if (!gexec[par]) {
+                    JRX_TRY(jrx_capture_graph(s, &gexec[par], [&]() -> jrx_status {
+                        Vep2Iter T = st;
+                        for (int r_ = 0; r_ < GIT; r_++) JRX_TRY(enqueue_iteration(T, iter + r_, false));
+                        return JRX_OK;
+                    }));
+                    if (!gexec[par]) graphs = false;
+                }
+                if (gexec[par]) {
+                    while (run >= GIT) {
+                        JRX_HIP(h, hipGraphLaunch(gexec[par], s));
+                        iter += GIT; run -= GIT;
+                        h->stat_graph_replays++;
+                    }
+                    continue;
+                }
+            }
+        }
+        JRX_TRY(enqueue_iteration(st, iter, can_stop(iter + 1)));
+        iter += 1;
+        if (is_check(iter)) {
             hipLaunchKernelGGL(k_velocity2d<true>, dim3(gc), dim3(256), 0, s, b);  // compute_Res!
             JRX_LAUNCH_CHECK(h);
             JRX_TRY(jrx2d_sumsq(h, s, &g, &q));
@@ -1107,14 +1108,14 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
             if (p->verbose && jrx_comm_rank(h) == 0) log.print2d(iter, nRx, nRy, nDV);      // igg.me == 0 (Stokes2D.jl:814)
             if (std::isnan(err)) {      // error("NaN(s)"): leave the caller's arrays consistent and the stream drained
                 gexec.reset();
-                (void)restore();
+                (void)st.restore(h, s);
                 return log.fail_nan(h, iter, jrx_drain_ms(s, h->ev[6], h->ev[7]));
             }
         }
     }
     gexec.reset();
     JRX_HIP(h, hipEventRecord(h->ev[7], s));
-    JRX_TRY(restore());
+    JRX_TRY(st.restore(h, s));
     a.txx_out = a.tyy_out = nullptr;
     hipLaunchKernelGGL(k_vep_epilogue, dim3(gv), dim3(256), 0, s, a);
     JRX_LAUNCH_CHECK(h);
@@ -1199,48 +1200,10 @@ jrx_status jrx_stokes2d_nonlinear_solve(jrx_handle *h, const jrx_vep2d_fields *f
     GraphExecs gexecs;       // released on every exit path
     hipGraphExec_t &gexec = gexecs[0];
     bool graphs = h->loop_graphs && !comm && !ubc;
-    auto unobserved_iteration = [&]() {
-        hipLaunchKernelGGL(k_vep_pre<false>, dim3(gv), dim3(256), 0, s, a, f->P);
-        hipLaunchKernelGGL(k_single_material, dim3(gc), dim3(256), 0, s, a, p->viscosity_relaxation, upd_rho, true, tg);
-        hipLaunchKernelGGL(k_maxloc, dim3(gc, 1), dim3(256), 0, s, etatau, (const double *)f->eta, nx, ny, 1);
-        hipLaunchKernelGGL(k_tau_nonlinear2d<false>, dim3(gc), dim3(256), 0, s, a, theta);
-        hipLaunchKernelGGL(k_center2vertex2d, dim3(gv), dim3(256), 0, s, f->txy, (const double *)f->txy_c, nx, ny, 3);        // the three passes of center2vertex! in one
-        if (p->periodic == 0) {      // flow_bcs! has been applied in full by now (iter >= 2): the velocity kernel refreshes the ghosts next to what it updates
-            hipLaunchKernelGGL((k_velocity2d<false, true>), dim3(gc), dim3(256), 0, s, b);
-            return JRX_OK;
-        }
-        hipLaunchKernelGGL(k_velocity2d<false>, dim3(gc), dim3(256), 0, s, b);
-        return jrx2d_bcs(h, s, f->Vx, f->Vy, nx, ny, p->free_slip, p->no_slip, p->periodic);
-    };
-    while (keep_going(iter)) {
-        if (graphs && iter >= 2) {
-            int64_t nxt = ((iter / p->nout) + 1) * p->nout;        // observed: the multiples of nout and iteration iterMax + 1
-            if (nxt > p->iterMax + 1) nxt = p->iterMax + 1;
-            int64_t run = nxt - 1 - iter;
-            if (run >= GIT) {
-                if (!gexec) {
-                    hipGraph_t gr = nullptr;
-                    bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                    if (ok) {
-                        for (int q = 0; q < GIT && ok; q++) ok = unobserved_iteration() == JRX_OK;
-                        ok = (hipStreamEndCapture(s, &gr) == hipSuccess && gr != nullptr) && ok;
-                    }
-                    if (ok) ok = hipGraphInstantiate(&gexec, gr, nullptr, nullptr, 0) == hipSuccess;
-                    if (gr) (void)hipGraphDestroy(gr);
-                    if (!ok) { (void)hipGetLastError(); gexec = nullptr; graphs = false; }
-                }
-                if (gexec) {
-                    while (run >= GIT) {
-                        JRX_HIP(h, hipGraphLaunch(gexec, s));
-                        iter += GIT; run -= GIT;
-                    }
-                    continue;
-                }
-            }
-        }
-        const int64_t it1 = iter + 1;
-        const bool check = (it1 % p->nout == 0) && it1 > 1;
-        const bool diag = check || !keep_going(it1);      // U is only observable after such an iteration
+    // One iteration, enqueued on s (the exchanges only on ranks with neighbours).  diag: a check follows, or the loop ends here -- U is only observable then.  folded: the form
+    // a replay takes -- flow_bcs! has been applied in full by then (iter >= 2), so without a periodic face the velocity kernel refreshes the ghosts next to what it updates
+    // and no flow_bcs! launch follows
+    auto enqueue_iteration = [&](bool diag, bool folded) -> jrx_status {
         hipLaunchKernelGGL(k_vep_pre<false>, dim3(gv), dim3(256), 0, s, a, f->P);                    // compute_∇V!, compute_P!, compute_strain_rate!
         hipLaunchKernelGGL(k_single_material, dim3(gc), dim3(256), 0, s, a, p->viscosity_relaxation, upd_rho, true, tg);   // update_ρg!, compute_viscosity_τII!
         hipLaunchKernelGGL(k_maxloc, dim3(gc, 1), dim3(256), 0, s, etatau, (const double *)f->eta, nx, ny, 1);            // compute_maxloc!(ητ, η) :437
@@ -1258,20 +1221,49 @@ jrx_status jrx_stokes2d_nonlinear_solve(jrx_handle *h, const jrx_vep2d_fields *f
             const int64_t ext[1][3] = {{nx + 1, ny + 1, 1}};
             JRX_TRY(jrx_halo_exchange(h, s, 1, arrs, ext, nn));
         }
-        hipLaunchKernelGGL(k_velocity2d<false>, dim3(gc), dim3(256), 0, s, b);                       // compute_V! (free-surface form) :463-474
+        const bool bcf = folded && p->periodic == 0;
+        if (bcf) hipLaunchKernelGGL((k_velocity2d<false, true>), dim3(gc), dim3(256), 0, s, b);
+        else hipLaunchKernelGGL(k_velocity2d<false>, dim3(gc), dim3(256), 0, s, b);                  // compute_V! (free-surface form) :463-474
         JRX_LAUNCH_CHECK(h);
         if (diag) {
             hipLaunchKernelGGL(k_scale3, dim3(256), dim3(256), 0, s, f->Ux, (const double *)f->Vx, (i64)(nx + 1) * (ny + 2), f->Uy,
                                (const double *)f->Vy, (i64)(nx + 2) * (ny + 1), (double *)nullptr, (const double *)nullptr, (i64)0, p->dt);
             JRX_LAUNCH_CHECK(h);
         }
-        if (!ubc) JRX_TRY(jrx2d_bcs(h, s, f->Vx, f->Vy, nx, ny, p->free_slip, p->no_slip, p->periodic));
-        else if (diag) JRX_TRY(jrx2d_bcs(h, s, f->Ux, f->Uy, nx, ny, p->free_slip, p->no_slip, p->periodic));
+        if (ubc) {
+            if (diag) JRX_TRY(jrx2d_bcs(h, s, f->Ux, f->Uy, nx, ny, p->free_slip, p->no_slip, p->periodic));
+        } else if (!bcf) JRX_TRY(jrx2d_bcs(h, s, f->Vx, f->Vy, nx, ny, p->free_slip, p->no_slip, p->periodic));
         if (comm) {
             double *arrs[2] = {f->Vx, f->Vy};
             const int64_t ext[2][3] = {{nx + 1, ny + 2, 1}, {nx + 2, ny + 1, 1}};
             JRX_TRY(jrx_halo_exchange(h, s, 2, arrs, ext, nn));
         }
+        return JRX_OK;
+    };
+    while (keep_going(iter)) {
+        if (graphs && iter >= 2) {
+            int64_t run = pt_replay::unobserved_run(iter, p->nout, p->iterMax + 1);      // observed: the multiples of nout and iteration iterMax + 1
+            if (run >= GIT) {
+                if (!gexec) {
+                    JRX_TRY(jrx_capture_graph(s, &gexec, [&]() -> jrx_status {
+                        for (int r_ = 0; r_ < GIT; r_++) JRX_TRY(enqueue_iteration(false, true));
+                        return JRX_OK;
+                    }));
+                    if (!gexec) graphs = false;
+                }
+                if (gexec) {
+                    while (run >= GIT) {
+                        JRX_HIP(h, hipGraphLaunch(gexec, s));
+                        iter += GIT; run -= GIT;
+                        h->stat_graph_replays++;
+                    }
+                    continue;
+                }
+            }
+        }
+        const int64_t it1 = iter + 1;
+        const bool check = (it1 % p->nout == 0) && it1 > 1;
+        JRX_TRY(enqueue_iteration(check || !keep_going(it1), false));      // U is only observable after an iteration a check follows or the loop ends at
         iter = it1;
         if (check) {
             hipLaunchKernelGGL(k_velocity2d<true>, dim3(gc), dim3(256), 0, s, b);                    // compute_Res! :479-490

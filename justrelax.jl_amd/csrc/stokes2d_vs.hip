@@ -524,14 +524,9 @@ jrx_status vs_flags(jrx_handle *h, VsArgs &a, size_t doubles)
 // the stress kernel's instantiation: softening laws take the general form, otherwise the phase count is a constant up to four (option vep3_np_const, as the sibling driver)
 void vs_launch_stress(jrx_handle *h, const VsArgs &a, unsigned gv, hipStream_t s, int part)
 {
-    if (a.soft) { hipLaunchKernelGGL((k_vs_stress<true, 0>), dim3(gv), dim3(256), 0, s, a, part); return; }
-    switch (h->vep3_np_const ? a.rh.nphase : 0) {
-    case 1: hipLaunchKernelGGL((k_vs_stress<false, 1>), dim3(gv), dim3(256), 0, s, a, part); break;
-    case 2: hipLaunchKernelGGL((k_vs_stress<false, 2>), dim3(gv), dim3(256), 0, s, a, part); break;
-    case 3: hipLaunchKernelGGL((k_vs_stress<false, 3>), dim3(gv), dim3(256), 0, s, a, part); break;
-    case 4: hipLaunchKernelGGL((k_vs_stress<false, 4>), dim3(gv), dim3(256), 0, s, a, part); break;
-    default: hipLaunchKernelGGL((k_vs_stress<false, 0>), dim3(gv), dim3(256), 0, s, a, part);
-    }
+    auto go = [&](auto SOFT, auto NP) { hipLaunchKernelGGL((k_vs_stress<SOFT(), NP()>), dim3(gv), dim3(256), 0, s, a, part); };
+    if (a.soft) go(std::true_type{}, std::integral_constant<int, 0>{});
+    else dispatch_const<0, 1, 2, 3, 4>(h->vep3_np_const && a.rh.nphase <= 4 ? a.rh.nphase : 0, [&](auto NP) { go(std::false_type{}, NP); });
 }
 
 }   // namespace

@@ -1334,9 +1334,7 @@ jrx_status jrx_stokes3d_solve(jrx_handle *h, const jrx_stokes3d_fields *f, const
     while (keep_going(iter)) {
         if (graphs && iter >= 2 && I.bcs_ordered[0] && I.all_user() && !I.stress_done) {
             // observed iterations: the multiples of nout and iteration iterMax + 1; between them err does not change, so keep_going holds
-            int64_t nxt = ((iter / p->nout) + 1) * p->nout;
-            if (nxt > p->iterMax + 1) nxt = p->iterMax + 1;
-            int64_t run = nxt - 1 - iter;                     // unobserved iterations from here
+            int64_t run = pt_replay::unobserved_run(iter, p->nout, p->iterMax + 1);      // unobserved iterations from here
             if (run >= GIT) {
                 if (!gexec[0]) {
                     JRX_TRY(jrx_capture_graph(s, &gexec[0], [&]() -> jrx_status {

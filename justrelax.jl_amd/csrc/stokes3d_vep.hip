@@ -1634,9 +1634,8 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
     bool graphs = h->loop_graphs && !comm && !ubc && p->periodic == 0 && (double)n <= kGraphCells3D;
     while (keep_going(iter)) {
         if (graphs && iter >= 2 && bcs_ordered) {
-            int64_t nxt = ((iter / p->nout) + 1) * p->nout;         // observed iterations: the multiples of nout and iteration iterMax + 1
-            if (nxt > p->iterMax + 1) nxt = p->iterMax + 1;
-            int64_t run = nxt - 2 - iter;                           // (the iteration before an observed one runs its boundary conditions in the reference's pass order: not part of a replay)
+            // observed iterations: the multiples of nout and iteration iterMax + 1 (the iteration before an observed one runs its boundary conditions in the reference's pass order: not part of a replay)
+            int64_t run = pt_replay::unobserved_run(iter, p->nout, p->iterMax + 1, 1);
             if (run >= GIT) {
                 const int par = st.odd() ? 1 : 0;
                 if (!gexec[par]) {

@@ -260,7 +260,10 @@ def test_2d_kernel_variants_are_bit_identical(env, ni, bcs):
 
 def test_graph_replay_of_unobserved_iterations_changes_nothing(env):
     """option loop_graphs: runs of unobserved one-launch iterations of the 2D visco-elastic loop and of the 2D heat-diffusion loop replay as captured hipGraphs
-    (32 iterations each); results, iteration counts and the fused-launch counters equal those of plain launches"""
+    (32 iterations each); results, iteration counts and the fused-launch counters equal those of plain launches.  The replay counter over the Stokes solve proves that
+    graphs ran: 0 with plain launches, 12 with graphs -- a replay needs a finished stress sweep and holds back the iteration before an observed one, which leaves 6 graphs
+    in each of the two runs of unobserved iterations (up to the check at 200, up to the last iteration).  The 12 was read from the parent of the change that began to count
+    the 2D replays, built with nothing but `stat_graph_replays++` added behind its hipGraphLaunch, on this very case"""
     import ctypes as C
     jr, orc, th = env["jr"], env["orc"], env["th"]
     from justrelax_jl_amd import _lib
@@ -274,16 +277,17 @@ def test_graph_replay_of_unobserved_iterations_changes_nothing(env):
         out = C.c_int64(0)
         h.call("jrx_get_option", C.c_char_p(k), C.byref(out))
         return out.value
-    outs = []
+    outs, replays = [], []
     try:
         for g in (0, 1):
             opt(b"loop_graphs", g)
             s = jr.miniapps.solcx2d(64, iterMax=399, nout=200)
             s.pt.ϵ_rel = s.pt.ϵ_abs = 1e-300
             stokes, ρg, K, G = upload_stokes(s, jr.AMDGPUBackend)
-            c0 = opt(b"stat_fused2d")
+            c0, r0 = opt(b"stat_fused2d"), opt(b"stat_graph_replays")
             r = jr.solve_(stokes, s.pt, s.grid, s.flow_bcs, ρg, G, K, s.dt, None, kwargs=s.kwargs)
             fused = opt(b"stat_fused2d") - c0
+            replays.append(opt(b"stat_graph_replays") - r0)
             st = download_stokes(stokes)
             s2 = jr.miniapps.diffusion2d(64, iterMax=500, nout=250)
             b = s2.flow_bcs
@@ -298,6 +302,8 @@ def test_graph_replay_of_unobserved_iterations_changes_nothing(env):
             outs.append((r.iter, list(r.err_evo1), fused, st, list(rt.norm_ResT), opt(b"stat_thermal_fused") - c1, jr.to_numpy(thermal.T), jr.to_numpy(thermal.qTx)))
     finally:
         opt(b"loop_graphs", 1)
+    print("stat_graph_replays deltas of the Stokes solve (loop_graphs 0, 1):", replays)
+    assert replays == [0, 12]
     a, b_ = outs
     assert a[0] == b_[0] == 400 and a[1] == b_[1] and a[2] == b_[2] > 300
     for k in a[3]:

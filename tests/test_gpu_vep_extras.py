@@ -317,13 +317,15 @@ def test_sinking_block_reference_test_on_the_device(jr, oracle):
 def test_vep2d_graph_replay_changes_nothing(jr, rho):
     """option loop_graphs: runs of unobserved iterations of the 2D visco-elasto-plastic loop replay as captured hipGraphs of 32 iterations (three launches each,
     the (τxx, τyy) sets ping-pong inside); every field, the iteration count and the error history equal those of plain launches -- yielding state, with and without
-    the in-loop density update"""
+    the in-loop density update.  The replay counter proves that graphs ran: 0 with plain launches, 8 with graphs -- iteration 0 plain, from iteration 1 a run of 148
+    unobserved iterations (4 graphs, 20 plain), the check at 150, a run of 149 (4 graphs, 21 plain), the last iteration.  The 8 was read from the parent of the change
+    that began to count the 2D replays, built with nothing but `stat_graph_replays++` added behind its hipGraphLaunch, on this very case (both densities)"""
     import ctypes as C
     from justrelax_jl_amd import _lib
     from justrelax_jl_amd.arrays import from_numpy
     from test_gpu_vep2d import _download, _upload
     h = _lib.default_handle(0)
-    outs = []
+    outs, replays = [], []
     try:
         for g in (0, 1):
             h.call("jrx_set_option", C.c_char_p(b"loop_graphs"), C.c_int64(g))
@@ -337,10 +339,14 @@ def test_vep2d_graph_replay_changes_nothing(jr, rho):
             phases = _phases_rho(s.extra["phases"], g=0.3) if rho else s.extra["phases"]
             st, pr, ρg = _upload(jr, s)
             args = dict(T=from_numpy(np.asfortranarray(rng.uniform(0.0, 2.0, size=s.ni)), st.P.device), P=st.P) if rho else None
+            c0 = h.get_option("stat_graph_replays")
             r = jr.solve_(st, s.pt, s.grid, s.flow_bcs, ρg, pr, phases, args, s.dt, None, kwargs=s.kwargs)
+            replays.append(h.get_option("stat_graph_replays") - c0)
             outs.append((r.iter, list(r.err_evo1), _download(jr, st), jr.to_numpy(ρg[1])))
     finally:
         h.call("jrx_set_option", C.c_char_p(b"loop_graphs"), C.c_int64(1))
+    print("stat_graph_replays deltas (loop_graphs 0, 1):", replays)
+    assert replays == [0, 8]
     a, b = outs
     assert a[0] == b[0] == 300 and a[1] == b[1]
     for k in a[2]:
@@ -350,7 +356,9 @@ def test_vep2d_graph_replay_changes_nothing(jr, rho):
 
 def test_single_phase_driver_graph_replay_changes_nothing(jr):
     """option loop_graphs in the single-phase non-linear driver: the replayed iteration (center2vertex! in one pass, flow_bcs! folded into compute_V!, 16
-    iterations per graph) leaves every array, ghost entries included, and the error history as the plain launches do"""
+    iterations per graph) leaves every array, ghost entries included, and the error history as the plain launches do.  The replay counter proves that graphs ran: 0 with
+    plain launches, 18 with graphs -- iterations 0 and 1 plain, then runs of 97, 99 and 99 unobserved iterations with 6 graphs in each.  The 18 was read from the parent
+    of the change that began to count the 2D replays, built with nothing but `stat_graph_replays++` added behind its hipGraphLaunch, on this very case"""
     import ctypes as C
     import torch
     from justrelax_jl_amd import _lib
@@ -358,7 +366,7 @@ def test_single_phase_driver_graph_replay_changes_nothing(jr):
     from test_gpu_vep2d import VEP_MAP, _get
     h = _lib.default_handle(0)
     dev = torch.device("cuda", torch.cuda.current_device())
-    outs = []
+    outs, replays = [], []
     try:
         for g in (0, 1):
             h.call("jrx_set_option", C.c_char_p(b"loop_graphs"), C.c_int64(g))
@@ -369,10 +377,14 @@ def test_single_phase_driver_graph_replay_changes_nothing(jr):
             for k, path in VEP_MAP.items():
                 _get(st, path).copy_(from_numpy(s.arrays[k], dev))
             ρg = (from_numpy(s.arrays["fx"], dev), from_numpy(s.arrays["fy"], dev))
+            c0 = h.get_option("stat_graph_replays")
             r = jr.solve_(st, s.pt, s.grid, s.flow_bcs, ρg, ph, dict(T=from_numpy(s.arrays["T"], dev), P=st.P), s.dt, None, kwargs=s.kwargs)
+            replays.append(h.get_option("stat_graph_replays") - c0)
             outs.append((r.iter, list(r.err_evo1), {k: jr.to_numpy(_get(st, path)) for k, path in VEP_MAP.items()}, jr.to_numpy(ρg[1])))
     finally:
         h.call("jrx_set_option", C.c_char_p(b"loop_graphs"), C.c_int64(1))
+    print("stat_graph_replays deltas (loop_graphs 0, 1):", replays)
+    assert replays == [0, 18]
     a, b = outs
     assert a[0] == b[0] == 300 and a[1] == b[1]
     for k in a[2]:
