@@ -135,7 +135,8 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   "stat_rock_fraction_calls" / "stat_topography_advect_calls" / "stat_topography_phase_calls" = jrx_compute_rock_fraction2d / jrx_advect_topography2d /
  *   jrx_update_phases_topography2d calls that launched (their 3D forms jrx_compute_rock_fraction3d / jrx_advect_topography3d / jrx_update_phases_topography3d count in the same three),
  *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* and jrx_dyrel3d_* entry points,
- *   "stat_stepops_launches" = kernels launched by jrx_pureshear_bc2d / 3d, jrx_free_surface_bcs2d / 3d, jrx_subgrid_characteristic_time and jrx_compute_melt_fraction -- so that a caller
+ *   "stat_stepops_launches" = kernels launched by jrx_pureshear_bc2d / 3d, jrx_free_surface_bcs2d / 3d, jrx_subgrid_characteristic_time and jrx_compute_melt_fraction,
+ *   "stat_particles_launches" = kernels launched by the five jrx_particles2d_* entry points -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
 /* the caller has written to an operand array (tau_o, P0, Q, K, G, eta, rho g) since the last driver call: a cached verdict of the operand pass ("operand_cache") is dropped */
@@ -1239,6 +1240,80 @@ typedef struct jrx_melting {
  * scalars T_scalar / P_scalar apply.  Neither law above reads P.  n = {nx, ny, nz} (nz = 1 in 2D). */
 jrx_status jrx_compute_melt_fraction(jrx_handle *h, double *phi, const double *phase_c, const jrx_melting *m, const double *T, double T_scalar, const double *P,
                                      double P_scalar, const int64_t n[3], int32_t ndim);
+
+/* ------------------------------------------------------------------ 2D marker-in-cell particles: advect, re-bucket, interpolate, phase ratios
+ * The material of the reference's miniapps lives on JustPIC particles; per step they call advection!(particles, RungeKutta2(), @velocity(stokes), dt),
+ * move_particles!(particles, particle_args), update_phase_ratios!(phase_ratios, particles, pPhases), with grid2particle! / particle2grid! around them
+ * (miniapps/benchmarks/stokes2D/shear_heating/Shearheating2D.jl:69-82,221-232 gives the call shapes).  JustPIC's text is not in the reference tree, so nothing
+ * is restated: what is built is defined HERE, to the rounding, and tests/_particles2d.py is the same text in NumPy.  Every operator is a GATHER with loops
+ * bounded by max_xcell: nothing races, nothing depends on launch order, the device and the NumPy text leave the same bits.
+ * Scope: 2D, uniform grid, one block (a handle with a communicator is refused), fp64.  NOT built: 3D, non-uniform grids, particle injection
+ * (inject_particles_phase!), a marker chain, StressParticles.
+ *
+ * Layout.  The grid has (nx, ny) cells of size (dx, dy), cell (i, j) = [x0 + i dx, x0 + (i+1) dx) x [y0 + j dy, y0 + (j+1) dy), 0-based.  Every cell owns a BUCKET
+ * of max_xcell slots.  Every per-particle array -- px, py (coordinates), active (int32 mask: 1 = the slot holds a particle) and every particle field (pPhases, pT,
+ * ...: fp64) -- is column-major of shape (nx, ny, max_xcell): entry (i, j, s) at i + nx (j + ny s).  The SLOT index is SLOWEST, so the threads of a wave (neighbouring
+ * cells i) read neighbouring addresses in every slot loop: the accesses coalesce.  This is the opposite of the PhaseRatios layout (phase index fastest), which is
+ * written, N contiguous doubles per thread.  A phase is stored as the double 1.0 ... N.  INVARIANT: an inactive slot holds 0 in every array (+0.0; active = 0); every
+ * operator keeps it, and the bit-for-bit tests rely on it.  The bucket of a particle need not be its owner cell between an advection and the next move.
+ * _dx = 1 / dx and _dy = 1 / dy are formed once on the host (checked: part->_dx == 1.0 / part->dx); nx ny max_xcell < 2^31 (32-bit offsets).
+ *
+ * Rounding: no fma (the library builds with -ffp-contract=off); every product and sum is rounded once, left to right as written.  (double)i is exact.
+ * Safety: an index derived from a coordinate is range-checked ON THE DOUBLE before the conversion to int (v >= 0 && v < n), so a NaN or an infinite coordinate
+ * is "outside", never a conversion.  No atomics except integer adds into the library's counter words; no loop on data.
+ *
+ * JRX_ERR_ARG (4) with a text naming the cause, nothing launched ("stat_particles_launches" unchanged) and nothing written: a NULL pointer, nx or ny < 1,
+ * max_xcell < 1, 2^31 or more slots, x0 / y0 not finite, dx / dy not positive and finite, _dx / _dy not their inverses, dt not finite, nargs outside
+ * 0 .. JRX_MAXPHASE, nphase outside 1 .. JRX_MAXPHASE, src and dst of a move sharing an array or differing in any scalar, a handle with a communicator. */
+typedef struct jrx_particles2d {
+    double *px, *py;
+    int32_t *active;
+    int64_t nx, ny;
+    int32_t max_xcell;
+    double x0, y0, dx, dy, _dx, _dy;
+} jrx_particles2d;
+/* 1. advection!(particles, RungeKutta2(), @velocity(stokes), dt) -- the midpoint rule (alpha = 0.5), per active slot, in place:
+ *      (ux, uy) = V(x, y);  xm = x + (0.5 dt) ux,  ym = y + (0.5 dt) uy;  (wx, wy) = V(xm, ym);  x' = x + dt wx,  y' = y + dt wy.
+ *    Vx is (nx+1, ny+2) with nodes at (x0 + i dx, y0 + (j - 0.5) dy), Vy is (nx+2, ny+1) with nodes at (x0 + (i - 0.5) dx, y0 + j dy): stokes.V with its ghost
+ *    layers.  The node-grid origins (ox, oy) = (x0, y0 - 0.5 dy) and (x0 - 0.5 dx, y0) are formed once on the host.  A component A of extents (mx, my) at (x, y):
+ *      sx = (x - ox) _dx;  fx = floor(sx);  i0 = fx >= 0 ? (fx < mx - 1 ? (int)fx : mx - 2) : 0;  tx = sx - (double)i0;   sy, j0, ty likewise with _dy, my
+ *      A(x, y) = (1 - ty) ((1 - tx) A[i0, j0] + tx A[i0+1, j0]) + ty ((1 - tx) A[i0, j0+1] + tx A[i0+1, j0+1])
+ *    A point outside the node box therefore EXTRAPOLATES linearly from the outermost pair of nodes (tx < 0 or tx > 1); nothing is clamped.  If sx or sy of any
+ *    of the four evaluations is not finite (NaN or infinite coordinate), the particle is left exactly as it was. */
+jrx_status jrx_particles2d_advect_rk2(jrx_handle *h, const jrx_particles2d *part, const double *Vx, const double *Vy, double dt);
+/* 2. move_particles!(particles, particle_args) -- out of place: src is read, every array of dst and of args_dst is written in full.
+ *    Owner of a particle: cx = (x - x0) _dx, fx = floor(cx); inside along x iff fx >= 0 && fx < nx (on the doubles), then ic = (int)fx; jc likewise.  A particle
+ *    exactly on the upper boundary (or with a NaN coordinate) is outside.
+ *    ONE thread per destination cell (i, j) fills its dst slots from 0 upward:
+ *      first the active particles of src cell (i, j), in slot order, whose owner is (i, j);
+ *      then, for dj = -1, 0, 1 (outermost) and di = -1, 0, 1, (0, 0) skipped, the active particles of src cell (i + di, j + dj) (where that cell exists), in
+ *      slot order, whose owner is (i, j).
+ *    A particle that finds all max_xcell slots taken is dropped and counted in n_overflow.  The remaining dst slots are zeroed (coordinates, mask, args).
+ *    Over its own src cell the same thread counts the active particles (n_active_before), those whose owner is outside the grid (n_outside) and those inside the
+ *    grid whose owner is more than one cell away along x or y (n_far): nobody gathers these, they are lost.  n_active_after counts the filled dst slots.
+ *    args_src / args_dst: host arrays of nargs device pointers (particle fields and their twins; may be NULL when nargs = 0).
+ *    counts = {n_active_before, n_active_after, n_outside, n_far, n_overflow}; n_active_before = n_active_after + n_outside + n_far + n_overflow.
+ *    One launch plus one read of the five counter words. */
+jrx_status jrx_particles2d_move(jrx_handle *h, const jrx_particles2d *src, const jrx_particles2d *dst, const double *const *args_src, double *const *args_dst,
+                                int32_t nargs, int64_t counts[5]);
+/* 3. grid2particle!(pF, xvi, F, particles): F is a vertex field (nx+1, ny+1).  Per active slot (i, j, s), bilinear over the four vertices of the slot's BUCKET
+ *    cell (i, j) -- not of the owner recomputed from the coordinate:
+ *      tx = (x - (x0 + (double)i dx)) _dx,  ty = (y - (y0 + (double)j dy)) _dy,  pF = (1 - ty) ((1 - tx) F[i, j] + tx F[i+1, j]) + ty ((1 - tx) F[i, j+1] + tx F[i+1, j+1]).
+ *    An inactive slot of pF is set to 0. */
+jrx_status jrx_particles2d_grid2particle(jrx_handle *h, double *pF, const double *F, const jrx_particles2d *part);
+/* 4. particle2grid!(F, pF, xvi, particles): one thread per vertex (i, j), xv = x0 + (double)i dx, yv = y0 + (double)j dy, reads its up to four cells at offsets
+ *    {-1, 0}: the first dimension's offset outermost, -1 before 0 (the order of jrx_update_phase_ratios2d), cells outside the grid skipped, slots in order:
+ *      w = (1 - fabs(x - xv) _dx) (1 - fabs(y - yv) _dy);  num += w pF;  den += w;     F[i, j] = num / den;  where den == 0, F[i, j] is left as it was. */
+jrx_status jrx_particles2d_particle2grid(jrx_handle *h, double *F, const double *pF, const jrx_particles2d *part);
+/* 5. update_phase_ratios!(phase_ratios, particles, pPhases): center (nphase, nx, ny), vertex (nphase, nx+1, ny+1), Vx (nphase, nx+1, ny), Vy (nphase, nx, ny+1),
+ *    phase index fastest.  One launch, one thread per node (i, j) of the (nx+1, ny+1) box writes every member it owns.  With xv, yv as in (4) and the centres
+ *    xc = x0 + ((double)i + 0.5) dx, yc = y0 + ((double)j + 0.5) dy:
+ *      center[i, j]  (i < nx, j < ny): cell (i, j), weights to (xc, yc);         vertex[i, j]: the four cells of (4) in that order, weights to (xv, yv);
+ *      Vx[i, j]  (j < ny): cells (i-1, j), (i, j), weights to (xv, yc);           Vy[i, j]  (i < nx): cells (i, j-1), (i, j), weights to (xc, yv).
+ *    Weights as in (4) with the node's coordinates.  Per active slot: p = pPhases; skipped unless p >= 1 && p < nphase + 1; k = (int)p; w_k += w; W += w, slots
+ *    in order.  ratio_k = w_k / W.  Where W == 0 the member is left unchanged and counted: *n_empty = the number of (node, member) pairs with W == 0. */
+jrx_status jrx_particles2d_phase_ratios(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, const double *pPhases, int32_t nphase,
+                                        const jrx_particles2d *part, int64_t *n_empty);
 
 #ifdef __cplusplus
 }

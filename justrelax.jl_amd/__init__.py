@@ -6,8 +6,8 @@ The directory name contains a dot, so import it through `__graft_entry__.load_pa
 
 Layout: csrc/ (hand-written HIP kernels for gfx950 + the C ABI declared in include/jrx.h),
 arrays.py / backend.py / grid.py (host-side mirror of the reference's types and traits),
-stokes.py / thermal.py / halo.py / gridops.py / advection.py / variational.py / dyrel.py / phases.py / stress_rotation.py / topography.py / stepops.py (the operator API: solve_, heatdiffusion_PT_, flow_bcs_,
-velocity2vertex_, WENO_advection_, solve_VariationalStokes_, solve_DYREL_, update_phase_ratios_2D_, rotate_stress_, compute_rock_fraction_, pureshear_bc_, compute_melt_fraction_, ...),
+stokes.py / thermal.py / halo.py / gridops.py / advection.py / variational.py / dyrel.py / phases.py / stress_rotation.py / topography.py / stepops.py / particles.py (the operator API: solve_, heatdiffusion_PT_, flow_bcs_,
+velocity2vertex_, WENO_advection_, solve_VariationalStokes_, solve_DYREL_, update_phase_ratios_2D_, rotate_stress_, compute_rock_fraction_, pureshear_bc_, compute_melt_fraction_, init_particles, move_particles_, ...),
 miniapps/ (synthetic-input builders restating the reference's benchmark scripts).
 Julia's `f!` is spelled `f_` here.
 """
@@ -27,9 +27,9 @@ from . import miniapps  # noqa: F401
 def __getattr__(name):
     # the operator API is imported lazily: it loads the HIP shared library and fails loudly if absent
     import importlib
-    if name.startswith("_") or name in ("stokes", "thermal", "halo", "checks", "build", "arrays", "grid", "backend", "convert", "gridops", "advection", "variational", "dyrel", "phases", "stress_rotation", "topography", "stepops"):
+    if name.startswith("_") or name in ("stokes", "thermal", "halo", "checks", "build", "arrays", "grid", "backend", "convert", "gridops", "advection", "variational", "dyrel", "phases", "stress_rotation", "topography", "stepops", "particles"):
         raise AttributeError(name)
-    for sub in ("stokes", "thermal", "halo", "gridops", "advection", "variational", "dyrel", "phases", "stress_rotation", "topography", "stepops"):
+    for sub in ("stokes", "thermal", "halo", "gridops", "advection", "variational", "dyrel", "phases", "stress_rotation", "topography", "stepops", "particles"):
         mod = importlib.import_module(f"{__name__}.{sub}")
         if hasattr(mod, name):
             return getattr(mod, name)

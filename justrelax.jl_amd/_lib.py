@@ -94,6 +94,11 @@ class Melting(C.Structure):      # jrx_melting
     _fields_ = [("nphase", C.c_int32), ("kind", C.c_int32 * 8)] + [(k, C.c_double * 8) for k in ("a", "b", "c")]
 
 
+class Particles2D(C.Structure):      # jrx_particles2d
+    _fields_ = [("px", C.c_void_p), ("py", C.c_void_p), ("active", C.c_void_p), ("nx", C.c_int64), ("ny", C.c_int64), ("max_xcell", C.c_int32)] + \
+               [(k, C.c_double) for k in ("x0", "y0", "dx", "dy", "_dx", "_dy")]
+
+
 TPH_NAMES = ["P", "phase_c", "phase_qx", "phase_qy", "phase_qz"]
 ThermalPhaseFields = _ptr_struct("ThermalPhaseFields", TPH_NAMES)
 
@@ -246,6 +251,13 @@ def load(check_symbols: bool = False):
         L.jrx_compute_rock_fraction3d.argtypes = [C.c_void_p] * 10 + [C.c_int64] * 3 + [C.c_double] * 2
         L.jrx_advect_topography3d.argtypes = [C.c_void_p] * 6 + [C.c_int64] * 3 + [C.c_double] * 5
         L.jrx_update_phases_topography3d.argtypes = [C.c_void_p, _vpp, C.c_int32, C.c_void_p] + [C.c_int64] * 3 + [C.c_double] * 2 + [C.c_int32]
+        # the particle operators: the struct by reference; move: src, dst, two host arrays of device pointers, nargs, five counter words; phase ratios: the four members, pPhases, N, the struct, n_empty
+        _pp = C.POINTER(Particles2D)
+        L.jrx_particles2d_advect_rk2.argtypes = [C.c_void_p, _pp, C.c_void_p, C.c_void_p, C.c_double]
+        L.jrx_particles2d_move.argtypes = [C.c_void_p, _pp, _pp, _vpp, _vpp, C.c_int32, _ip]
+        L.jrx_particles2d_grid2particle.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _pp]
+        L.jrx_particles2d_particle2grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _pp]
+        L.jrx_particles2d_phase_ratios.argtypes = [C.c_void_p] * 6 + [C.c_int32, _pp, _ip]
         _lib = L
     if check_symbols:
         missing = [s for s in declared_symbols() if not hasattr(_lib, s)]

@@ -127,6 +127,7 @@ int find_opt(jrx_handle *h, const char *key, bool tuning, OptRef *out)
         {"stat_topography_phase_calls", 2, &h->stat_topography_phase_calls},
         {"stat_dyrel_launches", 2, &h->stat_dyrel_launches},
         {"stat_stepops_launches", 2, &h->stat_stepops_launches},
+        {"stat_particles_launches", 2, &h->stat_particles_launches},
     };
     const OptRef tun[] = {
         {"fused_split", 0, &h->fused_split}, {"fused_tile", 1, &h->fused_tile}, {"fused_ylds", 0, &h->fused_ylds}, {"fused_hiface", 0, &h->fused_hiface}, {"visc_fold", 0, &h->visc_fold}, {"zero_forces", 0, &h->zero_forces}, {"scratch_stagger", 1, &h->scratch_stagger}, {"scratch_contiguous", 0, &h->scratch_contiguous}, {"end_flips", 0, &h->end_flips}, {"comm_bcs_lazy", 0, &h->comm_bcs_lazy}, {"fused_first_pct", 1, &h->fused_first_pct},

@@ -1,0 +1,524 @@
+// particles.hip -- 2D marker-in-cell particles in gather form: advection!(particles, RungeKutta2(), V, dt), move_particles!, grid2particle!, particle2grid!
+// and update_phase_ratios!(phase_ratios, particles, pPhases), for gfx950.
+//
+// Reference: none to restate.  The reference's miniapps take these from JustPIC (miniapps/benchmarks/stokes2D/shear_heating/Shearheating2D.jl:69-82,221-232 shows
+// the calls), which is not in the reference tree.  include/jrx.h states the definitions built here; tests/_particles2d.py is the same text in NumPy.
+//
+// Layout: every per-particle array is (nx, ny, max_xcell) column-major, the slot index slowest (include/jrx.h): a thread owns a cell (or a node) and walks the
+// slots, so in every trip of a slot loop the lanes of a wave read consecutive addresses.  An inactive slot holds 0 everywhere.
+//
+// Every kernel is a gather: a thread writes only what it owns (its cell's slots, its node's members), reads whatever it needs, and every loop is bounded by
+// max_xcell or a constant.  Nothing races and nothing depends on launch order; the only atomics are integer adds of per-wave counts into the counter words
+// (sums of integers: the order does not matter).  fp64, no fma (-ffp-contract=off): every product and sum is rounded once in the order written.
+// An index derived from a coordinate is range-checked on the double before the conversion to int: a NaN or infinite coordinate never reaches a conversion.
+// Addressing: 32-bit element offsets (nx ny max_xcell < 2^31, checked).
+//
+// k_pt_phase_ratios<N>: the phase count is a template argument (1 .. JRX_MAXPHASE) and the phase index of a particle is applied by an unrolled select, so the
+// 4 N + 4 accumulators of a node stay in registers (a run-time index into them would put them in scratch).
+#include <cfloat>
+#include "jrx_internal.hpp"
+
+namespace {
+
+constexpr int kPtTX = 64, kPtTY = 4;                  // tile of cells / nodes: 64 x 4
+
+struct PtGeom {                                       // jrx_particles2d by value, 32-bit extents
+    double *px, *py;
+    int *active;
+    double x0, y0, dx, dy, idx, idy;
+    int nx, ny, mx, nbx;                              // mx = max_xcell; nbx = blocks along x of the launch
+};
+
+__device__ __forceinline__ bool pt_finite(double v) { return fabs(v) <= DBL_MAX; }
+
+__device__ __forceinline__ void pt_index(int nbx, int &i, int &j)
+{
+    i = ((int)blockIdx.x % nbx) * kPtTX + (int)threadIdx.x;
+    j = ((int)blockIdx.x / nbx) * kPtTY + (int)threadIdx.y;
+}
+
+// floor(s) as an index of the left node of an interpolation pair among m nodes: clamped on the double, so the pair exists and a point outside extrapolates
+__device__ __forceinline__ int pt_pair(double s, int m)
+{
+    const double f = floor(s);
+    return f >= 0.0 ? (f < (double)(m - 1) ? (int)f : m - 2) : 0;
+}
+
+// one staggered component A of extents (mx, my), node grid origin (ox, oy), at (x, y); false (and no load) when a scaled coordinate is not finite
+__device__ __forceinline__ bool pt_interp(const double *__restrict__ A, int mx, int my, double ox, double oy, double idx, double idy, double x, double y, double &v)
+{
+    const double sx = (x - ox) * idx, sy = (y - oy) * idy;
+    if (!pt_finite(sx) || !pt_finite(sy)) return false;
+    const int i0 = pt_pair(sx, mx), j0 = pt_pair(sy, my);
+    const double tx = sx - (double)i0, ty = sy - (double)j0;
+    const double *p = A + j0 * mx + i0;
+    const double v00 = p[0], v10 = p[1], v01 = p[mx], v11 = p[mx + 1];
+    v = (1.0 - ty) * ((1.0 - tx) * v00 + tx * v10) + ty * ((1.0 - tx) * v01 + tx * v11);
+    return true;
+}
+
+// the weight of a particle at coordinate x to a node at xn
+__device__ __forceinline__ double pt_w(double x, double xn, double idx) { return 1.0 - fabs(x - xn) * idx; }
+
+// sum of a per-thread count over the wave, added to *word by lane 0 (blocks are 64 x 4: a wave is one row of the tile)
+__device__ __forceinline__ void pt_count(unsigned long long *word, int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (threadIdx.x == 0 && v != 0) atomicAdd(word, (unsigned long long)v);
+}
+
+// ------------------------------------------------------------------------------------------------ 1. advection, midpoint rule
+struct PtAdvArgs {
+    PtGeom g;
+    const double *Vx, *Vy;
+    double oyx, oxy;          // y origin of the Vx nodes (y0 - 0.5 dy), x origin of the Vy nodes (x0 - 0.5 dx)
+    double dt, hdt;           // dt, 0.5 dt
+};
+
+__global__ __launch_bounds__(256) void k_pt_advect_rk2(const PtAdvArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i >= g.nx || j >= g.ny) return;
+    const int nc = g.nx * g.ny;
+    int lin = j * g.nx + i;
+    for (int s = 0; s < g.mx; s++, lin += nc) {
+        if (g.active[lin] == 0) continue;
+        const double x = g.px[lin], y = g.py[lin];
+        double ux, uy, wx, wy;
+        if (!pt_interp(a.Vx, g.nx + 1, g.ny + 2, g.x0, a.oyx, g.idx, g.idy, x, y, ux)) continue;
+        if (!pt_interp(a.Vy, g.nx + 2, g.ny + 1, a.oxy, g.y0, g.idx, g.idy, x, y, uy)) continue;
+        const double xm = x + a.hdt * ux, ym = y + a.hdt * uy;
+        if (!pt_interp(a.Vx, g.nx + 1, g.ny + 2, g.x0, a.oyx, g.idx, g.idy, xm, ym, wx)) continue;
+        if (!pt_interp(a.Vy, g.nx + 2, g.ny + 1, a.oxy, g.y0, g.idx, g.idy, xm, ym, wy)) continue;
+        g.px[lin] = x + a.dt * wx;
+        g.py[lin] = y + a.dt * wy;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ 2. move: a destination cell gathers its particles
+struct PtMoveArgs {
+    PtGeom src;
+    double *dpx, *dpy;
+    int *dactive;
+    const double *as[JRX_MAXPHASE];
+    double *ad[JRX_MAXPHASE];
+    int nargs;
+    unsigned long long *counts;      // n_active_before, n_active_after, n_outside, n_far, n_overflow
+};
+
+// owner cell of (x, y): 0 outside the grid, 1 inside (ic, jc set)
+__device__ __forceinline__ bool pt_owner(const PtGeom &g, double x, double y, int &ic, int &jc)
+{
+    const double fx = floor((x - g.x0) * g.idx), fy = floor((y - g.y0) * g.idy);
+    if (!(fx >= 0.0 && fx < (double)g.nx && fy >= 0.0 && fy < (double)g.ny)) return false;
+    ic = (int)fx, jc = (int)fy;
+    return true;
+}
+
+__device__ __forceinline__ void pt_place(const PtMoveArgs &a, int from, int to, double x, double y)
+{
+    a.dpx[to] = x, a.dpy[to] = y, a.dactive[to] = 1;
+#pragma unroll
+    for (int k = 0; k < JRX_MAXPHASE; k++)
+        if (k < a.nargs) a.ad[k][to] = a.as[k][from];
+}
+
+__global__ __launch_bounds__(256) void k_pt_move(const PtMoveArgs a)
+{
+    const PtGeom &g = a.src;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    const bool live = i < g.nx && j < g.ny;
+    const int nc = g.nx * g.ny, mx = g.mx;
+    int n = 0, n_before = 0, n_outside = 0, n_far = 0, n_overflow = 0;
+    if (live) {
+        const int base = j * g.nx + i;
+        // the cell's own particles first: they always fit
+        for (int s = 0, lin = base; s < mx; s++, lin += nc) {
+            if (g.active[lin] == 0) continue;
+            n_before++;
+            const double x = g.px[lin], y = g.py[lin];
+            int ic, jc;
+            if (!pt_owner(g, x, y, ic, jc)) { n_outside++; continue; }
+            const int di = ic - i, dj = jc - j;
+            if (di < -1 || di > 1 || dj < -1 || dj > 1) { n_far++; continue; }
+            if (di == 0 && dj == 0) {
+                pt_place(a, lin, base + n * nc, x, y);
+                n++;
+            }
+        }
+        // then the eight neighbours, dj outermost
+        for (int dj = -1; dj <= 1; dj++) {
+            const int jn = j + dj;
+            if (jn < 0 || jn >= g.ny) continue;
+            for (int di = -1; di <= 1; di++) {
+                const int in = i + di;
+                if ((di == 0 && dj == 0) || in < 0 || in >= g.nx) continue;
+                for (int s = 0, lin = jn * g.nx + in; s < mx; s++, lin += nc) {
+                    if (g.active[lin] == 0) continue;
+                    const double x = g.px[lin], y = g.py[lin];
+                    int ic, jc;
+                    if (!pt_owner(g, x, y, ic, jc) || ic != i || jc != j) continue;
+                    if (n < mx) {
+                        pt_place(a, lin, base + n * nc, x, y);
+                        n++;
+                    } else {
+                        n_overflow++;
+                    }
+                }
+            }
+        }
+        for (int s = n, to = base + n * nc; s < mx; s++, to += nc) {
+            a.dpx[to] = 0.0, a.dpy[to] = 0.0, a.dactive[to] = 0;
+#pragma unroll
+            for (int k = 0; k < JRX_MAXPHASE; k++)
+                if (k < a.nargs) a.ad[k][to] = 0.0;
+        }
+    }
+    pt_count(a.counts + 0, n_before);
+    pt_count(a.counts + 1, n);
+    pt_count(a.counts + 2, n_outside);
+    pt_count(a.counts + 3, n_far);
+    pt_count(a.counts + 4, n_overflow);
+}
+
+// ------------------------------------------------------------------------------------------------ 3. grid2particle
+struct PtG2PArgs {
+    PtGeom g;
+    double *pF;
+    const double *F;          // (nx + 1, ny + 1)
+};
+
+__global__ __launch_bounds__(256) void k_pt_grid2particle(const PtG2PArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i >= g.nx || j >= g.ny) return;
+    const int nc = g.nx * g.ny;
+    const double *f = a.F + j * (g.nx + 1) + i;
+    const double f00 = f[0], f10 = f[1], f01 = f[g.nx + 1], f11 = f[g.nx + 2];
+    const double xv = g.x0 + (double)i * g.dx, yv = g.y0 + (double)j * g.dy;
+    int lin = j * g.nx + i;
+    for (int s = 0; s < g.mx; s++, lin += nc) {
+        double v = 0.0;
+        if (g.active[lin] != 0) {
+            const double tx = (g.px[lin] - xv) * g.idx, ty = (g.py[lin] - yv) * g.idy;
+            v = (1.0 - ty) * ((1.0 - tx) * f00 + tx * f10) + ty * ((1.0 - tx) * f01 + tx * f11);
+        }
+        a.pF[lin] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ 4. particle2grid
+struct PtP2GArgs {
+    PtGeom g;
+    double *F;                // (nx + 1, ny + 1)
+    const double *pF;
+};
+
+__global__ __launch_bounds__(256) void k_pt_particle2grid(const PtP2GArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i > g.nx || j > g.ny) return;
+    const int nc = g.nx * g.ny;
+    const double xv = g.x0 + (double)i * g.dx, yv = g.y0 + (double)j * g.dy;
+    double num = 0.0, den = 0.0;
+#pragma unroll
+    for (int oi = -1; oi <= 0; oi++) {
+#pragma unroll
+        for (int oj = -1; oj <= 0; oj++) {
+            const int ic = i + oi, jc = j + oj;
+            if (ic < 0 || ic >= g.nx || jc < 0 || jc >= g.ny) continue;
+            for (int s = 0, lin = jc * g.nx + ic; s < g.mx; s++, lin += nc) {
+                if (g.active[lin] == 0) continue;
+                const double w = pt_w(g.px[lin], xv, g.idx) * pt_w(g.py[lin], yv, g.idy);
+                num += w * a.pF[lin];
+                den += w;
+            }
+        }
+    }
+    if (!(den == 0.0)) a.F[j * (g.nx + 1) + i] = num / den;
+}
+
+// ------------------------------------------------------------------------------------------------ 5. phase ratios
+struct PtPrArgs {
+    PtGeom g;
+    double *center, *vertex, *Vx, *Vy;
+    const double *pPhases;
+    unsigned long long *n_empty;
+};
+
+template <int N>
+__device__ __forceinline__ void pt_add(double (&acc)[N], double &W, int k, double w)
+{
+#pragma unroll
+    for (int q = 0; q < N; q++) acc[q] = q == k ? acc[q] + w : acc[q];
+    W += w;
+}
+
+// ratio_k = w_k / W into N contiguous doubles; 1 (and nothing written) where W == 0
+template <int N>
+__device__ __forceinline__ int pt_ratio(const double (&acc)[N], double W, double *__restrict__ out)
+{
+    if (W == 0.0) return 1;
+#pragma unroll
+    for (int q = 0; q < N; q++) out[q] = acc[q] / W;
+    return 0;
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void k_pt_phase_ratios(const PtPrArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    const bool live = i <= g.nx && j <= g.ny;
+    int empty = 0;
+    if (live) {
+        const int nc = g.nx * g.ny;
+        const double xv = g.x0 + (double)i * g.dx, yv = g.y0 + (double)j * g.dy;
+        const double xc = g.x0 + ((double)i + 0.5) * g.dx, yc = g.y0 + ((double)j + 0.5) * g.dy;
+        double ac[N], av[N], ax[N], ay[N];
+        double Wc = 0.0, Wv = 0.0, Wx = 0.0, Wy = 0.0;
+#pragma unroll
+        for (int q = 0; q < N; q++) ac[q] = av[q] = ax[q] = ay[q] = 0.0;
+#pragma unroll
+        for (int oi = -1; oi <= 0; oi++) {
+#pragma unroll
+            for (int oj = -1; oj <= 0; oj++) {
+                const int ic = i + oi, jc = j + oj;
+                if (ic < 0 || ic >= g.nx || jc < 0 || jc >= g.ny) continue;
+                for (int s = 0, lin = jc * g.nx + ic; s < g.mx; s++, lin += nc) {
+                    if (g.active[lin] == 0) continue;
+                    const double p = a.pPhases[lin];
+                    if (!(p >= 1.0 && p < (double)(N + 1))) continue;
+                    const int k = (int)p - 1;
+                    const double x = g.px[lin], y = g.py[lin];
+                    const double wxv = pt_w(x, xv, g.idx), wyv = pt_w(y, yv, g.idy);
+                    pt_add<N>(av, Wv, k, wxv * wyv);
+                    if (oi == 0 || oj == 0) {                       // compile-time after unrolling: the own cell feeds every member, (i-1, j) Vx, (i, j-1) Vy
+                        const double wxc = pt_w(x, xc, g.idx), wyc = pt_w(y, yc, g.idy);
+                        if (oj == 0) pt_add<N>(ax, Wx, k, wxv * wyc);
+                        if (oi == 0) pt_add<N>(ay, Wy, k, wxc * wyv);
+                        if (oi == 0 && oj == 0) pt_add<N>(ac, Wc, k, wxc * wyc);
+                    }
+                }
+            }
+        }
+        const bool hx = i < g.nx, hy = j < g.ny;
+        if (hx && hy) empty += pt_ratio<N>(ac, Wc, a.center + (size_t)(j * g.nx + i) * N);
+        empty += pt_ratio<N>(av, Wv, a.vertex + (size_t)(j * (g.nx + 1) + i) * N);
+        if (hy) empty += pt_ratio<N>(ax, Wx, a.Vx + (size_t)(j * (g.nx + 1) + i) * N);
+        if (hx) empty += pt_ratio<N>(ay, Wy, a.Vy + (size_t)(j * g.nx + i) * N);
+    }
+    pt_count(a.n_empty, empty);
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+bool pt_overlaps(const void *a, i64 abytes, const void *b, i64 bbytes)
+{
+    const char *pa = (const char *)a, *pb = (const char *)b;
+    return pa < pb + bbytes && pb < pa + abytes;
+}
+
+// the checks every entry point shares; fills g (without nbx)
+jrx_status pt_geom(jrx_handle *h, const char *fn, const char *what, const jrx_particles2d *p, PtGeom *g)
+{
+    if (!p) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, what);
+    if (!p->px || !p->py || !p->active) return jrx_fail(h, JRX_ERR_ARG, "%s: %s.%s is NULL", fn, what, !p->px ? "px" : (!p->py ? "py" : "active"));
+    if (p->nx < 1 || p->ny < 1) return jrx_fail(h, JRX_ERR_ARG, "%s: %s has %lld x %lld cells", fn, what, (long long)p->nx, (long long)p->ny);
+    if (p->max_xcell < 1) return jrx_fail(h, JRX_ERR_ARG, "%s: %s.max_xcell = %d", fn, what, (int)p->max_xcell);
+    if ((double)p->nx * (double)p->ny * (double)p->max_xcell >= 2147483648.0 || (double)(p->nx + 2) * (double)(p->ny + 2) * JRX_MAXPHASE >= 2147483648.0)
+        return jrx_fail(h, JRX_ERR_ARG, "%s: %s has 2^31 or more slots or nodes (32-bit offsets)", fn, what);
+    if (!std::isfinite(p->x0) || !std::isfinite(p->y0)) return jrx_fail(h, JRX_ERR_ARG, "%s: %s has origin (%g, %g) (must be finite)", fn, what, p->x0, p->y0);
+    if (!(p->dx > 0.0) || !(p->dy > 0.0) || !std::isfinite(p->dx) || !std::isfinite(p->dy))
+        return jrx_fail(h, JRX_ERR_ARG, "%s: %s has spacings (%g, %g) (must be positive and finite: a uniform grid)", fn, what, p->dx, p->dy);
+    if (p->_dx != 1.0 / p->dx || p->_dy != 1.0 / p->dy)
+        return jrx_fail(h, JRX_ERR_ARG, "%s: %s._dx, ._dy = (%g, %g) are not 1 / dx, 1 / dy", fn, what, p->_dx, p->_dy);
+    if (jrx_comm_active(h)) return jrx_fail(h, JRX_ERR_ARG, "%s: a handle with a communicator (particles are built for one block)", fn);
+    *g = PtGeom{p->px, p->py, (int *)p->active, p->x0, p->y0, p->dx, p->dy, p->_dx, p->_dy, (int)p->nx, (int)p->ny, (int)p->max_xcell, 0};
+    return JRX_OK;
+}
+
+i64 pt_slots(const PtGeom &g) { return (i64)g.nx * g.ny * g.mx; }
+
+// an array of `bytes` bytes must not share memory with the coordinates or the mask of g
+jrx_status pt_apart(jrx_handle *h, const char *fn, const char *name, const void *p, i64 bytes, const PtGeom &g)
+{
+    const i64 ns = pt_slots(g);
+    if (pt_overlaps(p, bytes, g.px, 8 * ns) || pt_overlaps(p, bytes, g.py, 8 * ns) || pt_overlaps(p, bytes, g.active, 4 * ns))
+        return jrx_fail(h, JRX_ERR_ARG, "%s: %s overlaps the particle coordinates or the mask", fn, name);
+    return JRX_OK;
+}
+
+// grid of 64 x 4 tiles over an (ex, ey) box
+unsigned pt_blocks(PtGeom &g, int ex, int ey)
+{
+    g.nbx = (ex + kPtTX - 1) / kPtTX;
+    return (unsigned)((i64)g.nbx * ((ey + kPtTY - 1) / kPtTY));
+}
+
+// the counter words: six 64-bit integers in the tail of the handle's reduction scratch (every entry point here is synchronous)
+unsigned long long *pt_words(jrx_handle *h) { return (unsigned long long *)(h->d_sums + 10); }
+
+jrx_status pt_read_words(jrx_handle *h, int n, int64_t *out)
+{
+    JRX_HIP(h, hipMemcpyAsync(h->h_sums + 10, h->d_sums + 10, sizeof(int64_t) * n, hipMemcpyDeviceToHost, h->stream));
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    memcpy(out, h->h_sums + 10, sizeof(int64_t) * n);
+    return JRX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+jrx_status jrx_particles2d_advect_rk2(jrx_handle *h, const jrx_particles2d *part, const double *Vx, const double *Vy, double dt)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "advection!(particles)";
+    PtAdvArgs a = {};
+    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    if (!Vx || !Vy) return jrx_fail(h, JRX_ERR_ARG, "%s: V.%s is NULL", fn, !Vx ? "Vx" : "Vy");
+    if (!std::isfinite(dt)) return jrx_fail(h, JRX_ERR_ARG, "%s: dt = %g (must be finite)", fn, dt);
+    JRX_TRY(pt_apart(h, fn, "V.Vx", Vx, 8 * (i64)(a.g.nx + 1) * (a.g.ny + 2), a.g));
+    JRX_TRY(pt_apart(h, fn, "V.Vy", Vy, 8 * (i64)(a.g.nx + 2) * (a.g.ny + 1), a.g));
+    JRX_TRY(jrx_check_device(h));
+    a.Vx = Vx, a.Vy = Vy;
+    a.oyx = part->y0 - 0.5 * part->dy, a.oxy = part->x0 - 0.5 * part->dx;
+    a.dt = dt, a.hdt = 0.5 * dt;
+    const unsigned nb = pt_blocks(a.g, a.g.nx, a.g.ny);
+    h->stat_particles_launches++;
+    hipLaunchKernelGGL(k_pt_advect_rk2, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+    JRX_LAUNCH_CHECK(h);
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_particles2d_move(jrx_handle *h, const jrx_particles2d *src, const jrx_particles2d *dst, const double *const *args_src, double *const *args_dst,
+                                int32_t nargs, int64_t counts[5])
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "move_particles!";
+    PtMoveArgs a = {};
+    PtGeom d;
+    JRX_TRY(pt_geom(h, fn, "particles (source)", src, &a.src));
+    JRX_TRY(pt_geom(h, fn, "particles (destination)", dst, &d));
+    if (!counts) return jrx_fail(h, JRX_ERR_ARG, "%s: counts is NULL", fn);
+    if (src->nx != dst->nx || src->ny != dst->ny || src->max_xcell != dst->max_xcell || src->x0 != dst->x0 || src->y0 != dst->y0 || src->dx != dst->dx ||
+        src->dy != dst->dy)
+        return jrx_fail(h, JRX_ERR_ARG, "%s: source and destination differ in extents, max_xcell, origin or spacing", fn);
+    if (nargs < 0 || nargs > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d particle fields (0 .. %d are built)", fn, (int)nargs, JRX_MAXPHASE);
+    if (nargs > 0 && (!args_src || !args_dst)) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL with %d particle fields", fn, !args_src ? "args_src" : "args_dst", (int)nargs);
+    const i64 ns = pt_slots(d);
+    for (int k = 0; k < nargs; k++)
+        if (!args_src[k] || !args_dst[k]) return jrx_fail(h, JRX_ERR_ARG, "%s: particle field %d (%s) is NULL", fn, k + 1, !args_src[k] ? "source" : "destination");
+    // nothing written may share memory with anything read or with another output
+    const void *out[3 + JRX_MAXPHASE] = {d.px, d.py, d.active};
+    i64 ob[3 + JRX_MAXPHASE] = {8 * ns, 8 * ns, 4 * ns};
+    for (int k = 0; k < nargs; k++) out[3 + k] = args_dst[k], ob[3 + k] = 8 * ns;
+    for (int m = 0; m < 3 + nargs; m++) {
+        JRX_TRY(pt_apart(h, fn, "an array of the destination", out[m], ob[m], a.src));
+        for (int k = 0; k < nargs; k++)
+            if (pt_overlaps(out[m], ob[m], args_src[k], 8 * ns)) return jrx_fail(h, JRX_ERR_ARG, "%s: an array of the destination overlaps source particle field %d", fn, k + 1);
+        for (int q = m + 1; q < 3 + nargs; q++)
+            if (pt_overlaps(out[m], ob[m], out[q], ob[q])) return jrx_fail(h, JRX_ERR_ARG, "%s: two arrays of the destination overlap", fn);
+    }
+    JRX_TRY(jrx_check_device(h));
+    a.dpx = d.px, a.dpy = d.py, a.dactive = d.active;
+    for (int k = 0; k < nargs; k++) a.as[k] = args_src[k], a.ad[k] = args_dst[k];
+    a.nargs = (int)nargs;
+    a.counts = pt_words(h);
+    const unsigned nb = pt_blocks(a.src, a.src.nx, a.src.ny);
+    JRX_HIP(h, hipMemsetAsync(a.counts, 0, sizeof(int64_t) * 5, h->stream));
+    h->stat_particles_launches++;
+    hipLaunchKernelGGL(k_pt_move, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+    JRX_LAUNCH_CHECK(h);
+    return pt_read_words(h, 5, counts);
+}
+
+jrx_status jrx_particles2d_grid2particle(jrx_handle *h, double *pF, const double *F, const jrx_particles2d *part)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "grid2particle!";
+    PtG2PArgs a = {};
+    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    if (!pF || !F) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, !pF ? "pF" : "F");
+    const i64 ns = pt_slots(a.g), nv = (i64)(a.g.nx + 1) * (a.g.ny + 1);
+    JRX_TRY(pt_apart(h, fn, "pF", pF, 8 * ns, a.g));
+    if (pt_overlaps(pF, 8 * ns, F, 8 * nv)) return jrx_fail(h, JRX_ERR_ARG, "%s: pF overlaps F", fn);
+    JRX_TRY(jrx_check_device(h));
+    a.pF = pF, a.F = F;
+    const unsigned nb = pt_blocks(a.g, a.g.nx, a.g.ny);
+    h->stat_particles_launches++;
+    hipLaunchKernelGGL(k_pt_grid2particle, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+    JRX_LAUNCH_CHECK(h);
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_particles2d_particle2grid(jrx_handle *h, double *F, const double *pF, const jrx_particles2d *part)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "particle2grid!";
+    PtP2GArgs a = {};
+    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    if (!pF || !F) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, !F ? "F" : "pF");
+    const i64 ns = pt_slots(a.g), nv = (i64)(a.g.nx + 1) * (a.g.ny + 1);
+    JRX_TRY(pt_apart(h, fn, "F", F, 8 * nv, a.g));
+    if (pt_overlaps(pF, 8 * ns, F, 8 * nv)) return jrx_fail(h, JRX_ERR_ARG, "%s: F overlaps pF", fn);
+    JRX_TRY(jrx_check_device(h));
+    a.F = F, a.pF = pF;
+    const unsigned nb = pt_blocks(a.g, a.g.nx + 1, a.g.ny + 1);
+    h->stat_particles_launches++;
+    hipLaunchKernelGGL(k_pt_particle2grid, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+    JRX_LAUNCH_CHECK(h);
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    return JRX_OK;
+}
+
+jrx_status jrx_particles2d_phase_ratios(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, const double *pPhases, int32_t nphase,
+                                        const jrx_particles2d *part, int64_t *n_empty)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "update_phase_ratios!(particles)";
+    PtPrArgs a = {};
+    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    double *const out[4] = {center, vertex, Vx, Vy};
+    static const char *const names[4] = {"center", "vertex", "Vx", "Vy"};
+    for (int m = 0; m < 4; m++)
+        if (!out[m]) return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios.%s is NULL", fn, names[m]);
+    if (!pPhases) return jrx_fail(h, JRX_ERR_ARG, "%s: pPhases is NULL", fn);
+    if (!n_empty) return jrx_fail(h, JRX_ERR_ARG, "%s: n_empty is NULL", fn);
+    if (nphase < 1 || nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d phases (1 .. %d are built)", fn, (int)nphase, JRX_MAXPHASE);
+    const i64 nx = a.g.nx, ny = a.g.ny, ns = pt_slots(a.g);
+    const i64 ob[4] = {8 * nphase * nx * ny, 8 * nphase * (nx + 1) * (ny + 1), 8 * nphase * (nx + 1) * ny, 8 * nphase * nx * (ny + 1)};
+    for (int m = 0; m < 4; m++) {
+        JRX_TRY(pt_apart(h, fn, names[m], out[m], ob[m], a.g));
+        if (pt_overlaps(out[m], ob[m], pPhases, 8 * ns)) return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios.%s overlaps pPhases", fn, names[m]);
+        for (int q = m + 1; q < 4; q++)
+            if (pt_overlaps(out[m], ob[m], out[q], ob[q])) return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios.%s and phase_ratios.%s overlap", fn, names[m], names[q]);
+    }
+    JRX_TRY(jrx_check_device(h));
+    a.center = center, a.vertex = vertex, a.Vx = Vx, a.Vy = Vy, a.pPhases = pPhases;
+    a.n_empty = pt_words(h) + 5;
+    const unsigned nb = pt_blocks(a.g, a.g.nx + 1, a.g.ny + 1);
+    JRX_HIP(h, hipMemsetAsync(a.n_empty, 0, sizeof(int64_t), h->stream));
+    h->stat_particles_launches++;
+    dispatch_const<1, 2, 3, 4, 5, 6, 7, 8>((int)nphase, [&](auto NN) {
+        hipLaunchKernelGGL((k_pt_phase_ratios<NN()>), dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+    });
+    JRX_LAUNCH_CHECK(h);
+    JRX_HIP(h, hipMemcpyAsync(h->h_sums + 15, h->d_sums + 15, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
+    memcpy(n_empty, h->h_sums + 15, sizeof(int64_t));
+    return JRX_OK;
+}
+
+}  // extern "C"

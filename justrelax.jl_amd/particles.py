@@ -1,0 +1,306 @@
+"""2D marker-in-cell particles on the device: init_particles, init_cell_arrays, RungeKutta2, advection!, move_particles!, grid2particle!, particle2grid! and
+update_phase_ratios!(phase_ratios, particles, pPhases) -- the chain the reference's miniapps take from JustPIC (miniapps/benchmarks/stokes2D/shear_heating/
+Shearheating2D.jl:69-82,221-232).  Julia's `f!` is spelled `f_`.  JustPIC's text is not in the reference tree: include/jrx.h holds the definitions of what is
+built, tests/_particles2d.py restates them in NumPy.  Every operator forwards to one C-ABI entry point (csrc/particles.hip); only the seeding is computed
+here, on the host.
+
+Built: 2D, uniform grid, one block, fp64.  Refused by name: 3D, a non-uniform Geometry, a handle with a communicator (by the library), particle injection, a marker
+chain, StressParticles.
+
+A time step with particles (examples/sinking_block2d_particles.py):
+
+    advection_(particles, RungeKutta2(), stokes.V, dt); move_particles_(particles, particle_args); update_phase_ratios_(phase_ratios, particles, pPhases);
+    compute_ρg_(...); solve_(...)
+
+Layout: every per-particle array is (nx, ny, max_xcell) column-major, the slot index slowest; an inactive slot holds 0 in every array.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .arrays import from_numpy, fzeros, ptr
+from .backend import device_of
+from .gridops import _h
+from .phases import _ULPS          # the vertex spacing may vary by this many ulp of the largest coordinate, as for update_phase_ratios_2D_
+
+COUNTS = ("n_active_before", "n_active_after", "n_outside", "n_far", "n_overflow")
+
+
+def _not_built(what):
+    raise NotImplementedError(f"{what}: not built (particles are 2D, uniform grid, one block; injection, marker chains and StressParticles are not provided)")
+
+
+def inject_particles_phase_(*a, **k):
+    _not_built("inject_particles_phase!")
+
+
+def MarkerChain(*a, **k):
+    _not_built("MarkerChain")
+
+
+def StressParticles(*a, **k):
+    _not_built("StressParticles")
+
+
+class RungeKutta2:
+    """RungeKutta2(): the midpoint rule (α = 0.5), the only member of the family that is built"""
+
+    def __init__(self, α=0.5):
+        if float(α) != 0.5:
+            raise NotImplementedError(f"RungeKutta2(α = {α}): only the midpoint rule α = 0.5 is built")
+        self.α = 0.5
+
+
+def _lattice(nxcell):
+    nsx = max(d for d in range(1, int(np.floor(np.sqrt(nxcell))) + 1) if nxcell % d == 0)
+    return nsx, nxcell // nsx
+
+
+def _izeros(shape, device):
+    t = torch.zeros(tuple(shape)[::-1], dtype=torch.int32, device=device)
+    return t.permute(*range(len(shape) - 1, -1, -1))
+
+
+class Particles:
+    """What init_particles returns: coords = (px, py) and index (the int32 mask `active`), each (nx, ny, max_xcell); the grid (x0, y0, dx, dy and the inverses
+    formed once here); a second set of buffers for the out-of-place move, and one twin per particle field of init_cell_arrays."""
+
+    def __init__(self, device, ni, max_xcell, min_xcell, nxcell, x0, y0, dx, dy):
+        self.ni, self.max_xcell, self.min_xcell, self.nxcell = tuple(ni), int(max_xcell), int(min_xcell), int(nxcell)
+        self.x0, self.y0, self.dx, self.dy = float(x0), float(y0), float(dx), float(dy)
+        self._dx, self._dy = 1.0 / self.dx, 1.0 / self.dy
+        self.di = (self.dx, self.dy)
+        shape = self.ni + (self.max_xcell,)
+        self.device = device
+        self.coords = (fzeros(shape, device), fzeros(shape, device))
+        self.index = _izeros(shape, device)
+        self._coords2 = (fzeros(shape, device), fzeros(shape, device))
+        self._index2 = _izeros(shape, device)
+        self._twins = {}          # id(particle field) -> (field, twin)
+
+    @property
+    def shape(self):
+        return self.ni + (self.max_xcell,)
+
+    def _struct(self, second=False):
+        px, py = self._coords2 if second else self.coords
+        idx = self._index2 if second else self.index
+        return _lib.Particles2D(ptr(px), ptr(py), idx.data_ptr(), self.ni[0], self.ni[1], self.max_xcell, self.x0, self.y0, self.dx, self.dy, self._dx, self._dy)
+
+    def _swap(self, fields):
+        self.coords, self._coords2 = self._coords2, self.coords
+        self.index, self._index2 = self._index2, self.index
+        for f in fields:          # the caller's tensor object keeps its identity and takes the storage that was just written
+            twin = self._twins[id(f)][1]
+            f.data, twin.data = twin.data, f.data
+
+
+def _uniform_vertices(xvi, ni, fn):
+    if hasattr(xvi, "xvi"):          # a Geometry
+        if getattr(xvi, "nonuniform", False):
+            raise NotImplementedError(f"{fn}: a non-uniform Geometry (particles are built for uniform grids)")
+        xvi = xvi.xvi
+    ni = tuple(int(n) for n in ni)
+    if len(ni) != 2 or len(xvi) != 2:
+        raise NotImplementedError(f"{fn}: {len(ni)}D extents with {len(xvi)} vertex vectors (particles are built in 2D)")
+    if any(n < 1 for n in ni):
+        raise ValueError(f"{fn}: ni = {ni}")
+    xv = [np.ascontiguousarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=np.float64) for x in xvi]
+    for d in range(2):
+        if xv[d].shape != (ni[d] + 1,):
+            raise ValueError(f"{fn}: dimension {d + 1} has {ni[d]} cells, xvi[{d}] has {xv[d].size} entries (expected {ni[d] + 1})")
+        steps = np.diff(xv[d])
+        if not np.all(np.isfinite(xv[d])) or not steps[0] > 0.0 or not np.all(np.abs(steps - steps[0]) <= _ULPS * np.spacing(np.abs(xv[d]).max())):
+            raise NotImplementedError(f"{fn}: the vertices of dimension {d + 1} are not uniform (particles are built for uniform grids)")
+    return ni, xv
+
+
+def init_particles(backend_tag, nxcell, max_xcell, min_xcell, xvi, ni, *, rng=None):
+    """init_particles(backend, nxcell, max_xcell, min_xcell, xvi, ni): nxcell particles per cell in slots 0 .. nxcell - 1 on a regular nsx x nsy sub-cell lattice
+    (nsx the largest divisor of nxcell not above its square root): slot s = a + nsx b at (x0 + i dx) + (a + u) dx / nsx, (y0 + j dy) + (b + v) dy / nsy, u = v = 0.5.
+    With rng, a NumPy Generator, u = 0.05 + 0.9 r with r = rng.random((nx, ny, nxcell)), drawn for x first and then for y: jittered inside the sub-cell.  Built on the
+    host, so the same arguments give the same particles.  xvi: the two vertex vectors, or a Geometry."""
+    fn = "init_particles"
+    ni, xv = _uniform_vertices(xvi, ni, fn)
+    nxcell, max_xcell, min_xcell = int(nxcell), int(max_xcell), int(min_xcell)
+    if not 0 <= min_xcell <= nxcell <= max_xcell or nxcell < 1:
+        raise ValueError(f"{fn}: need 0 <= min_xcell <= nxcell <= max_xcell and nxcell >= 1, got nxcell = {nxcell}, max_xcell = {max_xcell}, min_xcell = {min_xcell}")
+    nx, ny = ni
+    if nx * ny * max_xcell >= 2 ** 31:
+        raise ValueError(f"{fn}: {nx} x {ny} x {max_xcell} slots: 2^31 or more (32-bit offsets)")
+    dev = device_of(backend_tag)
+    x0, y0, dx, dy = float(xv[0][0]), float(xv[1][0]), float(xv[0][1] - xv[0][0]), float(xv[1][1] - xv[1][0])
+    nsx, nsy = _lattice(nxcell)
+    s = np.arange(nxcell)
+    a, b = (s % nsx).astype(np.float64)[None, None, :], (s // nsx).astype(np.float64)[None, None, :]
+    if rng is None:
+        u = v = np.full((nx, ny, nxcell), 0.5)
+    else:
+        u = 0.05 + 0.9 * rng.random((nx, ny, nxcell))
+        v = 0.05 + 0.9 * rng.random((nx, ny, nxcell))
+    px, py = np.zeros((nx, ny, max_xcell)), np.zeros((nx, ny, max_xcell))
+    px[:, :, :nxcell] = (x0 + np.arange(nx, dtype=np.float64) * dx)[:, None, None] + (a + u) * (dx / nsx)
+    py[:, :, :nxcell] = (y0 + np.arange(ny, dtype=np.float64) * dy)[None, :, None] + (b + v) * (dy / nsy)
+    p = Particles(dev, ni, max_xcell, min_xcell, nxcell, x0, y0, dx, dy)
+    p.coords[0].copy_(from_numpy(px, dev))
+    p.coords[1].copy_(from_numpy(py, dev))
+    p.index[:, :, :nxcell] = 1
+    return p
+
+
+def init_cell_arrays(particles, n):
+    """init_cell_arrays(particles, Val(n)): n particle fields (nx, ny, max_xcell), zero; each gets a twin for the out-of-place move"""
+    n = int(n)
+    if not 1 <= n <= _lib.MAXPHASE:
+        raise ValueError(f"init_cell_arrays: {n} particle fields (1 .. {_lib.MAXPHASE})")
+    out = []
+    for _ in range(n):
+        f, twin = fzeros(particles.shape, particles.device), fzeros(particles.shape, particles.device)
+        particles._twins[id(f)] = (f, twin)
+        out.append(f)
+    return tuple(out)
+
+
+def _check_particles(particles, fn):
+    if not isinstance(particles, Particles):
+        raise TypeError(f"{fn}: particles must come from init_particles, got {type(particles).__name__}")
+    if len(particles.ni) != 2:
+        raise NotImplementedError(f"{fn}: {len(particles.ni)}D particles (2D is built)")
+
+
+def _check_field(particles, f, name, fn):
+    if not isinstance(f, torch.Tensor) or f.dtype != torch.float64 or tuple(f.shape) != particles.shape:
+        raise ValueError(f"{fn}: {name} must be an fp64 array of {particles.shape} (init_cell_arrays), got "
+                         f"{tuple(f.shape) if isinstance(f, torch.Tensor) else type(f).__name__}")
+    if f.device != particles.coords[0].device:
+        raise ValueError(f"{fn}: {name} is on {f.device}, the particles on {particles.coords[0].device}")
+
+
+def _check_grid(particles, grid, fn):
+    """a Geometry handed along is the particles' grid"""
+    if grid is None:
+        return
+    if getattr(grid, "nonuniform", False):
+        raise NotImplementedError(f"{fn}: a non-uniform Geometry (particles are built for uniform grids)")
+    if len(grid.ni) != 2:
+        raise NotImplementedError(f"{fn}: a {len(grid.ni)}D grid (particles are built in 2D)")
+    if tuple(grid.ni) != particles.ni:
+        raise ValueError(f"{fn}: the grid has {tuple(grid.ni)} cells, the particles {particles.ni}")
+
+
+def advection_(particles, method, V, dt, *, grid=None, handle=None):
+    """advection!(particles, RungeKutta2(), @velocity(stokes), dt): every particle by the midpoint rule through the bilinear interpolant of V = stokes.V (or the
+    tuple (Vx, Vy), ghost layers included), in place (include/jrx.h, jrx_particles2d_advect_rk2).  Follow it with move_particles_."""
+    fn = "advection!"
+    _check_particles(particles, fn)
+    if not isinstance(method, RungeKutta2):
+        raise NotImplementedError(f"{fn}: {type(method).__name__} (RungeKutta2() is built)")
+    _check_grid(particles, grid, fn)
+    Vs = tuple(getattr(V, k) for k in ("Vx", "Vy", "Vz") if getattr(V, k, None) is not None) if hasattr(V, "Vx") else tuple(V)
+    if len(Vs) != 2 or any(v.dim() != 2 for v in Vs):
+        raise NotImplementedError(f"{fn}: V has {len(Vs)} components of {[v.dim() for v in Vs]} dimensions (2D is built)")
+    nx, ny = particles.ni
+    if tuple(tuple(v.shape) for v in Vs) != ((nx + 1, ny + 2), (nx + 2, ny + 1)):
+        raise ValueError(f"{fn}: V is {', '.join(str(tuple(v.shape)) for v in Vs)}; {particles.ni} cells need {(nx + 1, ny + 2)}, {(nx + 2, ny + 1)}")
+    h = _h(particles.coords[0], handle)
+    for k, v in zip(("V.Vx", "V.Vy"), Vs):
+        if v.device != particles.coords[0].device:
+            raise ValueError(f"{fn}: {k} is on {v.device}, the particles on {particles.coords[0].device}")
+    s = particles._struct()
+    h.call("jrx_particles2d_advect_rk2", C.byref(s), C.c_void_p(ptr(Vs[0])), C.c_void_p(ptr(Vs[1])), C.c_double(float(dt)))
+
+
+def move_particles_(particles, particle_args=(), *, handle=None):
+    """move_particles!(particles, particle_args): every particle into the bucket of the cell that owns its coordinate, particle_args (fields of init_cell_arrays)
+    along with it; out of place into the second set of buffers, which then becomes the current one (the tensors of particle_args keep their identity).  Returns the
+    counters as a dict.  RuntimeError naming the counter when particles were lost to a full bucket (n_overflow) or to a jump of more than one cell (n_far): the state
+    is then valid, without those particles.  Particles that left the grid (n_outside) are dropped silently, as the count says."""
+    fn = "move_particles!"
+    _check_particles(particles, fn)
+    args = tuple(particle_args)
+    if len(args) > _lib.MAXPHASE:
+        raise ValueError(f"{fn}: {len(args)} particle fields (0 .. {_lib.MAXPHASE})")
+    for k, f in enumerate(args):
+        _check_field(particles, f, f"particle_args[{k}]", fn)
+        if id(f) not in particles._twins:
+            raise ValueError(f"{fn}: particle_args[{k}] does not come from init_cell_arrays of these particles (it has no twin to move into)")
+    if len({id(f) for f in args}) != len(args):
+        raise ValueError(f"{fn}: a particle field is listed twice")
+    h = _h(particles.coords[0], handle)
+    n = len(args)
+    src, dst = particles._struct(), particles._struct(second=True)
+    a_src = (C.c_void_p * max(n, 1))(*(ptr(f) for f in args))
+    a_dst = (C.c_void_p * max(n, 1))(*(ptr(particles._twins[id(f)][1]) for f in args))
+    counts = (C.c_int64 * 5)()
+    h.call("jrx_particles2d_move", C.byref(src), C.byref(dst), a_src, a_dst, C.c_int32(n), counts)
+    particles._swap(args)
+    out = dict(zip(COUNTS, (int(c) for c in counts)))
+    for k in ("n_far", "n_overflow"):
+        if out[k]:
+            err = RuntimeError(f"{fn}: {k} = {out[k]} particles were lost ({'they moved more than one cell: reduce dt' if k == 'n_far' else 'their cell is full: raise max_xcell'}); "
+                               f"counts = {out}")
+            err.counts = out
+            raise err
+    return out
+
+
+def grid2particle_(pF, F, particles, *, handle=None):
+    """grid2particle!(pF, xvi, F, particles): the vertex field F (nx+1, ny+1) to the particles, bilinear in the cell of each particle's bucket"""
+    fn = "grid2particle!"
+    _check_particles(particles, fn)
+    _check_field(particles, pF, "pF", fn)
+    nx, ny = particles.ni
+    if not isinstance(F, torch.Tensor) or tuple(F.shape) != (nx + 1, ny + 1):
+        raise ValueError(f"{fn}: F is {tuple(F.shape) if isinstance(F, torch.Tensor) else type(F).__name__}; {particles.ni} cells need the vertex field {(nx + 1, ny + 1)}")
+    h = _h(pF, handle)
+    if F.device != pF.device:
+        raise ValueError(f"{fn}: F is on {F.device}, pF on {pF.device}")
+    s = particles._struct()
+    h.call("jrx_particles2d_grid2particle", C.c_void_p(ptr(pF)), C.c_void_p(ptr(F)), C.byref(s))
+
+
+def particle2grid_(F, pF, particles, *, handle=None):
+    """particle2grid!(F, pF, xvi, particles): the particle field pF to the vertex field F (nx+1, ny+1), weighted by the bilinear distance of each particle of the
+    up to four cells around a vertex; a vertex without a particle around it keeps its value"""
+    fn = "particle2grid!"
+    _check_particles(particles, fn)
+    _check_field(particles, pF, "pF", fn)
+    nx, ny = particles.ni
+    if not isinstance(F, torch.Tensor) or tuple(F.shape) != (nx + 1, ny + 1):
+        raise ValueError(f"{fn}: F is {tuple(F.shape) if isinstance(F, torch.Tensor) else type(F).__name__}; {particles.ni} cells need the vertex field {(nx + 1, ny + 1)}")
+    h = _h(pF, handle)
+    if F.device != pF.device:
+        raise ValueError(f"{fn}: F is on {F.device}, pF on {pF.device}")
+    s = particles._struct()
+    h.call("jrx_particles2d_particle2grid", C.c_void_p(ptr(F)), C.c_void_p(ptr(pF)), C.byref(s))
+
+
+def update_phase_ratios_(phase_ratios, particles, pPhases, *, handle=None):
+    """update_phase_ratios!(phase_ratios, particles, pPhases): center, vertex, Vx and Vy of phase_ratios from the phases 1.0 .. N of the particles, one launch.
+    Returns n_empty, the number of (node, member) pairs no particle weight reached (left unchanged)."""
+    fn = "update_phase_ratios!"
+    _check_particles(particles, fn)
+    _check_field(particles, pPhases, "pPhases", fn)
+    N = int(phase_ratios.nphases)
+    if not 1 <= N <= _lib.MAXPHASE:
+        raise ValueError(f"{fn}: {N} phases (1 .. {_lib.MAXPHASE})")
+    nx, ny = particles.ni
+    if phase_ratios.center.dim() != 3:
+        raise NotImplementedError(f"{fn}: a {phase_ratios.center.dim() - 1}D PhaseRatios (2D is built)")
+    want = dict(center=(N, nx, ny), vertex=(N, nx + 1, ny + 1), Vx=(N, nx + 1, ny), Vy=(N, nx, ny + 1))
+    for k, shp in want.items():
+        m = getattr(phase_ratios, k, None)
+        if m is None or tuple(m.shape) != shp:
+            raise ValueError(f"{fn}: phase_ratios.{k} is {None if m is None else tuple(m.shape)}, the particles {particles.ni} need {shp}")
+    h = _h(pPhases, handle)
+    if phase_ratios.center.device != pPhases.device:
+        raise ValueError(f"{fn}: phase_ratios is on {phase_ratios.center.device}, pPhases on {pPhases.device}")
+    s = particles._struct()
+    n_empty = C.c_int64()
+    h.call("jrx_particles2d_phase_ratios", *(C.c_void_p(ptr(getattr(phase_ratios, k))) for k in want), C.c_void_p(ptr(pPhases)), C.c_int32(N), C.byref(s),
+           C.byref(n_empty))
+    return int(n_empty.value)
