@@ -136,7 +136,7 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   jrx_update_phases_topography2d calls that launched (their 3D forms jrx_compute_rock_fraction3d / jrx_advect_topography3d / jrx_update_phases_topography3d count in the same three),
  *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* and jrx_dyrel3d_* entry points,
  *   "stat_stepops_launches" = kernels launched by jrx_pureshear_bc2d / 3d, jrx_free_surface_bcs2d / 3d, jrx_subgrid_characteristic_time and jrx_compute_melt_fraction,
- *   "stat_particles_launches" = kernels launched by the five jrx_particles2d_* entry points -- so that a caller
+ *   "stat_particles_launches" = kernels launched by the jrx_particles2d_* entry points (one each, except the two chains of "particles_stress_fused" = 0) -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
 /* the caller has written to an operand array (tau_o, P0, Q, K, G, eta, rho g) since the last driver call: a cached verdict of the operand pass ("operand_cache") is dropped */
@@ -1248,7 +1248,7 @@ jrx_status jrx_compute_melt_fraction(jrx_handle *h, double *phi, const double *p
  * is restated: what is built is defined HERE, to the rounding, and tests/_particles2d.py is the same text in NumPy.  Every operator is a GATHER with loops
  * bounded by max_xcell: nothing races, nothing depends on launch order, the device and the NumPy text leave the same bits.
  * Scope: 2D, uniform grid, one block (a handle with a communicator is refused), fp64.  NOT built: 3D, non-uniform grids, particle injection
- * (inject_particles_phase!), a marker chain, StressParticles.
+ * (inject_particles_phase!), a marker chain, StressParticles (operators 6 - 9 below carry the stress through the reference's tuple methods instead).
  *
  * Layout.  The grid has (nx, ny) cells of size (dx, dy), cell (i, j) = [x0 + i dx, x0 + (i+1) dx) x [y0 + j dy, y0 + (j+1) dy), 0-based.  Every cell owns a BUCKET
  * of max_xcell slots.  Every per-particle array -- px, py (coordinates), active (int32 mask: 1 = the slot holds a particle) and every particle field (pPhases, pT,
@@ -1314,6 +1314,35 @@ jrx_status jrx_particles2d_particle2grid(jrx_handle *h, double *F, const double 
  *    in order.  ratio_k = w_k / W.  Where W == 0 the member is left unchanged and counted: *n_empty = the number of (node, member) pairs with W == 0. */
 jrx_status jrx_particles2d_phase_ratios(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, const double *pPhases, int32_t nphase,
                                         const jrx_particles2d *part, int64_t *n_empty);
+/* Operators 6 - 9 carry the elastic stress on the particles: rotate_stress!(pτxx, pτyy, pτxy, pω, stokes, particles, dt), stress2grid!(stokes, pτxx, pτyy, pτxy,
+ * particles) and rotate_stress_particles!((τ...), (ω,), particles, dt) -- the tuple methods of src/stress_rotation/stress_rotation_particles.jl:92-99,224-235,
+ * 264-276 (StressParticles, the wrapper type of :205-222, is not built) -- and the two JustPIC operators they call, centroid2particle! / particle2centroid!,
+ * which every thermal miniapp needs too (centroid2particle!(pT, T_buffer, particles)).  Layout, rounding, safety and refusals as above; further refusals: nx < 2
+ * or ny < 2 where operator 6 is involved, an unknown method, an output that overlaps an input, another output or the particles' own arrays.
+ * 6. centroid2particle!(pF, F, particles): F is a centre field (nx, ny), nodes at (x0 + (i + 0.5) dx, y0 + (j + 0.5) dy).  Per active slot pF = A(x, y), A the
+ *    interpolant of (1) with extents (nx, ny) and node-grid origin (x0 + 0.5 dx, y0 + 0.5 dy), formed once on the host: the pair is found from the COORDINATE (not
+ *    from the bucket), and a particle in the outer half cells extrapolates linearly from the outermost pair of centres.  A slot whose scaled coordinate is not
+ *    finite is left as it was; an inactive slot is set to 0.  Needs nx >= 2 && ny >= 2. */
+jrx_status jrx_particles2d_centroid2particle(jrx_handle *h, double *pF, const double *F, const jrx_particles2d *part);
+/* 7. particle2centroid!(F, pF, particles): one thread per cell (i, j) walks its own bucket in slot order; xc = x0 + ((double)i + 0.5) dx, yc likewise;
+ *      w = (1 - fabs(x - xc) _dx) (1 - fabs(y - yc) _dy);  num += w pF;  den += w;     F[i, j] = num / den;  where den == 0, F[i, j] is left as it was
+ *    (the `center` rule of (5)). */
+jrx_status jrx_particles2d_particle2centroid(jrx_handle *h, double *F, const double *pF, const jrx_particles2d *part);
+/* 8. rotate_stress_particles!((pτxx, pτyy, pτxy), (pω,), particles, dt; method): per active slot, in place, θ = dt pω, then JRX_ROTATE_MATRIX or
+ *    JRX_ROTATE_JAUMANN exactly as jrx_rotate_stress2d defines them per point (one device function serves both).  The reference's particle Jaumann kernel
+ *    (:151-167) has the sign defect listed with jrx_rotate_stress2d and is not followed; its `method` keyword does not select an algorithm, here it does.
+ *    An inactive slot is not touched (it holds 0).  ptau = {pτxx, pτyy, pτxy}: a HOST array of DEVICE pointers. */
+jrx_status jrx_particles2d_rotate(jrx_handle *h, double *const ptau[3], const double *pomega, const jrx_particles2d *part, double dt, int32_t method);
+/* 9. The two calls of a time step.  rotate_stress!: (6) of tau_xx into pτxx, (6) of tau_yy into pτyy, (3) of tau_xy into pτxy, (3) of omega_xy into pω, then (8).
+ *    stress2grid!: tau_o = {xx, yy, xy_c, xy, xx_v, yy_v} (the member order of jrx_rotate_stress2d; all six required); xx, yy, xy_c from pτxx, pτyy, pτxy by (7),
+ *    xx_v, yy_v, xy from pτxx, pτyy, pτxy by (4).  Each is defined as that chain and built as ONE launch that leaves the chain's bits in every output, corner cases
+ *    included (inactive slots; a non-finite coordinate keeps pτxx, pτyy and sends what (3) makes of it through (8)): a thread per cell reads active, x, y of a
+ *    slot once and writes the four particle fields; a thread per node of the (nx+1, ny+1) box loads each particle of its up to four cells once, in the cell and
+ *    slot order of (4), the own cell also feeding the centre it owns (i < nx && j < ny) in the order of (7).  Tuning key "particles_stress_fused"
+ *    (include/jrx_tuning.h) = 0 runs the chains: 5 and 6 launches. */
+jrx_status jrx_particles2d_rotate_stress(jrx_handle *h, double *const ptau[3], double *pomega, const double *tau_xx, const double *tau_yy, const double *tau_xy,
+                                         const double *omega_xy, const jrx_particles2d *part, double dt, int32_t method);
+jrx_status jrx_particles2d_stress2grid(jrx_handle *h, double *const tau_o[6], const double *const ptau[3], const jrx_particles2d *part);
 
 #ifdef __cplusplus
 }

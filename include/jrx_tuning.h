@@ -75,6 +75,9 @@
  *                                 0 = the reference's one launch per member (4 in 2D, 8 in 3D; bit-identical in every member)
  *   "rock_fraction3d_rows" (0)   jrx_compute_rock_fraction3d: vertex rows k a thread marches for its node (i, j); 0 = the built-in depth, 1 = a thread per node of the ni .+ 1 box
  *                                 (bit-identical at every depth; profiles/topography3d_bench.txt)
+ *   "particles_stress_fused" (1) jrx_particles2d_rotate_stress / jrx_particles2d_stress2grid: one launch each -- a thread per cell reads active, x, y of a slot once and writes the four
+ *                                 particle fields; a thread per node of the ni .+ 1 box reads each particle of its up to four cells once for all six members; 0 = the chains of
+ *                                 single-operator launches the definitions name (5 and 6; bit-identical in every output; profiles/particles2d_stress_bench.txt)
  *   "general_hif" (0)            3D fused kernel, general form (any dt), 64 x 4 tile: the stress nodes on the high faces i = nx, j = ny, k = nz are updated inside the kernel (one launch per
  *                                 unobserved iteration) and, with neighbours, the kernel's boundary tiles read the received planes ("fused_overlap" = 3: no flow_bcs! launch, no fix-up):
  *                                 4 / 3 = the instantiation built for four (128 VGPRs + 28 dwords of scratch: 10.99 ms at 512^3) / three (155 VGPRs: 7.95 ms) waves per SIMD; 0 = boundary-layer launch (7.47 + 0.11 ms)

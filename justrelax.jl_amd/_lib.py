@@ -258,6 +258,12 @@ def load(check_symbols: bool = False):
         L.jrx_particles2d_grid2particle.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _pp]
         L.jrx_particles2d_particle2grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _pp]
         L.jrx_particles2d_phase_ratios.argtypes = [C.c_void_p] * 6 + [C.c_int32, _pp, _ip]
+        # the stress on particles: pF / F, the struct | ptau[3] (a host array of device pointers), pω, the struct, dt, method | ptau[3], pω, τ.xx, τ.yy, τ.xy, ω.xy, the struct, dt, method | tau_o[6], ptau[3], the struct
+        L.jrx_particles2d_centroid2particle.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _pp]
+        L.jrx_particles2d_particle2centroid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _pp]
+        L.jrx_particles2d_rotate.argtypes = [C.c_void_p, _vpp, C.c_void_p, _pp, C.c_double, C.c_int32]
+        L.jrx_particles2d_rotate_stress.argtypes = [C.c_void_p, _vpp] + [C.c_void_p] * 5 + [_pp, C.c_double, C.c_int32]
+        L.jrx_particles2d_stress2grid.argtypes = [C.c_void_p, _vpp, _vpp, _pp]
         _lib = L
     if check_symbols:
         missing = [s for s in declared_symbols() if not hasattr(_lib, s)]

@@ -117,6 +117,7 @@ struct jrx_handle {
     int64_t stat_dyrel_launches = 0;     // kernels launched by the jrx_dyrel2d_* / jrx_dyrel3d_* entry points (dyrel2d.hip, dyrel3d.hip)
     int64_t stat_stepops_launches = 0;   // kernels launched by the per-step operators of stepops.hip (pureshear_bc!, free_surface_bcs!, subgrid_characteristic_time!, compute_melt_fraction!)
     int64_t stat_particles_launches = 0; // kernels launched by the jrx_particles2d_* entry points (particles.hip)
+    bool particles_stress_fused = true;  // tuning: jrx_particles2d_rotate_stress / _stress2grid as one launch each (0: the chains of single-operator launches, 5 and 6; bit-identical)
     // ---- read-only counters (jrx_get_option "stat_*"): launches of the fused kernels since jrx_create, so that tests and the bench can
     //      prove which kernel path ran
     int64_t stat_fused3d_inkernel = 0;   // launches of k_fused3d that finished the neighbour faces themselves (fused_overlap = 3)

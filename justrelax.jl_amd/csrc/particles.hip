@@ -1,8 +1,11 @@
 // particles.hip -- 2D marker-in-cell particles in gather form: advection!(particles, RungeKutta2(), V, dt), move_particles!, grid2particle!, particle2grid!
-// and update_phase_ratios!(phase_ratios, particles, pPhases), for gfx950.
+// and update_phase_ratios!(phase_ratios, particles, pPhases); and the elastic stress carried on them: centroid2particle!, particle2centroid!,
+// rotate_stress_particles!, rotate_stress!(pτxx, pτyy, pτxy, pω, stokes, particles, dt) and stress2grid!, for gfx950.
 //
-// Reference: none to restate.  The reference's miniapps take these from JustPIC (miniapps/benchmarks/stokes2D/shear_heating/Shearheating2D.jl:69-82,221-232 shows
-// the calls), which is not in the reference tree.  include/jrx.h states the definitions built here; tests/_particles2d.py is the same text in NumPy.
+// Reference: for the first five none to restate.  The reference's miniapps take them from JustPIC (miniapps/benchmarks/stokes2D/shear_heating/
+// Shearheating2D.jl:69-82,221-232 shows the calls), which is not in the reference tree.  include/jrx.h states the definitions built here; tests/_particles2d.py
+// is the same text in NumPy.  The stress operators follow the tuple methods of src/stress_rotation/stress_rotation_particles.jl:92-99,224-235,264-276 with
+// JustPIC's centroid2particle! / particle2centroid! defined in include/jrx.h (tests/_particles2d_stress.py); the per-point rotation is rotate_point.hpp.
 //
 // Layout: every per-particle array is (nx, ny, max_xcell) column-major, the slot index slowest (include/jrx.h): a thread owns a cell (or a node) and walks the
 // slots, so in every trip of a slot loop the lanes of a wave read consecutive addresses.  An inactive slot holds 0 everywhere.
@@ -17,6 +20,7 @@
 // 4 N + 4 accumulators of a node stay in registers (a run-time index into them would put them in scratch).
 #include <cfloat>
 #include "jrx_internal.hpp"
+#include "rotate_point.hpp"
 
 namespace {
 
@@ -44,16 +48,38 @@ __device__ __forceinline__ int pt_pair(double s, int m)
     return f >= 0.0 ? (f < (double)(m - 1) ? (int)f : m - 2) : 0;
 }
 
-// one staggered component A of extents (mx, my), node grid origin (ox, oy), at (x, y); false (and no load) when a scaled coordinate is not finite
-__device__ __forceinline__ bool pt_interp(const double *__restrict__ A, int mx, int my, double ox, double oy, double idx, double idy, double x, double y, double &v)
+// the bilinear form every interpolation here uses, in this order
+__device__ __forceinline__ double pt_bilin(double tx, double ty, double v00, double v10, double v01, double v11)
+{
+    return (1.0 - ty) * ((1.0 - tx) * v00 + tx * v10) + ty * ((1.0 - tx) * v01 + tx * v11);
+}
+
+// where (x, y) sits on a node grid of extents (mx, my) and origin (ox, oy): offset of the pair's first node and the local coordinates; false when a scaled
+// coordinate is not finite
+__device__ __forceinline__ bool pt_locate(int mx, int my, double ox, double oy, double idx, double idy, double x, double y, int &off, double &tx, double &ty)
 {
     const double sx = (x - ox) * idx, sy = (y - oy) * idy;
     if (!pt_finite(sx) || !pt_finite(sy)) return false;
     const int i0 = pt_pair(sx, mx), j0 = pt_pair(sy, my);
-    const double tx = sx - (double)i0, ty = sy - (double)j0;
-    const double *p = A + j0 * mx + i0;
+    tx = sx - (double)i0, ty = sy - (double)j0;
+    off = j0 * mx + i0;
+    return true;
+}
+
+__device__ __forceinline__ double pt_at(const double *__restrict__ A, int mx, int off, double tx, double ty)
+{
+    const double *p = A + off;
     const double v00 = p[0], v10 = p[1], v01 = p[mx], v11 = p[mx + 1];
-    v = (1.0 - ty) * ((1.0 - tx) * v00 + tx * v10) + ty * ((1.0 - tx) * v01 + tx * v11);
+    return pt_bilin(tx, ty, v00, v10, v01, v11);
+}
+
+// one staggered component A of extents (mx, my), node grid origin (ox, oy), at (x, y); false (and no load) when a scaled coordinate is not finite
+__device__ __forceinline__ bool pt_interp(const double *__restrict__ A, int mx, int my, double ox, double oy, double idx, double idy, double x, double y, double &v)
+{
+    int off;
+    double tx, ty;
+    if (!pt_locate(mx, my, ox, oy, idx, idy, x, y, off, tx, ty)) return false;
+    v = pt_at(A, mx, off, tx, ty);
     return true;
 }
 
@@ -207,7 +233,7 @@ __global__ __launch_bounds__(256) void k_pt_grid2particle(const PtG2PArgs a)
         double v = 0.0;
         if (g.active[lin] != 0) {
             const double tx = (g.px[lin] - xv) * g.idx, ty = (g.py[lin] - yv) * g.idy;
-            v = (1.0 - ty) * ((1.0 - tx) * f00 + tx * f10) + ty * ((1.0 - tx) * f01 + tx * f11);
+            v = pt_bilin(tx, ty, f00, f10, f01, f11);
         }
         a.pF[lin] = v;
     }
@@ -320,6 +346,169 @@ __global__ __launch_bounds__(256) void k_pt_phase_ratios(const PtPrArgs a)
     pt_count(a.n_empty, empty);
 }
 
+// ------------------------------------------------------------------------------------------------ 6. centroid2particle
+struct PtC2PArgs {
+    PtGeom g;
+    double *pF;
+    const double *F;          // (nx, ny)
+    double ox, oy;            // origin of the centre nodes (x0 + 0.5 dx, y0 + 0.5 dy)
+};
+
+__global__ __launch_bounds__(256) void k_pt_centroid2particle(const PtC2PArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i >= g.nx || j >= g.ny) return;
+    const int nc = g.nx * g.ny;
+    int lin = j * g.nx + i;
+    for (int s = 0; s < g.mx; s++, lin += nc) {
+        if (g.active[lin] == 0) {
+            a.pF[lin] = 0.0;
+            continue;
+        }
+        double v;
+        if (pt_interp(a.F, g.nx, g.ny, a.ox, a.oy, g.idx, g.idy, g.px[lin], g.py[lin], v)) a.pF[lin] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ 7. particle2centroid
+__global__ __launch_bounds__(256) void k_pt_particle2centroid(const PtP2GArgs a)          // F is (nx, ny) here
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i >= g.nx || j >= g.ny) return;
+    const int nc = g.nx * g.ny;
+    const double xc = g.x0 + ((double)i + 0.5) * g.dx, yc = g.y0 + ((double)j + 0.5) * g.dy;
+    double num = 0.0, den = 0.0;
+    for (int s = 0, lin = j * g.nx + i; s < g.mx; s++, lin += nc) {
+        if (g.active[lin] == 0) continue;
+        const double w = pt_w(g.px[lin], xc, g.idx) * pt_w(g.py[lin], yc, g.idy);
+        num += w * a.pF[lin];
+        den += w;
+    }
+    if (!(den == 0.0)) a.F[j * g.nx + i] = num / den;
+}
+
+// ------------------------------------------------------------------------------------------------ 8. rotation of the particle stress, in place
+struct PtRotArgs {
+    PtGeom g;
+    double *pxx, *pyy, *pxy, *pw;                 // the chain reads pw; the fused kernel writes it
+    const double *txx, *tyy, *txy, *wxy;          // fused kernel only: centre fields (nx, ny), vertex fields (nx + 1, ny + 1)
+    double ox, oy;                                // origin of the centre nodes
+    double dt;
+};
+
+template <int METHOD>
+__global__ __launch_bounds__(256) void k_pt_rotate(const PtRotArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i >= g.nx || j >= g.ny) return;
+    const int nc = g.nx * g.ny;
+    int lin = j * g.nx + i;
+    for (int s = 0; s < g.mx; s++, lin += nc) {
+        if (g.active[lin] == 0) continue;
+        double oxx, oyy, oxy;
+        rs_rot2<METHOD>(a.pxx[lin], a.pyy[lin], a.pxy[lin], a.dt * a.pw[lin], oxx, oyy, oxy);
+        a.pxx[lin] = oxx, a.pyy[lin] = oyy, a.pxy[lin] = oxy;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ 9a. rotate_stress!: operators 6, 6, 3, 3, 8 in one launch
+// A slot reads active, x, y once.  The centre pair of (x, y) is located once for xx and yy (the same node grid: the same offset and local coordinates as two calls
+// of pt_interp); the four vertex values of xy and ω are the bucket cell's, loaded once per thread.  A slot whose scaled coordinate is not finite keeps its xx and
+// yy as the chain does -- they are then read -- and still takes xy and ω from the vertices and goes through the rotation.
+template <int METHOD>
+__global__ __launch_bounds__(256) void k_pt_rotate_stress(const PtRotArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i >= g.nx || j >= g.ny) return;
+    const int nc = g.nx * g.ny;
+    const double *fs = a.txy + j * (g.nx + 1) + i, *fw = a.wxy + j * (g.nx + 1) + i;
+    const double s00 = fs[0], s10 = fs[1], s01 = fs[g.nx + 1], s11 = fs[g.nx + 2];
+    const double w00 = fw[0], w10 = fw[1], w01 = fw[g.nx + 1], w11 = fw[g.nx + 2];
+    const double xv = g.x0 + (double)i * g.dx, yv = g.y0 + (double)j * g.dy;
+    int lin = j * g.nx + i;
+    for (int s = 0; s < g.mx; s++, lin += nc) {
+        if (g.active[lin] == 0) {
+            a.pxx[lin] = 0.0, a.pyy[lin] = 0.0, a.pxy[lin] = 0.0, a.pw[lin] = 0.0;
+            continue;
+        }
+        const double x = g.px[lin], y = g.py[lin];
+        int off;
+        double cx, cy, xx, yy;
+        if (pt_locate(g.nx, g.ny, a.ox, a.oy, g.idx, g.idy, x, y, off, cx, cy)) {
+            xx = pt_at(a.txx, g.nx, off, cx, cy);
+            yy = pt_at(a.tyy, g.nx, off, cx, cy);
+        } else {
+            xx = a.pxx[lin], yy = a.pyy[lin];
+        }
+        const double tx = (x - xv) * g.idx, ty = (y - yv) * g.idy;
+        const double xy = pt_bilin(tx, ty, s00, s10, s01, s11);
+        const double w = pt_bilin(tx, ty, w00, w10, w01, w11);
+        double oxx, oyy, oxy;
+        rs_rot2<METHOD>(xx, yy, xy, a.dt * w, oxx, oyy, oxy);
+        a.pxx[lin] = oxx, a.pyy[lin] = oyy, a.pxy[lin] = oxy, a.pw[lin] = w;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ 9b. stress2grid!: operator 7 three times and operator 4 three times in one launch
+struct PtS2GArgs {
+    PtGeom g;
+    double *cxx, *cyy, *cxy;          // centres (nx, ny): τ_o.xx, yy, xy_c
+    double *vxx, *vyy, *vxy;          // vertices (nx + 1, ny + 1): τ_o.xx_v, yy_v, xy
+    const double *pxx, *pyy, *pxy;
+};
+
+// A thread per node of the (nx + 1, ny + 1) box, the cells of operator 4 in its order; the own cell (i, j) comes last and also feeds the centre the thread owns,
+// in slot order as operator 7 walks it.  The three fields of a location share their weights, so one denominator each: eight accumulators.
+__global__ __launch_bounds__(256) void k_pt_stress2grid(const PtS2GArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i > g.nx || j > g.ny) return;
+    const int nc = g.nx * g.ny;
+    const double xv = g.x0 + (double)i * g.dx, yv = g.y0 + (double)j * g.dy;
+    const double xc = g.x0 + ((double)i + 0.5) * g.dx, yc = g.y0 + ((double)j + 0.5) * g.dy;
+    double nvxx = 0.0, nvyy = 0.0, nvxy = 0.0, dv = 0.0;
+    double ncxx = 0.0, ncyy = 0.0, ncxy = 0.0, dc = 0.0;
+#pragma unroll
+    for (int oi = -1; oi <= 0; oi++) {
+#pragma unroll
+        for (int oj = -1; oj <= 0; oj++) {
+            const int ic = i + oi, jc = j + oj;
+            if (ic < 0 || ic >= g.nx || jc < 0 || jc >= g.ny) continue;
+            for (int s = 0, lin = jc * g.nx + ic; s < g.mx; s++, lin += nc) {
+                if (g.active[lin] == 0) continue;
+                const double x = g.px[lin], y = g.py[lin];
+                const double xx = a.pxx[lin], yy = a.pyy[lin], xy = a.pxy[lin];
+                const double w = pt_w(x, xv, g.idx) * pt_w(y, yv, g.idy);
+                nvxx += w * xx, nvyy += w * yy, nvxy += w * xy;
+                dv += w;
+                if (oi == 0 && oj == 0) {          // compile-time after unrolling
+                    const double wc = pt_w(x, xc, g.idx) * pt_w(y, yc, g.idy);
+                    ncxx += wc * xx, ncyy += wc * yy, ncxy += wc * xy;
+                    dc += wc;
+                }
+            }
+        }
+    }
+    if (!(dv == 0.0)) {
+        const int lin = j * (g.nx + 1) + i;
+        a.vxx[lin] = nvxx / dv, a.vyy[lin] = nvyy / dv, a.vxy[lin] = nvxy / dv;
+    }
+    if (i < g.nx && j < g.ny && !(dc == 0.0)) {
+        const int lin = j * g.nx + i;
+        a.cxx[lin] = ncxx / dc, a.cyy[lin] = ncyy / dc, a.cxy[lin] = ncxy / dc;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 bool pt_overlaps(const void *a, i64 abytes, const void *b, i64 bbytes)
 {
@@ -372,6 +561,94 @@ jrx_status pt_read_words(jrx_handle *h, int n, int64_t *out)
     JRX_HIP(h, hipMemcpyAsync(h->h_sums + 10, h->d_sums + 10, sizeof(int64_t) * n, hipMemcpyDeviceToHost, h->stream));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     memcpy(out, h->h_sums + 10, sizeof(int64_t) * n);
+    return JRX_OK;
+}
+
+// ---- operators 6 - 9: an entry point checks everything first, then launches one kernel or its chain; the launchers below check nothing
+struct PtArr {
+    const void *p;
+    i64 bytes;
+    const char *name;
+};
+
+// every array present; no output shares memory with the particles' own arrays, an input or another output
+jrx_status pt_disjoint(jrx_handle *h, const char *fn, const PtArr *out, int nout, const PtArr *in, int nin, const PtGeom &g)
+{
+    for (int m = 0; m < nout; m++)
+        if (!out[m].p) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, out[m].name);
+    for (int k = 0; k < nin; k++)
+        if (!in[k].p) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, in[k].name);
+    for (int m = 0; m < nout; m++) {
+        JRX_TRY(pt_apart(h, fn, out[m].name, out[m].p, out[m].bytes, g));
+        for (int k = 0; k < nin; k++)
+            if (pt_overlaps(out[m].p, out[m].bytes, in[k].p, in[k].bytes)) return jrx_fail(h, JRX_ERR_ARG, "%s: %s overlaps %s", fn, out[m].name, in[k].name);
+        for (int q = m + 1; q < nout; q++)
+            if (pt_overlaps(out[m].p, out[m].bytes, out[q].p, out[q].bytes)) return jrx_fail(h, JRX_ERR_ARG, "%s: %s and %s overlap", fn, out[m].name, out[q].name);
+    }
+    return JRX_OK;
+}
+
+jrx_status pt_centres(jrx_handle *h, const char *fn, const PtGeom &g)
+{
+    if (g.nx < 2 || g.ny < 2) return jrx_fail(h, JRX_ERR_ARG, "%s: %d x %d cells (interpolation between centres needs nx >= 2 and ny >= 2)", fn, g.nx, g.ny);
+    return JRX_OK;
+}
+
+jrx_status pt_method(jrx_handle *h, const char *fn, double dt, int32_t method)
+{
+    if (!std::isfinite(dt)) return jrx_fail(h, JRX_ERR_ARG, "%s: dt = %g (must be finite)", fn, dt);
+    if (method != JRX_ROTATE_MATRIX && method != JRX_ROTATE_JAUMANN)
+        return jrx_fail(h, JRX_ERR_ARG, "%s: unknown method %d (%d = matrix, %d = jaumann)", fn, (int)method, JRX_ROTATE_MATRIX, JRX_ROTATE_JAUMANN);
+    return JRX_OK;
+}
+
+void pt_launch_g2p(jrx_handle *h, PtGeom g, double *pF, const double *F)
+{
+    PtG2PArgs a = {g, pF, F};
+    const unsigned nb = pt_blocks(a.g, g.nx, g.ny);
+    h->stat_particles_launches++;
+    hipLaunchKernelGGL(k_pt_grid2particle, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+}
+
+void pt_launch_p2g(jrx_handle *h, PtGeom g, double *F, const double *pF)
+{
+    PtP2GArgs a = {g, F, pF};
+    const unsigned nb = pt_blocks(a.g, g.nx + 1, g.ny + 1);
+    h->stat_particles_launches++;
+    hipLaunchKernelGGL(k_pt_particle2grid, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+}
+
+void pt_launch_c2p(jrx_handle *h, PtGeom g, double *pF, const double *F)
+{
+    PtC2PArgs a = {g, pF, F, g.x0 + 0.5 * g.dx, g.y0 + 0.5 * g.dy};
+    const unsigned nb = pt_blocks(a.g, g.nx, g.ny);
+    h->stat_particles_launches++;
+    hipLaunchKernelGGL(k_pt_centroid2particle, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+}
+
+void pt_launch_p2c(jrx_handle *h, PtGeom g, double *F, const double *pF)
+{
+    PtP2GArgs a = {g, F, pF};
+    const unsigned nb = pt_blocks(a.g, g.nx, g.ny);
+    h->stat_particles_launches++;
+    hipLaunchKernelGGL(k_pt_particle2centroid, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+}
+
+// fused = false: operator 8 alone on a.pxx, pyy, pxy, pw; true: the one-launch rotate_stress!
+void pt_launch_rotate(jrx_handle *h, PtRotArgs a, int32_t method, bool fused)
+{
+    const unsigned nb = pt_blocks(a.g, a.g.nx, a.g.ny);
+    h->stat_particles_launches++;
+    dispatch_const<0, 1>((int)method, [&](auto MM) {
+        if (fused) hipLaunchKernelGGL((k_pt_rotate_stress<MM()>), dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+        else hipLaunchKernelGGL((k_pt_rotate<MM()>), dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+    });
+}
+
+jrx_status pt_finish(jrx_handle *h)
+{
+    JRX_LAUNCH_CHECK(h);
+    JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
 
@@ -447,40 +724,26 @@ jrx_status jrx_particles2d_grid2particle(jrx_handle *h, double *pF, const double
 {
     if (!h) return JRX_ERR_ARG;
     const char *fn = "grid2particle!";
-    PtG2PArgs a = {};
-    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
-    if (!pF || !F) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, !pF ? "pF" : "F");
-    const i64 ns = pt_slots(a.g), nv = (i64)(a.g.nx + 1) * (a.g.ny + 1);
-    JRX_TRY(pt_apart(h, fn, "pF", pF, 8 * ns, a.g));
-    if (pt_overlaps(pF, 8 * ns, F, 8 * nv)) return jrx_fail(h, JRX_ERR_ARG, "%s: pF overlaps F", fn);
+    PtGeom g;
+    JRX_TRY(pt_geom(h, fn, "particles", part, &g));
+    const PtArr out[1] = {{pF, 8 * pt_slots(g), "pF"}}, in[1] = {{F, 8 * (i64)(g.nx + 1) * (g.ny + 1), "F"}};
+    JRX_TRY(pt_disjoint(h, fn, out, 1, in, 1, g));
     JRX_TRY(jrx_check_device(h));
-    a.pF = pF, a.F = F;
-    const unsigned nb = pt_blocks(a.g, a.g.nx, a.g.ny);
-    h->stat_particles_launches++;
-    hipLaunchKernelGGL(k_pt_grid2particle, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    pt_launch_g2p(h, g, pF, F);
+    return pt_finish(h);
 }
 
 jrx_status jrx_particles2d_particle2grid(jrx_handle *h, double *F, const double *pF, const jrx_particles2d *part)
 {
     if (!h) return JRX_ERR_ARG;
     const char *fn = "particle2grid!";
-    PtP2GArgs a = {};
-    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
-    if (!pF || !F) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, !F ? "F" : "pF");
-    const i64 ns = pt_slots(a.g), nv = (i64)(a.g.nx + 1) * (a.g.ny + 1);
-    JRX_TRY(pt_apart(h, fn, "F", F, 8 * nv, a.g));
-    if (pt_overlaps(pF, 8 * ns, F, 8 * nv)) return jrx_fail(h, JRX_ERR_ARG, "%s: F overlaps pF", fn);
+    PtGeom g;
+    JRX_TRY(pt_geom(h, fn, "particles", part, &g));
+    const PtArr out[1] = {{F, 8 * (i64)(g.nx + 1) * (g.ny + 1), "F"}}, in[1] = {{pF, 8 * pt_slots(g), "pF"}};
+    JRX_TRY(pt_disjoint(h, fn, out, 1, in, 1, g));
     JRX_TRY(jrx_check_device(h));
-    a.F = F, a.pF = pF;
-    const unsigned nb = pt_blocks(a.g, a.g.nx + 1, a.g.ny + 1);
-    h->stat_particles_launches++;
-    hipLaunchKernelGGL(k_pt_particle2grid, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    pt_launch_p2g(h, g, F, pF);
+    return pt_finish(h);
 }
 
 jrx_status jrx_particles2d_phase_ratios(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, const double *pPhases, int32_t nphase,
@@ -519,6 +782,110 @@ jrx_status jrx_particles2d_phase_ratios(jrx_handle *h, double *center, double *v
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     memcpy(n_empty, h->h_sums + 15, sizeof(int64_t));
     return JRX_OK;
+}
+
+jrx_status jrx_particles2d_centroid2particle(jrx_handle *h, double *pF, const double *F, const jrx_particles2d *part)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "centroid2particle!";
+    PtGeom g;
+    JRX_TRY(pt_geom(h, fn, "particles", part, &g));
+    JRX_TRY(pt_centres(h, fn, g));
+    const PtArr out[1] = {{pF, 8 * pt_slots(g), "pF"}}, in[1] = {{F, 8 * (i64)g.nx * g.ny, "F"}};
+    JRX_TRY(pt_disjoint(h, fn, out, 1, in, 1, g));
+    JRX_TRY(jrx_check_device(h));
+    pt_launch_c2p(h, g, pF, F);
+    return pt_finish(h);
+}
+
+jrx_status jrx_particles2d_particle2centroid(jrx_handle *h, double *F, const double *pF, const jrx_particles2d *part)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "particle2centroid!";
+    PtGeom g;
+    JRX_TRY(pt_geom(h, fn, "particles", part, &g));
+    const PtArr out[1] = {{F, 8 * (i64)g.nx * g.ny, "F"}}, in[1] = {{pF, 8 * pt_slots(g), "pF"}};
+    JRX_TRY(pt_disjoint(h, fn, out, 1, in, 1, g));
+    JRX_TRY(jrx_check_device(h));
+    pt_launch_p2c(h, g, F, pF);
+    return pt_finish(h);
+}
+
+jrx_status jrx_particles2d_rotate(jrx_handle *h, double *const ptau[3], const double *pomega, const jrx_particles2d *part, double dt, int32_t method)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "rotate_stress_particles!";
+    PtRotArgs a = {};
+    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    if (!ptau) return jrx_fail(h, JRX_ERR_ARG, "%s: ptau is NULL", fn);
+    JRX_TRY(pt_method(h, fn, dt, method));
+    const i64 ns = 8 * pt_slots(a.g);
+    const PtArr out[3] = {{ptau[0], ns, "pτxx"}, {ptau[1], ns, "pτyy"}, {ptau[2], ns, "pτxy"}}, in[1] = {{pomega, ns, "pω"}};
+    JRX_TRY(pt_disjoint(h, fn, out, 3, in, 1, a.g));
+    JRX_TRY(jrx_check_device(h));
+    a.pxx = ptau[0], a.pyy = ptau[1], a.pxy = ptau[2], a.pw = const_cast<double *>(pomega), a.dt = dt;
+    pt_launch_rotate(h, a, method, false);
+    return pt_finish(h);
+}
+
+jrx_status jrx_particles2d_rotate_stress(jrx_handle *h, double *const ptau[3], double *pomega, const double *tau_xx, const double *tau_yy, const double *tau_xy,
+                                         const double *omega_xy, const jrx_particles2d *part, double dt, int32_t method)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "rotate_stress!(particles)";
+    PtRotArgs a = {};
+    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    JRX_TRY(pt_centres(h, fn, a.g));
+    if (!ptau) return jrx_fail(h, JRX_ERR_ARG, "%s: ptau is NULL", fn);
+    JRX_TRY(pt_method(h, fn, dt, method));
+    const PtGeom &g = a.g;
+    const i64 ns = 8 * pt_slots(g), nc = 8 * (i64)g.nx * g.ny, nv = 8 * (i64)(g.nx + 1) * (g.ny + 1);
+    const PtArr out[4] = {{ptau[0], ns, "pτxx"}, {ptau[1], ns, "pτyy"}, {ptau[2], ns, "pτxy"}, {pomega, ns, "pω"}};
+    const PtArr in[4] = {{tau_xx, nc, "τ.xx"}, {tau_yy, nc, "τ.yy"}, {tau_xy, nv, "τ.xy"}, {omega_xy, nv, "ω.xy"}};
+    JRX_TRY(pt_disjoint(h, fn, out, 4, in, 4, g));
+    JRX_TRY(jrx_check_device(h));
+    a.pxx = ptau[0], a.pyy = ptau[1], a.pxy = ptau[2], a.pw = pomega, a.dt = dt;
+    if (h->particles_stress_fused) {
+        a.txx = tau_xx, a.tyy = tau_yy, a.txy = tau_xy, a.wxy = omega_xy;
+        a.ox = g.x0 + 0.5 * g.dx, a.oy = g.y0 + 0.5 * g.dy;
+        pt_launch_rotate(h, a, method, true);
+    } else {
+        pt_launch_c2p(h, g, ptau[0], tau_xx);
+        pt_launch_c2p(h, g, ptau[1], tau_yy);
+        pt_launch_g2p(h, g, ptau[2], tau_xy);
+        pt_launch_g2p(h, g, pomega, omega_xy);
+        pt_launch_rotate(h, a, method, false);
+    }
+    return pt_finish(h);
+}
+
+jrx_status jrx_particles2d_stress2grid(jrx_handle *h, double *const tau_o[6], const double *const ptau[3], const jrx_particles2d *part)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "stress2grid!";
+    PtS2GArgs a = {};
+    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    if (!tau_o || !ptau) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, !tau_o ? "tau_o" : "ptau");
+    const PtGeom &g = a.g;
+    const i64 ns = 8 * pt_slots(g), nc = 8 * (i64)g.nx * g.ny, nv = 8 * (i64)(g.nx + 1) * (g.ny + 1);
+    const PtArr out[6] = {{tau_o[0], nc, "τ_o.xx"}, {tau_o[1], nc, "τ_o.yy"}, {tau_o[2], nc, "τ_o.xy_c"}, {tau_o[3], nv, "τ_o.xy"}, {tau_o[4], nv, "τ_o.xx_v"},
+                          {tau_o[5], nv, "τ_o.yy_v"}};
+    const PtArr in[3] = {{ptau[0], ns, "pτxx"}, {ptau[1], ns, "pτyy"}, {ptau[2], ns, "pτxy"}};
+    JRX_TRY(pt_disjoint(h, fn, out, 6, in, 3, g));
+    JRX_TRY(jrx_check_device(h));
+    if (h->particles_stress_fused) {
+        a.cxx = tau_o[0], a.cyy = tau_o[1], a.cxy = tau_o[2], a.vxy = tau_o[3], a.vxx = tau_o[4], a.vyy = tau_o[5];
+        a.pxx = ptau[0], a.pyy = ptau[1], a.pxy = ptau[2];
+        const unsigned nb = pt_blocks(a.g, g.nx + 1, g.ny + 1);
+        h->stat_particles_launches++;
+        hipLaunchKernelGGL(k_pt_stress2grid, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+    } else {
+        for (int c = 0; c < 3; c++) pt_launch_p2c(h, g, tau_o[c], ptau[c]);                 // xx, yy, xy_c
+        pt_launch_p2g(h, g, tau_o[4], ptau[0]);                                             // xx_v, yy_v, xy
+        pt_launch_p2g(h, g, tau_o[5], ptau[1]);
+        pt_launch_p2g(h, g, tau_o[3], ptau[2]);
+    }
+    return pt_finish(h);
 }
 
 }  // extern "C"

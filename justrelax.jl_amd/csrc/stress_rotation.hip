@@ -20,6 +20,7 @@
 // -ffp-contract=off): every product and sum is rounded once, in the order written, which is the order of tests/_stress_rotation.py.
 // Addressing: 32-bit element offsets (every array below 2^31 entries, checked).
 #include "jrx_internal.hpp"
+#include "rotate_point.hpp"
 
 namespace {
 
@@ -144,26 +145,7 @@ __device__ __forceinline__ double rs_upwind(const double *__restrict__ A, const 
 }
 
 // ------------------------------------------------------------------------------------------------ rotations
-// METHOD 0: τ' = R (τ R') with R = [c -s; s c], θ = dt ω (stress_rotation_particles.jl:175-197); METHOD 1: τ + dt (W τ - τ W), the corrected Jaumann rate
-template <int METHOD>
-__device__ __forceinline__ void rs_rot2(double xx, double yy, double xy, double th, double &oxx, double &oyy, double &oxy)
-{
-    if (METHOD == 0) {
-        double s, c;
-        sincos(th, &s, &c);
-        const double ms = -s;
-        const double m11 = xx * c + xy * ms, m12 = xx * s + xy * c;          // τ R'
-        const double m21 = xy * c + yy * ms, m22 = xy * s + yy * c;
-        oxx = c * m11 + ms * m21;                                           // R (τ R')
-        oxy = c * m12 + ms * m22;
-        oyy = s * m12 + c * m22;
-    } else {
-        const double t2 = 2.0 * th;
-        oxx = xx - t2 * xy;
-        oyy = yy + t2 * xy;
-        oxy = xy + th * (xx - yy);
-    }
-}
+// rs_rot2<METHOD>, the per-point 2D rotation: rotate_point.hpp (shared with particles.hip)
 
 // t, o: xx, yy, zz, yz, xz, xy; w: ω_yz, ω_xz, ω_xy (the axial vector).  METHOD 0: Rodrigues, θ = dt |w|, n = w / |w| (|w| == 0: n = 0, R = I, no division);
 // METHOD 1: τ + (A τ - τ A) with A = [dt w]x

@@ -4,13 +4,21 @@ Shearheating2D.jl:69-82,221-232).  Julia's `f!` is spelled `f_`.  JustPIC's text
 built, tests/_particles2d.py restates them in NumPy.  Every operator forwards to one C-ABI entry point (csrc/particles.hip); only the seeding is computed
 here, on the host.
 
+The elastic stress travels on the particles too: centroid2particle_, particle2centroid_, rotate_stress_particles_, stress2grid_ and the particle form of
+rotate_stress_ (the tuple methods of src/stress_rotation/stress_rotation_particles.jl:92-99,224-235,264-276; tests/_particles2d_stress.py restates them).
+
 Built: 2D, uniform grid, one block, fp64.  Refused by name: 3D, a non-uniform Geometry, a handle with a communicator (by the library), particle injection, a marker
-chain, StressParticles.
+chain, StressParticles (the wrapper type; its tuple methods are what is built).
 
 A time step with particles (examples/sinking_block2d_particles.py):
 
     advection_(particles, RungeKutta2(), stokes.V, dt); move_particles_(particles, particle_args); update_phase_ratios_(phase_ratios, particles, pPhases);
     compute_ρg_(...); solve_(...)
+
+A visco-elastic step with the stress on particles (examples/stress_rotation2d_particles.py), pτxx, pτyy, pτxy, pω from init_cell_arrays:
+
+    stress2grid_(stokes, pτxx, pτyy, pτxy, particles); solve_(...); compute_vorticity(stokes, di)
+    rotate_stress_(pτxx, pτyy, pτxy, pω, stokes, particles, dt); advection_(...); move_particles_(particles, (pτxx, pτyy, pτxy, pω, ...))
 
 Layout: every per-particle array is (nx, ny, max_xcell) column-major, the slot index slowest; an inactive slot holds 0 in every array.
 """
@@ -25,6 +33,7 @@ from . import _lib
 from .arrays import from_numpy, fzeros, ptr
 from .backend import device_of
 from .gridops import _h
+from .stress_rotation import METHODS
 from .phases import _ULPS          # the vertex spacing may vary by this many ulp of the largest coordinate, as for update_phase_ratios_2D_
 
 COUNTS = ("n_active_before", "n_active_after", "n_outside", "n_far", "n_overflow")
@@ -304,3 +313,116 @@ def update_phase_ratios_(phase_ratios, particles, pPhases, *, handle=None):
     h.call("jrx_particles2d_phase_ratios", *(C.c_void_p(ptr(getattr(phase_ratios, k))) for k in want), C.c_void_p(ptr(pPhases)), C.c_int32(N), C.byref(s),
            C.byref(n_empty))
     return int(n_empty.value)
+
+
+# ---------------------------------------------------------------------------------------------- the elastic stress on particles
+def _check_grid_field(particles, F, name, shape, kind, fn):
+    if not isinstance(F, torch.Tensor) or F.dtype != torch.float64 or tuple(F.shape) != shape:
+        raise ValueError(f"{fn}: {name} is {tuple(F.shape) if isinstance(F, torch.Tensor) else type(F).__name__}; {particles.ni} cells need the {kind} field {shape}")
+    if F.device != particles.coords[0].device:
+        raise ValueError(f"{fn}: {name} is on {F.device}, the particles on {particles.coords[0].device}")
+
+
+def _method(method, fn):
+    m = method.lstrip(":") if isinstance(method, str) else method
+    if m not in METHODS:
+        raise ValueError(f"{fn}: unknown method {method!r} (one of {sorted(METHODS)})")
+    return C.c_int32(METHODS[m])
+
+
+def _check_stokes(particles, stokes, fn):
+    ni = getattr(stokes, "_ni", None)
+    if ni is None or not hasattr(stokes, "τ_o"):
+        raise TypeError(f"{fn}: stokes must be a StokesArrays, got {type(stokes).__name__}")
+    if len(ni) != 2:
+        raise NotImplementedError(f"{fn}: a {len(ni)}D StokesArrays (particles are built in 2D)")
+    if tuple(ni) != particles.ni:
+        raise ValueError(f"{fn}: stokes has {tuple(ni)} cells, the particles {particles.ni}")
+    if stokes.P.device != particles.coords[0].device:
+        raise ValueError(f"{fn}: stokes is on {stokes.P.device}, the particles on {particles.coords[0].device}")
+
+
+def _vec(ts):
+    return (C.c_void_p * len(ts))(*(ptr(t) for t in ts))
+
+
+def centroid2particle_(pF, F, particles, *, handle=None):
+    """centroid2particle!(pF, F, particles): the centre field F (nx, ny) to the particles, bilinear between the four centres around each particle's coordinate;
+    a particle in the outer half cells extrapolates from the outermost pair.  Needs nx >= 2 and ny >= 2 (include/jrx.h, operator 6)."""
+    fn = "centroid2particle!"
+    _check_particles(particles, fn)
+    _check_field(particles, pF, "pF", fn)
+    _check_grid_field(particles, F, "F", particles.ni, "centre", fn)
+    if min(particles.ni) < 2:
+        raise ValueError(f"{fn}: {particles.ni} cells (interpolation between centres needs nx >= 2 and ny >= 2)")
+    h = _h(pF, handle)
+    s = particles._struct()
+    h.call("jrx_particles2d_centroid2particle", C.c_void_p(ptr(pF)), C.c_void_p(ptr(F)), C.byref(s))
+
+
+def particle2centroid_(F, pF, particles, *, handle=None):
+    """particle2centroid!(F, pF, particles): the particle field pF to the centre field F (nx, ny), each cell from its own bucket weighted by the bilinear
+    distance to the centre; a cell without a particle keeps its value (operator 7)"""
+    fn = "particle2centroid!"
+    _check_particles(particles, fn)
+    _check_field(particles, pF, "pF", fn)
+    _check_grid_field(particles, F, "F", particles.ni, "centre", fn)
+    h = _h(pF, handle)
+    s = particles._struct()
+    h.call("jrx_particles2d_particle2centroid", C.c_void_p(ptr(F)), C.c_void_p(ptr(pF)), C.byref(s))
+
+
+def _stress_fields(particles, pτ, fn):
+    pτ = tuple(pτ)
+    if len(pτ) != 3:
+        raise NotImplementedError(f"{fn}: {len(pτ)} stress components (2D is built: pτxx, pτyy, pτxy)")
+    for name, f in zip(("pτxx", "pτyy", "pτxy"), pτ):
+        _check_field(particles, f, name, fn)
+    return pτ
+
+
+def rotate_stress_particles_(pτ, pω, particles, dt, *, method="matrix", handle=None):
+    """rotate_stress_particles!((pτxx, pτyy, pτxy), (pω,), particles, dt; method = :matrix): every particle's stress rotated in place by θ = dt pω, with the
+    rotation matrix ("matrix") or the corrected Jaumann rate ("jaumann") of rotate_stress_ on grids (operator 8)"""
+    fn = "rotate_stress_particles!"
+    _check_particles(particles, fn)
+    pτ = _stress_fields(particles, pτ, fn)
+    pω = (pω,) if isinstance(pω, torch.Tensor) else tuple(pω)
+    if len(pω) != 1:
+        raise NotImplementedError(f"{fn}: {len(pω)} vorticity components (2D is built: one)")
+    _check_field(particles, pω[0], "pω", fn)
+    m = _method(method, fn)
+    h = _h(pτ[0], handle)
+    s = particles._struct()
+    h.call("jrx_particles2d_rotate", _vec(pτ), C.c_void_p(ptr(pω[0])), C.byref(s), C.c_double(float(dt)), m)
+
+
+def _rotate_stress_particles_form(pτxx, pτyy, pτxy, pω, stokes, particles, dt, *, method="matrix", handle=None):
+    """the particle form of rotate_stress_ (stress_rotation.py dispatches here): stokes.τ.xx, τ.yy (centres) and τ.xy, ω.xy (vertices) to the particles, then the
+    rotation of rotate_stress_particles_; one launch (operator 9)"""
+    fn = "rotate_stress!"
+    _check_particles(particles, fn)
+    pτ = _stress_fields(particles, (pτxx, pτyy, pτxy), fn)
+    _check_field(particles, pω, "pω", fn)
+    _check_stokes(particles, stokes, fn)
+    if min(particles.ni) < 2:
+        raise ValueError(f"{fn}: {particles.ni} cells (interpolation between centres needs nx >= 2 and ny >= 2)")
+    m = _method(method, fn)
+    h = _h(pτ[0], handle)
+    s = particles._struct()
+    τ = stokes.τ
+    h.call("jrx_particles2d_rotate_stress", _vec(pτ), C.c_void_p(ptr(pω)), C.c_void_p(ptr(τ.xx)), C.c_void_p(ptr(τ.yy)), C.c_void_p(ptr(τ.xy)),
+           C.c_void_p(ptr(stokes.ω.xy)), C.byref(s), C.c_double(float(dt)), m)
+
+
+def stress2grid_(stokes, pτxx, pτyy, pτxy, particles, *, handle=None):
+    """stress2grid!(stokes, pτxx, pτyy, pτxy, particles): stokes.τ_o.xx, yy, xy_c (centres, particle2centroid_) and τ_o.xx_v, yy_v, xy (vertices, particle2grid_)
+    from the particle stress, one launch; a node no particle weight reaches keeps its value (operator 9).  τ_o.xx_v, yy_v are allocated on first touch."""
+    fn = "stress2grid!"
+    _check_particles(particles, fn)
+    pτ = _stress_fields(particles, (pτxx, pτyy, pτxy), fn)
+    _check_stokes(particles, stokes, fn)
+    h = _h(pτ[0], handle)
+    s = particles._struct()
+    τ_o = stokes.τ_o
+    h.call("jrx_particles2d_stress2grid", _vec([τ_o.xx, τ_o.yy, τ_o.xy_c, τ_o.xy, τ_o.xx_v, τ_o.yy_v]), _vec(pτ), C.byref(s))

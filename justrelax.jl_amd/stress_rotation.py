@@ -26,12 +26,25 @@ ADVECTIONS = {"none": 0, "upwind": 1}          # JRX_ADVECT_NONE, JRX_ADVECT_UPW
 _MEMBERS = {2: ("xx", "yy", "xy_c", "xy"), 3: ("xx", "yy", "zz", "yz_c", "xz_c", "xy_c", "yz", "xz", "xy")}
 
 
-def rotate_stress_(stokes, grid_or_di, dt, *, method="matrix", advection="upwind", handle=None):
-    """rotate_stress!(stokes, grid_or_di, dt; method = :matrix, advection = :upwind): stokes.τ_o = Rot(stokes.τ, stokes.ω dt) - dt Adv(stokes.τ, stokes.V), every
+def rotate_stress_(stokes, grid_or_di, dt, *particle_form, method="matrix", advection="upwind", handle=None):
+    """rotate_stress!(pτxx, pτyy, pτxy, pω, stokes, particles, dt; method = :matrix) when the first argument is a particle field (a tensor): the particle form,
+    particles.py -- stokes.τ and stokes.ω.xy to the particles and the rotation there; advection_ / move_particles_ then carry the stress, stress2grid_ puts it back.
+    Otherwise the grid form:
+
+    rotate_stress!(stokes, grid_or_di, dt; method = :matrix, advection = :upwind): stokes.τ_o = Rot(stokes.τ, stokes.ω dt) - dt Adv(stokes.τ, stokes.V), every
     member at its own node (include/jrx.h, jrx_rotate_stress2d / 3d).  Reads stokes.τ, stokes.ω (as the drivers' epilogue or compute_vorticity_ leave it) and
     stokes.V; writes stokes.τ_o.  grid_or_di: a uniform Geometry or the legacy tuple of spacings.  method: "matrix" (rotation matrix; exact for any angle) or
     "jaumann" (first order in dt ω).  advection: "upwind" or "none" (a caller may then advect τ_o with WENO_advection_).  The 2D vertex normals xx_v, yy_v are
     carried along only when both tensors have them allocated."""
+    if isinstance(stokes, torch.Tensor):
+        from .particles import _rotate_stress_particles_form
+        if len(particle_form) != 4:
+            raise TypeError(f"rotate_stress!: the particle form takes (pτxx, pτyy, pτxy, pω, stokes, particles, dt), got {3 + len(particle_form)} arguments")
+        if advection != "upwind":
+            raise ValueError("rotate_stress!: the particle form has no advection keyword (advection_ and move_particles_ carry the stress)")
+        return _rotate_stress_particles_form(stokes, grid_or_di, dt, *particle_form, method=method, handle=handle)
+    if particle_form:
+        raise TypeError(f"rotate_stress!: the grid form takes (stokes, grid_or_di, dt), got {3 + len(particle_form)} arguments")
     _require_gpu(stokes)
     name = lambda s: s.lstrip(":") if isinstance(s, str) else s
     if name(method) not in METHODS:
