@@ -136,7 +136,7 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   jrx_update_phases_topography2d calls that launched (their 3D forms jrx_compute_rock_fraction3d / jrx_advect_topography3d / jrx_update_phases_topography3d count in the same three),
  *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* and jrx_dyrel3d_* entry points,
  *   "stat_stepops_launches" = kernels launched by jrx_pureshear_bc2d / 3d, jrx_free_surface_bcs2d / 3d, jrx_subgrid_characteristic_time and jrx_compute_melt_fraction,
- *   "stat_particles_launches" = kernels launched by the jrx_particles2d_* entry points (one each, except the two chains of "particles_stress_fused" = 0) -- so that a caller
+ *   "stat_particles_launches" = kernels launched by the jrx_particles2d_* entry points (one each, except the chains of "particles_stress_fused" = 0 and the two subgrid-diffusion calls: 2 / 3, chains 7) -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
 /* the caller has written to an operand array (tau_o, P0, Q, K, G, eta, rho g) since the last driver call: a cached verdict of the operand pass ("operand_cache") is dropped */
@@ -1248,7 +1248,8 @@ jrx_status jrx_compute_melt_fraction(jrx_handle *h, double *phi, const double *p
  * is restated: what is built is defined HERE, to the rounding, and tests/_particles2d.py is the same text in NumPy.  Every operator is a GATHER with loops
  * bounded by max_xcell: nothing races, nothing depends on launch order, the device and the NumPy text leave the same bits.
  * Scope: 2D, uniform grid, one block (a handle with a communicator is refused), fp64.  NOT built: 3D, non-uniform grids, particle injection
- * (inject_particles_phase!), a marker chain, StressParticles (operators 6 - 9 below carry the stress through the reference's tuple methods instead).
+ * (inject_particles_phase!), a marker chain, StressParticles (operators 6 - 9 below carry the stress through the reference's tuple methods instead),
+ * grid2particle_flip!.
  *
  * Layout.  The grid has (nx, ny) cells of size (dx, dy), cell (i, j) = [x0 + i dx, x0 + (i+1) dx) x [y0 + j dy, y0 + (j+1) dy), 0-based.  Every cell owns a BUCKET
  * of max_xcell slots.  Every per-particle array -- px, py (coordinates), active (int32 mask: 1 = the slot holds a particle) and every particle field (pPhases, pT,
@@ -1343,6 +1344,39 @@ jrx_status jrx_particles2d_rotate(jrx_handle *h, double *const ptau[3], const do
 jrx_status jrx_particles2d_rotate_stress(jrx_handle *h, double *const ptau[3], double *pomega, const double *tau_xx, const double *tau_yy, const double *tau_xy,
                                          const double *omega_xy, const jrx_particles2d *part, double dt, int32_t method);
 jrx_status jrx_particles2d_stress2grid(jrx_handle *h, double *const tau_o[6], const double *const ptau[3], const jrx_particles2d *part);
+/* Operators 10 and 11 carry the TEMPERATURE on the particles: subgrid_diffusion_centroid!(pT, T_buffer, thermal.ΔT, subgrid_arrays, particles, dt) and
+ * subgrid_diffusion!(...) with subgrid_arrays of loc = :vertex -- JustPIC's, as every thermo-mechanical miniapp of the reference calls them behind
+ * heatdiffusion_PT! (miniapps/subduction/2D/Subduction2D.jl:221-243, test/test_Blankenbach.jl:225, test/test_thermalstresses.jl:420, docs/src/man/advection.md:42-53),
+ * the one consumer of jrx_subgrid_characteristic_time (whose dt₀ the caller brings to the particles with (6)).  The scheme is Gerya & Yuen's subgrid diffusion;
+ * tests/_particles2d_subgrid.py is this text in NumPy.  Layout, rounding, the +0.0 invariant, safety and refusals as above.
+ * 10. subgrid_diffusion_centroid!.  pT (read and written), pT0, pdT (= pΔT) and pdt0 (= dt₀, read only) are particle fields; T_grid (the grid temperature BEFORE
+ *    the diffusion solve, the miniapps' T_buffer) and dT_subgrid (= ΔT_subgrid, written) are centre fields (nx, ny); dT_grid, the grid change of the solve, read
+ *    only, is (nx, ny) with dT_extent = JRX_SUBGRID_DT_NODES, or thermal.ΔT itself, (nx+2, ny+2) read at the cell's own node [i+1, j+1], with
+ *    JRX_SUBGRID_DT_GHOSTED (the convention of args.ΔT of the multiphase drivers; the ghost entries are not read).  d in [0, 1], dt >= 0.  The operator is this CHAIN:
+ *      1. pT0 = pT, every slot.
+ *      2. pT = (6) of T_grid (so a slot whose scaled coordinate is not finite keeps its value, which is pT0).
+ *      3. per active slot, a = pdt0:  m = a > 1e-9 ? a : 1e-9 (a NaN gives 1e-9);  x = ((-d) dt) / m, the product formed once on the host;  f = 1 - exp(x);
+ *         δ = (pT - pT0) f;  pT0 = pT0 + δ;  pdT = δ.  An inactive slot of pdT is set to 0.
+ *      4. dT_subgrid = +0.0 everywhere, then (7) of pdT into it (a cell with den == 0 keeps the 0).
+ *      5. dT_subgrid[i, j] = dT_grid[i, j] - dT_subgrid[i, j].
+ *      6. pdT = (6) of dT_subgrid (a slot whose scaled coordinate is not finite keeps δ).
+ *      7. per active slot pT = pT0 + pdT; an inactive slot of pT is set to 0.
+ *    Afterwards pT0 holds pT0 + δ, pdT the interpolated remainder, dT_subgrid the remainder.  exp is the device's: against NumPy d = 0 is bit for bit (exp(-0) = 1),
+ *    d > 0 differs by that one function.  Needs nx >= 2 && ny >= 2.
+ *    Built as TWO launches that leave the chain's bits in pT, pT0, pdT and dT_subgrid: a thread per cell walks its bucket once, does 1 - 3 per slot with the
+ *    interpolated temperature in a register, accumulates num and den of (7) in slot order -- (7) reads only the cell's own bucket -- and writes
+ *    dT_grid - num / den; a second launch does 6 and 7 (it reads the neighbours' remainders).
+ * 11. subgrid_diffusion! with loc = :vertex: the same seven steps with (3) in place of (6) and (4) in place of (7) -- so a non-finite coordinate gives NaN, as (3)
+ *    does -- and T_grid, dT_grid, dT_subgrid vertex fields (nx+1, ny+1); JRX_SUBGRID_DT_GHOSTED: (nx+3, ny+3) read at [i+1, j+1].  THREE launches: per cell
+ *    (1 - 3), per vertex (the four-cell gather of (4) and the subtraction), per cell (6, 7).
+ *    Tuning key "particles_subgrid_fused" (include/jrx_tuning.h) = 0 runs the chains: 7 launches each (steps 1, 2, 3, the launch of 4, 5, 6, 7; the fill of 4 is
+ *    a memset).  Further refusals: d outside [0, 1] or not finite, dt negative or not finite, another dT_extent. */
+#define JRX_SUBGRID_DT_NODES 0
+#define JRX_SUBGRID_DT_GHOSTED 1
+jrx_status jrx_particles2d_subgrid_diffusion_centroid(jrx_handle *h, double *pT, const double *T_grid, const double *dT_grid, int32_t dT_extent, double *pT0,
+                                                      double *pdT, const double *pdt0, double *dT_subgrid, const jrx_particles2d *part, double d, double dt);
+jrx_status jrx_particles2d_subgrid_diffusion_vertex(jrx_handle *h, double *pT, const double *T_grid, const double *dT_grid, int32_t dT_extent, double *pT0, double *pdT,
+                                                    const double *pdt0, double *dT_subgrid, const jrx_particles2d *part, double d, double dt);
 
 #ifdef __cplusplus
 }

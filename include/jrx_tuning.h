@@ -78,6 +78,9 @@
  *   "particles_stress_fused" (1) jrx_particles2d_rotate_stress / jrx_particles2d_stress2grid: one launch each -- a thread per cell reads active, x, y of a slot once and writes the four
  *                                 particle fields; a thread per node of the ni .+ 1 box reads each particle of its up to four cells once for all six members; 0 = the chains of
  *                                 single-operator launches the definitions name (5 and 6; bit-identical in every output; profiles/particles2d_stress_bench.txt)
+ *   "particles_subgrid_fused" (1) jrx_particles2d_subgrid_diffusion_centroid / _vertex: two / three launches -- a thread per cell does steps 1 - 3 of the definition in one walk of
+ *                                 its bucket (centre form: and the cell's remainder), a thread per vertex the four-cell gather (vertex form), a thread per cell steps 6 and 7;
+ *                                 0 = the chain of seven launches the definition names (bit-identical in pT, pT0, pΔT, ΔT_subgrid; profiles/particles2d_subgrid_bench.txt)
  *   "general_hif" (0)            3D fused kernel, general form (any dt), 64 x 4 tile: the stress nodes on the high faces i = nx, j = ny, k = nz are updated inside the kernel (one launch per
  *                                 unobserved iteration) and, with neighbours, the kernel's boundary tiles read the received planes ("fused_overlap" = 3: no flow_bcs! launch, no fix-up):
  *                                 4 / 3 = the instantiation built for four (128 VGPRs + 28 dwords of scratch: 10.99 ms at 512^3) / three (155 VGPRs: 7.95 ms) waves per SIMD; 0 = boundary-layer launch (7.47 + 0.11 ms)

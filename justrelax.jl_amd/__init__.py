@@ -7,7 +7,7 @@ The directory name contains a dot, so import it through `__graft_entry__.load_pa
 Layout: csrc/ (hand-written HIP kernels for gfx950 + the C ABI declared in include/jrx.h),
 arrays.py / backend.py / grid.py (host-side mirror of the reference's types and traits),
 stokes.py / thermal.py / halo.py / gridops.py / advection.py / variational.py / dyrel.py / phases.py / stress_rotation.py / topography.py / stepops.py / particles.py (the operator API: solve_, heatdiffusion_PT_, flow_bcs_,
-velocity2vertex_, WENO_advection_, solve_VariationalStokes_, solve_DYREL_, update_phase_ratios_2D_, rotate_stress_, compute_rock_fraction_, pureshear_bc_, compute_melt_fraction_, init_particles, move_particles_, centroid2particle_, particle2centroid_, rotate_stress_particles_, stress2grid_, ...),
+velocity2vertex_, WENO_advection_, solve_VariationalStokes_, solve_DYREL_, update_phase_ratios_2D_, rotate_stress_, compute_rock_fraction_, pureshear_bc_, compute_melt_fraction_, init_particles, move_particles_, centroid2particle_, particle2centroid_, rotate_stress_particles_, stress2grid_, SubgridDiffusionCellArrays, subgrid_diffusion_centroid_, subgrid_diffusion_, ...),
 miniapps/ (synthetic-input builders restating the reference's benchmark scripts).
 Julia's `f!` is spelled `f_` here.
 """

@@ -138,7 +138,7 @@ int find_opt(jrx_handle *h, const char *key, bool tuning, OptRef *out)
         {"general_hif", 1, &h->general_hif}, {"field_shuffle", 0, &h->field_shuffle}, {"field_pool_pct", 1, &h->field_pool_pct}, {"fused_kz", 1, &h->fused_kz}, {"fused_ym", 1, &h->fused_ym}, {"nbr_feeder", 0, &h->nbr_feeder}, {"stat_fused3d_ym", 2, &h->stat_fused3d_ym}, {"scratch_poison", 1, &h->scratch_poison},
         {"weno_fused", 0, &h->weno_fused}, {"weno_rows", 1, &h->weno_rows},
         {"phase_ratios_fused", 0, &h->phase_ratios_fused}, {"rock_fraction3d_rows", 1, &h->rock_fraction3d_rows},
-        {"particles_stress_fused", 0, &h->particles_stress_fused},
+        {"particles_stress_fused", 0, &h->particles_stress_fused}, {"particles_subgrid_fused", 0, &h->particles_subgrid_fused},
     };
     if (tuning) {
         for (const OptRef &o : tun)

@@ -118,6 +118,7 @@ struct jrx_handle {
     int64_t stat_stepops_launches = 0;   // kernels launched by the per-step operators of stepops.hip (pureshear_bc!, free_surface_bcs!, subgrid_characteristic_time!, compute_melt_fraction!)
     int64_t stat_particles_launches = 0; // kernels launched by the jrx_particles2d_* entry points (particles.hip)
     bool particles_stress_fused = true;  // tuning: jrx_particles2d_rotate_stress / _stress2grid as one launch each (0: the chains of single-operator launches, 5 and 6; bit-identical)
+    bool particles_subgrid_fused = true; // tuning: jrx_particles2d_subgrid_diffusion_centroid / _vertex as 2 / 3 launches (0: the chain of the definition, 7 launches; bit-identical)
     // ---- read-only counters (jrx_get_option "stat_*"): launches of the fused kernels since jrx_create, so that tests and the bench can
     //      prove which kernel path ran
     int64_t stat_fused3d_inkernel = 0;   // launches of k_fused3d that finished the neighbour faces themselves (fused_overlap = 3)

@@ -1,6 +1,7 @@
 // particles.hip -- 2D marker-in-cell particles in gather form: advection!(particles, RungeKutta2(), V, dt), move_particles!, grid2particle!, particle2grid!
 // and update_phase_ratios!(phase_ratios, particles, pPhases); and the elastic stress carried on them: centroid2particle!, particle2centroid!,
-// rotate_stress_particles!, rotate_stress!(pτxx, pτyy, pτxy, pω, stokes, particles, dt) and stress2grid!, for gfx950.
+// rotate_stress_particles!, rotate_stress!(pτxx, pτyy, pτxy, pω, stokes, particles, dt) and stress2grid!; and the temperature: subgrid_diffusion_centroid! and
+// subgrid_diffusion! (operators 10 and 11: Gerya & Yuen's subgrid diffusion, the consumer of subgrid_characteristic_time!), for gfx950.
 //
 // Reference: for the first five none to restate.  The reference's miniapps take them from JustPIC (miniapps/benchmarks/stokes2D/shear_heating/
 // Shearheating2D.jl:69-82,221-232 shows the calls), which is not in the reference tree.  include/jrx.h states the definitions built here; tests/_particles2d.py
@@ -509,6 +510,193 @@ __global__ __launch_bounds__(256) void k_pt_stress2grid(const PtS2GArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ 10. / 11. subgrid diffusion of the particle temperature
+// VERTEX = false: subgrid_diffusion_centroid! (operators 6 and 7 inside); true: subgrid_diffusion! with loc = :vertex (operators 3 and 4 inside).
+struct PtSgArgs {
+    PtGeom g;
+    double *pT, *pT0, *pdT;       // pT0, pdT: subgrid_arrays.pT0, .pΔT
+    const double *pdt0;           // subgrid_arrays.dt₀
+    const double *T;              // T_grid: (nx, ny) or (nx + 1, ny + 1)
+    const double *dTg;            // ΔT_grid: node (i, j) of the form's node box at dTg[dto + j * dtn + i]
+    double *dTs;                  // subgrid_arrays.ΔT_subgrid, the extents of T
+    int dtn, dto;
+    double ox, oy;                // origin of the centre nodes
+    double ndt;                   // (-d) dt, formed once on the host
+};
+
+// step 3 of the definition: δ of a slot from the interpolated and the carried temperature
+__device__ __forceinline__ double pt_sg_delta(double pTn, double p0, double a, double ndt)
+{
+    const double m = a > 1e-9 ? a : 1e-9;          // a NaN compares false: the floor
+    const double f = 1.0 - exp(ndt / m);
+    return (pTn - p0) * f;
+}
+
+// the chain's own launches: steps 1, 3, 5 and 7 (steps 2, 4 and 6 are the launches of operators 6 / 3 and 7 / 4)
+__global__ __launch_bounds__(256) void k_pt_sg_copy(const PtSgArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i >= g.nx || j >= g.ny) return;
+    const int nc = g.nx * g.ny;
+    int lin = j * g.nx + i;
+    for (int s = 0; s < g.mx; s++, lin += nc) a.pT0[lin] = a.pT[lin];
+}
+
+__global__ __launch_bounds__(256) void k_pt_sg_delta(const PtSgArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i >= g.nx || j >= g.ny) return;
+    const int nc = g.nx * g.ny;
+    int lin = j * g.nx + i;
+    for (int s = 0; s < g.mx; s++, lin += nc) {
+        if (g.active[lin] == 0) {
+            a.pdT[lin] = 0.0;
+            continue;
+        }
+        const double p0 = a.pT0[lin];
+        const double dl = pt_sg_delta(a.pT[lin], p0, a.pdt0[lin], a.ndt);
+        a.pT0[lin] = p0 + dl;
+        a.pdT[lin] = dl;
+    }
+}
+
+// a thread per node of the (ex, ey) box: ΔT_subgrid = ΔT_grid - ΔT_subgrid
+__global__ __launch_bounds__(256) void k_pt_sg_remainder(const PtSgArgs a, int ex, int ey)
+{
+    int i, j;
+    pt_index(a.g.nbx, i, j);
+    if (i >= ex || j >= ey) return;
+    const int k = j * ex + i;
+    a.dTs[k] = a.dTg[a.dto + j * a.dtn + i] - a.dTs[k];
+}
+
+__global__ __launch_bounds__(256) void k_pt_sg_add(const PtSgArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i >= g.nx || j >= g.ny) return;
+    const int nc = g.nx * g.ny;
+    int lin = j * g.nx + i;
+    for (int s = 0; s < g.mx; s++, lin += nc) a.pT[lin] = g.active[lin] != 0 ? a.pT0[lin] + a.pdT[lin] : 0.0;
+}
+
+// The fused forms.  First launch, a thread per cell, one walk of its bucket: steps 1 - 3 per slot.  Centre form: the same thread accumulates num and den of operator
+// 7 in slot order (it reads only this bucket) and writes the cell's remainder, steps 4 and 5; δ goes to memory only where the last launch will need it, in a slot
+// whose scaled coordinate is not finite (it finds that out as this launch does, from the same numbers).  The interpolated temperature of step 2 lives in a register:
+// pT is written by the last launch alone.  Vertex form: δ of every slot goes to pΔT for the four-cell gather of the second launch.
+template <bool VERTEX>
+__global__ __launch_bounds__(256) void k_pt_sg_cell(const PtSgArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i >= g.nx || j >= g.ny) return;
+    const int nc = g.nx * g.ny;
+    double f00 = 0.0, f10 = 0.0, f01 = 0.0, f11 = 0.0;
+    if (VERTEX) {
+        const double *f = a.T + j * (g.nx + 1) + i;
+        f00 = f[0], f10 = f[1], f01 = f[g.nx + 1], f11 = f[g.nx + 2];
+    }
+    const double xv = g.x0 + (double)i * g.dx, yv = g.y0 + (double)j * g.dy;
+    const double xc = g.x0 + ((double)i + 0.5) * g.dx, yc = g.y0 + ((double)j + 0.5) * g.dy;
+    double num = 0.0, den = 0.0;
+    int lin = j * g.nx + i;
+    for (int s = 0; s < g.mx; s++, lin += nc) {
+        const double p0 = a.pT[lin];
+        if (g.active[lin] == 0) {
+            a.pT0[lin] = p0;
+            if (VERTEX) a.pdT[lin] = 0.0;
+            continue;
+        }
+        const double x = g.px[lin], y = g.py[lin];
+        double pTn = p0;
+        bool ok = true;
+        if (VERTEX) pTn = pt_bilin((x - xv) * g.idx, (y - yv) * g.idy, f00, f10, f01, f11);
+        else ok = pt_interp(a.T, g.nx, g.ny, a.ox, a.oy, g.idx, g.idy, x, y, pTn);
+        const double dl = pt_sg_delta(pTn, p0, a.pdt0[lin], a.ndt);
+        a.pT0[lin] = p0 + dl;
+        if (VERTEX) {
+            a.pdT[lin] = dl;
+        } else {
+            if (!ok) a.pdT[lin] = dl;
+            const double w = pt_w(x, xc, g.idx) * pt_w(y, yc, g.idy);
+            num += w * dl;
+            den += w;
+        }
+    }
+    if (!VERTEX) {
+        const int k = j * g.nx + i;
+        a.dTs[k] = a.dTg[a.dto + j * a.dtn + i] - (den == 0.0 ? 0.0 : num / den);
+    }
+}
+
+// vertex form, second launch: a thread per vertex, the four-cell gather of operator 4 over pΔT and the subtraction of step 5
+__global__ __launch_bounds__(256) void k_pt_sg_vertex(const PtSgArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i > g.nx || j > g.ny) return;
+    const int nc = g.nx * g.ny;
+    const double xv = g.x0 + (double)i * g.dx, yv = g.y0 + (double)j * g.dy;
+    double num = 0.0, den = 0.0;
+#pragma unroll
+    for (int oi = -1; oi <= 0; oi++) {
+#pragma unroll
+        for (int oj = -1; oj <= 0; oj++) {
+            const int ic = i + oi, jc = j + oj;
+            if (ic < 0 || ic >= g.nx || jc < 0 || jc >= g.ny) continue;
+            for (int s = 0, lin = jc * g.nx + ic; s < g.mx; s++, lin += nc) {
+                if (g.active[lin] == 0) continue;
+                const double w = pt_w(g.px[lin], xv, g.idx) * pt_w(g.py[lin], yv, g.idy);
+                num += w * a.pdT[lin];
+                den += w;
+            }
+        }
+    }
+    a.dTs[j * (g.nx + 1) + i] = a.dTg[a.dto + j * a.dtn + i] - (den == 0.0 ? 0.0 : num / den);
+}
+
+// last launch, a thread per cell: steps 6 and 7 -- the remainder back to the slots (it reads the neighbours' nodes: hence a launch of its own) and pT = pT0 + pΔT
+template <bool VERTEX>
+__global__ __launch_bounds__(256) void k_pt_sg_back(const PtSgArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    if (i >= g.nx || j >= g.ny) return;
+    const int nc = g.nx * g.ny;
+    double f00 = 0.0, f10 = 0.0, f01 = 0.0, f11 = 0.0;
+    if (VERTEX) {
+        const double *f = a.dTs + j * (g.nx + 1) + i;
+        f00 = f[0], f10 = f[1], f01 = f[g.nx + 1], f11 = f[g.nx + 2];
+    }
+    const double xv = g.x0 + (double)i * g.dx, yv = g.y0 + (double)j * g.dy;
+    int lin = j * g.nx + i;
+    for (int s = 0; s < g.mx; s++, lin += nc) {
+        if (g.active[lin] == 0) {
+            a.pdT[lin] = 0.0, a.pT[lin] = 0.0;
+            continue;
+        }
+        const double x = g.px[lin], y = g.py[lin];
+        double v;
+        if (VERTEX) {
+            v = pt_bilin((x - xv) * g.idx, (y - yv) * g.idy, f00, f10, f01, f11);
+            a.pdT[lin] = v;
+        } else if (pt_interp(a.dTs, g.nx, g.ny, a.ox, a.oy, g.idx, g.idy, x, y, v)) {
+            a.pdT[lin] = v;
+        } else {
+            v = a.pdT[lin];          // δ, as the first launch left it
+        }
+        a.pT[lin] = a.pT0[lin] + v;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 bool pt_overlaps(const void *a, i64 abytes, const void *b, i64 bbytes)
 {
@@ -650,6 +838,60 @@ jrx_status pt_finish(jrx_handle *h)
     JRX_LAUNCH_CHECK(h);
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
+}
+
+// operators 10 and 11: everything checked first, then the fused launches (2 / 3) or the chain of the definition (7 launches and one fill)
+jrx_status pt_subgrid(jrx_handle *h, const char *fn, bool vertex, double *pT, const double *T_grid, const double *dT_grid, int32_t dT_extent, double *pT0, double *pdT,
+                      const double *pdt0, double *dT_subgrid, const jrx_particles2d *part, double d, double dt)
+{
+    PtSgArgs a = {};
+    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    if (!vertex) JRX_TRY(pt_centres(h, fn, a.g));
+    if (!(d >= 0.0 && d <= 1.0)) return jrx_fail(h, JRX_ERR_ARG, "%s: d = %g (must lie in [0, 1])", fn, d);
+    if (!std::isfinite(dt) || dt < 0.0) return jrx_fail(h, JRX_ERR_ARG, "%s: dt = %g (must be finite and not negative)", fn, dt);
+    if (dT_extent != JRX_SUBGRID_DT_NODES && dT_extent != JRX_SUBGRID_DT_GHOSTED)
+        return jrx_fail(h, JRX_ERR_ARG, "%s: unknown ΔT extent code %d (%d = the node box, %d = one ghost layer around it)", fn, (int)dT_extent, JRX_SUBGRID_DT_NODES,
+                        JRX_SUBGRID_DT_GHOSTED);
+    const PtGeom &g = a.g;
+    const int ex = g.nx + (vertex ? 1 : 0), ey = g.ny + (vertex ? 1 : 0), gh = dT_extent == JRX_SUBGRID_DT_GHOSTED ? 1 : 0;
+    const i64 ns = 8 * pt_slots(g), nn = 8 * (i64)ex * ey, nd = 8 * (i64)(ex + 2 * gh) * (ey + 2 * gh);
+    const PtArr out[4] = {{pT, ns, "pT"}, {pT0, ns, "subgrid_arrays.pT0"}, {pdT, ns, "subgrid_arrays.pΔT"}, {dT_subgrid, nn, "subgrid_arrays.ΔT_subgrid"}};
+    const PtArr in[3] = {{T_grid, nn, "T_grid"}, {dT_grid, nd, "ΔT_grid"}, {pdt0, ns, "subgrid_arrays.dt₀"}};
+    JRX_TRY(pt_disjoint(h, fn, out, 4, in, 3, g));
+    JRX_TRY(jrx_check_device(h));
+    a.pT = pT, a.pT0 = pT0, a.pdT = pdT, a.pdt0 = pdt0, a.T = T_grid, a.dTg = dT_grid, a.dTs = dT_subgrid;
+    a.dtn = ex + 2 * gh, a.dto = gh * (a.dtn + 1);
+    a.ox = g.x0 + 0.5 * g.dx, a.oy = g.y0 + 0.5 * g.dy;
+    a.ndt = (-d) * dt;
+    const dim3 tile(kPtTX, kPtTY);
+    const unsigned nbc = pt_blocks(a.g, g.nx, g.ny);          // the cell launches; nbx of a.g is theirs
+    PtSgArgs n = a;                                           // the node launches of the vertex form and of step 5
+    const unsigned nbn = pt_blocks(n.g, ex, ey);
+    if (h->particles_subgrid_fused) {
+        h->stat_particles_launches += vertex ? 3 : 2;
+        if (vertex) {
+            hipLaunchKernelGGL(k_pt_sg_cell<true>, dim3(nbc), tile, 0, h->stream, a);
+            hipLaunchKernelGGL(k_pt_sg_vertex, dim3(nbn), tile, 0, h->stream, n);
+            hipLaunchKernelGGL(k_pt_sg_back<true>, dim3(nbc), tile, 0, h->stream, a);
+        } else {
+            hipLaunchKernelGGL(k_pt_sg_cell<false>, dim3(nbc), tile, 0, h->stream, a);
+            hipLaunchKernelGGL(k_pt_sg_back<false>, dim3(nbc), tile, 0, h->stream, a);
+        }
+        return pt_finish(h);
+    }
+    h->stat_particles_launches += 4;
+    hipLaunchKernelGGL(k_pt_sg_copy, dim3(nbc), tile, 0, h->stream, a);                      // 1
+    if (vertex) pt_launch_g2p(h, g, pT, T_grid);                                              // 2
+    else pt_launch_c2p(h, g, pT, T_grid);
+    hipLaunchKernelGGL(k_pt_sg_delta, dim3(nbc), tile, 0, h->stream, a);                     // 3
+    JRX_HIP(h, hipMemsetAsync(dT_subgrid, 0, (size_t)nn, h->stream));                         // 4: +0.0 is all bits zero
+    if (vertex) pt_launch_p2g(h, g, dT_subgrid, pdT);
+    else pt_launch_p2c(h, g, dT_subgrid, pdT);
+    hipLaunchKernelGGL(k_pt_sg_remainder, dim3(nbn), tile, 0, h->stream, n, ex, ey);         // 5
+    if (vertex) pt_launch_g2p(h, g, pdT, dT_subgrid);                                         // 6
+    else pt_launch_c2p(h, g, pdT, dT_subgrid);
+    hipLaunchKernelGGL(k_pt_sg_add, dim3(nbc), tile, 0, h->stream, a);                       // 7
+    return pt_finish(h);
 }
 
 }  // namespace
@@ -886,6 +1128,20 @@ jrx_status jrx_particles2d_stress2grid(jrx_handle *h, double *const tau_o[6], co
         pt_launch_p2g(h, g, tau_o[3], ptau[2]);
     }
     return pt_finish(h);
+}
+
+jrx_status jrx_particles2d_subgrid_diffusion_centroid(jrx_handle *h, double *pT, const double *T_grid, const double *dT_grid, int32_t dT_extent, double *pT0,
+                                                      double *pdT, const double *pdt0, double *dT_subgrid, const jrx_particles2d *part, double d, double dt)
+{
+    if (!h) return JRX_ERR_ARG;
+    return pt_subgrid(h, "subgrid_diffusion_centroid!", false, pT, T_grid, dT_grid, dT_extent, pT0, pdT, pdt0, dT_subgrid, part, d, dt);
+}
+
+jrx_status jrx_particles2d_subgrid_diffusion_vertex(jrx_handle *h, double *pT, const double *T_grid, const double *dT_grid, int32_t dT_extent, double *pT0, double *pdT,
+                                                    const double *pdt0, double *dT_subgrid, const jrx_particles2d *part, double d, double dt)
+{
+    if (!h) return JRX_ERR_ARG;
+    return pt_subgrid(h, "subgrid_diffusion!", true, pT, T_grid, dT_grid, dT_extent, pT0, pdT, pdt0, dT_subgrid, part, d, dt);
 }
 
 }  // extern "C"

@@ -20,6 +20,13 @@ A visco-elastic step with the stress on particles (examples/stress_rotation2d_pa
     stress2grid_(stokes, pτxx, pτyy, pτxy, particles); solve_(...); compute_vorticity(stokes, di)
     rotate_stress_(pτxx, pτyy, pτxy, pω, stokes, particles, dt); advection_(...); move_particles_(particles, (pτxx, pτyy, pτxy, pω, ...))
 
+A thermal step with the temperature on particles (examples/thermal_particles2d.py), subgrid_arrays = SubgridDiffusionCellArrays(particles, loc="center"):
+
+    particle2centroid_(T, pT, particles); T_buffer = T; heatdiffusion_PT_(...); subgrid_characteristic_time_(dt0, ...)
+    centroid2particle_(subgrid_arrays.dt0, dt0, particles); subgrid_diffusion_centroid_(pT, T_buffer, thermal.ΔT, subgrid_arrays, particles, dt)
+
+(JustPIC's subgrid_diffusion_centroid! / subgrid_diffusion!, operators 10 and 11 of include/jrx.h; tests/_particles2d_subgrid.py restates them).
+
 Layout: every per-particle array is (nx, ny, max_xcell) column-major, the slot index slowest; an inactive slot holds 0 in every array.
 """
 from __future__ import annotations
@@ -426,3 +433,76 @@ def stress2grid_(stokes, pτxx, pτyy, pτxy, particles, *, handle=None):
     s = particles._struct()
     τ_o = stokes.τ_o
     h.call("jrx_particles2d_stress2grid", _vec([τ_o.xx, τ_o.yy, τ_o.xy_c, τ_o.xy, τ_o.xx_v, τ_o.yy_v]), _vec(pτ), C.byref(s))
+
+
+# ---------------------------------------------------------------------------------------------- the temperature on particles
+SUBGRID_LOCS = ("vertex", "center")
+
+
+class SubgridDiffusionCellArrays:
+    """SubgridDiffusionCellArrays(particles; loc = :vertex): the scratch of subgrid_diffusion_ (loc "vertex") or subgrid_diffusion_centroid_ (loc "center") --
+    pT0, pΔT and dt0 (the reference's dt₀: Python takes no subscript digit in a name) of the particle shape, ΔT_subgrid (nx, ny) for "center" and (nx+1, ny+1) for
+    "vertex".  They are refilled in every step and get no twins: none of them travels with move_particles_."""
+
+    def __init__(self, particles, loc="vertex"):
+        fn = "SubgridDiffusionCellArrays"
+        _check_particles(particles, fn)
+        loc = loc.lstrip(":") if isinstance(loc, str) else loc
+        if loc not in SUBGRID_LOCS:
+            raise ValueError(f"{fn}: unknown loc {loc!r} (one of {SUBGRID_LOCS})")
+        self.loc, self.ni = loc, particles.ni
+        nx, ny = particles.ni
+        self.pT0, self.pΔT, self.dt0 = (fzeros(particles.shape, particles.device) for _ in range(3))
+        self.ΔT_subgrid = fzeros((nx, ny) if loc == "center" else (nx + 1, ny + 1), particles.device)
+
+
+def _subgrid(fn, loc, pT, T_grid, ΔT_grid, subgrid_arrays, particles, dt, d, handle):
+    _check_particles(particles, fn)
+    if not isinstance(subgrid_arrays, SubgridDiffusionCellArrays):
+        raise TypeError(f"{fn}: subgrid_arrays must be a SubgridDiffusionCellArrays, got {type(subgrid_arrays).__name__}")
+    if subgrid_arrays.loc != loc:
+        other = "subgrid_diffusion!" if loc == "center" else "subgrid_diffusion_centroid!"
+        raise ValueError(f"{fn}: subgrid_arrays has loc = {subgrid_arrays.loc!r}, this operator needs {loc!r} ({other} takes {subgrid_arrays.loc!r})")
+    if subgrid_arrays.ni != particles.ni:
+        raise ValueError(f"{fn}: subgrid_arrays was made for {subgrid_arrays.ni} cells, the particles have {particles.ni}")
+    sa = subgrid_arrays
+    _check_field(particles, pT, "pT", fn)
+    for name in ("pT0", "pΔT", "dt0"):
+        _check_field(particles, getattr(sa, name), f"subgrid_arrays.{name}", fn)
+    nx, ny = particles.ni
+    kind, ext = ("centre", (nx, ny)) if loc == "center" else ("vertex", (nx + 1, ny + 1))
+    _check_grid_field(particles, T_grid, "T_grid", ext, kind, fn)
+    _check_grid_field(particles, sa.ΔT_subgrid, "subgrid_arrays.ΔT_subgrid", ext, kind, fn)
+    ghosted = (ext[0] + 2, ext[1] + 2)
+    if not isinstance(ΔT_grid, torch.Tensor) or ΔT_grid.dtype != torch.float64 or tuple(ΔT_grid.shape) not in (ext, ghosted):
+        raise ValueError(f"{fn}: ΔT_grid is {tuple(ΔT_grid.shape) if isinstance(ΔT_grid, torch.Tensor) else type(ΔT_grid).__name__}; {particles.ni} cells need the "
+                         f"{kind} field {ext} or, with its ghost layer (thermal.ΔT), {ghosted}")
+    if ΔT_grid.device != particles.coords[0].device:
+        raise ValueError(f"{fn}: ΔT_grid is on {ΔT_grid.device}, the particles on {particles.coords[0].device}")
+    if loc == "center" and min(particles.ni) < 2:
+        raise ValueError(f"{fn}: {particles.ni} cells (interpolation between centres needs nx >= 2 and ny >= 2)")
+    d, dt = float(d), float(dt)
+    if not 0.0 <= d <= 1.0:
+        raise ValueError(f"{fn}: d = {d} (must lie in [0, 1])")
+    if not (np.isfinite(dt) and dt >= 0.0):
+        raise ValueError(f"{fn}: dt = {dt} (must be finite and not negative)")
+    h = _h(pT, handle)
+    s = particles._struct()
+    code = _lib.SUBGRID_DT_GHOSTED if tuple(ΔT_grid.shape) == ghosted else _lib.SUBGRID_DT_NODES
+    h.call("jrx_particles2d_subgrid_diffusion_centroid" if loc == "center" else "jrx_particles2d_subgrid_diffusion_vertex", C.c_void_p(ptr(pT)),
+           C.c_void_p(ptr(T_grid)), C.c_void_p(ptr(ΔT_grid)), C.c_int32(code), C.c_void_p(ptr(sa.pT0)), C.c_void_p(ptr(sa.pΔT)), C.c_void_p(ptr(sa.dt0)),
+           C.c_void_p(ptr(sa.ΔT_subgrid)), C.byref(s), C.c_double(d), C.c_double(dt))
+
+
+def subgrid_diffusion_centroid_(pT, T_grid, ΔT_grid, subgrid_arrays, particles, dt, *, d=1.0, handle=None):
+    """subgrid_diffusion_centroid!(pT, T_buffer, thermal.ΔT, subgrid_arrays, particles, dt; d = 1.0): the particle temperature pT takes the grid's diffusion step --
+    the part of its difference to the grid temperature T_grid (centres, BEFORE the solve) that decays within dt at the particle's own rate subgrid_arrays.dt0
+    (subgrid_characteristic_time_, then centroid2particle_(subgrid_arrays.dt0, dt0, particles): the caller's two steps), and the remainder of the grid's change
+    ΔT_grid, (nx, ny) or thermal.ΔT itself (nx+2, ny+2), interpolated back; d = 0 adds the interpolated ΔT_grid only.  Two launches (include/jrx.h, operator 10)."""
+    _subgrid("subgrid_diffusion_centroid!", "center", pT, T_grid, ΔT_grid, subgrid_arrays, particles, dt, d, handle)
+
+
+def subgrid_diffusion_(pT, T_grid, ΔT_grid, subgrid_arrays, particles, dt, *, d=1.0, handle=None):
+    """subgrid_diffusion!(pT, T_grid, ΔT_grid, subgrid_arrays, particles, dt; d = 1.0) with subgrid_arrays of loc "vertex": as subgrid_diffusion_centroid_ with the
+    vertex fields T_grid, ΔT_grid (nx+1, ny+1), grid2particle_ / particle2grid_ in place of the centre operators.  Three launches (operator 11)."""
+    _subgrid("subgrid_diffusion!", "vertex", pT, T_grid, ΔT_grid, subgrid_arrays, particles, dt, d, handle)
