@@ -1247,8 +1247,8 @@ jrx_status jrx_compute_melt_fraction(jrx_handle *h, double *phi, const double *p
  * (miniapps/benchmarks/stokes2D/shear_heating/Shearheating2D.jl:69-82,221-232 gives the call shapes).  JustPIC's text is not in the reference tree, so nothing
  * is restated: what is built is defined HERE, to the rounding, and tests/_particles2d.py is the same text in NumPy.  Every operator is a GATHER with loops
  * bounded by max_xcell: nothing races, nothing depends on launch order, the device and the NumPy text leave the same bits.
- * Scope: 2D, uniform grid, one block (a handle with a communicator is refused), fp64.  NOT built: 3D, non-uniform grids, particle injection
- * (inject_particles_phase!), a marker chain, StressParticles (operators 6 - 9 below carry the stress through the reference's tuple methods instead),
+ * Scope: 2D, uniform grid, one block (a handle with a communicator is refused), fp64.  NOT built: 3D, non-uniform grids, a marker chain,
+ * force_injection!, clean_particles!, StressParticles (operators 6 - 9 below carry the stress through the reference's tuple methods instead),
  * grid2particle_flip!.
  *
  * Layout.  The grid has (nx, ny) cells of size (dx, dy), cell (i, j) = [x0 + i dx, x0 + (i+1) dx) x [y0 + j dy, y0 + (j+1) dy), 0-based.  Every cell owns a BUCKET
@@ -1377,6 +1377,42 @@ jrx_status jrx_particles2d_subgrid_diffusion_centroid(jrx_handle *h, double *pT,
                                                       double *pdT, const double *pdt0, double *dT_subgrid, const jrx_particles2d *part, double d, double dt);
 jrx_status jrx_particles2d_subgrid_diffusion_vertex(jrx_handle *h, double *pT, const double *T_grid, const double *dT_grid, int32_t dT_extent, double *pT0, double *pdT,
                                                     const double *pdt0, double *dT_subgrid, const jrx_particles2d *part, double d, double dt);
+/* 12. inject_particles_phase!(particles, pPhases, args, fields) -- every particle miniapp of the reference calls it right after move_particles!, in every time step
+ *    (miniapps/subduction/2D/Subduction2D.jl:246-263 with five vertex fields, SinkingBlock2D.jl:182 with (), (), test/test_shearheating2D.jl:215 with (pT,),
+ *    (T_buffer,)): a cell left with fewer than min_xcell particles is refilled.  JustPIC places the new particles at random; HERE the placement is deterministic
+ *    -- the empty sites of the sub-cell lattice of init_particles -- so that tests/_particles2d_inject.py restates it and the device leaves the same bits.
+ *    Layout, rounding (no fma), safety and the +0.0 invariant as above.  GATHER form: ONE launch, one thread per cell (i, j), plus one read of the counter words.
+ *    Donor set: the slots with active != 0 AT ENTRY (the mask holds 0 or 1).  No such slot is written, in any array: a thread reads only what nobody writes, and
+ *    there are no float atomics.  The MASK is therefore written OUT OF PLACE: active_out[i, j, s] is written for every slot, a copy of part->active with 1 in the
+ *    slots this call fills; px, py, pPhases and args[k] are written in place, and only in slots inactive at entry.  The caller then makes active_out the mask.
+ *    nsx, nsy: the sub-cell lattice (init_particles: nsx the largest divisor of nxcell not above its square root, nsy = nxcell / nsx); hx = dx / nsx and
+ *    hy = dy / nsy are formed once on the host.  For cell (i, j):
+ *      1. n = the number of active slots of the cell's own bucket.  If n >= min_xcell the mask is copied and nothing else happens.
+ *      2. Otherwise the cell is DEFICIENT (n_deficient).  xc = x0 + (double)i dx, yc = y0 + (double)j dy.
+ *      3. Occupancy of the nsx x nsy lattice over the active slots of the own bucket, in slot order: a = floor(((x - xc) _dx) (double)nsx), b likewise with y, yc,
+ *         _dy, nsy; site q = a + nsx b is occupied iff a >= 0 && a < nsx && b >= 0 && b < nsy, tested on the doubles.  A NaN or infinite coordinate, or a particle
+ *         not yet moved into its owner cell, occupies no site; it still counts in n.  The occupancy is one 64-bit word: nsx nsy <= 64.
+ *      4. For q = 0 .. nsx nsy - 1 in order (a = q mod nsx, b = q div nsx), while n < min_xcell, occupied sites skipped: the new point is
+ *         x = xc + ((double)a + 0.5) hx, y = yc + ((double)b + 0.5) hy -- the bits init_particles gives without rng.
+ *      5. Its donor: the cell's own bucket first, then the eight neighbours in the order of (2) (dj = -1, 0, 1 outermost, di = -1, 0, 1, cells outside the grid
+ *         skipped), slots in order: ex = xd - x; ey = yd - y; d2 = ex ex + ey ey; a candidate wins iff d2 < best, best starting at +infinity.  The first of
+ *         equals stays; a NaN or infinite d2 never wins.
+ *      6. No donor: the cell is counted ONCE in n_no_donor and left as it is from there on (it heals in a later step, once its neighbours are filled).
+ *      7. Otherwise the new particle goes into the lowest slot of the bucket that was inactive at entry and has not been filled in this call: coordinates (x, y),
+ *         1 in active_out, pPhases = the donor's, and args[k] by field_loc[k]: JRX_INJECT_VERTEX -- fields[k] is (nx+1, ny+1), the expression of (3) at (x, y)
+ *         over the vertices of cell (i, j); JRX_INJECT_CENTRE -- fields[k] is (nx, ny), A(x, y) of (6) (not written if a scaled coordinate is not finite);
+ *         JRX_INJECT_DONOR -- fields[k] is not read (may be NULL), args[k] of the donor's slot.  n++, n_injected++.
+ *      8. There are always enough sites: occupied sites <= n < min_xcell <= nsx nsy.
+ *    A particle field that is not listed keeps +0.0 in the new slot.  args, fields: HOST arrays of nargs DEVICE pointers, field_loc a host array (all three may be
+ *    NULL when nargs = 0).  counts = {n_active_before, n_active_after, n_deficient, n_injected, n_no_donor}; n_active_after = n_active_before + n_injected.
+ *    Further refusals: min_xcell < 1, > max_xcell or > nsx nsy; nsx or nsy < 1, nsx nsy > 64; an unknown field_loc; JRX_INJECT_CENTRE with nx < 2 or ny < 2;
+ *    active_out overlapping the mask; pPhases, any args[k], active_out and the particles' arrays not pairwise disjoint; a fields[k] that is read overlapping
+ *    anything written. */
+#define JRX_INJECT_VERTEX 0   /* fields[k] is (nx+1, ny+1): operator 3's form at the new point        */
+#define JRX_INJECT_CENTRE 1   /* fields[k] is (nx, ny): operator 6's interpolant A(x, y); nx, ny >= 2 */
+#define JRX_INJECT_DONOR  2   /* fields[k] is not read: the value of args[k] in the donor's slot      */
+jrx_status jrx_particles2d_inject(jrx_handle *h, const jrx_particles2d *part, int32_t *active_out, double *pPhases, double *const *args, const double *const *fields,
+                                  const int32_t *field_loc, int32_t nargs, int32_t min_xcell, int32_t nsx, int32_t nsy, int64_t counts[5]);
 
 #ifdef __cplusplus
 }

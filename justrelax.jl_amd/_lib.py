@@ -112,6 +112,7 @@ RockRatio2D = _ptr_struct("RockRatio2D", ["center", "vertex", "Vx", "Vy"])      
 RockRatio3D = _ptr_struct("RockRatio3D", ["center", "vertex", "Vx", "Vy", "Vz", "yz", "xz", "xy"])      # jrx_rock_ratio3d
 MAXPHASE = 8
 SUBGRID_DT_NODES, SUBGRID_DT_GHOSTED = 0, 1          # JRX_SUBGRID_DT_*: the extent of ΔT_grid handed to the subgrid-diffusion entry points
+INJECT_VERTEX, INJECT_CENTRE, INJECT_DONOR = 0, 1, 2          # JRX_INJECT_*: where inject_particles_phase! takes a particle field of a new particle from
 DYREL_NAMES = ["gamma_eff", "etab", "P_num", "Dx", "Dy", "lmaxVx", "lmaxVy", "dVxdtau", "dVydtau", "dtauVx", "dtauVy", "dVx", "dVy", "betaVx", "betaVy",
                "cVx", "cVy", "alphaVx", "alphaVy", "Rx0", "Ry0", "txx_v", "tyy_v", "toxx_v", "toyy_v", "lambda", "lambda_v", "dPpsi", "dT", "melt_fraction"]
 DYREL2DFields = _ptr_struct("DYREL2DFields", DYREL_NAMES)      # jrx_dyrel2d_fields
@@ -268,6 +269,8 @@ def load(check_symbols: bool = False):
         # the temperature on particles, both forms: pT, T_grid, ΔT_grid, its extent code, pT0, pΔT, dt₀, ΔT_subgrid, the struct, d, dt
         L.jrx_particles2d_subgrid_diffusion_centroid.argtypes = [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 4 + [_pp, C.c_double, C.c_double]
         L.jrx_particles2d_subgrid_diffusion_vertex.argtypes = [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 4 + [_pp, C.c_double, C.c_double]
+        # injection: the struct, active_out, pPhases, args[], fields[] (host arrays of device pointers), field_loc[] (a host array), nargs, min_xcell, nsx, nsy, five counter words
+        L.jrx_particles2d_inject.argtypes = [C.c_void_p, _pp, C.c_void_p, C.c_void_p, _vpp, _vpp, C.POINTER(C.c_int32)] + [C.c_int32] * 4 + [_ip]
         _lib = L
     if check_symbols:
         missing = [s for s in declared_symbols() if not hasattr(_lib, s)]

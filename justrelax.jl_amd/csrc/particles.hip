@@ -1,7 +1,8 @@
 // particles.hip -- 2D marker-in-cell particles in gather form: advection!(particles, RungeKutta2(), V, dt), move_particles!, grid2particle!, particle2grid!
 // and update_phase_ratios!(phase_ratios, particles, pPhases); and the elastic stress carried on them: centroid2particle!, particle2centroid!,
 // rotate_stress_particles!, rotate_stress!(pτxx, pτyy, pτxy, pω, stokes, particles, dt) and stress2grid!; and the temperature: subgrid_diffusion_centroid! and
-// subgrid_diffusion! (operators 10 and 11: Gerya & Yuen's subgrid diffusion, the consumer of subgrid_characteristic_time!), for gfx950.
+// subgrid_diffusion! (operators 10 and 11: Gerya & Yuen's subgrid diffusion, the consumer of subgrid_characteristic_time!); and the refill of thinned cells,
+// inject_particles_phase! (operator 12: deterministic, on the empty sites of the seeding lattice; tests/_particles2d_inject.py), for gfx950.
 //
 // Reference: for the first five none to restate.  The reference's miniapps take them from JustPIC (miniapps/benchmarks/stokes2D/shear_heating/
 // Shearheating2D.jl:69-82,221-232 shows the calls), which is not in the reference tree.  include/jrx.h states the definitions built here; tests/_particles2d.py
@@ -87,11 +88,18 @@ __device__ __forceinline__ bool pt_interp(const double *__restrict__ A, int mx, 
 // the weight of a particle at coordinate x to a node at xn
 __device__ __forceinline__ double pt_w(double x, double xn, double idx) { return 1.0 - fabs(x - xn) * idx; }
 
-// sum of a per-thread count over the wave, added to *word by lane 0 (blocks are 64 x 4: a wave is one row of the tile)
-__device__ __forceinline__ void pt_count(unsigned long long *word, int v)
+// sum of a per-thread count over the wave (blocks are 64 x 4: a wave is one row of the tile); lane 0 holds it
+__device__ __forceinline__ int pt_wave_sum(int v)
 {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// ... added to *word by lane 0
+__device__ __forceinline__ void pt_count(unsigned long long *word, int v)
+{
+    v = pt_wave_sum(v);
     if (threadIdx.x == 0 && v != 0) atomicAdd(word, (unsigned long long)v);
 }
 
@@ -697,6 +705,173 @@ __global__ __launch_bounds__(256) void k_pt_sg_back(const PtSgArgs a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ 12. injection into deficient cells
+struct PtInjArgs {
+    PtGeom g;
+    int *aout;                            // the mask, out of place
+    double *pph;
+    double *args[JRX_MAXPHASE];
+    const double *fields[JRX_MAXPHASE];
+    int loc[JRX_MAXPHASE];
+    int nargs, minx, nsx, nsy;
+    double hx, hy;                        // dx / nsx, dy / nsy, formed once on the host
+    double ox, oy;                        // origin of the centre nodes
+    unsigned long long *counts;           // three words: n_active_before | n_active_after << 32, n_deficient | n_injected << 32, n_no_donor
+};
+
+// the donor scan of one bucket for the point (x, y): strict <, so the first of equals stays and a NaN or infinite distance never wins
+// The scan is one lane's chain of loads, each a trip to memory (few lanes of a wave are deficient): four slots at a time, their masks loaded together and then
+// the coordinates of the active ones, the comparisons in slot order.
+__device__ __forceinline__ void pt_nearest(const PtGeom &g, int cell, int nc, double x, double y, double &best, int &donor)
+{
+    int s = 0, lin = cell;
+    for (; s + 4 <= g.mx; s += 4, lin += 4 * nc) {
+        int m[4];
+        double xs[4], ys[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) m[u] = g.active[lin + u * nc];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            xs[u] = ys[u] = 0.0;
+            if (m[u] != 0) xs[u] = g.px[lin + u * nc], ys[u] = g.py[lin + u * nc];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            if (m[u] == 0) continue;
+            const double ex = xs[u] - x, ey = ys[u] - y;
+            const double d2 = ex * ex + ey * ey;
+            if (d2 < best) best = d2, donor = lin + u * nc;
+        }
+    }
+    for (; s < g.mx; s++, lin += nc) {
+        if (g.active[lin] == 0) continue;
+        const double ex = g.px[lin] - x, ey = g.py[lin] - y;
+        const double d2 = ex * ex + ey * ey;
+        if (d2 < best) best = d2, donor = lin;
+    }
+}
+
+// steps 2 - 7 of the definition for the deficient cell (i, j) holding n particles; it reads only slots active at entry and writes only slots inactive at entry
+__device__ __forceinline__ void pt_inject_cell(const PtInjArgs &a, int i, int j, int &n, int &n_injected, int &n_no_donor)
+{
+    const PtGeom &g = a.g;
+    const int nc = g.nx * g.ny, base = j * g.nx + i;
+    const double xc = g.x0 + (double)i * g.dx, yc = g.y0 + (double)j * g.dy;
+    const double fnx = (double)a.nsx, fny = (double)a.nsy;
+    unsigned long long occ = 0;
+    for (int s = 0, lin = base; s < g.mx; s++, lin += nc) {
+        if (g.active[lin] == 0) continue;
+        const double fa = floor(((g.px[lin] - xc) * g.idx) * fnx), fb = floor(((g.py[lin] - yc) * g.idy) * fny);
+        if (fa >= 0.0 && fa < fnx && fb >= 0.0 && fb < fny) occ |= 1ull << ((int)fa + a.nsx * (int)fb);
+    }
+    int sfree = 0, to = base;             // the lowest slot not yet looked at
+    for (int qb = 0, q = 0; qb < a.nsy; qb++) {
+        for (int qa = 0; qa < a.nsx; qa++, q++) {
+            if (n >= a.minx) return;
+            if ((occ >> q) & 1ull) continue;
+            const double x = xc + ((double)qa + 0.5) * a.hx, y = yc + ((double)qb + 0.5) * a.hy;
+            double best = HUGE_VAL;
+            int donor = -1;
+            pt_nearest(g, base, nc, x, y, best, donor);
+            // the neighbour loops stay rolled: nine copies of the scan cost 36 VGPRs and a wave of occupancy on the path every thread takes
+#pragma unroll 1
+            for (int dj = -1; dj <= 1; dj++) {
+                const int jn = j + dj;
+                if (jn < 0 || jn >= g.ny) continue;
+#pragma unroll 1
+                for (int di = -1; di <= 1; di++) {
+                    const int in = i + di;
+                    if ((di == 0 && dj == 0) || in < 0 || in >= g.nx) continue;
+                    pt_nearest(g, jn * g.nx + in, nc, x, y, best, donor);
+                }
+            }
+            if (donor < 0) {
+                n_no_donor = 1;
+                return;
+            }
+            while (sfree < g.mx && g.active[to] != 0) sfree++, to += nc;
+            if (sfree >= g.mx) return;    // not reached: n < min_xcell <= max_xcell leaves a slot
+            g.px[to] = x, g.py[to] = y, a.aout[to] = 1;
+            a.pph[to] = a.pph[donor];
+#pragma unroll
+            for (int k = 0; k < JRX_MAXPHASE; k++) {
+                if (k >= a.nargs) continue;
+                if (a.loc[k] == JRX_INJECT_DONOR) {
+                    a.args[k][to] = a.args[k][donor];
+                } else if (a.loc[k] == JRX_INJECT_VERTEX) {
+                    const double *f = a.fields[k] + j * (g.nx + 1) + i;
+                    const double f00 = f[0], f10 = f[1], f01 = f[g.nx + 1], f11 = f[g.nx + 2];
+                    a.args[k][to] = pt_bilin((x - xc) * g.idx, (y - yc) * g.idy, f00, f10, f01, f11);
+                } else {
+                    double v;
+                    if (pt_interp(a.fields[k], g.nx, g.ny, a.ox, a.oy, g.idx, g.idy, x, y, v)) a.args[k][to] = v;
+                }
+            }
+            sfree++, to += nc;
+            n++, n_injected++;
+        }
+    }
+}
+
+// A thread per cell.  Every thread copies its bucket's mask to the output and counts it: one coalesced read and one coalesced write per slot, the whole of the
+// common path.  Only a thread whose count is below min_xcell goes on to pt_inject_cell.
+__global__ __launch_bounds__(256) void k_pt_inject(const PtInjArgs a)
+{
+    const PtGeom &g = a.g;
+    int i, j;
+    pt_index(g.nbx, i, j);
+    int n = 0, n_before = 0, n_deficient = 0, n_injected = 0, n_no_donor = 0;
+    if (i < g.nx && j < g.ny) {
+        const int nc = g.nx * g.ny;
+        {
+            // the two masks do not overlap (checked by the entry point): four loads in flight before the four stores
+            const int *__restrict__ in = g.active;
+            int *__restrict__ out = a.aout;
+            int s = 0, lin = j * g.nx + i;
+            for (; s + 4 <= g.mx; s += 4, lin += 4 * nc) {
+                const int m0 = in[lin], m1 = in[lin + nc], m2 = in[lin + 2 * nc], m3 = in[lin + 3 * nc];
+                out[lin] = m0, out[lin + nc] = m1, out[lin + 2 * nc] = m2, out[lin + 3 * nc] = m3;
+                n += (m0 != 0) + (m1 != 0) + (m2 != 0) + (m3 != 0);
+            }
+            for (; s < g.mx; s++, lin += nc) {
+                const int m = in[lin];
+                out[lin] = m;
+                n += m != 0;
+            }
+        }
+        n_before = n;
+        if (n < a.minx) {
+            n_deficient = 1;
+            pt_inject_cell(a, i, j, n, n_injected, n_no_donor);
+        }
+    }
+    // The five counts of the block, in three atomics at the most.  Every wave of every launch has particles to count, and one atomic per wave and count on one
+    // cache line took longer than the copy of the mask (measured: 400 us of a 1024^2 launch).  So the waves meet in LDS, and two counts share a word: each
+    // total is below 2^31 (the slots are), so the low halves never carry into the high ones.
+    __shared__ int sm[kPtTY][5];
+    int v[5] = {n_before, n, n_deficient, n_injected, n_no_donor};
+#pragma unroll
+    for (int k = 0; k < 5; k++) v[k] = pt_wave_sum(v[k]);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) sm[threadIdx.y][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+        unsigned long long t[5];
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            int sum = 0;
+#pragma unroll
+            for (int r = 0; r < kPtTY; r++) sum += sm[r][k];
+            t[k] = (unsigned long long)sum;
+        }
+        if (t[0] | t[1]) atomicAdd(a.counts + 0, t[0] | (t[1] << 32));
+        if (t[2] | t[3]) atomicAdd(a.counts + 1, t[2] | (t[3] << 32));
+        if (t[4]) atomicAdd(a.counts + 2, t[4]);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 bool pt_overlaps(const void *a, i64 abytes, const void *b, i64 bbytes)
 {
@@ -1142,6 +1317,66 @@ jrx_status jrx_particles2d_subgrid_diffusion_vertex(jrx_handle *h, double *pT, c
 {
     if (!h) return JRX_ERR_ARG;
     return pt_subgrid(h, "subgrid_diffusion!", true, pT, T_grid, dT_grid, dT_extent, pT0, pdT, pdt0, dT_subgrid, part, d, dt);
+}
+
+jrx_status jrx_particles2d_inject(jrx_handle *h, const jrx_particles2d *part, int32_t *active_out, double *pPhases, double *const *args, const double *const *fields,
+                                  const int32_t *field_loc, int32_t nargs, int32_t min_xcell, int32_t nsx, int32_t nsy, int64_t counts[5])
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "inject_particles_phase!";
+    PtInjArgs a = {};
+    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    const PtGeom &g = a.g;
+    if (!active_out || !pPhases || !counts) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, !active_out ? "active_out" : (!pPhases ? "pPhases" : "counts"));
+    if (nsx < 1 || nsy < 1 || (i64)nsx * nsy > 64)
+        return jrx_fail(h, JRX_ERR_ARG, "%s: a lattice of %d x %d sub-cells (both must be >= 1 and their product <= 64)", fn, (int)nsx, (int)nsy);
+    if (min_xcell < 1 || min_xcell > g.mx || min_xcell > nsx * nsy)
+        return jrx_fail(h, JRX_ERR_ARG, "%s: min_xcell = %d (must lie in 1 .. min(max_xcell = %d, nsx nsy = %d))", fn, (int)min_xcell, g.mx, (int)(nsx * nsy));
+    if (nargs < 0 || nargs > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d particle fields (0 .. %d are built)", fn, (int)nargs, JRX_MAXPHASE);
+    if (nargs > 0 && (!args || !fields || !field_loc))
+        return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL with %d particle fields", fn, !args ? "args" : (!fields ? "fields" : "field_loc"), (int)nargs);
+    for (int k = 0; k < nargs; k++) {
+        const int loc = field_loc[k];
+        if (loc != JRX_INJECT_VERTEX && loc != JRX_INJECT_CENTRE && loc != JRX_INJECT_DONOR)
+            return jrx_fail(h, JRX_ERR_ARG, "%s: unknown field_loc %d of particle field %d (%d = vertex, %d = centre, %d = donor)", fn, loc, k + 1, JRX_INJECT_VERTEX,
+                            JRX_INJECT_CENTRE, JRX_INJECT_DONOR);
+        if (!args[k]) return jrx_fail(h, JRX_ERR_ARG, "%s: particle field %d is NULL", fn, k + 1);
+        if (loc != JRX_INJECT_DONOR && !fields[k]) return jrx_fail(h, JRX_ERR_ARG, "%s: grid field %d is NULL", fn, k + 1);
+        if (loc == JRX_INJECT_CENTRE) JRX_TRY(pt_centres(h, fn, g));
+    }
+    // everything written -- the mask's copy, the phases, the particle fields, and the coordinates in place -- apart from the mask that is read and from each other
+    const i64 ns = pt_slots(g);
+    if (pt_overlaps(active_out, 4 * ns, g.active, 4 * ns)) return jrx_fail(h, JRX_ERR_ARG, "%s: active_out overlaps the mask (the mask is written out of place)", fn);
+    PtArr out[2 + JRX_MAXPHASE] = {{active_out, 4 * ns, "active_out"}, {pPhases, 8 * ns, "pPhases"}};
+    static const char *const names[JRX_MAXPHASE] = {"particle field 1", "particle field 2", "particle field 3", "particle field 4",
+                                                    "particle field 5", "particle field 6", "particle field 7", "particle field 8"};
+    for (int k = 0; k < nargs; k++) out[2 + k] = PtArr{args[k], 8 * ns, names[k]};
+    PtArr in[JRX_MAXPHASE];
+    int nin = 0;
+    for (int k = 0; k < nargs; k++) {
+        if (field_loc[k] == JRX_INJECT_DONOR) continue;
+        const bool v = field_loc[k] == JRX_INJECT_VERTEX;
+        in[nin++] = PtArr{fields[k], 8 * (i64)(g.nx + (v ? 1 : 0)) * (g.ny + (v ? 1 : 0)), v ? "a vertex field" : "a centre field"};
+    }
+    JRX_TRY(pt_disjoint(h, fn, out, 2 + nargs, in, nin, g));
+    for (int k = 0; k < nin; k++) JRX_TRY(pt_apart(h, fn, in[k].name, in[k].p, in[k].bytes, g));          // px, py are written too
+    JRX_TRY(jrx_check_device(h));
+    a.aout = (int *)active_out, a.pph = pPhases;
+    for (int k = 0; k < nargs; k++) a.args[k] = args[k], a.fields[k] = fields[k], a.loc[k] = field_loc[k];
+    a.nargs = (int)nargs, a.minx = (int)min_xcell, a.nsx = (int)nsx, a.nsy = (int)nsy;
+    a.hx = g.dx / (double)nsx, a.hy = g.dy / (double)nsy;
+    a.ox = g.x0 + 0.5 * g.dx, a.oy = g.y0 + 0.5 * g.dy;
+    a.counts = pt_words(h);
+    const unsigned nb = pt_blocks(a.g, g.nx, g.ny);
+    JRX_HIP(h, hipMemsetAsync(a.counts, 0, sizeof(int64_t) * 3, h->stream));
+    h->stat_particles_launches++;
+    hipLaunchKernelGGL(k_pt_inject, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+    JRX_LAUNCH_CHECK(h);
+    int64_t w[3];
+    JRX_TRY(pt_read_words(h, 3, w));
+    const int64_t lo = 0xffffffffll;
+    counts[0] = w[0] & lo, counts[1] = (w[0] >> 32) & lo, counts[2] = w[1] & lo, counts[3] = (w[1] >> 32) & lo, counts[4] = w[2];
+    return JRX_OK;
 }
 
 }  // extern "C"

@@ -7,13 +7,16 @@ here, on the host.
 The elastic stress travels on the particles too: centroid2particle_, particle2centroid_, rotate_stress_particles_, stress2grid_ and the particle form of
 rotate_stress_ (the tuple methods of src/stress_rotation/stress_rotation_particles.jl:92-99,224-235,264-276; tests/_particles2d_stress.py restates them).
 
-Built: 2D, uniform grid, one block, fp64.  Refused by name: 3D, a non-uniform Geometry, a handle with a communicator (by the library), particle injection, a marker
-chain, StressParticles (the wrapper type; its tuple methods are what is built).
+Built: 2D, uniform grid, one block, fp64.  Refused by name: 3D, a non-uniform Geometry, a handle with a communicator (by the library), a marker chain,
+StressParticles (the wrapper type; its tuple methods are what is built).
 
-A time step with particles (examples/sinking_block2d_particles.py):
+A time step with particles (examples/sinking_block2d_particles.py; with the refill, examples/rotating_box2d_injection.py):
 
-    advection_(particles, RungeKutta2(), stokes.V, dt); move_particles_(particles, particle_args); update_phase_ratios_(phase_ratios, particles, pPhases);
-    compute_ρg_(...); solve_(...)
+    advection_(particles, RungeKutta2(), stokes.V, dt); move_particles_(particles, particle_args); inject_particles_phase_(particles, pPhases, args, fields);
+    update_phase_ratios_(phase_ratios, particles, pPhases); compute_ρg_(...); solve_(...)
+
+inject_particles_phase_ refills the cells that fell below min_xcell particles (operator 12 of include/jrx.h; tests/_particles2d_inject.py restates it): new
+particles on the empty sites of the sub-cell lattice of init_particles, the phase from the nearest particle, the other fields from the grid or from that particle.
 
 A visco-elastic step with the stress on particles (examples/stress_rotation2d_particles.py), pτxx, pτyy, pτxy, pω from init_cell_arrays:
 
@@ -44,14 +47,77 @@ from .stress_rotation import METHODS
 from .phases import _ULPS          # the vertex spacing may vary by this many ulp of the largest coordinate, as for update_phase_ratios_2D_
 
 COUNTS = ("n_active_before", "n_active_after", "n_outside", "n_far", "n_overflow")
+INJECT_COUNTS = ("n_active_before", "n_active_after", "n_deficient", "n_injected", "n_no_donor")
+INJECT_LOCS = {"vertex": _lib.INJECT_VERTEX, "center": _lib.INJECT_CENTRE, "donor": _lib.INJECT_DONOR}
 
 
 def _not_built(what):
-    raise NotImplementedError(f"{what}: not built (particles are 2D, uniform grid, one block; injection, marker chains and StressParticles are not provided)")
+    raise NotImplementedError(f"{what}: not built (particles are 2D, uniform grid, one block; marker chains and StressParticles are not provided)")
 
 
-def inject_particles_phase_(*a, **k):
-    _not_built("inject_particles_phase!")
+def inject_particles_phase_(particles=None, pPhases=None, args=(), fields=(), *, loc=None, min_xcell=None, handle=None):
+    """inject_particles_phase!(particles, pPhases, args, fields): every cell with fewer than min_xcell particles (default: particles.min_xcell) is refilled, one
+    launch.  The new particles sit on the empty sites of the sub-cell lattice of init_particles (deterministic, where JustPIC draws them at random); each takes its
+    phase from the nearest particle of its own and the eight neighbouring cells, and args[k] from fields[k]: a vertex field (nx+1, ny+1) or a centre field (nx, ny)
+    interpolated at the new point, or None for the donor's value.  loc may name the kinds ("vertex", "center", "donor") and must agree with the shapes.  A particle
+    field that is not listed keeps 0 in the new slots.  Returns the counters as a dict; a cell with no particle in its neighbourhood is counted in n_no_donor and
+    heals in a later step (include/jrx.h, operator 12).  Call it after move_particles_."""
+    fn = "inject_particles_phase!"
+    if particles is None:
+        _not_built(f"{fn} without particles")
+    _check_particles(particles, fn)
+    _check_field(particles, pPhases, "pPhases", fn)
+    args, fields = tuple(args), tuple(fields)
+    if len(args) != len(fields):
+        raise ValueError(f"{fn}: {len(args)} particle fields and {len(fields)} grid fields (one per particle field; None copies the donor's value)")
+    if len(args) > _lib.MAXPHASE:
+        raise ValueError(f"{fn}: {len(args)} particle fields (0 .. {_lib.MAXPHASE})")
+    loc = (None,) * len(args) if loc is None else tuple(loc)
+    if len(loc) != len(args):
+        raise ValueError(f"{fn}: loc names {len(loc)} kinds for {len(args)} particle fields")
+    nx, ny = particles.ni
+    shapes = {(nx + 1, ny + 1): "vertex", (nx, ny): "center"}
+    codes = []
+    for k, (f, F, want) in enumerate(zip(args, fields, loc)):
+        _check_field(particles, f, f"args[{k}]", fn)
+        if f is pPhases:
+            raise ValueError(f"{fn}: args[{k}] is pPhases (the phases are carried by the operator itself)")
+        want = want.lstrip(":") if isinstance(want, str) else want
+        if want is not None and want not in INJECT_LOCS:
+            raise ValueError(f"{fn}: unknown loc[{k}] = {want!r} (one of {sorted(INJECT_LOCS)})")
+        if F is None:
+            kind = "donor"
+        elif isinstance(F, torch.Tensor) and F.dtype == torch.float64 and tuple(F.shape) in shapes:
+            kind = shapes[tuple(F.shape)]
+            if F.device != particles.coords[0].device:
+                raise ValueError(f"{fn}: fields[{k}] is on {F.device}, the particles on {particles.coords[0].device}")
+        else:
+            raise ValueError(f"{fn}: fields[{k}] is {tuple(F.shape) if isinstance(F, torch.Tensor) else type(F).__name__}; {particles.ni} cells need an fp64 vertex "
+                             f"field {(nx + 1, ny + 1)}, a centre field {(nx, ny)} or None (the donor's value)")
+        if want is not None and want != kind:
+            raise ValueError(f"{fn}: loc[{k}] = {want!r}, but fields[{k}] is {'None' if F is None else tuple(F.shape)}: a {kind} field")
+        if kind == "center" and min(particles.ni) < 2:
+            raise ValueError(f"{fn}: {particles.ni} cells (interpolation between centres needs nx >= 2 and ny >= 2)")
+        codes.append(INJECT_LOCS[kind])
+    if len({id(f) for f in args}) != len(args):
+        raise ValueError(f"{fn}: a particle field is listed twice")
+    min_xcell = particles.min_xcell if min_xcell is None else int(min_xcell)
+    nsx, nsy = _lattice(particles.nxcell)
+    if not 1 <= min_xcell <= min(particles.max_xcell, nsx * nsy):
+        raise ValueError(f"{fn}: min_xcell = {min_xcell} (must lie in 1 .. min(max_xcell = {particles.max_xcell}, nxcell = {nsx * nsy}))")
+    if nsx * nsy > 64:
+        raise ValueError(f"{fn}: nxcell = {nsx * nsy} (the lattice of new sites holds 64 at the most)")
+    h = _h(particles.coords[0], handle)
+    n = len(args)
+    s = particles._struct()
+    a_args = (C.c_void_p * max(n, 1))(*(ptr(f) for f in args))
+    a_fields = (C.c_void_p * max(n, 1))(*(None if F is None else ptr(F) for F in fields))
+    a_loc = (C.c_int32 * max(n, 1))(*codes)
+    counts = (C.c_int64 * 5)()
+    h.call("jrx_particles2d_inject", C.byref(s), C.c_void_p(particles._index2.data_ptr()), C.c_void_p(ptr(pPhases)), a_args, a_fields, a_loc, C.c_int32(n),
+           C.c_int32(min_xcell), C.c_int32(nsx), C.c_int32(nsy), counts)
+    particles.index, particles._index2 = particles._index2, particles.index          # the mask was written out of place
+    return dict(zip(INJECT_COUNTS, (int(c) for c in counts)))
 
 
 def MarkerChain(*a, **k):
