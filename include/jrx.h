@@ -136,7 +136,7 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   jrx_update_phases_topography2d calls that launched (their 3D forms jrx_compute_rock_fraction3d / jrx_advect_topography3d / jrx_update_phases_topography3d count in the same three),
  *   "stat_principal_calls" = jrx_principal_stresses2d / 3d calls that launched, "stat_dyrel_launches" = kernels launched by the jrx_dyrel2d_* and jrx_dyrel3d_* entry points,
  *   "stat_stepops_launches" = kernels launched by jrx_pureshear_bc2d / 3d, jrx_free_surface_bcs2d / 3d, jrx_subgrid_characteristic_time and jrx_compute_melt_fraction,
- *   "stat_particles_launches" = kernels launched by the jrx_particles2d_* entry points (one each, except the chains of "particles_stress_fused" = 0 and the two subgrid-diffusion calls: 2 / 3, chains 7) -- so that a caller
+ *   "stat_particles_launches" = kernels launched by the jrx_particles2d_* and jrx_particles3d_* entry points (one each, except the chains of "particles_stress_fused" = 0 and the two subgrid-diffusion calls: 2 / 3, chains 7) -- so that a caller
  *   (and the tests, and bench.py for the kernel it prices) can prove which path ran. */
 jrx_status jrx_set_option(jrx_handle *h, const char *key, int64_t value);
 /* the caller has written to an operand array (tau_o, P0, Q, K, G, eta, rho g) since the last driver call: a cached verdict of the operand pass ("operand_cache") is dropped */
@@ -1247,7 +1247,7 @@ jrx_status jrx_compute_melt_fraction(jrx_handle *h, double *phi, const double *p
  * (miniapps/benchmarks/stokes2D/shear_heating/Shearheating2D.jl:69-82,221-232 gives the call shapes).  JustPIC's text is not in the reference tree, so nothing
  * is restated: what is built is defined HERE, to the rounding, and tests/_particles2d.py is the same text in NumPy.  Every operator is a GATHER with loops
  * bounded by max_xcell: nothing races, nothing depends on launch order, the device and the NumPy text leave the same bits.
- * Scope: 2D, uniform grid, one block (a handle with a communicator is refused), fp64.  NOT built: 3D, non-uniform grids, a marker chain,
+ * Scope: 2D here (3D: the core chain, in the section after this one), uniform grid, one block (a handle with a communicator is refused), fp64.  NOT built: non-uniform grids, a marker chain,
  * force_injection!, clean_particles!, StressParticles (operators 6 - 9 below carry the stress through the reference's tuple methods instead),
  * grid2particle_flip!.
  *
@@ -1413,6 +1413,74 @@ jrx_status jrx_particles2d_subgrid_diffusion_vertex(jrx_handle *h, double *pT, c
 #define JRX_INJECT_DONOR  2   /* fields[k] is not read: the value of args[k] in the donor's slot      */
 jrx_status jrx_particles2d_inject(jrx_handle *h, const jrx_particles2d *part, int32_t *active_out, double *pPhases, double *const *args, const double *const *fields,
                                   const int32_t *field_loc, int32_t nargs, int32_t min_xcell, int32_t nsx, int32_t nsy, int64_t counts[5]);
+
+/* ------------------------------------------------------------------ 3D marker-in-cell particles: advect, re-bucket, interpolate, phase ratios
+ * The core chain of the reference's 3D miniapps (miniapps/benchmarks/stokes3D/shear_heating/Shearheating3D.jl:63-78,224-233: init_particles, init_cell_arrays,
+ * advection!, move_particles!, particle2centroid!, update_phase_ratios!) on the layout and under the rules of the 2D section above, which this section EXTENDS:
+ * operators 1 - 7 there, with a third index.  tests/_particles3d.py is this text in NumPy.  Every operator is a gather with loops bounded by max_xcell; no atomics
+ * except integer adds into the counter words; no fma, every product and sum rounded once, left to right; an index derived from a coordinate is range-checked on
+ * the double before the conversion; an inactive slot holds +0.0 / 0 in every array.
+ * Scope: 3D, uniform grid, one block, fp64.  NOT built in 3D: inject_particles_phase!, the stress operators (8, 9), subgrid diffusion (10, 11), non-uniform
+ * grids, decomposed grids (a handle with a communicator is refused), marker chains, StressParticles.  Without injection a flow that crosses the boundary loses
+ * material there; n_outside reports it.
+ *
+ * Layout.  (nx, ny, nz) cells of size (dx, dy, dz); every per-particle array is (nx, ny, nz, max_xcell) column-major, the SLOT index slowest: entry (i, j, k, s) at
+ * i + nx (j + ny (k + nz s)).  nx ny nz max_xcell < 2^31 and (nx+2)(ny+2)(nz+2) < 2^31 (32-bit offsets).  _dx, _dy, _dz are formed once on the host (checked).
+ * Grid fields are column-major; phase-ratio members have the phase index fastest.
+ *
+ * JRX_ERR_ARG with a text naming the cause, nothing launched ("stat_particles_launches" unchanged) and nothing written: as in 2D -- a NULL pointer, an extent
+ * < 1, max_xcell < 1, 2^31 or more slots, an origin that is not finite, a spacing that is not positive and finite, _dx / _dy / _dz not the inverses, dt not
+ * finite, nargs outside 0 .. JRX_MAXPHASE, nphase outside 1 .. JRX_MAXPHASE, src and dst of a move sharing an array or differing in a scalar, an output that
+ * overlaps an input, another output or the particles' own arrays, an extent < 2 for operator 6, a handle with a communicator. */
+typedef struct jrx_particles3d {
+    double *px, *py, *pz;
+    int32_t *active;
+    int64_t nx, ny, nz;
+    int32_t max_xcell;
+    double x0, y0, z0, dx, dy, dz, _dx, _dy, _dz;
+} jrx_particles3d;
+/* 1. advection!(particles, RungeKutta2(), @velocity(stokes), dt) -- the midpoint rule of 2D operator 1 with three components:
+ *      (ux, uy, uz) = V(x, y, z);  xm = x + (0.5 dt) ux, ym, zm likewise;  (wx, wy, wz) = V(xm, ym, zm);  x' = x + dt wx,  y' = y + dt wy,  z' = z + dt wz.
+ *    Vx is (nx+1, ny+2, nz+2) with nodes at (x0 + i dx, y0 + (j - 0.5) dy, z0 + (k - 0.5) dz), Vy is (nx+2, ny+1, nz+2), Vz is (nx+2, ny+2, nz+1), likewise:
+ *    stokes.V with its ghost layers; the origins x0 - 0.5 dx, ... are formed once on the host.  Per axis s, i0, t exactly as in 2D (so a point outside the node
+ *    box extrapolates).  With B(m) the 2D bilinear expression on the plane k0 + m,
+ *      A(x, y, z) = (1 - tz) B(0) + tz B(1).
+ *    If any scaled coordinate of any of the six evaluations is not finite, the particle is left exactly as it was. */
+jrx_status jrx_particles3d_advect_rk2(jrx_handle *h, const jrx_particles3d *part, const double *Vx, const double *Vy, const double *Vz, double dt);
+/* 2. move_particles!(particles, particle_args) -- out of place.  Owner per axis as in 2D (fx = floor((x - x0) _dx), inside iff fx >= 0 && fx < nx on the double).
+ *    ONE thread per destination cell (i, j, k) fills its dst slots from 0 upward: first the active particles of src cell (i, j, k), in slot order, whose owner
+ *    is (i, j, k); then, for dk = -1, 0, 1 (outermost), dj = -1, 0, 1, di = -1, 0, 1 (innermost), (0, 0, 0) skipped, the active particles of src cell
+ *    (i + di, j + dj, k + dk) (where that cell exists), in slot order, whose owner is (i, j, k).  A particle that finds the bucket full is counted in n_overflow;
+ *    the remaining dst slots are zeroed.  Over its own cell a thread counts n_active_before, n_outside and n_far (the owner is inside the grid and more than one
+ *    cell away along any axis).  counts and their sum rule as in 2D.
+ *    work: NULL, or a device buffer of nx ny nz max_xcell BYTES owned by the caller, disjoint from everything else.  NULL (or tuning key
+ *    "particles3d_move_codes" = 0): the direct form, one launch -- a destination cell computes the owner of every particle of its 27 cells from the three
+ *    coordinates.  With work: two launches -- a pre-pass, a thread per source cell, stores each slot's owner in one byte ((dk+1) 9 + (dj+1) 3 + (di+1) for a
+ *    neighbour offset, 255 inactive, 254 outside, 253 far) and takes n_active_before, n_outside, n_far; the gather reads the bytes of its 27 cells and loads
+ *    coordinates and fields only of the slots it takes.  Both forms leave identical bits in every output and counter. */
+jrx_status jrx_particles3d_move(jrx_handle *h, const jrx_particles3d *src, const jrx_particles3d *dst, const double *const *args_src, double *const *args_dst,
+                                int32_t nargs, uint8_t *work, int64_t counts[5]);
+/* 3. grid2particle!(pF, xvi, F, particles): F is a vertex field (nx+1, ny+1, nz+1).  Per active slot (i, j, k, s), trilinear over the eight vertices of the slot's
+ *    BUCKET cell: tx = (x - (x0 + (double)i dx)) _dx, ty, tz likewise, combined as in (1).  An inactive slot of pF is set to 0. */
+jrx_status jrx_particles3d_grid2particle(jrx_handle *h, double *pF, const double *F, const jrx_particles3d *part);
+/* 4. particle2grid!(F, pF, xvi, particles): one thread per vertex (i, j, k) reads its up to eight cells at offsets {-1, 0}: the first dimension's offset
+ *    outermost, the third innermost, -1 before 0 (the order of jrx_update_phase_ratios3d), cells outside the grid skipped, slots in order:
+ *      w = (1 - fabs(x - xv) _dx) (1 - fabs(y - yv) _dy) (1 - fabs(z - zv) _dz);  num += w pF;  den += w;     F = num / den;  where den == 0, F is left as it was. */
+jrx_status jrx_particles3d_particle2grid(jrx_handle *h, double *F, const double *pF, const jrx_particles3d *part);
+/* 5. update_phase_ratios!(phase_ratios, particles, pPhases): members[8] = center, vertex, Vx, Vy, Vz, yz, xz, xy (a HOST array of device pointers), each
+ *    (nphase, nx + sx, ny + sy, nz + sz) with the stagger (sx, sy, sz) = (0,0,0), (1,1,1), (1,0,0), (0,1,0), (0,0,1), (0,1,1), (1,0,1), (1,1,0).  A member exists at
+ *    node (i, j, k) when i < nx + sx, j < ny + sy, k < nz + sz.  It gathers the cells at offsets {-1, 0} along its staggered axes and {0} along the others, in the
+ *    nesting order of (4); the weight of (4) goes to the vertex coordinate x0 + (double)i dx along a staggered axis and to the centre coordinate
+ *    x0 + ((double)i + 0.5) dx along the others.  Phase acceptance, ratio_k = w_k / W and the W == 0 rule (member left unchanged, counted in *n_empty) as in 2D.
+ *    One launch, or two launches of four members each at nphase = JRX_MAXPHASE (the same bits; tuning key "particles3d_ratios_split"). */
+jrx_status jrx_particles3d_phase_ratios(jrx_handle *h, double *const members[8], const double *pPhases, int32_t nphase, const jrx_particles3d *part,
+                                        int64_t *n_empty);
+/* 6. centroid2particle!(pF, F, particles): F is a centre field (nx, ny, nz).  Per active slot pF = A(x, y, z), A the interpolant of (1) with extents (nx, ny, nz)
+ *    and node-grid origin (x0 + 0.5 dx, y0 + 0.5 dy, z0 + 0.5 dz): the pair is found from the COORDINATE, the outer half cells extrapolate.  A slot whose scaled
+ *    coordinate is not finite is left as it was; an inactive slot is set to 0.  Needs every extent >= 2. */
+jrx_status jrx_particles3d_centroid2particle(jrx_handle *h, double *pF, const double *F, const jrx_particles3d *part);
+/* 7. particle2centroid!(F, pF, particles): one thread per cell walks its own bucket in slot order, weights of (4) to the centre; an empty cell keeps its value. */
+jrx_status jrx_particles3d_particle2centroid(jrx_handle *h, double *F, const double *pF, const jrx_particles3d *part);
 
 #ifdef __cplusplus
 }

@@ -81,6 +81,12 @@
  *   "particles_subgrid_fused" (1) jrx_particles2d_subgrid_diffusion_centroid / _vertex: two / three launches -- a thread per cell does steps 1 - 3 of the definition in one walk of
  *                                 its bucket (centre form: and the cell's remainder), a thread per vertex the four-cell gather (vertex form), a thread per cell steps 6 and 7;
  *                                 0 = the chain of seven launches the definition names (bit-identical in pT, pT0, pΔT, ΔT_subgrid; profiles/particles2d_subgrid_bench.txt)
+ *   "particles3d_move_codes" (1) jrx_particles3d_move with a work buffer: a pre-pass stores each slot's owner as one byte and the gather reads bytes from its 27 cells, loading
+ *                                 coordinates and fields only of the slots it takes; 0 = the direct form (the owner of every particle of 27 cells from its coordinates), which a
+ *                                 NULL work buffer selects too (bit-identical; profiles/particles3d_bench.txt)
+ *   "particles3d_ratios_split" (2) jrx_particles3d_phase_ratios: 0 = one launch, one walk of a node's eight cells for all eight members; 1 = two launches of four members each
+ *                                 (center, Vx, Vy, Vz | vertex, yz, xz, xy); 2 = two launches at nphase = 8, one otherwise (bit-identical; at 128^3 one launch is 23 % faster at two
+ *                                 phases, two launches 11 % faster at eight: profiles/particles3d_bench.txt)
  *   "general_hif" (0)            3D fused kernel, general form (any dt), 64 x 4 tile: the stress nodes on the high faces i = nx, j = ny, k = nz are updated inside the kernel (one launch per
  *                                 unobserved iteration) and, with neighbours, the kernel's boundary tiles read the received planes ("fused_overlap" = 3: no flow_bcs! launch, no fix-up):
  *                                 4 / 3 = the instantiation built for four (128 VGPRs + 28 dwords of scratch: 10.99 ms at 512^3) / three (155 VGPRs: 7.95 ms) waves per SIMD; 0 = boundary-layer launch (7.47 + 0.11 ms)

@@ -99,6 +99,11 @@ class Particles2D(C.Structure):      # jrx_particles2d
                [(k, C.c_double) for k in ("x0", "y0", "dx", "dy", "_dx", "_dy")]
 
 
+class Particles3D(C.Structure):      # jrx_particles3d
+    _fields_ = [("px", C.c_void_p), ("py", C.c_void_p), ("pz", C.c_void_p), ("active", C.c_void_p), ("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64),
+                ("max_xcell", C.c_int32)] + [(k, C.c_double) for k in ("x0", "y0", "z0", "dx", "dy", "dz", "_dx", "_dy", "_dz")]
+
+
 TPH_NAMES = ["P", "phase_c", "phase_qx", "phase_qy", "phase_qz"]
 ThermalPhaseFields = _ptr_struct("ThermalPhaseFields", TPH_NAMES)
 
@@ -271,6 +276,13 @@ def load(check_symbols: bool = False):
         L.jrx_particles2d_subgrid_diffusion_vertex.argtypes = [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 4 + [_pp, C.c_double, C.c_double]
         # injection: the struct, active_out, pPhases, args[], fields[] (host arrays of device pointers), field_loc[] (a host array), nargs, min_xcell, nsx, nsy, five counter words
         L.jrx_particles2d_inject.argtypes = [C.c_void_p, _pp, C.c_void_p, C.c_void_p, _vpp, _vpp, C.POINTER(C.c_int32)] + [C.c_int32] * 4 + [_ip]
+        # the 3D particle operators: as in 2D with Vz; move: and the byte work buffer (NULL: the direct form) before the counter words; phase ratios: members[8] (a host array of device pointers)
+        _p3 = C.POINTER(Particles3D)
+        L.jrx_particles3d_advect_rk2.argtypes = [C.c_void_p, _p3] + [C.c_void_p] * 3 + [C.c_double]
+        L.jrx_particles3d_move.argtypes = [C.c_void_p, _p3, _p3, _vpp, _vpp, C.c_int32, C.c_void_p, _ip]
+        for name in ("grid2particle", "particle2grid", "centroid2particle", "particle2centroid"):
+            getattr(L, "jrx_particles3d_" + name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _p3]
+        L.jrx_particles3d_phase_ratios.argtypes = [C.c_void_p, _vpp, C.c_void_p, C.c_int32, _p3, _ip]
         _lib = L
     if check_symbols:
         missing = [s for s in declared_symbols() if not hasattr(_lib, s)]

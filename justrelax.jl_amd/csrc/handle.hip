@@ -139,6 +139,7 @@ int find_opt(jrx_handle *h, const char *key, bool tuning, OptRef *out)
         {"weno_fused", 0, &h->weno_fused}, {"weno_rows", 1, &h->weno_rows},
         {"phase_ratios_fused", 0, &h->phase_ratios_fused}, {"rock_fraction3d_rows", 1, &h->rock_fraction3d_rows},
         {"particles_stress_fused", 0, &h->particles_stress_fused}, {"particles_subgrid_fused", 0, &h->particles_subgrid_fused},
+        {"particles3d_move_codes", 0, &h->particles3d_move_codes}, {"particles3d_ratios_split", 1, &h->particles3d_ratios_split},
     };
     if (tuning) {
         for (const OptRef &o : tun)

@@ -116,9 +116,11 @@ struct jrx_handle {
     int64_t stat_principal_calls = 0;    // jrx_principal_stresses2d / 3d calls that launched
     int64_t stat_dyrel_launches = 0;     // kernels launched by the jrx_dyrel2d_* / jrx_dyrel3d_* entry points (dyrel2d.hip, dyrel3d.hip)
     int64_t stat_stepops_launches = 0;   // kernels launched by the per-step operators of stepops.hip (pureshear_bc!, free_surface_bcs!, subgrid_characteristic_time!, compute_melt_fraction!)
-    int64_t stat_particles_launches = 0; // kernels launched by the jrx_particles2d_* entry points (particles.hip)
+    int64_t stat_particles_launches = 0; // kernels launched by the jrx_particles2d_* / jrx_particles3d_* entry points (particles.hip, particles3d.hip)
     bool particles_stress_fused = true;  // tuning: jrx_particles2d_rotate_stress / _stress2grid as one launch each (0: the chains of single-operator launches, 5 and 6; bit-identical)
     bool particles_subgrid_fused = true; // tuning: jrx_particles2d_subgrid_diffusion_centroid / _vertex as 2 / 3 launches (0: the chain of the definition, 7 launches; bit-identical)
+    bool particles3d_move_codes = true;  // tuning: jrx_particles3d_move with a work buffer runs the one-byte-owner pre-pass and the byte gather (0: the direct 27-cell gather; bit-identical)
+    int particles3d_ratios_split = 2;    // tuning: jrx_particles3d_phase_ratios: 0 = one launch for all eight members, 1 = two launches of four, 2 = two launches at nphase = 8 only (bit-identical)
     // ---- read-only counters (jrx_get_option "stat_*"): launches of the fused kernels since jrx_create, so that tests and the bench can
     //      prove which kernel path ran
     int64_t stat_fused3d_inkernel = 0;   // launches of k_fused3d that finished the neighbour faces themselves (fused_overlap = 3)

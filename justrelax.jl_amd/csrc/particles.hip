@@ -20,8 +20,7 @@
 //
 // k_pt_phase_ratios<N>: the phase count is a template argument (1 .. JRX_MAXPHASE) and the phase index of a particle is applied by an unrolled select, so the
 // 4 N + 4 accumulators of a node stay in registers (a run-time index into them would put them in scratch).
-#include <cfloat>
-#include "jrx_internal.hpp"
+#include "particles_common.hpp"          // the helpers shared with particles3d.hip
 #include "rotate_point.hpp"
 
 namespace {
@@ -35,25 +34,10 @@ struct PtGeom {                                       // jrx_particles2d by valu
     int nx, ny, mx, nbx;                              // mx = max_xcell; nbx = blocks along x of the launch
 };
 
-__device__ __forceinline__ bool pt_finite(double v) { return fabs(v) <= DBL_MAX; }
-
 __device__ __forceinline__ void pt_index(int nbx, int &i, int &j)
 {
     i = ((int)blockIdx.x % nbx) * kPtTX + (int)threadIdx.x;
     j = ((int)blockIdx.x / nbx) * kPtTY + (int)threadIdx.y;
-}
-
-// floor(s) as an index of the left node of an interpolation pair among m nodes: clamped on the double, so the pair exists and a point outside extrapolates
-__device__ __forceinline__ int pt_pair(double s, int m)
-{
-    const double f = floor(s);
-    return f >= 0.0 ? (f < (double)(m - 1) ? (int)f : m - 2) : 0;
-}
-
-// the bilinear form every interpolation here uses, in this order
-__device__ __forceinline__ double pt_bilin(double tx, double ty, double v00, double v10, double v01, double v11)
-{
-    return (1.0 - ty) * ((1.0 - tx) * v00 + tx * v10) + ty * ((1.0 - tx) * v01 + tx * v11);
 }
 
 // where (x, y) sits on a node grid of extents (mx, my) and origin (ox, oy): offset of the pair's first node and the local coordinates; false when a scaled
@@ -83,24 +67,6 @@ __device__ __forceinline__ bool pt_interp(const double *__restrict__ A, int mx, 
     if (!pt_locate(mx, my, ox, oy, idx, idy, x, y, off, tx, ty)) return false;
     v = pt_at(A, mx, off, tx, ty);
     return true;
-}
-
-// the weight of a particle at coordinate x to a node at xn
-__device__ __forceinline__ double pt_w(double x, double xn, double idx) { return 1.0 - fabs(x - xn) * idx; }
-
-// sum of a per-thread count over the wave (blocks are 64 x 4: a wave is one row of the tile); lane 0 holds it
-__device__ __forceinline__ int pt_wave_sum(int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// ... added to *word by lane 0
-__device__ __forceinline__ void pt_count(unsigned long long *word, int v)
-{
-    v = pt_wave_sum(v);
-    if (threadIdx.x == 0 && v != 0) atomicAdd(word, (unsigned long long)v);
 }
 
 // ------------------------------------------------------------------------------------------------ 1. advection, midpoint rule
@@ -873,12 +839,6 @@ __global__ __launch_bounds__(256) void k_pt_inject(const PtInjArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-bool pt_overlaps(const void *a, i64 abytes, const void *b, i64 bbytes)
-{
-    const char *pa = (const char *)a, *pb = (const char *)b;
-    return pa < pb + bbytes && pb < pa + abytes;
-}
-
 // the checks every entry point shares; fills g (without nbx)
 jrx_status pt_geom(jrx_handle *h, const char *fn, const char *what, const jrx_particles2d *p, PtGeom *g)
 {
@@ -916,24 +876,7 @@ unsigned pt_blocks(PtGeom &g, int ex, int ey)
     return (unsigned)((i64)g.nbx * ((ey + kPtTY - 1) / kPtTY));
 }
 
-// the counter words: six 64-bit integers in the tail of the handle's reduction scratch (every entry point here is synchronous)
-unsigned long long *pt_words(jrx_handle *h) { return (unsigned long long *)(h->d_sums + 10); }
-
-jrx_status pt_read_words(jrx_handle *h, int n, int64_t *out)
-{
-    JRX_HIP(h, hipMemcpyAsync(h->h_sums + 10, h->d_sums + 10, sizeof(int64_t) * n, hipMemcpyDeviceToHost, h->stream));
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    memcpy(out, h->h_sums + 10, sizeof(int64_t) * n);
-    return JRX_OK;
-}
-
 // ---- operators 6 - 9: an entry point checks everything first, then launches one kernel or its chain; the launchers below check nothing
-struct PtArr {
-    const void *p;
-    i64 bytes;
-    const char *name;
-};
-
 // every array present; no output shares memory with the particles' own arrays, an input or another output
 jrx_status pt_disjoint(jrx_handle *h, const char *fn, const PtArr *out, int nout, const PtArr *in, int nin, const PtGeom &g)
 {
@@ -1006,13 +949,6 @@ void pt_launch_rotate(jrx_handle *h, PtRotArgs a, int32_t method, bool fused)
         if (fused) hipLaunchKernelGGL((k_pt_rotate_stress<MM()>), dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
         else hipLaunchKernelGGL((k_pt_rotate<MM()>), dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
     });
-}
-
-jrx_status pt_finish(jrx_handle *h)
-{
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
 }
 
 // operators 10 and 11: everything checked first, then the fused launches (2 / 3) or the chain of the definition (7 launches and one fill)

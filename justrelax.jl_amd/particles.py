@@ -1,4 +1,4 @@
-"""2D marker-in-cell particles on the device: init_particles, init_cell_arrays, RungeKutta2, advection!, move_particles!, grid2particle!, particle2grid! and
+"""Marker-in-cell particles on the device, 2D and (the core chain) 3D: init_particles, init_cell_arrays, RungeKutta2, advection!, move_particles!, grid2particle!, particle2grid! and
 update_phase_ratios!(phase_ratios, particles, pPhases) -- the chain the reference's miniapps take from JustPIC (miniapps/benchmarks/stokes2D/shear_heating/
 Shearheating2D.jl:69-82,221-232).  Julia's `f!` is spelled `f_`.  JustPIC's text is not in the reference tree: include/jrx.h holds the definitions of what is
 built, tests/_particles2d.py restates them in NumPy.  Every operator forwards to one C-ABI entry point (csrc/particles.hip); only the seeding is computed
@@ -7,8 +7,12 @@ here, on the host.
 The elastic stress travels on the particles too: centroid2particle_, particle2centroid_, rotate_stress_particles_, stress2grid_ and the particle form of
 rotate_stress_ (the tuple methods of src/stress_rotation/stress_rotation_particles.jl:92-99,224-235,264-276; tests/_particles2d_stress.py restates them).
 
-Built: 2D, uniform grid, one block, fp64.  Refused by name: 3D, a non-uniform Geometry, a handle with a communicator (by the library), a marker chain,
-StressParticles (the wrapper type; its tuple methods are what is built).
+Built: uniform grid, one block, fp64.  2D: everything below.  3D (csrc/particles3d.hip, tests/_particles3d.py; the chain of Shearheating3D.jl:63-78,224-233):
+init_particles(backend, nxcell, max_xcell, min_xcell, *grid.xi_vel), init_cell_arrays, advection_, move_particles_, grid2particle_, particle2grid_,
+centroid2particle_, particle2centroid_ and update_phase_ratios_ (all eight members); these dispatch on len(particles.ni).  Refused by name: in 3D
+inject_particles_phase_, the stress operators and subgrid diffusion (a flow that crosses the boundary loses material there; n_outside reports it); in any
+dimension a non-uniform Geometry, a handle with a communicator (by the library), a marker chain, StressParticles (the wrapper type; its tuple methods are what
+is built).
 
 A time step with particles (examples/sinking_block2d_particles.py; with the refill, examples/rotating_box2d_injection.py):
 
@@ -30,7 +34,7 @@ A thermal step with the temperature on particles (examples/thermal_particles2d.p
 
 (JustPIC's subgrid_diffusion_centroid! / subgrid_diffusion!, operators 10 and 11 of include/jrx.h; tests/_particles2d_subgrid.py restates them).
 
-Layout: every per-particle array is (nx, ny, max_xcell) column-major, the slot index slowest; an inactive slot holds 0 in every array.
+Layout: every per-particle array is (nx, ny[, nz], max_xcell) column-major, the slot index slowest; an inactive slot holds 0 in every array.
 """
 from __future__ import annotations
 
@@ -52,7 +56,7 @@ INJECT_LOCS = {"vertex": _lib.INJECT_VERTEX, "center": _lib.INJECT_CENTRE, "dono
 
 
 def _not_built(what):
-    raise NotImplementedError(f"{what}: not built (particles are 2D, uniform grid, one block; marker chains and StressParticles are not provided)")
+    raise NotImplementedError(f"{what}: not built (particles are built for uniform grids and one block, the core chain in 2D and 3D, everything else in 2D; marker chains and StressParticles are not provided)")
 
 
 def inject_particles_phase_(particles=None, pPhases=None, args=(), fields=(), *, loc=None, min_xcell=None, handle=None):
@@ -142,36 +146,49 @@ def _lattice(nxcell):
     return nsx, nxcell // nsx
 
 
+def _lattice3(nxcell):
+    """(nsx, nsy, nsz) of the 3D seeding lattice: nsx the largest divisor of nxcell with nsx^3 <= nxcell, nsy the largest divisor of the rest with nsy^2 <= rest"""
+    nsx = max(d for d in range(1, nxcell + 1) if nxcell % d == 0 and d * d * d <= nxcell)
+    rest = nxcell // nsx
+    nsy = max(d for d in range(1, rest + 1) if rest % d == 0 and d * d <= rest)
+    return nsx, nsy, rest // nsy
+
+
 def _izeros(shape, device):
     t = torch.zeros(tuple(shape)[::-1], dtype=torch.int32, device=device)
     return t.permute(*range(len(shape) - 1, -1, -1))
 
 
 class Particles:
-    """What init_particles returns: coords = (px, py) and index (the int32 mask `active`), each (nx, ny, max_xcell); the grid (x0, y0, dx, dy and the inverses
-    formed once here); a second set of buffers for the out-of-place move, and one twin per particle field of init_cell_arrays."""
+    """What init_particles returns: coords = (px, py[, pz]) and index (the int32 mask `active`), each (nx, ny[, nz], max_xcell); the grid (x0, y0[, z0], dx, dy[, dz]
+    and the inverses formed once here); a second set of buffers for the out-of-place move, and one twin per particle field of init_cell_arrays.  3D particles also
+    own the byte buffer of the move (one byte per slot: include/jrx.h, jrx_particles3d_move)."""
 
-    def __init__(self, device, ni, max_xcell, min_xcell, nxcell, x0, y0, dx, dy):
+    def __init__(self, device, ni, max_xcell, min_xcell, nxcell, origin, spacing):
         self.ni, self.max_xcell, self.min_xcell, self.nxcell = tuple(ni), int(max_xcell), int(min_xcell), int(nxcell)
-        self.x0, self.y0, self.dx, self.dy = float(x0), float(y0), float(dx), float(dy)
-        self._dx, self._dy = 1.0 / self.dx, 1.0 / self.dy
-        self.di = (self.dx, self.dy)
+        nd = len(self.ni)
+        self.origin, self.di = tuple(float(v) for v in origin), tuple(float(v) for v in spacing)
+        self._di = tuple(1.0 / v for v in self.di)
+        for axis, c in enumerate("xyz"[:nd]):
+            setattr(self, c + "0", self.origin[axis]), setattr(self, "d" + c, self.di[axis]), setattr(self, "_d" + c, self._di[axis])
         shape = self.ni + (self.max_xcell,)
         self.device = device
-        self.coords = (fzeros(shape, device), fzeros(shape, device))
+        self.coords = tuple(fzeros(shape, device) for _ in range(nd))
         self.index = _izeros(shape, device)
-        self._coords2 = (fzeros(shape, device), fzeros(shape, device))
+        self._coords2 = tuple(fzeros(shape, device) for _ in range(nd))
         self._index2 = _izeros(shape, device)
         self._twins = {}          # id(particle field) -> (field, twin)
+        self._work = torch.zeros(int(np.prod(shape)), dtype=torch.uint8, device=device) if nd == 3 else None
 
     @property
     def shape(self):
         return self.ni + (self.max_xcell,)
 
     def _struct(self, second=False):
-        px, py = self._coords2 if second else self.coords
+        coords = self._coords2 if second else self.coords
         idx = self._index2 if second else self.index
-        return _lib.Particles2D(ptr(px), ptr(py), idx.data_ptr(), self.ni[0], self.ni[1], self.max_xcell, self.x0, self.y0, self.dx, self.dy, self._dx, self._dy)
+        cls = _lib.Particles2D if len(self.ni) == 2 else _lib.Particles3D
+        return cls(*(ptr(c) for c in coords), idx.data_ptr(), *self.ni, self.max_xcell, *self.origin, *self.di, *self._di)
 
     def _swap(self, fields):
         self.coords, self._coords2 = self._coords2, self.coords
@@ -181,18 +198,19 @@ class Particles:
             f.data, twin.data = twin.data, f.data
 
 
-def _uniform_vertices(xvi, ni, fn):
+def _uniform_vertices(xvi, ni, fn, dims=(2,)):
     if hasattr(xvi, "xvi"):          # a Geometry
         if getattr(xvi, "nonuniform", False):
             raise NotImplementedError(f"{fn}: a non-uniform Geometry (particles are built for uniform grids)")
         xvi = xvi.xvi
     ni = tuple(int(n) for n in ni)
-    if len(ni) != 2 or len(xvi) != 2:
-        raise NotImplementedError(f"{fn}: {len(ni)}D extents with {len(xvi)} vertex vectors (particles are built in 2D)")
+    if len(ni) not in dims or len(xvi) != len(ni):
+        raise NotImplementedError(f"{fn}: {len(ni)}D extents with {len(xvi)} vertex vectors (this form, (xvi, ni), is built in 2D; 3D particles come from "
+                                  f"{fn}(backend, nxcell, max_xcell, min_xcell, *grid.xi_vel))")
     if any(n < 1 for n in ni):
         raise ValueError(f"{fn}: ni = {ni}")
     xv = [np.ascontiguousarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=np.float64) for x in xvi]
-    for d in range(2):
+    for d in range(len(ni)):
         if xv[d].shape != (ni[d] + 1,):
             raise ValueError(f"{fn}: dimension {d + 1} has {ni[d]} cells, xvi[{d}] has {xv[d].size} entries (expected {ni[d] + 1})")
         steps = np.diff(xv[d])
@@ -201,41 +219,47 @@ def _uniform_vertices(xvi, ni, fn):
     return ni, xv
 
 
-def init_particles(backend_tag, nxcell, max_xcell, min_xcell, xvi, ni, *, rng=None):
-    """init_particles(backend, nxcell, max_xcell, min_xcell, xvi, ni): nxcell particles per cell in slots 0 .. nxcell - 1 on a regular nsx x nsy sub-cell lattice
-    (nsx the largest divisor of nxcell not above its square root): slot s = a + nsx b at (x0 + i dx) + (a + u) dx / nsx, (y0 + j dy) + (b + v) dy / nsy, u = v = 0.5.
-    With rng, a NumPy Generator, u = 0.05 + 0.9 r with r = rng.random((nx, ny, nxcell)), drawn for x first and then for y: jittered inside the sub-cell.  Built on the
-    host, so the same arguments give the same particles.  xvi: the two vertex vectors, or a Geometry."""
+def init_particles(backend_tag, nxcell, max_xcell, min_xcell, *grids, rng=None):
+    """init_particles(backend, nxcell, max_xcell, min_xcell, grid.xi_vel...) -- the reference's call shape, two velocity grids for 2D and three for 3D: the vertex
+    vector of axis d is xi_vel[d][d] -- or, in 2D, init_particles(backend, nxcell, max_xcell, min_xcell, xvi, ni) with the two vertex vectors (or a Geometry) and
+    the extents; both give the same particles.  nxcell particles per cell in slots 0 .. nxcell - 1 on a regular sub-cell lattice.  2D: nsx x nsy, nsx the largest
+    divisor of nxcell not above its square root, slot s = a + nsx b at (x0 + i dx) + (a + u) dx / nsx, (y0 + j dy) + (b + v) dy / nsy.  3D: nsx x nsy x nsz, nsx the
+    largest divisor with nsx^3 <= nxcell, nsy the largest divisor of the rest r = nxcell / nsx with nsy^2 <= r, nsz = r / nsy (8: 2 2 2; 20: 2 2 5), slot
+    s = a + nsx (b + nsy c).  u = v = w = 0.5; with rng, a NumPy Generator, 0.05 + 0.9 r with r = rng.random(ni + (nxcell,)), drawn for x, then y, then z:
+    jittered inside the sub-cell.  Built on the host, so the same arguments give the same particles."""
     fn = "init_particles"
-    ni, xv = _uniform_vertices(xvi, ni, fn)
+    if len(grids) == 2 and (hasattr(grids[0], "xvi") or all(isinstance(n, (int, np.integer)) for n in grids[1])):
+        ni, xv = _uniform_vertices(grids[0], grids[1], fn)
+    elif len(grids) in (2, 3) and all(not hasattr(g, "xvi") and len(g) == len(grids) for g in grids):
+        xvi = tuple(grids[d][d] for d in range(len(grids)))
+        ni, xv = _uniform_vertices(xvi, tuple(len(x) - 1 for x in xvi), fn, dims=(2, 3))
+    else:
+        raise TypeError(f"{fn}: expected (xvi, ni) or the {len(grids)} velocity grids grid.xi_vel..., each with {len(grids)} coordinate vectors")
+    nd = len(ni)
     nxcell, max_xcell, min_xcell = int(nxcell), int(max_xcell), int(min_xcell)
     if not 0 <= min_xcell <= nxcell <= max_xcell or nxcell < 1:
         raise ValueError(f"{fn}: need 0 <= min_xcell <= nxcell <= max_xcell and nxcell >= 1, got nxcell = {nxcell}, max_xcell = {max_xcell}, min_xcell = {min_xcell}")
-    nx, ny = ni
-    if nx * ny * max_xcell >= 2 ** 31:
-        raise ValueError(f"{fn}: {nx} x {ny} x {max_xcell} slots: 2^31 or more (32-bit offsets)")
+    if int(np.prod(ni, dtype=object)) * max_xcell >= 2 ** 31:
+        raise ValueError(f"{fn}: {' x '.join(str(n) for n in ni)} x {max_xcell} slots: 2^31 or more (32-bit offsets)")
     dev = device_of(backend_tag)
-    x0, y0, dx, dy = float(xv[0][0]), float(xv[1][0]), float(xv[0][1] - xv[0][0]), float(xv[1][1] - xv[1][0])
-    nsx, nsy = _lattice(nxcell)
+    origin, spacing = [float(x[0]) for x in xv], [float(x[1] - x[0]) for x in xv]
+    ns = _lattice(nxcell) if nd == 2 else _lattice3(nxcell)
     s = np.arange(nxcell)
-    a, b = (s % nsx).astype(np.float64)[None, None, :], (s // nsx).astype(np.float64)[None, None, :]
-    if rng is None:
-        u = v = np.full((nx, ny, nxcell), 0.5)
-    else:
-        u = 0.05 + 0.9 * rng.random((nx, ny, nxcell))
-        v = 0.05 + 0.9 * rng.random((nx, ny, nxcell))
-    px, py = np.zeros((nx, ny, max_xcell)), np.zeros((nx, ny, max_xcell))
-    px[:, :, :nxcell] = (x0 + np.arange(nx, dtype=np.float64) * dx)[:, None, None] + (a + u) * (dx / nsx)
-    py[:, :, :nxcell] = (y0 + np.arange(ny, dtype=np.float64) * dy)[None, :, None] + (b + v) * (dy / nsy)
-    p = Particles(dev, ni, max_xcell, min_xcell, nxcell, x0, y0, dx, dy)
-    p.coords[0].copy_(from_numpy(px, dev))
-    p.coords[1].copy_(from_numpy(py, dev))
-    p.index[:, :, :nxcell] = 1
+    sub = [s % ns[0], s // ns[0]] if nd == 2 else [s % ns[0], (s // ns[0]) % ns[1], s // (ns[0] * ns[1])]
+    shape = ni + (nxcell,)
+    jitter = [np.full(shape, 0.5) if rng is None else 0.05 + 0.9 * rng.random(shape) for _ in range(nd)]
+    p = Particles(dev, ni, max_xcell, min_xcell, nxcell, origin, spacing)
+    for d in range(nd):
+        cell = (origin[d] + np.arange(ni[d], dtype=np.float64) * spacing[d]).reshape([-1 if q == d else 1 for q in range(nd + 1)])
+        c = np.zeros(ni + (max_xcell,))
+        c[..., :nxcell] = cell + (sub[d].astype(np.float64).reshape((1,) * nd + (-1,)) + jitter[d]) * (spacing[d] / ns[d])
+        p.coords[d].copy_(from_numpy(c, dev))
+    p.index[..., :nxcell] = 1
     return p
 
 
 def init_cell_arrays(particles, n):
-    """init_cell_arrays(particles, Val(n)): n particle fields (nx, ny, max_xcell), zero; each gets a twin for the out-of-place move"""
+    """init_cell_arrays(particles, Val(n)): n particle fields (nx, ny[, nz], max_xcell), zero; each gets a twin for the out-of-place move"""
     n = int(n)
     if not 1 <= n <= _lib.MAXPHASE:
         raise ValueError(f"init_cell_arrays: {n} particle fields (1 .. {_lib.MAXPHASE})")
@@ -247,11 +271,13 @@ def init_cell_arrays(particles, n):
     return tuple(out)
 
 
-def _check_particles(particles, fn):
+def _check_particles(particles, fn, dims=(2,)):
+    """dims: the dimensions this operator is built in; 3D particles are refused by name before anything reaches the device"""
     if not isinstance(particles, Particles):
         raise TypeError(f"{fn}: particles must come from init_particles, got {type(particles).__name__}")
-    if len(particles.ni) != 2:
-        raise NotImplementedError(f"{fn}: {len(particles.ni)}D particles (2D is built)")
+    if len(particles.ni) not in dims:
+        raise NotImplementedError(f"{fn}: {len(particles.ni)}D particles ({' and '.join(f'{d}D' for d in dims)} {'are' if len(dims) > 1 else 'is'} built"
+                                  f"{'; in 3D: advect, move, the four interpolations and the phase ratios' if len(particles.ni) == 3 else ''})")
 
 
 def _check_field(particles, f, name, fn):
@@ -268,32 +294,34 @@ def _check_grid(particles, grid, fn):
         return
     if getattr(grid, "nonuniform", False):
         raise NotImplementedError(f"{fn}: a non-uniform Geometry (particles are built for uniform grids)")
-    if len(grid.ni) != 2:
-        raise NotImplementedError(f"{fn}: a {len(grid.ni)}D grid (particles are built in 2D)")
+    if len(grid.ni) != len(particles.ni):
+        raise NotImplementedError(f"{fn}: a {len(grid.ni)}D grid " + ("(particles are built in 2D)" if len(particles.ni) == 2 else "with 3D particles"))
     if tuple(grid.ni) != particles.ni:
         raise ValueError(f"{fn}: the grid has {tuple(grid.ni)} cells, the particles {particles.ni}")
 
 
 def advection_(particles, method, V, dt, *, grid=None, handle=None):
-    """advection!(particles, RungeKutta2(), @velocity(stokes), dt): every particle by the midpoint rule through the bilinear interpolant of V = stokes.V (or the
-    tuple (Vx, Vy), ghost layers included), in place (include/jrx.h, jrx_particles2d_advect_rk2).  Follow it with move_particles_."""
+    """advection!(particles, RungeKutta2(), @velocity(stokes), dt): every particle by the midpoint rule through the bilinear (3D: trilinear) interpolant of
+    V = stokes.V (or the tuple of its components, ghost layers included), in place (include/jrx.h, jrx_particles2d_advect_rk2 / jrx_particles3d_advect_rk2).
+    Follow it with move_particles_."""
     fn = "advection!"
-    _check_particles(particles, fn)
+    _check_particles(particles, fn, (2, 3))
     if not isinstance(method, RungeKutta2):
         raise NotImplementedError(f"{fn}: {type(method).__name__} (RungeKutta2() is built)")
     _check_grid(particles, grid, fn)
+    nd = len(particles.ni)
     Vs = tuple(getattr(V, k) for k in ("Vx", "Vy", "Vz") if getattr(V, k, None) is not None) if hasattr(V, "Vx") else tuple(V)
-    if len(Vs) != 2 or any(v.dim() != 2 for v in Vs):
-        raise NotImplementedError(f"{fn}: V has {len(Vs)} components of {[v.dim() for v in Vs]} dimensions (2D is built)")
-    nx, ny = particles.ni
-    if tuple(tuple(v.shape) for v in Vs) != ((nx + 1, ny + 2), (nx + 2, ny + 1)):
-        raise ValueError(f"{fn}: V is {', '.join(str(tuple(v.shape)) for v in Vs)}; {particles.ni} cells need {(nx + 1, ny + 2)}, {(nx + 2, ny + 1)}")
+    if len(Vs) != nd or any(v.dim() != nd for v in Vs):
+        raise NotImplementedError(f"{fn}: V has {len(Vs)} components of {[v.dim() for v in Vs]} dimensions ({nd}D particles need {nd} components of {nd} dimensions)")
+    want = tuple(tuple(n + (1 if a == d else 2) for a, n in enumerate(particles.ni)) for d in range(nd))
+    if tuple(tuple(v.shape) for v in Vs) != want:
+        raise ValueError(f"{fn}: V is {', '.join(str(tuple(v.shape)) for v in Vs)}; {particles.ni} cells need {', '.join(str(w) for w in want)}")
     h = _h(particles.coords[0], handle)
-    for k, v in zip(("V.Vx", "V.Vy"), Vs):
+    for k, v in zip(("V.Vx", "V.Vy", "V.Vz"), Vs):
         if v.device != particles.coords[0].device:
             raise ValueError(f"{fn}: {k} is on {v.device}, the particles on {particles.coords[0].device}")
     s = particles._struct()
-    h.call("jrx_particles2d_advect_rk2", C.byref(s), C.c_void_p(ptr(Vs[0])), C.c_void_p(ptr(Vs[1])), C.c_double(float(dt)))
+    h.call(f"jrx_particles{nd}d_advect_rk2", C.byref(s), *(C.c_void_p(ptr(v)) for v in Vs), C.c_double(float(dt)))
 
 
 def move_particles_(particles, particle_args=(), *, handle=None):
@@ -302,7 +330,7 @@ def move_particles_(particles, particle_args=(), *, handle=None):
     counters as a dict.  RuntimeError naming the counter when particles were lost to a full bucket (n_overflow) or to a jump of more than one cell (n_far): the state
     is then valid, without those particles.  Particles that left the grid (n_outside) are dropped silently, as the count says."""
     fn = "move_particles!"
-    _check_particles(particles, fn)
+    _check_particles(particles, fn, (2, 3))
     args = tuple(particle_args)
     if len(args) > _lib.MAXPHASE:
         raise ValueError(f"{fn}: {len(args)} particle fields (0 .. {_lib.MAXPHASE})")
@@ -318,7 +346,10 @@ def move_particles_(particles, particle_args=(), *, handle=None):
     a_src = (C.c_void_p * max(n, 1))(*(ptr(f) for f in args))
     a_dst = (C.c_void_p * max(n, 1))(*(ptr(particles._twins[id(f)][1]) for f in args))
     counts = (C.c_int64 * 5)()
-    h.call("jrx_particles2d_move", C.byref(src), C.byref(dst), a_src, a_dst, C.c_int32(n), counts)
+    if len(particles.ni) == 2:
+        h.call("jrx_particles2d_move", C.byref(src), C.byref(dst), a_src, a_dst, C.c_int32(n), counts)
+    else:          # the particles' byte buffer: the library stores every slot's owner in it (tuning key particles3d_move_codes = 0: the direct form)
+        h.call("jrx_particles3d_move", C.byref(src), C.byref(dst), a_src, a_dst, C.c_int32(n), C.c_void_p(particles._work.data_ptr()), counts)
     particles._swap(args)
     out = dict(zip(COUNTS, (int(c) for c in counts)))
     for k in ("n_far", "n_overflow"):
@@ -330,50 +361,45 @@ def move_particles_(particles, particle_args=(), *, handle=None):
     return out
 
 
-def grid2particle_(pF, F, particles, *, handle=None):
-    """grid2particle!(pF, xvi, F, particles): the vertex field F (nx+1, ny+1) to the particles, bilinear in the cell of each particle's bucket"""
-    fn = "grid2particle!"
-    _check_particles(particles, fn)
+def _vertex_op(fn, entry, first, second, F, pF, particles, handle):
+    _check_particles(particles, fn, (2, 3))
     _check_field(particles, pF, "pF", fn)
-    nx, ny = particles.ni
-    if not isinstance(F, torch.Tensor) or tuple(F.shape) != (nx + 1, ny + 1):
-        raise ValueError(f"{fn}: F is {tuple(F.shape) if isinstance(F, torch.Tensor) else type(F).__name__}; {particles.ni} cells need the vertex field {(nx + 1, ny + 1)}")
+    want = tuple(n + 1 for n in particles.ni)
+    if not isinstance(F, torch.Tensor) or tuple(F.shape) != want:
+        raise ValueError(f"{fn}: F is {tuple(F.shape) if isinstance(F, torch.Tensor) else type(F).__name__}; {particles.ni} cells need the vertex field {want}")
     h = _h(pF, handle)
     if F.device != pF.device:
         raise ValueError(f"{fn}: F is on {F.device}, pF on {pF.device}")
     s = particles._struct()
-    h.call("jrx_particles2d_grid2particle", C.c_void_p(ptr(pF)), C.c_void_p(ptr(F)), C.byref(s))
+    h.call(f"jrx_particles{len(particles.ni)}d_{entry}", C.c_void_p(ptr(first)), C.c_void_p(ptr(second)), C.byref(s))
+
+
+def grid2particle_(pF, F, particles, *, handle=None):
+    """grid2particle!(pF, xvi, F, particles): the vertex field F (nx+1, ny+1[, nz+1]) to the particles, bilinear (trilinear) in the cell of each particle's bucket"""
+    _vertex_op("grid2particle!", "grid2particle", pF, F, F, pF, particles, handle)
 
 
 def particle2grid_(F, pF, particles, *, handle=None):
-    """particle2grid!(F, pF, xvi, particles): the particle field pF to the vertex field F (nx+1, ny+1), weighted by the bilinear distance of each particle of the
-    up to four cells around a vertex; a vertex without a particle around it keeps its value"""
-    fn = "particle2grid!"
-    _check_particles(particles, fn)
-    _check_field(particles, pF, "pF", fn)
-    nx, ny = particles.ni
-    if not isinstance(F, torch.Tensor) or tuple(F.shape) != (nx + 1, ny + 1):
-        raise ValueError(f"{fn}: F is {tuple(F.shape) if isinstance(F, torch.Tensor) else type(F).__name__}; {particles.ni} cells need the vertex field {(nx + 1, ny + 1)}")
-    h = _h(pF, handle)
-    if F.device != pF.device:
-        raise ValueError(f"{fn}: F is on {F.device}, pF on {pF.device}")
-    s = particles._struct()
-    h.call("jrx_particles2d_particle2grid", C.c_void_p(ptr(F)), C.c_void_p(ptr(pF)), C.byref(s))
+    """particle2grid!(F, pF, xvi, particles): the particle field pF to the vertex field F (nx+1, ny+1[, nz+1]), weighted by the bilinear (trilinear) distance of
+    each particle of the up to four (eight) cells around a vertex; a vertex without a particle around it keeps its value"""
+    _vertex_op("particle2grid!", "particle2grid", F, pF, F, pF, particles, handle)
 
 
 def update_phase_ratios_(phase_ratios, particles, pPhases, *, handle=None):
-    """update_phase_ratios!(phase_ratios, particles, pPhases): center, vertex, Vx and Vy of phase_ratios from the phases 1.0 .. N of the particles, one launch.
-    Returns n_empty, the number of (node, member) pairs no particle weight reached (left unchanged)."""
+    """update_phase_ratios!(phase_ratios, particles, pPhases): center, vertex, Vx and Vy (3D: and Vz, yz, xz, xy) of phase_ratios from the phases 1.0 .. N of the
+    particles, one launch.  Returns n_empty, the number of (node, member) pairs no particle weight reached (left unchanged)."""
     fn = "update_phase_ratios!"
-    _check_particles(particles, fn)
+    _check_particles(particles, fn, (2, 3))
     _check_field(particles, pPhases, "pPhases", fn)
     N = int(phase_ratios.nphases)
     if not 1 <= N <= _lib.MAXPHASE:
         raise ValueError(f"{fn}: {N} phases (1 .. {_lib.MAXPHASE})")
-    nx, ny = particles.ni
-    if phase_ratios.center.dim() != 3:
-        raise NotImplementedError(f"{fn}: a {phase_ratios.center.dim() - 1}D PhaseRatios (2D is built)")
-    want = dict(center=(N, nx, ny), vertex=(N, nx + 1, ny + 1), Vx=(N, nx + 1, ny), Vy=(N, nx, ny + 1))
+    nd = len(particles.ni)
+    if phase_ratios.center.dim() != nd + 1:
+        raise NotImplementedError(f"{fn}: a {phase_ratios.center.dim() - 1}D PhaseRatios " + ("(2D is built)" if nd == 2 else "with 3D particles"))
+    stag = dict(center=(0, 0), vertex=(1, 1), Vx=(1, 0), Vy=(0, 1)) if nd == 2 else \
+        dict(center=(0, 0, 0), vertex=(1, 1, 1), Vx=(1, 0, 0), Vy=(0, 1, 0), Vz=(0, 0, 1), yz=(0, 1, 1), xz=(1, 0, 1), xy=(1, 1, 0))
+    want = {k: (N,) + tuple(n + s for n, s in zip(particles.ni, st)) for k, st in stag.items()}
     for k, shp in want.items():
         m = getattr(phase_ratios, k, None)
         if m is None or tuple(m.shape) != shp:
@@ -383,8 +409,11 @@ def update_phase_ratios_(phase_ratios, particles, pPhases, *, handle=None):
         raise ValueError(f"{fn}: phase_ratios is on {phase_ratios.center.device}, pPhases on {pPhases.device}")
     s = particles._struct()
     n_empty = C.c_int64()
-    h.call("jrx_particles2d_phase_ratios", *(C.c_void_p(ptr(getattr(phase_ratios, k))) for k in want), C.c_void_p(ptr(pPhases)), C.c_int32(N), C.byref(s),
-           C.byref(n_empty))
+    if nd == 2:
+        h.call("jrx_particles2d_phase_ratios", *(C.c_void_p(ptr(getattr(phase_ratios, k))) for k in want), C.c_void_p(ptr(pPhases)), C.c_int32(N), C.byref(s),
+               C.byref(n_empty))
+    else:
+        h.call("jrx_particles3d_phase_ratios", _vec([getattr(phase_ratios, k) for k in want]), C.c_void_p(ptr(pPhases)), C.c_int32(N), C.byref(s), C.byref(n_empty))
     return int(n_empty.value)
 
 
@@ -420,29 +449,29 @@ def _vec(ts):
 
 
 def centroid2particle_(pF, F, particles, *, handle=None):
-    """centroid2particle!(pF, F, particles): the centre field F (nx, ny) to the particles, bilinear between the four centres around each particle's coordinate;
-    a particle in the outer half cells extrapolates from the outermost pair.  Needs nx >= 2 and ny >= 2 (include/jrx.h, operator 6)."""
+    """centroid2particle!(pF, F, particles): the centre field F (nx, ny[, nz]) to the particles, bilinear (trilinear) between the four (eight) centres around each
+    particle's coordinate; a particle in the outer half cells extrapolates from the outermost pair.  Needs every extent >= 2 (include/jrx.h, operator 6)."""
     fn = "centroid2particle!"
-    _check_particles(particles, fn)
+    _check_particles(particles, fn, (2, 3))
     _check_field(particles, pF, "pF", fn)
     _check_grid_field(particles, F, "F", particles.ni, "centre", fn)
     if min(particles.ni) < 2:
-        raise ValueError(f"{fn}: {particles.ni} cells (interpolation between centres needs nx >= 2 and ny >= 2)")
+        raise ValueError(f"{fn}: {particles.ni} cells (interpolation between centres needs {'nx >= 2 and ny >= 2' if len(particles.ni) == 2 else 'every extent >= 2'})")
     h = _h(pF, handle)
     s = particles._struct()
-    h.call("jrx_particles2d_centroid2particle", C.c_void_p(ptr(pF)), C.c_void_p(ptr(F)), C.byref(s))
+    h.call(f"jrx_particles{len(particles.ni)}d_centroid2particle", C.c_void_p(ptr(pF)), C.c_void_p(ptr(F)), C.byref(s))
 
 
 def particle2centroid_(F, pF, particles, *, handle=None):
-    """particle2centroid!(F, pF, particles): the particle field pF to the centre field F (nx, ny), each cell from its own bucket weighted by the bilinear
-    distance to the centre; a cell without a particle keeps its value (operator 7)"""
+    """particle2centroid!(F, pF, particles): the particle field pF to the centre field F (nx, ny[, nz]), each cell from its own bucket weighted by the bilinear
+    (trilinear) distance to the centre; a cell without a particle keeps its value (operator 7)"""
     fn = "particle2centroid!"
-    _check_particles(particles, fn)
+    _check_particles(particles, fn, (2, 3))
     _check_field(particles, pF, "pF", fn)
     _check_grid_field(particles, F, "F", particles.ni, "centre", fn)
     h = _h(pF, handle)
     s = particles._struct()
-    h.call("jrx_particles2d_particle2centroid", C.c_void_p(ptr(F)), C.c_void_p(ptr(pF)), C.byref(s))
+    h.call(f"jrx_particles{len(particles.ni)}d_particle2centroid", C.c_void_p(ptr(F)), C.c_void_p(ptr(pF)), C.byref(s))
 
 
 def _stress_fields(particles, pτ, fn):
