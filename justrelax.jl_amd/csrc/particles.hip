@@ -18,6 +18,11 @@
 // An index derived from a coordinate is range-checked on the double before the conversion to int: a NaN or infinite coordinate never reaches a conversion.
 // Addressing: 32-bit element offsets (nx ny max_xcell < 2^31, checked).
 //
+// Launches: 64 x 4 tiles over the box of cells (nx, ny) or of nodes (nx + 1, ny + 1) a kernel covers, in a one-dimensional grid; the kernel hands the x extent
+// of its box to pt_index, which derives the block count along x from it as pt_blocks does on the host.  The geometry struct carries no launch parameter.
+// Host side: the checks shared with particles3d.hip are in particles_common.hpp (the particle set, the overlap rules, move, phase ratios, the counter read-back);
+// here are the conversion of jrx_particles2d (pt_geom), one launcher (pt_launch), one path for the four field operators (pt_field_op) and the entry points.
+//
 // k_pt_phase_ratios<N>: the phase count is a template argument (1 .. JRX_MAXPHASE) and the phase index of a particle is applied by an unrolled select, so the
 // 4 N + 4 accumulators of a node stay in registers (a run-time index into them would put them in scratch).
 #include "particles_common.hpp"          // the helpers shared with particles3d.hip
@@ -31,11 +36,16 @@ struct PtGeom {                                       // jrx_particles2d by valu
     double *px, *py;
     int *active;
     double x0, y0, dx, dy, idx, idy;
-    int nx, ny, mx, nbx;                              // mx = max_xcell; nbx = blocks along x of the launch
+    int nx, ny, mx;                                   // mx = max_xcell
 };
 
-__device__ __forceinline__ void pt_index(int nbx, int &i, int &j)
+// tiles over an (ex, ey) box, row after row of tiles in a one-dimensional grid (no 65535 limit along y); pt_index is its inverse
+unsigned pt_blocks(int ex, int ey) { return (unsigned)((i64)((ex + kPtTX - 1) / kPtTX) * ((ey + kPtTY - 1) / kPtTY)); }
+
+// the cell or node (i, j) of a thread in a launch over a box ex wide: a cell kernel passes nx, a node kernel nx + 1
+__device__ __forceinline__ void pt_index(int ex, int &i, int &j)
 {
+    const int nbx = (ex + kPtTX - 1) / kPtTX;
     i = ((int)blockIdx.x % nbx) * kPtTX + (int)threadIdx.x;
     j = ((int)blockIdx.x / nbx) * kPtTY + (int)threadIdx.y;
 }
@@ -81,7 +91,7 @@ __global__ __launch_bounds__(256) void k_pt_advect_rk2(const PtAdvArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx, i, j);
     if (i >= g.nx || j >= g.ny) return;
     const int nc = g.nx * g.ny;
     int lin = j * g.nx + i;
@@ -131,7 +141,7 @@ __global__ __launch_bounds__(256) void k_pt_move(const PtMoveArgs a)
 {
     const PtGeom &g = a.src;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx, i, j);
     const bool live = i < g.nx && j < g.ny;
     const int nc = g.nx * g.ny, mx = g.mx;
     int n = 0, n_before = 0, n_outside = 0, n_far = 0, n_overflow = 0;
@@ -187,17 +197,18 @@ __global__ __launch_bounds__(256) void k_pt_move(const PtMoveArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------ 3. grid2particle
-struct PtG2PArgs {
+struct PtFieldArgs {          // operators 3, 4, 6, 7: a particle field and a grid field; which is written depends on the operator
     PtGeom g;
     double *pF;
-    const double *F;          // (nx + 1, ny + 1)
+    double *F;                // vertices (nx + 1, ny + 1) for operators 3 and 4, centres (nx, ny) for 6 and 7
+    double ox, oy;            // origin of the centre nodes (x0 + 0.5 dx, y0 + 0.5 dy)
 };
 
-__global__ __launch_bounds__(256) void k_pt_grid2particle(const PtG2PArgs a)
+__global__ __launch_bounds__(256) void k_pt_grid2particle(const PtFieldArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx, i, j);
     if (i >= g.nx || j >= g.ny) return;
     const int nc = g.nx * g.ny;
     const double *f = a.F + j * (g.nx + 1) + i;
@@ -215,17 +226,11 @@ __global__ __launch_bounds__(256) void k_pt_grid2particle(const PtG2PArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------ 4. particle2grid
-struct PtP2GArgs {
-    PtGeom g;
-    double *F;                // (nx + 1, ny + 1)
-    const double *pF;
-};
-
-__global__ __launch_bounds__(256) void k_pt_particle2grid(const PtP2GArgs a)
+__global__ __launch_bounds__(256) void k_pt_particle2grid(const PtFieldArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx + 1, i, j);
     if (i > g.nx || j > g.ny) return;
     const int nc = g.nx * g.ny;
     const double xv = g.x0 + (double)i * g.dx, yv = g.y0 + (double)j * g.dy;
@@ -278,7 +283,7 @@ __global__ __launch_bounds__(256) void k_pt_phase_ratios(const PtPrArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx + 1, i, j);
     const bool live = i <= g.nx && j <= g.ny;
     int empty = 0;
     if (live) {
@@ -322,18 +327,11 @@ __global__ __launch_bounds__(256) void k_pt_phase_ratios(const PtPrArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------ 6. centroid2particle
-struct PtC2PArgs {
-    PtGeom g;
-    double *pF;
-    const double *F;          // (nx, ny)
-    double ox, oy;            // origin of the centre nodes (x0 + 0.5 dx, y0 + 0.5 dy)
-};
-
-__global__ __launch_bounds__(256) void k_pt_centroid2particle(const PtC2PArgs a)
+__global__ __launch_bounds__(256) void k_pt_centroid2particle(const PtFieldArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx, i, j);
     if (i >= g.nx || j >= g.ny) return;
     const int nc = g.nx * g.ny;
     int lin = j * g.nx + i;
@@ -348,11 +346,11 @@ __global__ __launch_bounds__(256) void k_pt_centroid2particle(const PtC2PArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------ 7. particle2centroid
-__global__ __launch_bounds__(256) void k_pt_particle2centroid(const PtP2GArgs a)          // F is (nx, ny) here
+__global__ __launch_bounds__(256) void k_pt_particle2centroid(const PtFieldArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx, i, j);
     if (i >= g.nx || j >= g.ny) return;
     const int nc = g.nx * g.ny;
     const double xc = g.x0 + ((double)i + 0.5) * g.dx, yc = g.y0 + ((double)j + 0.5) * g.dy;
@@ -380,7 +378,7 @@ __global__ __launch_bounds__(256) void k_pt_rotate(const PtRotArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx, i, j);
     if (i >= g.nx || j >= g.ny) return;
     const int nc = g.nx * g.ny;
     int lin = j * g.nx + i;
@@ -401,7 +399,7 @@ __global__ __launch_bounds__(256) void k_pt_rotate_stress(const PtRotArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx, i, j);
     if (i >= g.nx || j >= g.ny) return;
     const int nc = g.nx * g.ny;
     const double *fs = a.txy + j * (g.nx + 1) + i, *fw = a.wxy + j * (g.nx + 1) + i;
@@ -446,7 +444,7 @@ __global__ __launch_bounds__(256) void k_pt_stress2grid(const PtS2GArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx + 1, i, j);
     if (i > g.nx || j > g.ny) return;
     const int nc = g.nx * g.ny;
     const double xv = g.x0 + (double)i * g.dx, yv = g.y0 + (double)j * g.dy;
@@ -511,7 +509,7 @@ __global__ __launch_bounds__(256) void k_pt_sg_copy(const PtSgArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx, i, j);
     if (i >= g.nx || j >= g.ny) return;
     const int nc = g.nx * g.ny;
     int lin = j * g.nx + i;
@@ -522,7 +520,7 @@ __global__ __launch_bounds__(256) void k_pt_sg_delta(const PtSgArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx, i, j);
     if (i >= g.nx || j >= g.ny) return;
     const int nc = g.nx * g.ny;
     int lin = j * g.nx + i;
@@ -542,7 +540,7 @@ __global__ __launch_bounds__(256) void k_pt_sg_delta(const PtSgArgs a)
 __global__ __launch_bounds__(256) void k_pt_sg_remainder(const PtSgArgs a, int ex, int ey)
 {
     int i, j;
-    pt_index(a.g.nbx, i, j);
+    pt_index(ex, i, j);
     if (i >= ex || j >= ey) return;
     const int k = j * ex + i;
     a.dTs[k] = a.dTg[a.dto + j * a.dtn + i] - a.dTs[k];
@@ -552,7 +550,7 @@ __global__ __launch_bounds__(256) void k_pt_sg_add(const PtSgArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx, i, j);
     if (i >= g.nx || j >= g.ny) return;
     const int nc = g.nx * g.ny;
     int lin = j * g.nx + i;
@@ -568,7 +566,7 @@ __global__ __launch_bounds__(256) void k_pt_sg_cell(const PtSgArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx, i, j);
     if (i >= g.nx || j >= g.ny) return;
     const int nc = g.nx * g.ny;
     double f00 = 0.0, f10 = 0.0, f01 = 0.0, f11 = 0.0;
@@ -614,7 +612,7 @@ __global__ __launch_bounds__(256) void k_pt_sg_vertex(const PtSgArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx + 1, i, j);
     if (i > g.nx || j > g.ny) return;
     const int nc = g.nx * g.ny;
     const double xv = g.x0 + (double)i * g.dx, yv = g.y0 + (double)j * g.dy;
@@ -642,7 +640,7 @@ __global__ __launch_bounds__(256) void k_pt_sg_back(const PtSgArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx, i, j);
     if (i >= g.nx || j >= g.ny) return;
     const int nc = g.nx * g.ny;
     double f00 = 0.0, f10 = 0.0, f01 = 0.0, f11 = 0.0;
@@ -785,7 +783,7 @@ __global__ __launch_bounds__(256) void k_pt_inject(const PtInjArgs a)
 {
     const PtGeom &g = a.g;
     int i, j;
-    pt_index(g.nbx, i, j);
+    pt_index(g.nx, i, j);
     int n = 0, n_before = 0, n_deficient = 0, n_injected = 0, n_no_donor = 0;
     if (i < g.nx && j < g.ny) {
         const int nc = g.nx * g.ny;
@@ -839,58 +837,12 @@ __global__ __launch_bounds__(256) void k_pt_inject(const PtInjArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// the checks every entry point shares; fills g (without nbx)
-jrx_status pt_geom(jrx_handle *h, const char *fn, const char *what, const jrx_particles2d *p, PtGeom *g)
+// jrx_particles2d as the shared checks see it (particles_common.hpp), checked, and by value for the kernels
+jrx_status pt_geom(jrx_handle *h, const char *fn, const char *what, const jrx_particles2d *p, PtSet *S, PtGeom *g)
 {
-    if (!p) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, what);
-    if (!p->px || !p->py || !p->active) return jrx_fail(h, JRX_ERR_ARG, "%s: %s.%s is NULL", fn, what, !p->px ? "px" : (!p->py ? "py" : "active"));
-    if (p->nx < 1 || p->ny < 1) return jrx_fail(h, JRX_ERR_ARG, "%s: %s has %lld x %lld cells", fn, what, (long long)p->nx, (long long)p->ny);
-    if (p->max_xcell < 1) return jrx_fail(h, JRX_ERR_ARG, "%s: %s.max_xcell = %d", fn, what, (int)p->max_xcell);
-    if ((double)p->nx * (double)p->ny * (double)p->max_xcell >= 2147483648.0 || (double)(p->nx + 2) * (double)(p->ny + 2) * JRX_MAXPHASE >= 2147483648.0)
-        return jrx_fail(h, JRX_ERR_ARG, "%s: %s has 2^31 or more slots or nodes (32-bit offsets)", fn, what);
-    if (!std::isfinite(p->x0) || !std::isfinite(p->y0)) return jrx_fail(h, JRX_ERR_ARG, "%s: %s has origin (%g, %g) (must be finite)", fn, what, p->x0, p->y0);
-    if (!(p->dx > 0.0) || !(p->dy > 0.0) || !std::isfinite(p->dx) || !std::isfinite(p->dy))
-        return jrx_fail(h, JRX_ERR_ARG, "%s: %s has spacings (%g, %g) (must be positive and finite: a uniform grid)", fn, what, p->dx, p->dy);
-    if (p->_dx != 1.0 / p->dx || p->_dy != 1.0 / p->dy)
-        return jrx_fail(h, JRX_ERR_ARG, "%s: %s._dx, ._dy = (%g, %g) are not 1 / dx, 1 / dy", fn, what, p->_dx, p->_dy);
-    if (jrx_comm_active(h)) return jrx_fail(h, JRX_ERR_ARG, "%s: a handle with a communicator (particles are built for one block)", fn);
-    *g = PtGeom{p->px, p->py, (int *)p->active, p->x0, p->y0, p->dx, p->dy, p->_dx, p->_dy, (int)p->nx, (int)p->ny, (int)p->max_xcell, 0};
-    return JRX_OK;
-}
-
-i64 pt_slots(const PtGeom &g) { return (i64)g.nx * g.ny * g.mx; }
-
-// an array of `bytes` bytes must not share memory with the coordinates or the mask of g
-jrx_status pt_apart(jrx_handle *h, const char *fn, const char *name, const void *p, i64 bytes, const PtGeom &g)
-{
-    const i64 ns = pt_slots(g);
-    if (pt_overlaps(p, bytes, g.px, 8 * ns) || pt_overlaps(p, bytes, g.py, 8 * ns) || pt_overlaps(p, bytes, g.active, 4 * ns))
-        return jrx_fail(h, JRX_ERR_ARG, "%s: %s overlaps the particle coordinates or the mask", fn, name);
-    return JRX_OK;
-}
-
-// grid of 64 x 4 tiles over an (ex, ey) box
-unsigned pt_blocks(PtGeom &g, int ex, int ey)
-{
-    g.nbx = (ex + kPtTX - 1) / kPtTX;
-    return (unsigned)((i64)g.nbx * ((ey + kPtTY - 1) / kPtTY));
-}
-
-// ---- operators 6 - 9: an entry point checks everything first, then launches one kernel or its chain; the launchers below check nothing
-// every array present; no output shares memory with the particles' own arrays, an input or another output
-jrx_status pt_disjoint(jrx_handle *h, const char *fn, const PtArr *out, int nout, const PtArr *in, int nin, const PtGeom &g)
-{
-    for (int m = 0; m < nout; m++)
-        if (!out[m].p) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, out[m].name);
-    for (int k = 0; k < nin; k++)
-        if (!in[k].p) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, in[k].name);
-    for (int m = 0; m < nout; m++) {
-        JRX_TRY(pt_apart(h, fn, out[m].name, out[m].p, out[m].bytes, g));
-        for (int k = 0; k < nin; k++)
-            if (pt_overlaps(out[m].p, out[m].bytes, in[k].p, in[k].bytes)) return jrx_fail(h, JRX_ERR_ARG, "%s: %s overlaps %s", fn, out[m].name, in[k].name);
-        for (int q = m + 1; q < nout; q++)
-            if (pt_overlaps(out[m].p, out[m].bytes, out[q].p, out[q].bytes)) return jrx_fail(h, JRX_ERR_ARG, "%s: %s and %s overlap", fn, out[m].name, out[q].name);
-    }
+    *S = p ? PtSet{2, {p->px, p->py}, p->active, {p->nx, p->ny}, (int)p->max_xcell, {p->x0, p->y0}, {p->dx, p->dy}, {p->_dx, p->_dy}} : PtSet{};
+    JRX_TRY(pt_check_set(h, fn, what, *S));
+    *g = PtGeom{p->px, p->py, (int *)p->active, p->x0, p->y0, p->dx, p->dy, p->_dx, p->_dy, (int)p->nx, (int)p->ny, (int)p->max_xcell};
     return JRX_OK;
 }
 
@@ -908,46 +860,44 @@ jrx_status pt_method(jrx_handle *h, const char *fn, double dt, int32_t method)
     return JRX_OK;
 }
 
-void pt_launch_g2p(jrx_handle *h, PtGeom g, double *pF, const double *F)
+// One launch, counted: a thread per cell or node of the (ex, ey) box, the box whose x extent the kernel hands to pt_index.  The launchers check nothing: an entry
+// point checks everything first, then launches one kernel or its chain.
+template <typename K, typename... A>
+void pt_launch(jrx_handle *h, K kernel, int ex, int ey, const A &...a)
 {
-    PtG2PArgs a = {g, pF, F};
-    const unsigned nb = pt_blocks(a.g, g.nx, g.ny);
     h->stat_particles_launches++;
-    hipLaunchKernelGGL(k_pt_grid2particle, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+    hipLaunchKernelGGL(kernel, dim3(pt_blocks(ex, ey)), dim3(kPtTX, kPtTY), 0, h->stream, a...);
 }
 
-void pt_launch_p2g(jrx_handle *h, PtGeom g, double *F, const double *pF)
+// operators 3, 4, 6, 7 as one launch over the (nx + e, ny + e) box: e = 0, the cells; e = 1, the vertices of the F that operator 4 writes
+template <typename K>
+void pt_launch_field(jrx_handle *h, K kernel, int e, const PtGeom &g, const double *pF, const double *F)
 {
-    PtP2GArgs a = {g, F, pF};
-    const unsigned nb = pt_blocks(a.g, g.nx + 1, g.ny + 1);
-    h->stat_particles_launches++;
-    hipLaunchKernelGGL(k_pt_particle2grid, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+    pt_launch(h, kernel, g.nx + e, g.ny + e, PtFieldArgs{g, (double *)pF, (double *)F, g.x0 + 0.5 * g.dx, g.y0 + 0.5 * g.dy});
 }
 
-void pt_launch_c2p(jrx_handle *h, PtGeom g, double *pF, const double *F)
+// the entry points of operators 3, 4, 6, 7: one particle field, one grid field of extents (nx + e, ny + e)
+template <typename K>
+jrx_status pt_field_op(jrx_handle *h, const char *fn, K kernel, double *pF, double *F, const jrx_particles2d *part, int e, bool to_particles, bool centres)
 {
-    PtC2PArgs a = {g, pF, F, g.x0 + 0.5 * g.dx, g.y0 + 0.5 * g.dy};
-    const unsigned nb = pt_blocks(a.g, g.nx, g.ny);
-    h->stat_particles_launches++;
-    hipLaunchKernelGGL(k_pt_centroid2particle, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
-}
-
-void pt_launch_p2c(jrx_handle *h, PtGeom g, double *F, const double *pF)
-{
-    PtP2GArgs a = {g, F, pF};
-    const unsigned nb = pt_blocks(a.g, g.nx, g.ny);
-    h->stat_particles_launches++;
-    hipLaunchKernelGGL(k_pt_particle2centroid, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+    if (!h) return JRX_ERR_ARG;
+    PtSet S;
+    PtGeom g;
+    JRX_TRY(pt_geom(h, fn, "particles", part, &S, &g));
+    if (centres) JRX_TRY(pt_centres(h, fn, g));
+    const PtArr ap = {pF, 8 * pt_slots(S), "pF"}, af = {F, 8 * (i64)(g.nx + e) * (g.ny + e), "F"};
+    JRX_TRY(to_particles ? pt_disjoint(h, fn, &ap, 1, &af, 1, S) : pt_disjoint(h, fn, &af, 1, &ap, 1, S));
+    JRX_TRY(jrx_check_device(h));
+    pt_launch_field(h, kernel, to_particles ? 0 : e, g, pF, F);
+    return pt_finish(h);
 }
 
 // fused = false: operator 8 alone on a.pxx, pyy, pxy, pw; true: the one-launch rotate_stress!
-void pt_launch_rotate(jrx_handle *h, PtRotArgs a, int32_t method, bool fused)
+void pt_launch_rotate(jrx_handle *h, const PtRotArgs &a, int32_t method, bool fused)
 {
-    const unsigned nb = pt_blocks(a.g, a.g.nx, a.g.ny);
-    h->stat_particles_launches++;
     dispatch_const<0, 1>((int)method, [&](auto MM) {
-        if (fused) hipLaunchKernelGGL((k_pt_rotate_stress<MM()>), dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
-        else hipLaunchKernelGGL((k_pt_rotate<MM()>), dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+        if (fused) pt_launch(h, k_pt_rotate_stress<MM()>, a.g.nx, a.g.ny, a);
+        else pt_launch(h, k_pt_rotate<MM()>, a.g.nx, a.g.ny, a);
     });
 }
 
@@ -956,7 +906,8 @@ jrx_status pt_subgrid(jrx_handle *h, const char *fn, bool vertex, double *pT, co
                       const double *pdt0, double *dT_subgrid, const jrx_particles2d *part, double d, double dt)
 {
     PtSgArgs a = {};
-    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    PtSet S;
+    JRX_TRY(pt_geom(h, fn, "particles", part, &S, &a.g));
     if (!vertex) JRX_TRY(pt_centres(h, fn, a.g));
     if (!(d >= 0.0 && d <= 1.0)) return jrx_fail(h, JRX_ERR_ARG, "%s: d = %g (must lie in [0, 1])", fn, d);
     if (!std::isfinite(dt) || dt < 0.0) return jrx_fail(h, JRX_ERR_ARG, "%s: dt = %g (must be finite and not negative)", fn, dt);
@@ -964,44 +915,40 @@ jrx_status pt_subgrid(jrx_handle *h, const char *fn, bool vertex, double *pT, co
         return jrx_fail(h, JRX_ERR_ARG, "%s: unknown ΔT extent code %d (%d = the node box, %d = one ghost layer around it)", fn, (int)dT_extent, JRX_SUBGRID_DT_NODES,
                         JRX_SUBGRID_DT_GHOSTED);
     const PtGeom &g = a.g;
-    const int ex = g.nx + (vertex ? 1 : 0), ey = g.ny + (vertex ? 1 : 0), gh = dT_extent == JRX_SUBGRID_DT_GHOSTED ? 1 : 0;
-    const i64 ns = 8 * pt_slots(g), nn = 8 * (i64)ex * ey, nd = 8 * (i64)(ex + 2 * gh) * (ey + 2 * gh);
+    const int e = vertex ? 1 : 0, ex = g.nx + e, ey = g.ny + e, gh = dT_extent == JRX_SUBGRID_DT_GHOSTED ? 1 : 0;          // (ex, ey): the node box of the form
+    const i64 ns = 8 * pt_slots(S), nn = 8 * (i64)ex * ey, nd = 8 * (i64)(ex + 2 * gh) * (ey + 2 * gh);
     const PtArr out[4] = {{pT, ns, "pT"}, {pT0, ns, "subgrid_arrays.pT0"}, {pdT, ns, "subgrid_arrays.pΔT"}, {dT_subgrid, nn, "subgrid_arrays.ΔT_subgrid"}};
     const PtArr in[3] = {{T_grid, nn, "T_grid"}, {dT_grid, nd, "ΔT_grid"}, {pdt0, ns, "subgrid_arrays.dt₀"}};
-    JRX_TRY(pt_disjoint(h, fn, out, 4, in, 3, g));
+    JRX_TRY(pt_disjoint(h, fn, out, 4, in, 3, S));
     JRX_TRY(jrx_check_device(h));
     a.pT = pT, a.pT0 = pT0, a.pdT = pdT, a.pdt0 = pdt0, a.T = T_grid, a.dTg = dT_grid, a.dTs = dT_subgrid;
     a.dtn = ex + 2 * gh, a.dto = gh * (a.dtn + 1);
     a.ox = g.x0 + 0.5 * g.dx, a.oy = g.y0 + 0.5 * g.dy;
     a.ndt = (-d) * dt;
-    const dim3 tile(kPtTX, kPtTY);
-    const unsigned nbc = pt_blocks(a.g, g.nx, g.ny);          // the cell launches; nbx of a.g is theirs
-    PtSgArgs n = a;                                           // the node launches of the vertex form and of step 5
-    const unsigned nbn = pt_blocks(n.g, ex, ey);
     if (h->particles_subgrid_fused) {
-        h->stat_particles_launches += vertex ? 3 : 2;
         if (vertex) {
-            hipLaunchKernelGGL(k_pt_sg_cell<true>, dim3(nbc), tile, 0, h->stream, a);
-            hipLaunchKernelGGL(k_pt_sg_vertex, dim3(nbn), tile, 0, h->stream, n);
-            hipLaunchKernelGGL(k_pt_sg_back<true>, dim3(nbc), tile, 0, h->stream, a);
+            pt_launch(h, k_pt_sg_cell<true>, g.nx, g.ny, a);
+            pt_launch(h, k_pt_sg_vertex, ex, ey, a);
+            pt_launch(h, k_pt_sg_back<true>, g.nx, g.ny, a);
         } else {
-            hipLaunchKernelGGL(k_pt_sg_cell<false>, dim3(nbc), tile, 0, h->stream, a);
-            hipLaunchKernelGGL(k_pt_sg_back<false>, dim3(nbc), tile, 0, h->stream, a);
+            pt_launch(h, k_pt_sg_cell<false>, g.nx, g.ny, a);
+            pt_launch(h, k_pt_sg_back<false>, g.nx, g.ny, a);
         }
         return pt_finish(h);
     }
-    h->stat_particles_launches += 4;
-    hipLaunchKernelGGL(k_pt_sg_copy, dim3(nbc), tile, 0, h->stream, a);                      // 1
-    if (vertex) pt_launch_g2p(h, g, pT, T_grid);                                              // 2
-    else pt_launch_c2p(h, g, pT, T_grid);
-    hipLaunchKernelGGL(k_pt_sg_delta, dim3(nbc), tile, 0, h->stream, a);                     // 3
+    auto to_particles = [&](double *pF, const double *F) {          // operator 3 from vertices, 6 from centres
+        if (vertex) pt_launch_field(h, k_pt_grid2particle, 0, g, pF, F);
+        else pt_launch_field(h, k_pt_centroid2particle, 0, g, pF, F);
+    };
+    pt_launch(h, k_pt_sg_copy, g.nx, g.ny, a);                                                // 1
+    to_particles(pT, T_grid);                                                                 // 2
+    pt_launch(h, k_pt_sg_delta, g.nx, g.ny, a);                                               // 3
     JRX_HIP(h, hipMemsetAsync(dT_subgrid, 0, (size_t)nn, h->stream));                         // 4: +0.0 is all bits zero
-    if (vertex) pt_launch_p2g(h, g, dT_subgrid, pdT);
-    else pt_launch_p2c(h, g, dT_subgrid, pdT);
-    hipLaunchKernelGGL(k_pt_sg_remainder, dim3(nbn), tile, 0, h->stream, n, ex, ey);         // 5
-    if (vertex) pt_launch_g2p(h, g, pdT, dT_subgrid);                                         // 6
-    else pt_launch_c2p(h, g, pdT, dT_subgrid);
-    hipLaunchKernelGGL(k_pt_sg_add, dim3(nbc), tile, 0, h->stream, a);                       // 7
+    if (vertex) pt_launch_field(h, k_pt_particle2grid, 1, g, pdT, dT_subgrid);
+    else pt_launch_field(h, k_pt_particle2centroid, 0, g, pdT, dT_subgrid);
+    pt_launch(h, k_pt_sg_remainder, ex, ey, a, ex, ey);                                       // 5
+    to_particles(pdT, dT_subgrid);                                                            // 6
+    pt_launch(h, k_pt_sg_add, g.nx, g.ny, a);                                                 // 7
     return pt_finish(h);
 }
 
@@ -1014,21 +961,19 @@ jrx_status jrx_particles2d_advect_rk2(jrx_handle *h, const jrx_particles2d *part
     if (!h) return JRX_ERR_ARG;
     const char *fn = "advection!(particles)";
     PtAdvArgs a = {};
-    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    PtSet S;
+    JRX_TRY(pt_geom(h, fn, "particles", part, &S, &a.g));
+    const PtGeom &g = a.g;
     if (!Vx || !Vy) return jrx_fail(h, JRX_ERR_ARG, "%s: V.%s is NULL", fn, !Vx ? "Vx" : "Vy");
     if (!std::isfinite(dt)) return jrx_fail(h, JRX_ERR_ARG, "%s: dt = %g (must be finite)", fn, dt);
-    JRX_TRY(pt_apart(h, fn, "V.Vx", Vx, 8 * (i64)(a.g.nx + 1) * (a.g.ny + 2), a.g));
-    JRX_TRY(pt_apart(h, fn, "V.Vy", Vy, 8 * (i64)(a.g.nx + 2) * (a.g.ny + 1), a.g));
+    JRX_TRY(pt_apart(h, fn, {Vx, 8 * (i64)(g.nx + 1) * (g.ny + 2), "V.Vx"}, S));
+    JRX_TRY(pt_apart(h, fn, {Vy, 8 * (i64)(g.nx + 2) * (g.ny + 1), "V.Vy"}, S));
     JRX_TRY(jrx_check_device(h));
     a.Vx = Vx, a.Vy = Vy;
     a.oyx = part->y0 - 0.5 * part->dy, a.oxy = part->x0 - 0.5 * part->dx;
     a.dt = dt, a.hdt = 0.5 * dt;
-    const unsigned nb = pt_blocks(a.g, a.g.nx, a.g.ny);
-    h->stat_particles_launches++;
-    hipLaunchKernelGGL(k_pt_advect_rk2, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    pt_launch(h, k_pt_advect_rk2, g.nx, g.ny, a);
+    return pt_finish(h);
 }
 
 jrx_status jrx_particles2d_move(jrx_handle *h, const jrx_particles2d *src, const jrx_particles2d *dst, const double *const *args_src, double *const *args_dst,
@@ -1038,65 +983,39 @@ jrx_status jrx_particles2d_move(jrx_handle *h, const jrx_particles2d *src, const
     const char *fn = "move_particles!";
     PtMoveArgs a = {};
     PtGeom d;
-    JRX_TRY(pt_geom(h, fn, "particles (source)", src, &a.src));
-    JRX_TRY(pt_geom(h, fn, "particles (destination)", dst, &d));
-    if (!counts) return jrx_fail(h, JRX_ERR_ARG, "%s: counts is NULL", fn);
-    if (src->nx != dst->nx || src->ny != dst->ny || src->max_xcell != dst->max_xcell || src->x0 != dst->x0 || src->y0 != dst->y0 || src->dx != dst->dx ||
-        src->dy != dst->dy)
-        return jrx_fail(h, JRX_ERR_ARG, "%s: source and destination differ in extents, max_xcell, origin or spacing", fn);
-    if (nargs < 0 || nargs > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d particle fields (0 .. %d are built)", fn, (int)nargs, JRX_MAXPHASE);
-    if (nargs > 0 && (!args_src || !args_dst)) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL with %d particle fields", fn, !args_src ? "args_src" : "args_dst", (int)nargs);
-    const i64 ns = pt_slots(d);
-    for (int k = 0; k < nargs; k++)
-        if (!args_src[k] || !args_dst[k]) return jrx_fail(h, JRX_ERR_ARG, "%s: particle field %d (%s) is NULL", fn, k + 1, !args_src[k] ? "source" : "destination");
-    // nothing written may share memory with anything read or with another output
-    const void *out[3 + JRX_MAXPHASE] = {d.px, d.py, d.active};
-    i64 ob[3 + JRX_MAXPHASE] = {8 * ns, 8 * ns, 4 * ns};
-    for (int k = 0; k < nargs; k++) out[3 + k] = args_dst[k], ob[3 + k] = 8 * ns;
-    for (int m = 0; m < 3 + nargs; m++) {
-        JRX_TRY(pt_apart(h, fn, "an array of the destination", out[m], ob[m], a.src));
-        for (int k = 0; k < nargs; k++)
-            if (pt_overlaps(out[m], ob[m], args_src[k], 8 * ns)) return jrx_fail(h, JRX_ERR_ARG, "%s: an array of the destination overlaps source particle field %d", fn, k + 1);
-        for (int q = m + 1; q < 3 + nargs; q++)
-            if (pt_overlaps(out[m], ob[m], out[q], ob[q])) return jrx_fail(h, JRX_ERR_ARG, "%s: two arrays of the destination overlap", fn);
-    }
+    PtSet S, D;
+    JRX_TRY(pt_geom(h, fn, "particles (source)", src, &S, &a.src));
+    JRX_TRY(pt_geom(h, fn, "particles (destination)", dst, &D, &d));
+    JRX_TRY(pt_move_checks(h, fn, S, D, args_src, args_dst, nargs, nullptr, counts));
     JRX_TRY(jrx_check_device(h));
     a.dpx = d.px, a.dpy = d.py, a.dactive = d.active;
     for (int k = 0; k < nargs; k++) a.as[k] = args_src[k], a.ad[k] = args_dst[k];
     a.nargs = (int)nargs;
     a.counts = pt_words(h);
-    const unsigned nb = pt_blocks(a.src, a.src.nx, a.src.ny);
     JRX_HIP(h, hipMemsetAsync(a.counts, 0, sizeof(int64_t) * 5, h->stream));
-    h->stat_particles_launches++;
-    hipLaunchKernelGGL(k_pt_move, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+    pt_launch(h, k_pt_move, d.nx, d.ny, a);
     JRX_LAUNCH_CHECK(h);
-    return pt_read_words(h, 5, counts);
+    return pt_read_words(h, 0, 5, counts);
 }
 
 jrx_status jrx_particles2d_grid2particle(jrx_handle *h, double *pF, const double *F, const jrx_particles2d *part)
 {
-    if (!h) return JRX_ERR_ARG;
-    const char *fn = "grid2particle!";
-    PtGeom g;
-    JRX_TRY(pt_geom(h, fn, "particles", part, &g));
-    const PtArr out[1] = {{pF, 8 * pt_slots(g), "pF"}}, in[1] = {{F, 8 * (i64)(g.nx + 1) * (g.ny + 1), "F"}};
-    JRX_TRY(pt_disjoint(h, fn, out, 1, in, 1, g));
-    JRX_TRY(jrx_check_device(h));
-    pt_launch_g2p(h, g, pF, F);
-    return pt_finish(h);
+    return pt_field_op(h, "grid2particle!", k_pt_grid2particle, pF, (double *)F, part, 1, true, false);
 }
 
 jrx_status jrx_particles2d_particle2grid(jrx_handle *h, double *F, const double *pF, const jrx_particles2d *part)
 {
-    if (!h) return JRX_ERR_ARG;
-    const char *fn = "particle2grid!";
-    PtGeom g;
-    JRX_TRY(pt_geom(h, fn, "particles", part, &g));
-    const PtArr out[1] = {{F, 8 * (i64)(g.nx + 1) * (g.ny + 1), "F"}}, in[1] = {{pF, 8 * pt_slots(g), "pF"}};
-    JRX_TRY(pt_disjoint(h, fn, out, 1, in, 1, g));
-    JRX_TRY(jrx_check_device(h));
-    pt_launch_p2g(h, g, F, pF);
-    return pt_finish(h);
+    return pt_field_op(h, "particle2grid!", k_pt_particle2grid, (double *)pF, F, part, 1, false, false);
+}
+
+jrx_status jrx_particles2d_centroid2particle(jrx_handle *h, double *pF, const double *F, const jrx_particles2d *part)
+{
+    return pt_field_op(h, "centroid2particle!", k_pt_centroid2particle, pF, (double *)F, part, 0, true, true);
+}
+
+jrx_status jrx_particles2d_particle2centroid(jrx_handle *h, double *F, const double *pF, const jrx_particles2d *part)
+{
+    return pt_field_op(h, "particle2centroid!", k_pt_particle2centroid, (double *)pF, F, part, 0, false, false);
 }
 
 jrx_status jrx_particles2d_phase_ratios(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, const double *pPhases, int32_t nphase,
@@ -1104,64 +1023,20 @@ jrx_status jrx_particles2d_phase_ratios(jrx_handle *h, double *center, double *v
 {
     if (!h) return JRX_ERR_ARG;
     const char *fn = "update_phase_ratios!(particles)";
+    static const char *const names[4] = {"phase_ratios.center", "phase_ratios.vertex", "phase_ratios.Vx", "phase_ratios.Vy"};
+    static const int stag[4][3] = {{0, 0}, {1, 1}, {1, 0}, {0, 1}};
+    double *const members[4] = {center, vertex, Vx, Vy};
     PtPrArgs a = {};
-    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
-    double *const out[4] = {center, vertex, Vx, Vy};
-    static const char *const names[4] = {"center", "vertex", "Vx", "Vy"};
-    for (int m = 0; m < 4; m++)
-        if (!out[m]) return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios.%s is NULL", fn, names[m]);
-    if (!pPhases) return jrx_fail(h, JRX_ERR_ARG, "%s: pPhases is NULL", fn);
-    if (!n_empty) return jrx_fail(h, JRX_ERR_ARG, "%s: n_empty is NULL", fn);
-    if (nphase < 1 || nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d phases (1 .. %d are built)", fn, (int)nphase, JRX_MAXPHASE);
-    const i64 nx = a.g.nx, ny = a.g.ny, ns = pt_slots(a.g);
-    const i64 ob[4] = {8 * nphase * nx * ny, 8 * nphase * (nx + 1) * (ny + 1), 8 * nphase * (nx + 1) * ny, 8 * nphase * nx * (ny + 1)};
-    for (int m = 0; m < 4; m++) {
-        JRX_TRY(pt_apart(h, fn, names[m], out[m], ob[m], a.g));
-        if (pt_overlaps(out[m], ob[m], pPhases, 8 * ns)) return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios.%s overlaps pPhases", fn, names[m]);
-        for (int q = m + 1; q < 4; q++)
-            if (pt_overlaps(out[m], ob[m], out[q], ob[q])) return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios.%s and phase_ratios.%s overlap", fn, names[m], names[q]);
-    }
+    PtSet S;
+    JRX_TRY(pt_geom(h, fn, "particles", part, &S, &a.g));
+    JRX_TRY(pt_ratio_checks(h, fn, S, members, names, stag, 4, pPhases, nphase, n_empty));
     JRX_TRY(jrx_check_device(h));
     a.center = center, a.vertex = vertex, a.Vx = Vx, a.Vy = Vy, a.pPhases = pPhases;
     a.n_empty = pt_words(h) + 5;
-    const unsigned nb = pt_blocks(a.g, a.g.nx + 1, a.g.ny + 1);
     JRX_HIP(h, hipMemsetAsync(a.n_empty, 0, sizeof(int64_t), h->stream));
-    h->stat_particles_launches++;
-    dispatch_const<1, 2, 3, 4, 5, 6, 7, 8>((int)nphase, [&](auto NN) {
-        hipLaunchKernelGGL((k_pt_phase_ratios<NN()>), dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
-    });
+    dispatch_const<1, 2, 3, 4, 5, 6, 7, 8>((int)nphase, [&](auto NN) { pt_launch(h, k_pt_phase_ratios<NN()>, a.g.nx + 1, a.g.ny + 1, a); });
     JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipMemcpyAsync(h->h_sums + 15, h->d_sums + 15, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    memcpy(n_empty, h->h_sums + 15, sizeof(int64_t));
-    return JRX_OK;
-}
-
-jrx_status jrx_particles2d_centroid2particle(jrx_handle *h, double *pF, const double *F, const jrx_particles2d *part)
-{
-    if (!h) return JRX_ERR_ARG;
-    const char *fn = "centroid2particle!";
-    PtGeom g;
-    JRX_TRY(pt_geom(h, fn, "particles", part, &g));
-    JRX_TRY(pt_centres(h, fn, g));
-    const PtArr out[1] = {{pF, 8 * pt_slots(g), "pF"}}, in[1] = {{F, 8 * (i64)g.nx * g.ny, "F"}};
-    JRX_TRY(pt_disjoint(h, fn, out, 1, in, 1, g));
-    JRX_TRY(jrx_check_device(h));
-    pt_launch_c2p(h, g, pF, F);
-    return pt_finish(h);
-}
-
-jrx_status jrx_particles2d_particle2centroid(jrx_handle *h, double *F, const double *pF, const jrx_particles2d *part)
-{
-    if (!h) return JRX_ERR_ARG;
-    const char *fn = "particle2centroid!";
-    PtGeom g;
-    JRX_TRY(pt_geom(h, fn, "particles", part, &g));
-    const PtArr out[1] = {{F, 8 * (i64)g.nx * g.ny, "F"}}, in[1] = {{pF, 8 * pt_slots(g), "pF"}};
-    JRX_TRY(pt_disjoint(h, fn, out, 1, in, 1, g));
-    JRX_TRY(jrx_check_device(h));
-    pt_launch_p2c(h, g, F, pF);
-    return pt_finish(h);
+    return pt_read_words(h, 5, 1, n_empty);
 }
 
 jrx_status jrx_particles2d_rotate(jrx_handle *h, double *const ptau[3], const double *pomega, const jrx_particles2d *part, double dt, int32_t method)
@@ -1169,12 +1044,13 @@ jrx_status jrx_particles2d_rotate(jrx_handle *h, double *const ptau[3], const do
     if (!h) return JRX_ERR_ARG;
     const char *fn = "rotate_stress_particles!";
     PtRotArgs a = {};
-    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    PtSet S;
+    JRX_TRY(pt_geom(h, fn, "particles", part, &S, &a.g));
     if (!ptau) return jrx_fail(h, JRX_ERR_ARG, "%s: ptau is NULL", fn);
     JRX_TRY(pt_method(h, fn, dt, method));
-    const i64 ns = 8 * pt_slots(a.g);
+    const i64 ns = 8 * pt_slots(S);
     const PtArr out[3] = {{ptau[0], ns, "pτxx"}, {ptau[1], ns, "pτyy"}, {ptau[2], ns, "pτxy"}}, in[1] = {{pomega, ns, "pω"}};
-    JRX_TRY(pt_disjoint(h, fn, out, 3, in, 1, a.g));
+    JRX_TRY(pt_disjoint(h, fn, out, 3, in, 1, S));
     JRX_TRY(jrx_check_device(h));
     a.pxx = ptau[0], a.pyy = ptau[1], a.pxy = ptau[2], a.pw = const_cast<double *>(pomega), a.dt = dt;
     pt_launch_rotate(h, a, method, false);
@@ -1187,15 +1063,16 @@ jrx_status jrx_particles2d_rotate_stress(jrx_handle *h, double *const ptau[3], d
     if (!h) return JRX_ERR_ARG;
     const char *fn = "rotate_stress!(particles)";
     PtRotArgs a = {};
-    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    PtSet S;
+    JRX_TRY(pt_geom(h, fn, "particles", part, &S, &a.g));
     JRX_TRY(pt_centres(h, fn, a.g));
     if (!ptau) return jrx_fail(h, JRX_ERR_ARG, "%s: ptau is NULL", fn);
     JRX_TRY(pt_method(h, fn, dt, method));
     const PtGeom &g = a.g;
-    const i64 ns = 8 * pt_slots(g), nc = 8 * (i64)g.nx * g.ny, nv = 8 * (i64)(g.nx + 1) * (g.ny + 1);
+    const i64 ns = 8 * pt_slots(S), nc = 8 * (i64)g.nx * g.ny, nv = 8 * (i64)(g.nx + 1) * (g.ny + 1);
     const PtArr out[4] = {{ptau[0], ns, "pτxx"}, {ptau[1], ns, "pτyy"}, {ptau[2], ns, "pτxy"}, {pomega, ns, "pω"}};
     const PtArr in[4] = {{tau_xx, nc, "τ.xx"}, {tau_yy, nc, "τ.yy"}, {tau_xy, nv, "τ.xy"}, {omega_xy, nv, "ω.xy"}};
-    JRX_TRY(pt_disjoint(h, fn, out, 4, in, 4, g));
+    JRX_TRY(pt_disjoint(h, fn, out, 4, in, 4, S));
     JRX_TRY(jrx_check_device(h));
     a.pxx = ptau[0], a.pyy = ptau[1], a.pxy = ptau[2], a.pw = pomega, a.dt = dt;
     if (h->particles_stress_fused) {
@@ -1203,10 +1080,10 @@ jrx_status jrx_particles2d_rotate_stress(jrx_handle *h, double *const ptau[3], d
         a.ox = g.x0 + 0.5 * g.dx, a.oy = g.y0 + 0.5 * g.dy;
         pt_launch_rotate(h, a, method, true);
     } else {
-        pt_launch_c2p(h, g, ptau[0], tau_xx);
-        pt_launch_c2p(h, g, ptau[1], tau_yy);
-        pt_launch_g2p(h, g, ptau[2], tau_xy);
-        pt_launch_g2p(h, g, pomega, omega_xy);
+        pt_launch_field(h, k_pt_centroid2particle, 0, g, ptau[0], tau_xx);
+        pt_launch_field(h, k_pt_centroid2particle, 0, g, ptau[1], tau_yy);
+        pt_launch_field(h, k_pt_grid2particle, 0, g, ptau[2], tau_xy);
+        pt_launch_field(h, k_pt_grid2particle, 0, g, pomega, omega_xy);
         pt_launch_rotate(h, a, method, false);
     }
     return pt_finish(h);
@@ -1217,26 +1094,25 @@ jrx_status jrx_particles2d_stress2grid(jrx_handle *h, double *const tau_o[6], co
     if (!h) return JRX_ERR_ARG;
     const char *fn = "stress2grid!";
     PtS2GArgs a = {};
-    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    PtSet S;
+    JRX_TRY(pt_geom(h, fn, "particles", part, &S, &a.g));
     if (!tau_o || !ptau) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, !tau_o ? "tau_o" : "ptau");
     const PtGeom &g = a.g;
-    const i64 ns = 8 * pt_slots(g), nc = 8 * (i64)g.nx * g.ny, nv = 8 * (i64)(g.nx + 1) * (g.ny + 1);
+    const i64 ns = 8 * pt_slots(S), nc = 8 * (i64)g.nx * g.ny, nv = 8 * (i64)(g.nx + 1) * (g.ny + 1);
     const PtArr out[6] = {{tau_o[0], nc, "τ_o.xx"}, {tau_o[1], nc, "τ_o.yy"}, {tau_o[2], nc, "τ_o.xy_c"}, {tau_o[3], nv, "τ_o.xy"}, {tau_o[4], nv, "τ_o.xx_v"},
                           {tau_o[5], nv, "τ_o.yy_v"}};
     const PtArr in[3] = {{ptau[0], ns, "pτxx"}, {ptau[1], ns, "pτyy"}, {ptau[2], ns, "pτxy"}};
-    JRX_TRY(pt_disjoint(h, fn, out, 6, in, 3, g));
+    JRX_TRY(pt_disjoint(h, fn, out, 6, in, 3, S));
     JRX_TRY(jrx_check_device(h));
     if (h->particles_stress_fused) {
         a.cxx = tau_o[0], a.cyy = tau_o[1], a.cxy = tau_o[2], a.vxy = tau_o[3], a.vxx = tau_o[4], a.vyy = tau_o[5];
         a.pxx = ptau[0], a.pyy = ptau[1], a.pxy = ptau[2];
-        const unsigned nb = pt_blocks(a.g, g.nx + 1, g.ny + 1);
-        h->stat_particles_launches++;
-        hipLaunchKernelGGL(k_pt_stress2grid, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+        pt_launch(h, k_pt_stress2grid, g.nx + 1, g.ny + 1, a);
     } else {
-        for (int c = 0; c < 3; c++) pt_launch_p2c(h, g, tau_o[c], ptau[c]);                 // xx, yy, xy_c
-        pt_launch_p2g(h, g, tau_o[4], ptau[0]);                                             // xx_v, yy_v, xy
-        pt_launch_p2g(h, g, tau_o[5], ptau[1]);
-        pt_launch_p2g(h, g, tau_o[3], ptau[2]);
+        for (int c = 0; c < 3; c++) pt_launch_field(h, k_pt_particle2centroid, 0, g, ptau[c], tau_o[c]);          // xx, yy, xy_c
+        pt_launch_field(h, k_pt_particle2grid, 1, g, ptau[0], tau_o[4]);                                          // xx_v, yy_v, xy
+        pt_launch_field(h, k_pt_particle2grid, 1, g, ptau[1], tau_o[5]);
+        pt_launch_field(h, k_pt_particle2grid, 1, g, ptau[2], tau_o[3]);
     }
     return pt_finish(h);
 }
@@ -1261,7 +1137,8 @@ jrx_status jrx_particles2d_inject(jrx_handle *h, const jrx_particles2d *part, in
     if (!h) return JRX_ERR_ARG;
     const char *fn = "inject_particles_phase!";
     PtInjArgs a = {};
-    JRX_TRY(pt_geom(h, fn, "particles", part, &a.g));
+    PtSet S;
+    JRX_TRY(pt_geom(h, fn, "particles", part, &S, &a.g));
     const PtGeom &g = a.g;
     if (!active_out || !pPhases || !counts) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, !active_out ? "active_out" : (!pPhases ? "pPhases" : "counts"));
     if (nsx < 1 || nsy < 1 || (i64)nsx * nsy > 64)
@@ -1281,7 +1158,7 @@ jrx_status jrx_particles2d_inject(jrx_handle *h, const jrx_particles2d *part, in
         if (loc == JRX_INJECT_CENTRE) JRX_TRY(pt_centres(h, fn, g));
     }
     // everything written -- the mask's copy, the phases, the particle fields, and the coordinates in place -- apart from the mask that is read and from each other
-    const i64 ns = pt_slots(g);
+    const i64 ns = pt_slots(S);
     if (pt_overlaps(active_out, 4 * ns, g.active, 4 * ns)) return jrx_fail(h, JRX_ERR_ARG, "%s: active_out overlaps the mask (the mask is written out of place)", fn);
     PtArr out[2 + JRX_MAXPHASE] = {{active_out, 4 * ns, "active_out"}, {pPhases, 8 * ns, "pPhases"}};
     static const char *const names[JRX_MAXPHASE] = {"particle field 1", "particle field 2", "particle field 3", "particle field 4",
@@ -1294,8 +1171,8 @@ jrx_status jrx_particles2d_inject(jrx_handle *h, const jrx_particles2d *part, in
         const bool v = field_loc[k] == JRX_INJECT_VERTEX;
         in[nin++] = PtArr{fields[k], 8 * (i64)(g.nx + (v ? 1 : 0)) * (g.ny + (v ? 1 : 0)), v ? "a vertex field" : "a centre field"};
     }
-    JRX_TRY(pt_disjoint(h, fn, out, 2 + nargs, in, nin, g));
-    for (int k = 0; k < nin; k++) JRX_TRY(pt_apart(h, fn, in[k].name, in[k].p, in[k].bytes, g));          // px, py are written too
+    JRX_TRY(pt_disjoint(h, fn, out, 2 + nargs, in, nin, S));
+    for (int k = 0; k < nin; k++) JRX_TRY(pt_apart(h, fn, in[k], S));          // px, py are written too
     JRX_TRY(jrx_check_device(h));
     a.aout = (int *)active_out, a.pph = pPhases;
     for (int k = 0; k < nargs; k++) a.args[k] = args[k], a.fields[k] = fields[k], a.loc[k] = field_loc[k];
@@ -1303,13 +1180,11 @@ jrx_status jrx_particles2d_inject(jrx_handle *h, const jrx_particles2d *part, in
     a.hx = g.dx / (double)nsx, a.hy = g.dy / (double)nsy;
     a.ox = g.x0 + 0.5 * g.dx, a.oy = g.y0 + 0.5 * g.dy;
     a.counts = pt_words(h);
-    const unsigned nb = pt_blocks(a.g, g.nx, g.ny);
     JRX_HIP(h, hipMemsetAsync(a.counts, 0, sizeof(int64_t) * 3, h->stream));
-    h->stat_particles_launches++;
-    hipLaunchKernelGGL(k_pt_inject, dim3(nb), dim3(kPtTX, kPtTY), 0, h->stream, a);
+    pt_launch(h, k_pt_inject, g.nx, g.ny, a);
     JRX_LAUNCH_CHECK(h);
     int64_t w[3];
-    JRX_TRY(pt_read_words(h, 3, w));
+    JRX_TRY(pt_read_words(h, 0, 3, w));
     const int64_t lo = 0xffffffffll;
     counts[0] = w[0] & lo, counts[1] = (w[0] >> 32) & lo, counts[2] = w[1] & lo, counts[3] = (w[1] >> 32) & lo, counts[4] = w[2];
     return JRX_OK;

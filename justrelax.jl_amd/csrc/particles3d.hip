@@ -3,8 +3,9 @@
 // JustPIC (miniapps/benchmarks/stokes3D/shear_heating/Shearheating3D.jl:63-78,224-233).  JustPIC's text is not in the reference tree: include/jrx.h (section
 // "3D marker-in-cell particles") states the definitions built here, tests/_particles3d.py is the same text in NumPy.
 //
-// A file of its own beside particles.hip: the 2D file already holds twelve operators, and nothing of its kernels carries over but the per-axis helpers, which both
-// files take from particles_common.hpp.
+// A file of its own beside particles.hip: the 2D file already holds twelve operators, and nothing of its kernels carries over but the per-axis helpers.  Those, and
+// the whole host check layer (the checks of a particle set, the overlap rules, the checks of move and of the phase ratios, the counter read-back), both files take
+// from particles_common.hpp; here are the kernels, the conversion of jrx_particles3d (p3_geom), the launches and the entry points.
 //
 // Layout: every per-particle array is (nx, ny, nz, max_xcell) column-major, the slot index slowest.  A block is 64 x 2 x 2 threads, a thread owns a cell (or a
 // node) and walks the slots: in every trip of a slot loop the 64 lanes of a wave read 64 consecutive addresses.  An inactive slot holds 0 everywhere.
@@ -471,50 +472,14 @@ __global__ __launch_bounds__(256) void k_p3_particle2centroid(const P3FieldArgs 
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// the checks every entry point shares; fills g
-jrx_status p3_geom(jrx_handle *h, const char *fn, const char *what, const jrx_particles3d *p, P3Geom *g)
+// jrx_particles3d as the shared checks see it (particles_common.hpp), checked, and by value for the kernels
+jrx_status p3_geom(jrx_handle *h, const char *fn, const char *what, const jrx_particles3d *p, PtSet *S, P3Geom *g)
 {
-    if (!p) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, what);
-    if (!p->px || !p->py || !p->pz || !p->active)
-        return jrx_fail(h, JRX_ERR_ARG, "%s: %s.%s is NULL", fn, what, !p->px ? "px" : (!p->py ? "py" : (!p->pz ? "pz" : "active")));
-    if (p->nx < 1 || p->ny < 1 || p->nz < 1)
-        return jrx_fail(h, JRX_ERR_ARG, "%s: %s has %lld x %lld x %lld cells", fn, what, (long long)p->nx, (long long)p->ny, (long long)p->nz);
-    if (p->max_xcell < 1) return jrx_fail(h, JRX_ERR_ARG, "%s: %s.max_xcell = %d", fn, what, (int)p->max_xcell);
-    if ((double)p->nx * (double)p->ny * (double)p->nz * (double)p->max_xcell >= 2147483648.0 ||
-        (double)(p->nx + 2) * (double)(p->ny + 2) * (double)(p->nz + 2) >= 2147483648.0)
-        return jrx_fail(h, JRX_ERR_ARG, "%s: %s has 2^31 or more slots or nodes (32-bit offsets)", fn, what);
-    if (p->ny > 2 * 65535 - 2 || p->nz > 2 * 65535 - 2)
-        return jrx_fail(h, JRX_ERR_ARG, "%s: %s has more than %d cells along y or z (the launch grid)", fn, what, 2 * 65535 - 2);
-    if (!std::isfinite(p->x0) || !std::isfinite(p->y0) || !std::isfinite(p->z0))
-        return jrx_fail(h, JRX_ERR_ARG, "%s: %s has origin (%g, %g, %g) (must be finite)", fn, what, p->x0, p->y0, p->z0);
-    if (!(p->dx > 0.0) || !(p->dy > 0.0) || !(p->dz > 0.0) || !std::isfinite(p->dx) || !std::isfinite(p->dy) || !std::isfinite(p->dz))
-        return jrx_fail(h, JRX_ERR_ARG, "%s: %s has spacings (%g, %g, %g) (must be positive and finite: a uniform grid)", fn, what, p->dx, p->dy, p->dz);
-    if (p->_dx != 1.0 / p->dx || p->_dy != 1.0 / p->dy || p->_dz != 1.0 / p->dz)
-        return jrx_fail(h, JRX_ERR_ARG, "%s: %s._dx, ._dy, ._dz = (%g, %g, %g) are not 1 / dx, 1 / dy, 1 / dz", fn, what, p->_dx, p->_dy, p->_dz);
-    if (jrx_comm_active(h)) return jrx_fail(h, JRX_ERR_ARG, "%s: a handle with a communicator (particles are built for one block)", fn);
+    *S = p ? PtSet{3, {p->px, p->py, p->pz}, p->active, {p->nx, p->ny, p->nz}, (int)p->max_xcell, {p->x0, p->y0, p->z0}, {p->dx, p->dy, p->dz}, {p->_dx, p->_dy, p->_dz}}
+           : PtSet{};
+    JRX_TRY(pt_check_set(h, fn, what, *S));
     *g = P3Geom{p->px, p->py, p->pz, (int *)p->active, p->x0, p->y0, p->z0, p->dx, p->dy, p->dz, p->_dx, p->_dy, p->_dz, (int)p->nx, (int)p->ny, (int)p->nz,
                 (int)p->max_xcell};
-    return JRX_OK;
-}
-
-i64 p3_slots(const P3Geom &g) { return (i64)g.nx * g.ny * g.nz * g.mx; }
-
-// an array of `bytes` bytes must not share memory with the coordinates or the mask of g
-jrx_status p3_apart(jrx_handle *h, const char *fn, const char *name, const void *p, i64 bytes, const P3Geom &g)
-{
-    const i64 ns = p3_slots(g);
-    if (pt_overlaps(p, bytes, g.px, 8 * ns) || pt_overlaps(p, bytes, g.py, 8 * ns) || pt_overlaps(p, bytes, g.pz, 8 * ns) || pt_overlaps(p, bytes, g.active, 4 * ns))
-        return jrx_fail(h, JRX_ERR_ARG, "%s: %s overlaps the particle coordinates or the mask", fn, name);
-    return JRX_OK;
-}
-
-// both present; the output shares memory neither with the particles' own arrays nor with the input
-jrx_status p3_pair(jrx_handle *h, const char *fn, const PtArr &out, const PtArr &in, const P3Geom &g)
-{
-    if (!out.p) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, out.name);
-    if (!in.p) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, in.name);
-    JRX_TRY(p3_apart(h, fn, out.name, out.p, out.bytes, g));
-    if (pt_overlaps(out.p, out.bytes, in.p, in.bytes)) return jrx_fail(h, JRX_ERR_ARG, "%s: %s overlaps %s", fn, out.name, in.name);
     return JRX_OK;
 }
 
@@ -527,12 +492,13 @@ jrx_status p3_field_op(jrx_handle *h, const char *fn, K kernel, double *pF, doub
 {
     if (!h) return JRX_ERR_ARG;
     P3FieldArgs a = {};
-    JRX_TRY(p3_geom(h, fn, "particles", part, &a.g));
+    PtSet S;
+    JRX_TRY(p3_geom(h, fn, "particles", part, &S, &a.g));
     const P3Geom &g = a.g;
     if (centres && (g.nx < 2 || g.ny < 2 || g.nz < 2))
         return jrx_fail(h, JRX_ERR_ARG, "%s: %d x %d x %d cells (interpolation between centres needs every extent >= 2)", fn, g.nx, g.ny, g.nz);
-    const PtArr ap = {pF, 8 * p3_slots(g), "pF"}, af = {F, 8 * (i64)(g.nx + e) * (g.ny + e) * (g.nz + e), "F"};
-    JRX_TRY(to_particles ? p3_pair(h, fn, ap, af, g) : p3_pair(h, fn, af, ap, g));
+    const PtArr ap = {pF, 8 * pt_slots(S), "pF"}, af = {F, 8 * (i64)(g.nx + e) * (g.ny + e) * (g.nz + e), "F"};
+    JRX_TRY(to_particles ? pt_disjoint(h, fn, &ap, 1, &af, 1, S) : pt_disjoint(h, fn, &af, 1, &ap, 1, S));
     JRX_TRY(jrx_check_device(h));
     a.pF = pF, a.F = F;
     a.ox = g.x0 + 0.5 * g.dx, a.oy = g.y0 + 0.5 * g.dy, a.oz = g.z0 + 0.5 * g.dz;
@@ -551,13 +517,14 @@ jrx_status jrx_particles3d_advect_rk2(jrx_handle *h, const jrx_particles3d *part
     if (!h) return JRX_ERR_ARG;
     const char *fn = "advection!(particles)";
     P3AdvArgs a = {};
-    JRX_TRY(p3_geom(h, fn, "particles", part, &a.g));
+    PtSet S;
+    JRX_TRY(p3_geom(h, fn, "particles", part, &S, &a.g));
     const P3Geom &g = a.g;
     if (!Vx || !Vy || !Vz) return jrx_fail(h, JRX_ERR_ARG, "%s: V.%s is NULL", fn, !Vx ? "Vx" : (!Vy ? "Vy" : "Vz"));
     if (!std::isfinite(dt)) return jrx_fail(h, JRX_ERR_ARG, "%s: dt = %g (must be finite)", fn, dt);
-    JRX_TRY(p3_apart(h, fn, "V.Vx", Vx, 8 * (i64)(g.nx + 1) * (g.ny + 2) * (g.nz + 2), g));
-    JRX_TRY(p3_apart(h, fn, "V.Vy", Vy, 8 * (i64)(g.nx + 2) * (g.ny + 1) * (g.nz + 2), g));
-    JRX_TRY(p3_apart(h, fn, "V.Vz", Vz, 8 * (i64)(g.nx + 2) * (g.ny + 2) * (g.nz + 1), g));
+    JRX_TRY(pt_apart(h, fn, {Vx, 8 * (i64)(g.nx + 1) * (g.ny + 2) * (g.nz + 2), "V.Vx"}, S));
+    JRX_TRY(pt_apart(h, fn, {Vy, 8 * (i64)(g.nx + 2) * (g.ny + 1) * (g.nz + 2), "V.Vy"}, S));
+    JRX_TRY(pt_apart(h, fn, {Vz, 8 * (i64)(g.nx + 2) * (g.ny + 2) * (g.nz + 1), "V.Vz"}, S));
     JRX_TRY(jrx_check_device(h));
     a.Vx = Vx, a.Vy = Vy, a.Vz = Vz;
     a.hx = part->x0 - 0.5 * part->dx, a.hy = part->y0 - 0.5 * part->dy, a.hz = part->z0 - 0.5 * part->dz;
@@ -574,30 +541,10 @@ jrx_status jrx_particles3d_move(jrx_handle *h, const jrx_particles3d *src, const
     const char *fn = "move_particles!";
     P3MoveArgs a = {};
     P3Geom d;
-    JRX_TRY(p3_geom(h, fn, "particles (source)", src, &a.src));
-    JRX_TRY(p3_geom(h, fn, "particles (destination)", dst, &d));
-    if (!counts) return jrx_fail(h, JRX_ERR_ARG, "%s: counts is NULL", fn);
-    if (src->nx != dst->nx || src->ny != dst->ny || src->nz != dst->nz || src->max_xcell != dst->max_xcell || src->x0 != dst->x0 || src->y0 != dst->y0 ||
-        src->z0 != dst->z0 || src->dx != dst->dx || src->dy != dst->dy || src->dz != dst->dz)
-        return jrx_fail(h, JRX_ERR_ARG, "%s: source and destination differ in extents, max_xcell, origin or spacing", fn);
-    if (nargs < 0 || nargs > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d particle fields (0 .. %d are built)", fn, (int)nargs, JRX_MAXPHASE);
-    if (nargs > 0 && (!args_src || !args_dst)) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL with %d particle fields", fn, !args_src ? "args_src" : "args_dst", (int)nargs);
-    const i64 ns = p3_slots(d);
-    for (int q = 0; q < nargs; q++)
-        if (!args_src[q] || !args_dst[q]) return jrx_fail(h, JRX_ERR_ARG, "%s: particle field %d (%s) is NULL", fn, q + 1, !args_src[q] ? "source" : "destination");
-    // nothing written may share memory with anything read or with another output; the byte buffer is an output too
-    const void *out[5 + JRX_MAXPHASE] = {d.px, d.py, d.pz, d.active};
-    i64 ob[5 + JRX_MAXPHASE] = {8 * ns, 8 * ns, 8 * ns, 4 * ns};
-    int nout = 4;
-    for (int q = 0; q < nargs; q++) out[nout] = args_dst[q], ob[nout++] = 8 * ns;
-    if (work) out[nout] = work, ob[nout++] = ns;
-    for (int m = 0; m < nout; m++) {
-        JRX_TRY(p3_apart(h, fn, out[m] == work ? "work" : "an array of the destination", out[m], ob[m], a.src));
-        for (int q = 0; q < nargs; q++)
-            if (pt_overlaps(out[m], ob[m], args_src[q], 8 * ns)) return jrx_fail(h, JRX_ERR_ARG, "%s: an array of the destination overlaps source particle field %d", fn, q + 1);
-        for (int q = m + 1; q < nout; q++)
-            if (pt_overlaps(out[m], ob[m], out[q], ob[q])) return jrx_fail(h, JRX_ERR_ARG, "%s: two arrays of the destination overlap", fn);
-    }
+    PtSet S, D;
+    JRX_TRY(p3_geom(h, fn, "particles (source)", src, &S, &a.src));
+    JRX_TRY(p3_geom(h, fn, "particles (destination)", dst, &D, &d));
+    JRX_TRY(pt_move_checks(h, fn, S, D, args_src, args_dst, nargs, work, counts));          // the byte buffer is an output too
     JRX_TRY(jrx_check_device(h));
     a.dpx = d.px, a.dpy = d.py, a.dpz = d.pz, a.dactive = d.active;
     for (int q = 0; q < nargs; q++) a.as[q] = args_src[q], a.ad[q] = args_dst[q];
@@ -615,7 +562,7 @@ jrx_status jrx_particles3d_move(jrx_handle *h, const jrx_particles3d *src, const
         hipLaunchKernelGGL(k_p3_move, grid, kP3Block, 0, h->stream, a);
     }
     JRX_LAUNCH_CHECK(h);
-    return pt_read_words(h, 5, counts);
+    return pt_read_words(h, 0, 5, counts);
 }
 
 jrx_status jrx_particles3d_grid2particle(jrx_handle *h, double *pF, const double *F, const jrx_particles3d *part)
@@ -642,28 +589,15 @@ jrx_status jrx_particles3d_phase_ratios(jrx_handle *h, double *const members[8],
 {
     if (!h) return JRX_ERR_ARG;
     const char *fn = "update_phase_ratios!(particles)";
-    static const char *const names[kP3Members] = {"center", "vertex", "Vx", "Vy", "Vz", "yz", "xz", "xy"};
+    static const char *const names[kP3Members] = {"phase_ratios.center", "phase_ratios.vertex", "phase_ratios.Vx", "phase_ratios.Vy",
+                                                  "phase_ratios.Vz",     "phase_ratios.yz",     "phase_ratios.xz", "phase_ratios.xy"};
     static const int stag[kP3Members][3] = {{0, 0, 0}, {1, 1, 1}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {0, 1, 1}, {1, 0, 1}, {1, 1, 0}};
     P3PrArgs a = {};
-    JRX_TRY(p3_geom(h, fn, "particles", part, &a.g));
-    if (!members) return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios is NULL", fn);
-    for (int m = 0; m < kP3Members; m++)
-        if (!members[m]) return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios.%s is NULL", fn, names[m]);
-    if (!pPhases) return jrx_fail(h, JRX_ERR_ARG, "%s: pPhases is NULL", fn);
-    if (!n_empty) return jrx_fail(h, JRX_ERR_ARG, "%s: n_empty is NULL", fn);
-    if (nphase < 1 || nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d phases (1 .. %d are built)", fn, (int)nphase, JRX_MAXPHASE);
-    const P3Geom &g = a.g;
-    const i64 ns = p3_slots(g);
-    i64 ob[kP3Members];
-    for (int m = 0; m < kP3Members; m++) ob[m] = 8 * (i64)nphase * (g.nx + stag[m][0]) * (g.ny + stag[m][1]) * (g.nz + stag[m][2]);
-    for (int m = 0; m < kP3Members; m++) {
-        JRX_TRY(p3_apart(h, fn, names[m], members[m], ob[m], g));
-        if (pt_overlaps(members[m], ob[m], pPhases, 8 * ns)) return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios.%s overlaps pPhases", fn, names[m]);
-        for (int q = m + 1; q < kP3Members; q++)
-            if (pt_overlaps(members[m], ob[m], members[q], ob[q]))
-                return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios.%s and phase_ratios.%s overlap", fn, names[m], names[q]);
-    }
+    PtSet S;
+    JRX_TRY(p3_geom(h, fn, "particles", part, &S, &a.g));
+    JRX_TRY(pt_ratio_checks(h, fn, S, members, names, stag, kP3Members, pPhases, nphase, n_empty));
     JRX_TRY(jrx_check_device(h));
+    const P3Geom &g = a.g;
     for (int m = 0; m < kP3Members; m++) a.out[m] = members[m];
     a.pPhases = pPhases;
     a.n_empty = pt_words(h) + 5;
@@ -683,10 +617,7 @@ jrx_status jrx_particles3d_phase_ratios(jrx_handle *h, double *const members[8],
         }
     });
     JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipMemcpyAsync(h->h_sums + 15, h->d_sums + 15, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    memcpy(n_empty, h->h_sums + 15, sizeof(int64_t));
-    return JRX_OK;
+    return pt_read_words(h, 5, 1, n_empty);
 }
 
 }  // extern "C"

@@ -361,28 +361,28 @@ def move_particles_(particles, particle_args=(), *, handle=None):
     return out
 
 
-def _vertex_op(fn, entry, first, second, F, pF, particles, handle):
+def _field_op(entry, first, second, F, pF, kind, particles, handle):
+    """operators 3, 4, 6, 7: one particle field pF and one grid field F on the vertices or the centres; `first` is the one written"""
+    fn = entry + "!"
     _check_particles(particles, fn, (2, 3))
     _check_field(particles, pF, "pF", fn)
-    want = tuple(n + 1 for n in particles.ni)
-    if not isinstance(F, torch.Tensor) or tuple(F.shape) != want:
-        raise ValueError(f"{fn}: F is {tuple(F.shape) if isinstance(F, torch.Tensor) else type(F).__name__}; {particles.ni} cells need the vertex field {want}")
+    _check_grid_field(particles, F, "F", tuple(n + 1 for n in particles.ni) if kind == "vertex" else particles.ni, kind, fn)
+    if entry == "centroid2particle" and min(particles.ni) < 2:
+        raise ValueError(f"{fn}: {particles.ni} cells (interpolation between centres needs {'nx >= 2 and ny >= 2' if len(particles.ni) == 2 else 'every extent >= 2'})")
     h = _h(pF, handle)
-    if F.device != pF.device:
-        raise ValueError(f"{fn}: F is on {F.device}, pF on {pF.device}")
     s = particles._struct()
     h.call(f"jrx_particles{len(particles.ni)}d_{entry}", C.c_void_p(ptr(first)), C.c_void_p(ptr(second)), C.byref(s))
 
 
 def grid2particle_(pF, F, particles, *, handle=None):
     """grid2particle!(pF, xvi, F, particles): the vertex field F (nx+1, ny+1[, nz+1]) to the particles, bilinear (trilinear) in the cell of each particle's bucket"""
-    _vertex_op("grid2particle!", "grid2particle", pF, F, F, pF, particles, handle)
+    _field_op("grid2particle", pF, F, F, pF, "vertex", particles, handle)
 
 
 def particle2grid_(F, pF, particles, *, handle=None):
     """particle2grid!(F, pF, xvi, particles): the particle field pF to the vertex field F (nx+1, ny+1[, nz+1]), weighted by the bilinear (trilinear) distance of
     each particle of the up to four (eight) cells around a vertex; a vertex without a particle around it keeps its value"""
-    _vertex_op("particle2grid!", "particle2grid", F, pF, F, pF, particles, handle)
+    _field_op("particle2grid", F, pF, F, pF, "vertex", particles, handle)
 
 
 def update_phase_ratios_(phase_ratios, particles, pPhases, *, handle=None):
@@ -451,27 +451,13 @@ def _vec(ts):
 def centroid2particle_(pF, F, particles, *, handle=None):
     """centroid2particle!(pF, F, particles): the centre field F (nx, ny[, nz]) to the particles, bilinear (trilinear) between the four (eight) centres around each
     particle's coordinate; a particle in the outer half cells extrapolates from the outermost pair.  Needs every extent >= 2 (include/jrx.h, operator 6)."""
-    fn = "centroid2particle!"
-    _check_particles(particles, fn, (2, 3))
-    _check_field(particles, pF, "pF", fn)
-    _check_grid_field(particles, F, "F", particles.ni, "centre", fn)
-    if min(particles.ni) < 2:
-        raise ValueError(f"{fn}: {particles.ni} cells (interpolation between centres needs {'nx >= 2 and ny >= 2' if len(particles.ni) == 2 else 'every extent >= 2'})")
-    h = _h(pF, handle)
-    s = particles._struct()
-    h.call(f"jrx_particles{len(particles.ni)}d_centroid2particle", C.c_void_p(ptr(pF)), C.c_void_p(ptr(F)), C.byref(s))
+    _field_op("centroid2particle", pF, F, F, pF, "centre", particles, handle)
 
 
 def particle2centroid_(F, pF, particles, *, handle=None):
     """particle2centroid!(F, pF, particles): the particle field pF to the centre field F (nx, ny[, nz]), each cell from its own bucket weighted by the bilinear
     (trilinear) distance to the centre; a cell without a particle keeps its value (operator 7)"""
-    fn = "particle2centroid!"
-    _check_particles(particles, fn, (2, 3))
-    _check_field(particles, pF, "pF", fn)
-    _check_grid_field(particles, F, "F", particles.ni, "centre", fn)
-    h = _h(pF, handle)
-    s = particles._struct()
-    h.call(f"jrx_particles{len(particles.ni)}d_particle2centroid", C.c_void_p(ptr(F)), C.c_void_p(ptr(pF)), C.byref(s))
+    _field_op("particle2centroid", F, pF, F, pF, "centre", particles, handle)
 
 
 def _stress_fields(particles, pτ, fn):

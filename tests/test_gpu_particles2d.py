@@ -3,127 +3,24 @@ jrx_particles2d_* entry points) against the NumPy restatement (tests/_particles2
 particle fields, ratios and counters BIT FOR BIT (compared as 64-bit patterns: the kernels have no fma, the library is built without contraction, every
 kernel is a gather in a fixed order), the inputs untouched, sentinel-filled outputs fully written, and every refusal with "stat_particles_launches" unchanged.
 
-Sizes: (7, 5) is one block with ragged edges; (33, 17) has 561 cells and 612 nodes: more than two 256-thread blocks in y.  max_xcell = 12, nxcell = 4, jittered.
+Sizes: (7, 5) is one block with ragged edges; (33, 17) has 561 cells and 612 nodes: more than two 256-thread blocks in y; (128, 5) is the
+smallest shape whose cell launches have two block columns and whose node launches have three.  max_xcell = 12, nxcell = 4, jittered.  The helpers shared with the
+other particle files are in tests/_particles_gpu.py.
 Where a test asserts that a counter is zero or positive, the restatement shows it on the CPU before the device is asked.
 Not exercised: the refusal of a handle with a communicator (it needs a second rank)."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 
 import _particles2d as PT
+from _particles_gpu import D, MAX_XCELL, NXCELL, ORIGIN, SENTINEL, _V, _assert_state, _bits, _cloud, _dev, _device_particles, _host, _launches, _move, _rotation, _same, _up
+from _particles_gpu import h          # noqa: F401 -- the module's handle, a fixture
 
 pytestmark = pytest.mark.gpu
-SHAPES = [(7, 5), (33, 17)]
-DX, DY = 0.125, 0.09375
-ORIGIN = (0.25, -0.5)
-NXCELL, MAX_XCELL = 4, 12
-SENTINEL = -7.0e30
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _up(a):
-    from justrelax_jl_amd.arrays import from_numpy
-    return from_numpy(np.asarray(a, dtype=np.float64), _dev())
-
-
-@pytest.fixture(scope="module")
-def h(jr):
-    from justrelax_jl_amd import _lib
-    return _lib.Handle(_dev().index)
-
-
-def _xvi(ni):
-    return tuple(ORIGIN[d] + np.arange(ni[d] + 1) * (DX, DY)[d] for d in range(2))
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def _same(got, want):
-    return got.shape == want.shape and got.dtype == want.dtype and np.array_equal(_bits(got), _bits(want))
-
-
-@functools.lru_cache(maxsize=None)
-def _cloud0(ni):
-    """the seeded cloud and three particle fields: phases 1 .. 3 in vertical stripes with a random sprinkle, a temperature, an identity"""
-    q = PT.init_particles(NXCELL, MAX_XCELL, 2, _xvi(ni), ni, rng=np.random.default_rng(20261020 + ni[0]))
-    rng = np.random.default_rng(7 + ni[0])
-    a = q.active != 0
-    ph = np.where(a, 1.0 + np.floor(3.0 * (q.px - q.x0) / (ni[0] * DX)), 0.0)
-    ph = np.where(a & (rng.random(a.shape) < 0.2), rng.integers(1, 4, a.shape).astype(np.float64), ph)
-    pT = np.where(a, rng.uniform(300.0, 1600.0, a.shape), 0.0)
-    pid = np.where(a, np.arange(a.size).reshape(a.shape) + 1.0, 0.0)
-    return q, (ph, pT, pid)
-
-
-def _cloud(ni):
-    q, f = _cloud0(ni)
-    return PT.copy(q), tuple(x.copy() for x in f)
-
-
-def _V(ni, fx, fy):
-    """(Vx, Vy) from functions of the node coordinates, ghost layers included"""
-    nx, ny = ni
-    xv, yv = ORIGIN[0] + np.arange(nx + 1) * DX, ORIGIN[1] + np.arange(ny + 1) * DY
-    xg, yg = ORIGIN[0] + (np.arange(nx + 2) - 0.5) * DX, ORIGIN[1] + (np.arange(ny + 2) - 0.5) * DY
-    X, Y = np.meshgrid(xv, yg, indexing="ij")
-    Vx = np.asfortranarray(fx(X, Y) + 0.0 * X)
-    X, Y = np.meshgrid(xg, yv, indexing="ij")
-    return Vx, np.asfortranarray(fy(X, Y) + 0.0 * X)
-
-
-def _rotation(ni, courant=0.5):
-    cx, cy = ORIGIN[0] + 0.5 * ni[0] * DX, ORIGIN[1] + 0.5 * ni[1] * DY
-    w = courant * min(DX, DY) / np.hypot(0.5 * ni[0] * DX, 0.5 * ni[1] * DY)          # dt = 1
-    return _V(ni, lambda X, Y: -w * (Y - cy), lambda X, Y: w * (X - cx))
-
-
-def _device_particles(jr, q, fields=()):
-    """a device Particles holding the cloud q, its particle fields, and sentinels in everything the move writes"""
-    import torch
-    p = jr.init_particles(jr.AMDGPUBackend, q.nxcell, q.max_xcell, q.min_xcell, _xvi((q.nx, q.ny)), (q.nx, q.ny))
-    assert (p.x0, p.y0, p.dx, p.dy, p._dx, p._dy) == (q.x0, q.y0, q.dx, q.dy, q._dx, q._dy)
-    p.coords[0].copy_(_up(q.px)), p.coords[1].copy_(_up(q.py))
-    p.index.copy_(torch.from_numpy(np.ascontiguousarray(q.active.T)).permute(2, 1, 0).to(_dev()))
-    dev = jr.init_cell_arrays(p, len(fields)) if fields else ()
-    for d, f in zip(dev, fields):
-        d.copy_(_up(f))
-        p._twins[id(d)][1].fill_(SENTINEL)
-    p._coords2[0].fill_(SENTINEL), p._coords2[1].fill_(SENTINEL), p._index2.fill_(-77)
-    return p, dev
-
-
-def _host(jr, p):
-    return jr.to_numpy(p.coords[0]), jr.to_numpy(p.coords[1]), np.ascontiguousarray(p.index.permute(2, 1, 0).contiguous().cpu().numpy().T)
-
-
-def _assert_state(jr, p, dev, q, fields, what=""):
-    px, py, act = _host(jr, p)
-    assert _same(act, q.active), (what, "active", int((act != q.active).sum()))
-    assert _same(px, q.px), (what, "px", int((_bits(px) != _bits(q.px)).sum()))
-    assert _same(py, q.py), (what, "py", int((_bits(py) != _bits(q.py)).sum()))
-    for k, (d, f) in enumerate(zip(dev, fields)):
-        assert _same(jr.to_numpy(d), f), (what, "field", k)
-
-
-def _move(jr, p, dev, h):
-    """move_particles_ with the error of a lossy move turned back into its counts"""
-    try:
-        return jr.move_particles_(p, dev, handle=h), None
-    except RuntimeError as e:
-        return e.counts, str(e)
-
-
-def _launches(h):
-    return h.get_option("stat_particles_launches")
+SHAPES = [(7, 5), (33, 17), (128, 5)]
+DX, DY = D[:2]
+NXCELL = NXCELL[2]
 
 
 # ---------------------------------------------------------------------------------------------- advect + move

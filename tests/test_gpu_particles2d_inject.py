@@ -4,7 +4,8 @@ counters BIT FOR BIT, the grid fields and every slot active at entry untouched, 
 unchanged and nothing written.
 
 Shapes: (7, 5) is one block with ragged edges, (33, 17) has 561 cells in five blocks, (1, 6) has no x neighbours (vertex and donor fields only: centres need
-nx >= 2).  nxcell = 4 (a 2 x 2 lattice), max_xcell = 12; the cloud is that of tests/test_gpu_particles2d.py.  Where a test needs a counter to be positive or
+nx >= 2), (128, 5) is the smallest shape whose launch has two block columns.  nxcell = 4 (a 2 x 2 lattice), max_xcell = 12; the cloud is that of
+tests/test_gpu_particles2d.py (_cloud0 of tests/_particles_gpu.py).  Where a test needs a counter to be positive or
 zero, the restatement shows it on the CPU before the device is asked.  Not exercised: the refusal of a handle with a communicator (it needs a second rank)."""
 import ctypes as C
 import functools
@@ -14,52 +15,13 @@ import pytest
 
 import _particles2d as PT
 import _particles2d_inject as INJ
+from _particles_gpu import D, MAX_XCELL, NXCELL, ORIGIN, SENTINEL, _V, _assert_state, _bits, _cloud0, _dev, _device_particles, _host_int as _mask, _launches, _same, _up, _xvi
+from _particles_gpu import h          # noqa: F401 -- the module's handle, a fixture
 
 pytestmark = pytest.mark.gpu
-SHAPES = [(7, 5), (33, 17), (1, 6)]
-DX, DY = 0.125, 0.09375
-ORIGIN = (0.25, -0.5)
-NXCELL, MAX_XCELL = 4, 12
-SENTINEL = -7.0e30
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _up(a):
-    from justrelax_jl_amd.arrays import from_numpy
-    return from_numpy(np.asarray(a, dtype=np.float64), _dev())
-
-
-@pytest.fixture(scope="module")
-def h(jr):
-    from justrelax_jl_amd import _lib
-    return _lib.Handle(_dev().index)
-
-
-def _xvi(ni):
-    return tuple(ORIGIN[d] + np.arange(ni[d] + 1) * (DX, DY)[d] for d in range(2))
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def _same(got, want):
-    return got.shape == want.shape and got.dtype == want.dtype and np.array_equal(_bits(got), _bits(want))
-
-
-def _V(ni, fx, fy):
-    nx, ny = ni
-    xv, yv = ORIGIN[0] + np.arange(nx + 1) * DX, ORIGIN[1] + np.arange(ny + 1) * DY
-    xg, yg = ORIGIN[0] + (np.arange(nx + 2) - 0.5) * DX, ORIGIN[1] + (np.arange(ny + 2) - 0.5) * DY
-    X, Y = np.meshgrid(xv, yg, indexing="ij")
-    Vx = np.asfortranarray(fx(X, Y) + 0.0 * X)
-    X, Y = np.meshgrid(xg, yv, indexing="ij")
-    return Vx, np.asfortranarray(fy(X, Y) + 0.0 * X)
+SHAPES = [(7, 5), (33, 17), (1, 6), (128, 5)]
+DX, DY = D[:2]
+NXCELL = NXCELL[2]
 
 
 def _flow(ni, kind, courant=0.5):
@@ -68,19 +30,6 @@ def _flow(ni, kind, courant=0.5):
     if kind == "rotation":
         return _V(ni, lambda X, Y: -w * (Y - cy), lambda X, Y: w * (X - cx))
     return _V(ni, lambda X, Y: w * (X - cx), lambda X, Y: w * (Y - cy))          # diverging
-
-
-@functools.lru_cache(maxsize=None)
-def _cloud0(ni):
-    """the seeded cloud of tests/test_gpu_particles2d.py: phases 1 .. 3 in vertical stripes with a random sprinkle, a temperature, an identity"""
-    q = PT.init_particles(NXCELL, MAX_XCELL, 2, _xvi(ni), ni, rng=np.random.default_rng(20261020 + ni[0]))
-    rng = np.random.default_rng(7 + ni[0])
-    a = q.active != 0
-    ph = np.where(a, 1.0 + np.floor(3.0 * (q.px - q.x0) / (ni[0] * DX)), 0.0)
-    ph = np.where(a & (rng.random(a.shape) < 0.2), rng.integers(1, 4, a.shape).astype(np.float64), ph)
-    pT = np.where(a, rng.uniform(300.0, 1600.0, a.shape), 0.0)
-    pid = np.where(a, np.arange(a.size).reshape(a.shape) + 1.0, 0.0)
-    return q, (ph, pT, pid)
 
 
 @functools.lru_cache(maxsize=None)
@@ -102,35 +51,6 @@ def _moved0(ni):
 def _moved(ni):
     q, f, g = _moved0(ni)
     return PT.copy(q), [x.copy() for x in f], g
-
-
-def _device_particles(jr, q, fields=()):
-    """a device Particles holding the cloud q and its particle fields; -77 in the mask the injection writes"""
-    import torch
-    p = jr.init_particles(jr.AMDGPUBackend, q.nxcell, q.max_xcell, q.min_xcell, _xvi((q.nx, q.ny)), (q.nx, q.ny))
-    assert (p.x0, p.y0, p.dx, p.dy, p._dx, p._dy) == (q.x0, q.y0, q.dx, q.dy, q._dx, q._dy)
-    p.coords[0].copy_(_up(q.px)), p.coords[1].copy_(_up(q.py))
-    p.index.copy_(torch.from_numpy(np.ascontiguousarray(q.active.T)).permute(2, 1, 0).to(_dev()))
-    dev = jr.init_cell_arrays(p, len(fields)) if fields else ()
-    for d, f in zip(dev, fields):
-        d.copy_(_up(f))
-    p._index2.fill_(-77)
-    return p, dev
-
-
-def _mask(t):
-    return np.ascontiguousarray(t.permute(2, 1, 0).contiguous().cpu().numpy().T)
-
-
-def _assert_state(jr, p, dev, q, fields, what=""):
-    act = _mask(p.index)
-    assert _same(act, q.active), (what, "active", int((act != q.active).sum()))
-    for k, (g, w) in enumerate(zip((jr.to_numpy(p.coords[0]), jr.to_numpy(p.coords[1])) + tuple(jr.to_numpy(d) for d in dev), (q.px, q.py) + tuple(fields))):
-        assert _same(g, w), (what, ("px", "py")[k] if k < 2 else f"field {k - 2}", int((_bits(g) != _bits(w)).sum()))
-
-
-def _launches(h):
-    return h.get_option("stat_particles_launches")
 
 
 def _specs(ni):

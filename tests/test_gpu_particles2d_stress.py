@@ -7,7 +7,8 @@ chains ("particles_stress_fused" 1 against 0, device against device, both method
 sincos: within 1e-13 max|τ|, the project's bound for device arithmetic against NumPy (tests/test_gpu_stress_rotation.py); every case prints its measured figure.
 
 Sizes: (2, 2) is the smallest grid operator 6 accepts and three quarters of its area extrapolate; (7, 5) is one ragged block; (33, 17) has 561 cells and 612 nodes:
-more than two 256-thread blocks in y.  max_xcell = 12, nxcell = 4, jittered.  The cloud is the restatement's after one advect_rk2 + move under a rigid rotation:
+more than two 256-thread blocks in y; (128, 5) is the smallest shape whose cell launches have two block columns and whose node launches have three.
+max_xcell = 12, nxcell = 4, jittered.  The cloud is the restatement's after one advect_rk2 + move under a rigid rotation (_rotated of tests/_particles_gpu.py):
 buckets unevenly filled, inactive slots in every cell.  It is used as it is and, where the grid has one, with an interior cell emptied; a 2 x 2 grid has no interior
 cell (each of its cells is the only one of a corner vertex).  The restatement shows on the CPU, before the device is asked, that in the first cloud every centre
 and vertex has den > 0 and in the second exactly the emptied centre has den == 0 and no vertex has.
@@ -20,64 +21,22 @@ import pytest
 
 import _particles2d as PT
 import _particles2d_stress as PS
+from _particles_gpu import D, MAX_XCELL, SENTINEL, _P, _assert_cloud_untouched, _bits, _device_particles, _handle, _launches, _ndiff, _rotated, _rotation, _same, _up, _vec
 
 pytestmark = pytest.mark.gpu
-SHAPES = [(2, 2), (7, 5), (33, 17)]
+SHAPES = [(2, 2), (7, 5), (33, 17), (128, 5)]
 CASES = [(ni, e) for ni in SHAPES for e in (False, True) if not (e and ni == (2, 2))]
-DX, DY = 0.125, 0.09375
-ORIGIN = (0.25, -0.5)
-NXCELL, MAX_XCELL = 4, 12
-SENTINEL = -7.0e30
+DX, DY = D[:2]
 DT = 0.5          # |ω| <= 2: |ω dt| <= 1
 METHODS = {"matrix": 0, "jaumann": 1}
 RTOL = 1e-13
 
 
-def _dev():
-    import torch
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _up(a):
-    from justrelax_jl_amd.arrays import from_numpy
-    return from_numpy(np.array(a, dtype=np.float64, order="K"), _dev())          # a copy: the shared cases are read-only
-
-
 @pytest.fixture(scope="module")
 def h(jr):
-    from justrelax_jl_amd import _lib
-    hh = _lib.Handle(_dev().index)
+    hh = _handle()
     yield hh
     hh.set_option("particles_stress_fused", 1)
-
-
-def _xvi(ni):
-    return tuple(ORIGIN[d] + np.arange(ni[d] + 1) * (DX, DY)[d] for d in range(2))
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def _same(got, want):
-    return got.shape == want.shape and got.dtype == want.dtype and np.array_equal(_bits(got), _bits(want))
-
-
-def _ndiff(got, want):
-    return int((_bits(got) != _bits(want)).sum())
-
-
-def _rotation(ni, courant=0.5):
-    nx, ny = ni
-    cx, cy = ORIGIN[0] + 0.5 * nx * DX, ORIGIN[1] + 0.5 * ny * DY
-    w = courant * min(DX, DY) / np.hypot(0.5 * nx * DX, 0.5 * ny * DY)          # dt = 1
-    xv, yv = _xvi(ni)
-    xg, yg = ORIGIN[0] + (np.arange(nx + 2) - 0.5) * DX, ORIGIN[1] + (np.arange(ny + 2) - 0.5) * DY
-    X, Y = np.meshgrid(xv, yg, indexing="ij")
-    Vx = np.asfortranarray(-w * (Y - cy))
-    X, Y = np.meshgrid(xg, yv, indexing="ij")
-    return Vx, np.asfortranarray(w * (X - cx))
 
 
 def _frozen(*arrays):
@@ -89,11 +48,7 @@ def _frozen(*arrays):
 @functools.lru_cache(maxsize=None)
 def _case(ni, emptied):
     """(cloud, hole, (pτxx, pτyy, pτxy, pω), (τxx, τyy, τxy, ωxy)): computed once per case and shared read-only"""
-    q = PT.init_particles(NXCELL, MAX_XCELL, 2, _xvi(ni), ni, rng=np.random.default_rng(20261021 + ni[0]))
-    Vx, Vy = _rotation(ni)
-    PT.advect_rk2(q, Vx, Vy, 1.0)
-    q, _, c = PT.move(q)
-    assert c["n_far"] == 0 and c["n_overflow"] == 0
+    q = _rotated(ni)
     hole = (ni[0] // 2, ni[1] // 2) if emptied else None
     if emptied:
         q.active[hole], q.px[hole], q.py[hole] = 0, 0.0, 0.0
@@ -120,35 +75,6 @@ def _with_nan(q, second=np.nan):
     assert q.active[i, j, 0] == 1 and q.active[0, q.ny - 1, 0] == 1
     q.px[i, j, 0], q.py[0, q.ny - 1, 0] = np.nan, second
     return q, ((i, j, 0), (0, q.ny - 1, 0))
-
-
-def _device_particles(jr, q, fields=()):
-    import torch
-    p = jr.init_particles(jr.AMDGPUBackend, q.nxcell, q.max_xcell, q.min_xcell, _xvi((q.nx, q.ny)), (q.nx, q.ny))
-    assert (p.x0, p.y0, p.dx, p.dy, p._dx, p._dy) == (q.x0, q.y0, q.dx, q.dy, q._dx, q._dy)
-    p.coords[0].copy_(_up(q.px)), p.coords[1].copy_(_up(q.py))
-    p.index.copy_(torch.from_numpy(np.ascontiguousarray(q.active.T)).permute(2, 1, 0).to(_dev()))
-    dev = jr.init_cell_arrays(p, len(fields)) if fields else ()
-    for d, f in zip(dev, fields):
-        d.copy_(_up(f))
-    return p, dev
-
-
-def _assert_cloud_untouched(jr, p, q):
-    act = np.ascontiguousarray(p.index.permute(2, 1, 0).contiguous().cpu().numpy().T)
-    assert _same(jr.to_numpy(p.coords[0]), q.px) and _same(jr.to_numpy(p.coords[1]), q.py) and _same(act, q.active)
-
-
-def _launches(h):
-    return h.get_option("stat_particles_launches")
-
-
-def _P(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _vec(ts):
-    return (C.c_void_p * len(ts))(*(t.data_ptr() for t in ts))
 
 
 def _rotate_stress(h, p, pdev, gdev, method, fused):

@@ -11,7 +11,8 @@ tests/test_particles2d_subgrid_restatement.py).
 4. The refusals through the C ABI: status 4, a text, "stat_particles_launches" unchanged, the outputs still sentinel-filled.
 
 Sizes: (2, 2) is the smallest grid the centre form accepts and three quarters of its area extrapolate; (7, 5) is one ragged block; (33, 17) has 561 cells and 612
-vertices: more than two 256-thread blocks.  nxcell = 4, max_xcell = 12, jittered.  The cloud is the restatement's after one advect_rk2 + move under a rigid rotation.
+vertices: more than two 256-thread blocks; (128, 5) is the smallest shape whose cell launches have two block columns and whose node launches have three.
+nxcell = 4, max_xcell = 12, jittered.  The cloud is the restatement's after one advect_rk2 + move under a rigid rotation (_rotated of tests/_particles_gpu.py).
 Cases: the cloud as it is; centre form: an interior cell emptied ((2, 2) has none); vertex form: the corner cell (0, 0) emptied, so that vertex (0, 0) has den == 0,
 on (2, 2) too; a copy with a NaN x in one active slot and an infinite y in another.  The restatement shows on the CPU, before the device is asked, that in the plain
 cloud every centre and every vertex has den > 0 and in an emptied cloud exactly the one intended node has den == 0.
@@ -22,75 +23,38 @@ import functools
 import numpy as np
 import pytest
 
-import _particles2d as PT
 import _particles2d_stress as PS
 import _particles2d_subgrid as SG
+from _particles_gpu import D, MAX_XCELL, SENTINEL, _assert_cloud_untouched, _bits, _device_particles, _handle, _launches, _ndiff, _rotated, _same, _up
 
 pytestmark = pytest.mark.gpu
-SHAPES = [(2, 2), (7, 5), (33, 17)]
-CASES = [("center", ni, c) for ni in SHAPES for c in ("plain", "emptied", "non-finite") if not (c == "emptied" and ni == (2, 2))] + \
-        [("vertex", ni, c) for ni in SHAPES for c in ("plain", "emptied", "non-finite")]
+SHAPES = [(2, 2), (7, 5), (33, 17), (128, 5)]
+
+
+def _cases(shapes):
+    return [("center", ni, c) for ni in shapes for c in ("plain", "emptied", "non-finite") if not (c == "emptied" and ni == (2, 2))] + \
+           [("vertex", ni, c) for ni in shapes for c in ("plain", "emptied", "non-finite")]
+
+
+CASES = _cases(SHAPES[:3]) + _cases(SHAPES[3:])          # (128, 5) behind the others: the cases before it keep their test ids
 DS = [0.0, 0.3, 1.0]
-DX, DY = 0.125, 0.09375
-ORIGIN = (0.25, -0.5)
-NXCELL, MAX_XCELL = 4, 12
-SENTINEL = -7.0e30
+DX, DY = D[:2]
 DT = 2.0e3
 RTOL = 1e-13
 LAUNCHES = {("center", 1): 2, ("vertex", 1): 3, ("center", 0): 7, ("vertex", 0): 7}          # include/jrx.h, operators 10 and 11
 ENTRY = {"center": "jrx_particles2d_subgrid_diffusion_centroid", "vertex": "jrx_particles2d_subgrid_diffusion_vertex"}
 
 
-def _dev():
-    import torch
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _up(a):
-    from justrelax_jl_amd.arrays import from_numpy
-    return from_numpy(np.array(a, dtype=np.float64, order="K"), _dev())          # a copy: the shared cases are read-only
-
-
 @pytest.fixture(scope="module")
 def h(jr):
-    from justrelax_jl_amd import _lib
-    hh = _lib.Handle(_dev().index)
+    hh = _handle()
     default = hh.get_option("particles_subgrid_fused")
     yield hh
     hh.set_option("particles_subgrid_fused", default)
 
 
-def _xvi(ni):
-    return tuple(ORIGIN[d] + np.arange(ni[d] + 1) * (DX, DY)[d] for d in range(2))
-
-
 def _ext(loc, ni):
     return tuple(ni) if loc == "center" else (ni[0] + 1, ni[1] + 1)
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def _same(got, want):
-    return got.shape == want.shape and got.dtype == want.dtype and np.array_equal(_bits(got), _bits(want))
-
-
-def _ndiff(got, want):
-    return int((_bits(got) != _bits(want)).sum())
-
-
-def _rotation(ni, courant=0.5):
-    nx, ny = ni
-    cx, cy = ORIGIN[0] + 0.5 * nx * DX, ORIGIN[1] + 0.5 * ny * DY
-    w = courant * min(DX, DY) / np.hypot(0.5 * nx * DX, 0.5 * ny * DY)          # dt = 1
-    xv, yv = _xvi(ni)
-    xg, yg = ORIGIN[0] + (np.arange(nx + 2) - 0.5) * DX, ORIGIN[1] + (np.arange(ny + 2) - 0.5) * DY
-    X, Y = np.meshgrid(xv, yg, indexing="ij")
-    Vx = -w * (Y - cy)
-    X, Y = np.meshgrid(xg, yv, indexing="ij")
-    return Vx, w * (X - cx)
 
 
 def _ghosted(dT):
@@ -102,10 +66,7 @@ def _ghosted(dT):
 @functools.lru_cache(maxsize=None)
 def _case(loc, ni, case):
     """(cloud, pT, T_grid, ΔT_grid, ΔT_grid with sentinel ghosts, dt0): computed once per case and shared read-only"""
-    q = PT.init_particles(NXCELL, MAX_XCELL, 2, _xvi(ni), ni, rng=np.random.default_rng(20261021 + ni[0]))
-    PT.advect_rk2(q, *_rotation(ni), 1.0)
-    q, _, c = PT.move(q)
-    assert c["n_far"] == 0 and c["n_overflow"] == 0
+    q = _rotated(ni)
     hole = None
     if case == "emptied":
         hole = (ni[0] // 2, ni[1] // 2) if loc == "center" else (0, 0)
@@ -144,24 +105,6 @@ def _want(loc, ni, case, d):
     return SG.FORMS[loc](pT, T, dT, dt0, q, DT, d=d)
 
 
-def _device_particles(jr, q):
-    import torch
-    p = jr.init_particles(jr.AMDGPUBackend, q.nxcell, q.max_xcell, q.min_xcell, _xvi((q.nx, q.ny)), (q.nx, q.ny))
-    assert (p.x0, p.y0, p.dx, p.dy, p._dx, p._dy) == (q.x0, q.y0, q.dx, q.dy, q._dx, q._dy)
-    p.coords[0].copy_(_up(q.px)), p.coords[1].copy_(_up(q.py))
-    p.index.copy_(torch.from_numpy(np.ascontiguousarray(q.active.T)).permute(2, 1, 0).to(_dev()))
-    return p
-
-
-def _assert_cloud_untouched(jr, p, q):
-    act = np.ascontiguousarray(p.index.permute(2, 1, 0).contiguous().cpu().numpy().T)
-    assert _same(jr.to_numpy(p.coords[0]), q.px) and _same(jr.to_numpy(p.coords[1]), q.py) and _same(act, q.active)
-
-
-def _launches(h):
-    return h.get_option("stat_particles_launches")
-
-
 def _sentinel_arrays(jr, p, loc, dt0):
     sa = jr.SubgridDiffusionCellArrays(p, loc=loc)
     sa.pT0.fill_(SENTINEL), sa.pΔT.fill_(SENTINEL), sa.ΔT_subgrid.fill_(SENTINEL)
@@ -187,7 +130,7 @@ def _run(jr, h, loc, p, pT, T, dT, dt0, d, fused):
 def test_the_fused_form_equals_its_chain_and_the_restatement(jr, h, loc, ni, case, d):
     q, pT, T, dT, dTg, dt0 = _case(loc, ni, case)
     want = _want(loc, ni, case, d)
-    p = _device_particles(jr, q)
+    p, _ = _device_particles(jr, q)
     dT_dev, dTg_dev, T_dev = _up(dT), _up(dTg), _up(T)
     fused, nf, sa = _run(jr, h, loc, p, pT, T_dev, dT_dev, dt0, d, 1)
     chain, nc, _ = _run(jr, h, loc, p, pT, T_dev, dT_dev, dt0, d, 0)
@@ -227,7 +170,7 @@ def test_the_emptied_nodes_keep_the_whole_grid_change_on_the_device(jr, h):
     """what the emptied cases are there for, read off the device's ΔT_subgrid: the den == 0 node holds ΔT_grid itself, and no other node does"""
     for loc, ni in (("center", (7, 5)), ("vertex", (2, 2))):
         q, pT, T, dT, _, dt0 = _case(loc, ni, "emptied")
-        p = _device_particles(jr, q)
+        p, _ = _device_particles(jr, q)
         for fused in (1, 0):
             out, _, _ = _run(jr, h, loc, p, pT, _up(T), _up(dT), dt0, 1.0, fused)
             same = out["ΔT_subgrid"] == dT
@@ -241,7 +184,7 @@ def test_the_library_refuses_with_status_4_a_text_and_no_launch(jr, h):
     L = h.lib
     for loc in ("center", "vertex"):
         q, pT, T, dT, dTg, dt0 = _case(loc, ni, "plain")
-        p = _device_particles(jr, q)
+        p, _ = _device_particles(jr, q)
         (dpT,) = jr.init_cell_arrays(p, 1)
         dpT.fill_(SENTINEL)
         sa = _sentinel_arrays(jr, p, loc, dt0)
@@ -316,7 +259,7 @@ def test_dt0_reaches_the_particles_by_centroid2particle_and_the_step_follows(jr,
     ni = (7, 5)
     q, pT, T, dT, dTg, _ = _case("center", ni, "plain")
     g0 = np.asfortranarray(np.random.default_rng(5).uniform(1.0, 1.0e6, ni))
-    p = _device_particles(jr, q)
+    p, _ = _device_particles(jr, q)
     (dpT,) = jr.init_cell_arrays(p, 1)
     dpT.copy_(_up(pT))
     sa = jr.SubgridDiffusionCellArrays(p, loc="center")

@@ -8,7 +8,8 @@ Sizes: the kernels run 64 x 2 x 2 blocks.  (5, 4, 3) is smaller than a block alo
 ragged remainder (x: one block and 3 cells; y: four blocks and 1; z: and its node box of 7 three blocks and 1).  nxcell = 8, max_xcell = 12, jittered seeding;
 three phases, a temperature and an identity field.  Where a test asserts that a counter is zero or positive, the restatement shows it on the CPU before the
 device is asked.  The move runs in both forms (tuning key particles3d_move_codes = 1 and 0) against the same expected bits, the phase ratios as one launch and as
-two.  Not exercised: the refusal of a handle with a communicator (it needs a second rank)."""
+two.  The helpers shared with the 2D files are in tests/_particles_gpu.py.  Not exercised: the refusal of a handle with a communicator (it needs a second
+rank)."""
 import ctypes as C
 import functools
 
@@ -16,86 +17,13 @@ import numpy as np
 import pytest
 
 import _particles3d as PT
+from _particles_gpu import D, MAX_XCELL, NXCELL, ORIGIN, SENTINEL, _V, _assert_state, _bits, _cloud, _cloud0, _dev, _device_particles, _host, _host_int, _launches, _move
+from _particles_gpu import _rotation, _same, _up
+from _particles_gpu import h          # noqa: F401 -- the module's handle, a fixture
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(5, 4, 3), (67, 9, 6)]
-D = (0.125, 0.09375, 0.0625)
-ORIGIN = (0.25, -0.5, 1.0)
-NXCELL, MAX_XCELL = 8, 12
-SENTINEL = -7.0e30
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _up(a):
-    from justrelax_jl_amd.arrays import from_numpy
-    return from_numpy(np.asarray(a, dtype=np.float64), _dev())
-
-
-def _up_int(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a.T)).permute(*reversed(range(a.ndim))).to(_dev())
-
-
-@pytest.fixture(scope="module")
-def h(jr):
-    from justrelax_jl_amd import _lib
-    return _lib.Handle(_dev().index)
-
-
-def _xi_vel(ni):
-    xv = [ORIGIN[d] + np.arange(ni[d] + 1) * D[d] for d in range(3)]
-    gh = [ORIGIN[d] + (np.arange(ni[d] + 2) - 0.5) * D[d] for d in range(3)]
-    return tuple(tuple(xv[d] if d == c else gh[d] for d in range(3)) for c in range(3))
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def _same(got, want):
-    return got.shape == want.shape and got.dtype == want.dtype and np.array_equal(_bits(got), _bits(want))
-
-
-@functools.lru_cache(maxsize=None)
-def _cloud0(ni):
-    """the seeded cloud and three particle fields: phases 1 .. 3 in slabs along x with a random sprinkle, a temperature, an identity"""
-    q = PT.init_particles(NXCELL, MAX_XCELL, 2, *_xi_vel(ni), rng=np.random.default_rng(20261021 + ni[0]))
-    rng = np.random.default_rng(7 + ni[0])
-    a = q.active != 0
-    ph = np.where(a, 1.0 + np.floor(3.0 * (q.px - q.x0) / (ni[0] * D[0])), 0.0)
-    ph = np.where(a & (rng.random(a.shape) < 0.2), rng.integers(1, 4, a.shape).astype(np.float64), ph)
-    pT = np.where(a, rng.uniform(300.0, 1600.0, a.shape), 0.0)
-    pid = np.where(a, np.arange(a.size).reshape(a.shape) + 1.0, 0.0)
-    return q, (ph, pT, pid)
-
-
-def _cloud(ni):
-    q, f = _cloud0(ni)
-    return PT.copy(q), tuple(x.copy() for x in f)
-
-
-def _V(ni, fx, fy, fz):
-    """(Vx, Vy, Vz) from functions of the node coordinates, ghost layers included"""
-    out = []
-    for grids, f in zip(_xi_vel(ni), (fx, fy, fz)):
-        X, Y, Z = np.meshgrid(*grids, indexing="ij")
-        out.append(np.asfortranarray(f(X, Y, Z) + 0.0 * X))
-    return tuple(out)
-
-
-def _rotation(ni, courant=0.5):
-    """rigid rotation about a tilted axis through the box centre; dt = 1 and the fastest corner moves `courant` of the smallest spacing"""
-    c = [ORIGIN[d] + 0.5 * ni[d] * D[d] for d in range(3)]
-    axis = np.array([1.0, 2.0, 3.0]) / np.sqrt(14.0)
-    half = np.array([0.5 * ni[d] * D[d] for d in range(3)])
-    w = courant * min(D) / np.linalg.norm(half) * axis
-    return _V(ni, lambda X, Y, Z: w[1] * (Z - c[2]) - w[2] * (Y - c[1]), lambda X, Y, Z: w[2] * (X - c[0]) - w[0] * (Z - c[2]),
-              lambda X, Y, Z: w[0] * (Y - c[1]) - w[1] * (X - c[0]))
+NXCELL = NXCELL[3]
 
 
 @functools.lru_cache(maxsize=None)
@@ -111,45 +39,6 @@ def _advected(ni):
     return PT.copy(q), tuple(x.copy() for x in f)
 
 
-def _device_particles(jr, q, fields=()):
-    """a device Particles holding the cloud q, its particle fields, and sentinels in everything the move writes"""
-    ni = (q.nx, q.ny, q.nz)
-    p = jr.init_particles(jr.AMDGPUBackend, q.nxcell, q.max_xcell, q.min_xcell, *_xi_vel(ni))
-    assert p.ni == ni and (p.x0, p.y0, p.z0, p.dx, p.dy, p.dz, p._dx, p._dy, p._dz) == (q.x0, q.y0, q.z0, q.dx, q.dy, q.dz, q._dx, q._dy, q._dz)
-    for c, a in zip(p.coords, (q.px, q.py, q.pz)):
-        c.copy_(_up(a))
-    p.index.copy_(_up_int(q.active))
-    dev = jr.init_cell_arrays(p, len(fields)) if fields else ()
-    for d, f in zip(dev, fields):
-        d.copy_(_up(f))
-        p._twins[id(d)][1].fill_(SENTINEL)
-    for c in p._coords2:
-        c.fill_(SENTINEL)
-    p._index2.fill_(-77), p._work.fill_(99)
-    return p, dev
-
-
-def _host_int(t):
-    return np.ascontiguousarray(t.permute(*reversed(range(t.dim()))).contiguous().cpu().numpy().T)
-
-
-def _host(jr, p):
-    return tuple(jr.to_numpy(c) for c in p.coords) + (_host_int(p.index),)
-
-
-def _assert_state(jr, p, dev, q, fields, what=""):
-    px, py, pz, act = _host(jr, p)
-    assert _same(act, q.active), (what, "active", int((act != q.active).sum()))
-    for name, got, want in (("px", px, q.px), ("py", py, q.py), ("pz", pz, q.pz)):
-        assert _same(got, want), (what, name, int((_bits(got) != _bits(want)).sum()))
-    for k, (d, f) in enumerate(zip(dev, fields)):
-        assert _same(jr.to_numpy(d), f), (what, "field", k)
-
-
-def _launches(h):
-    return h.get_option("stat_particles_launches")
-
-
 def _move_both_forms(jr, h, src, fields, want, wfields, c, what=""):
     """the device move of the cloud `src` in the codes form and in the direct form against the same expected state; the buffers that were read stay as they were"""
     for codes in (1, 0):
@@ -157,10 +46,7 @@ def _move_both_forms(jr, h, src, fields, want, wfields, c, what=""):
         h.set_option("particles3d_move_codes", codes)
         try:
             n0 = _launches(h)
-            try:
-                got, msg = jr.move_particles_(p, dev, handle=h), None
-            except RuntimeError as e:
-                got, msg = e.counts, str(e)
+            got, msg = _move(jr, p, dev, h)
             assert _launches(h) == n0 + (2 if codes else 1)
         finally:
             h.set_option("particles3d_move_codes", 1)
