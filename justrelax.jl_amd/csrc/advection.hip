@@ -23,7 +23,7 @@
 //     the x stencil and the x-neighbour fluxes from the neighbouring lanes, and the y stencil and the y-neighbour fluxes of the current plane from LDS (two
 //     block barriers per plane).  The first and last wave of a block are the y halo: they evaluate only the y fluxes of their row.
 // Addressing: 32-bit element offsets (every array below 2^31 entries, checked).
-#include "jrx_internal.hpp"
+#include "op_args.hpp"
 
 namespace {
 
@@ -407,6 +407,51 @@ jrx_status launch_split3d(jrx_handle *h, const Weno3Args &a)
     return JRX_OK;
 }
 
+// The checks of both entry points.  v, vdim: the ND velocities; f: the 2 ND flux arrays -- the fused 3D form keeps every flux in registers and needs only fL
+// (its u1), so there fR .. fU may be NULL; the 2D entry point asks for all four in either form.  The velocities are only read and may share memory among
+// themselves; no other two arrays may.
+jrx_status weno_checks(jrx_handle *h, int ND, const double *u, const int64_t *udim, const double *const *v, const int64_t *const *vdim, const double *ut,
+                       double *const *f, const int64_t *wdim, int32_t method)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "WENO_advection!";
+    static const char *const vn[3] = {"vx", "vy", "vz"}, *const fname[6] = {"fL", "fR", "fB", "fT", "fD", "fU"};
+    bool null = !u || !udim || !ut || !f[0] || !wdim, fluxes = true;
+    for (int c = 0; c < ND; c++) null = null || !v[c] || !vdim[c];
+    for (int q = 1; q < 2 * ND; q++) fluxes = fluxes && f[q];
+    if (null || (ND == 2 && !fluxes)) return jrx_fail(h, JRX_ERR_ARG, "%s: NULL argument", fn);
+    if (!h->weno_fused && !fluxes) return jrx_fail(h, JRX_ERR_ARG, "%s: the per-kernel form (weno_fused = 0) needs all of fL, fR, fB, fT, fD, fU", fn);
+    if (method != 1 && method != 2) return jrx_fail(h, JRX_ERR_ARG, "%s: method must be 1 (JS) or 2 (Z), got %d", fn, (int)method);
+    if (!op_extents_ok(udim, ND)) return jrx_fail(h, JRX_ERR_ARG, "%s: size(u) = (%s)", fn, op_list(udim, ND, ", ").s);
+    for (int a = 0; a <= ND; a++) {
+        const int64_t *dim = a < ND ? vdim[a] : wdim;
+        const char *name = a < ND ? vn[a] : ND == 2 ? "weno.ut / fL / fR / fB / fT" : "weno.ut / fL / fR / fB / fT / fD / fU";
+        for (int d = 0; d < ND; d++)
+            if (dim[d] < udim[d])
+                return jrx_fail(h, JRX_ERR_ARG, "%s: %s is smaller than u along dimension %d (%lld < %lld)", fn, name, d + 1, (long long)dim[d], (long long)udim[d]);
+    }
+    // u, ut and the flux arrays that are there are written; ut stands for the flux arrays in the 2^31 test (they share its extents)
+    OpArr out[8] = {{u, 0, "u"}, {ut, 0, "ut"}}, in[3];
+    const int64_t *odim[2] = {udim, wdim};
+    int nout = 2;
+    for (int q = 0; q < 2 * ND; q++)
+        if (f[q]) out[nout++] = OpArr{f[q], 0, fname[q]};
+    for (int c = 0; c < ND; c++) in[c] = OpArr{v[c], 0, vn[c]};
+    for (int a = 0; a < ND + 2; a++) {                          // u, the velocities, ut
+        const int64_t *dim = a == 0 ? udim : a <= ND ? vdim[a - 1] : wdim;
+        if (op_2g(op_count(dim, ND, 0)))
+            return jrx_fail(h, JRX_ERR_UNSUPPORTED, "%s: %s has 2^31 or more entries (32-bit offsets)", fn, a == 0 ? "u" : a <= ND ? vn[a - 1] : "ut");
+    }
+    for (int m = 0; m < nout; m++) out[m].bytes = op_bytes(odim[m > 0], ND, 0, 0, 0);
+    for (int c = 0; c < ND; c++) in[c].bytes = op_bytes(vdim[c], ND, 0, 0, 0);
+    if (const OpClash c = op_disjoint(out, nout, in, ND)) {
+        if (c.two) return jrx_fail(h, JRX_ERR_ARG, "%s: %s and %s overlap", fn, out[c.a].name, out[c.b].name);
+        return c.a == 0 ? jrx_fail(h, JRX_ERR_ARG, "%s: u and %s overlap", fn, in[c.b].name)          // the names in argument order
+                        : jrx_fail(h, JRX_ERR_ARG, "%s: %s and %s overlap", fn, in[c.b].name, out[c.a].name);
+    }
+    return jrx_check_device(h);
+}
+
 }  // namespace
 
 extern "C" {
@@ -415,33 +460,10 @@ jrx_status jrx_weno5_advection2d(jrx_handle *h, double *u, const int64_t udim[2]
                                  const int64_t vydim[2], double *ut, double *fL, double *fR, double *fB, double *fT, const int64_t wdim[2], double dx, double dy,
                                  double dt, int32_t method)
 {
-    if (!h) return JRX_ERR_ARG;
-    if (!u || !udim || !vx || !vxdim || !vy || !vydim || !ut || !fL || !fR || !fB || !fT || !wdim)
-        return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: NULL argument");
-    if (method != 1 && method != 2) return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: method must be 1 (JS) or 2 (Z), got %d", (int)method);
-    if (udim[0] < 1 || udim[1] < 1) return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: size(u) = (%lld, %lld)", (long long)udim[0], (long long)udim[1]);
-    const int64_t *dims[4] = {udim, vxdim, vydim, wdim};
-    const char *names[4] = {"u", "vx", "vy", "weno.ut / fL / fR / fB / fT"};
-    for (int a = 1; a < 4; a++)
-        for (int d = 0; d < 2; d++)
-            if (dims[a][d] < udim[d])
-                return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: %s is smaller than u along dimension %d (%lld < %lld)", names[a], d + 1, (long long)dims[a][d],
-                                (long long)udim[d]);
-    // no two arrays may overlap, except the two read-only velocities
-    const void *p[8] = {u, vx, vy, ut, fL, fR, fB, fT};
-    const int64_t *pd[8] = {udim, vxdim, vydim, wdim, wdim, wdim, wdim, wdim};
-    const char *pn[8] = {"u", "vx", "vy", "ut", "fL", "fR", "fB", "fT"};
-    for (int a = 0; a < 8; a++) {
-        if ((double)pd[a][0] * (double)pd[a][1] >= 2147483648.0)
-            return jrx_fail(h, JRX_ERR_UNSUPPORTED, "WENO_advection!: %s has 2^31 or more entries (32-bit offsets)", pn[a]);
-        for (int b = a + 1; b < 8; b++) {
-            if (a == 1 && b == 2) continue;
-            const char *pa = (const char *)p[a], *pb = (const char *)p[b];
-            if (pa < pb + 8 * pd[b][0] * pd[b][1] && pb < pa + 8 * pd[a][0] * pd[a][1])
-                return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: %s and %s overlap", pn[a], pn[b]);
-        }
-    }
-    JRX_TRY(jrx_check_device(h));
+    const double *const v[2] = {vx, vy};
+    const int64_t *const vdim[2] = {vxdim, vydim};
+    double *const f[4] = {fL, fR, fB, fT};
+    JRX_TRY(weno_checks(h, 2, u, udim, v, vdim, ut, f, wdim, method));
     const int nx = (int)udim[0], ny = (int)udim[1], lu = (int)udim[0], lw = (int)wdim[0], lvx = (int)vxdim[0], lvy = (int)vydim[0];
     const double _dx = 1.0 / dx, _dy = 1.0 / dy;                // _di = inv.(di)
     h->stat_weno_calls++;
@@ -453,45 +475,17 @@ jrx_status jrx_weno5_advection2d(jrx_handle *h, double *u, const int64_t udim[2]
         if (method == 1) JRX_TRY(launch_split<1>(h, u, ut, fL, fR, fB, fT, vx, vy, nx, ny, lu, lw, lvx, lvy, _dx, _dy, dt));
         else JRX_TRY(launch_split<2>(h, u, ut, fL, fR, fB, fT, vx, vy, nx, ny, lu, lw, lvx, lvy, _dx, _dy, dt));
     }
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    return op_finish(h);
 }
 
 jrx_status jrx_weno5_advection3d(jrx_handle *h, double *u, const int64_t udim[3], const double *vx, const int64_t vxdim[3], const double *vy,
                                  const int64_t vydim[3], const double *vz, const int64_t vzdim[3], double *ut, double *fL, double *fR, double *fB, double *fT,
                                  double *fD, double *fU, const int64_t wdim[3], double dx, double dy, double dz, double dt, int32_t method)
 {
-    if (!h) return JRX_ERR_ARG;
-    if (!u || !udim || !vx || !vxdim || !vy || !vydim || !vz || !vzdim || !ut || !fL || !wdim) return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: NULL argument");
-    if (!h->weno_fused && (!fR || !fB || !fT || !fD || !fU))
-        return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: the per-kernel form (weno_fused = 0) needs all of fL, fR, fB, fT, fD, fU");
-    if (method != 1 && method != 2) return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: method must be 1 (JS) or 2 (Z), got %d", (int)method);
-    if (udim[0] < 1 || udim[1] < 1 || udim[2] < 1)
-        return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: size(u) = (%lld, %lld, %lld)", (long long)udim[0], (long long)udim[1], (long long)udim[2]);
-    const int64_t *dims[5] = {udim, vxdim, vydim, vzdim, wdim};
-    const char *names[5] = {"u", "vx", "vy", "vz", "weno.ut / fL / fR / fB / fT / fD / fU"};
-    for (int a = 1; a < 5; a++)
-        for (int d = 0; d < 3; d++)
-            if (dims[a][d] < udim[d])
-                return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: %s is smaller than u along dimension %d (%lld < %lld)", names[a], d + 1, (long long)dims[a][d],
-                                (long long)udim[d]);
-    // no two arrays may overlap, except the read-only velocities among themselves (a NULL flux array of the fused form is skipped)
-    const void *p[11] = {u, vx, vy, vz, ut, fL, fR, fB, fT, fD, fU};
-    const int64_t *pd[11] = {udim, vxdim, vydim, vzdim, wdim, wdim, wdim, wdim, wdim, wdim, wdim};
-    const char *pn[11] = {"u", "vx", "vy", "vz", "ut", "fL", "fR", "fB", "fT", "fD", "fU"};
-    for (int a = 0; a < 11; a++) {
-        if ((double)pd[a][0] * (double)pd[a][1] * (double)pd[a][2] >= 2147483648.0)
-            return jrx_fail(h, JRX_ERR_UNSUPPORTED, "WENO_advection!: %s has 2^31 or more entries (32-bit offsets)", pn[a]);
-        if (!p[a]) continue;
-        for (int b = a + 1; b < 11; b++) {
-            if (!p[b] || (a >= 1 && b <= 3)) continue;
-            const char *pa = (const char *)p[a], *pb = (const char *)p[b];
-            if (pa < pb + 8 * pd[b][0] * pd[b][1] * pd[b][2] && pb < pa + 8 * pd[a][0] * pd[a][1] * pd[a][2])
-                return jrx_fail(h, JRX_ERR_ARG, "WENO_advection!: %s and %s overlap", pn[a], pn[b]);
-        }
-    }
-    JRX_TRY(jrx_check_device(h));
+    const double *const v[3] = {vx, vy, vz};
+    const int64_t *const vdim[3] = {vxdim, vydim, vzdim};
+    double *const f[6] = {fL, fR, fB, fT, fD, fU};
+    JRX_TRY(weno_checks(h, 3, u, udim, v, vdim, ut, f, wdim, method));
     auto ext = [](const int64_t *d) { return WenoExt{(int)d[0], (int)(d[0] * d[1])}; };
     Weno3Args a;
     a.u = u; a.ut = ut; a.f[0] = fL; a.f[1] = fR; a.f[2] = fB; a.f[3] = fT; a.f[4] = fD; a.f[5] = fU;
@@ -506,9 +500,7 @@ jrx_status jrx_weno5_advection3d(jrx_handle *h, double *u, const int64_t udim[3]
     } else {
         JRX_TRY(method == 1 ? launch_split3d<1>(h, a) : launch_split3d<2>(h, a));
     }
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    return op_finish(h);
 }
 
 }  // extern "C"

@@ -7,7 +7,7 @@
 // src/ext/AMDGPU/2D.jl:301-352, 3D.jl:311-362.
 // Every operator is one streaming pass (a few reads and one to three writes per output value): HBM-bound, one thread per output,
 // x fastest across the lanes of a wave; nothing to tile.
-#include "jrx_internal.hpp"
+#include "op_args.hpp"
 #include "jrx_kernels.hpp"
 #include "jrx_material.hpp"
 
@@ -201,11 +201,32 @@ __global__ __launch_bounds__(256) void k_shear_heating(const ShArgs a)
     a.sh[c] = fmax(0.0, chi * H);
 }
 
-jrx_status done(jrx_handle *h)
+// velocity2vertex!: out the ND outputs of extents m (at most ni .+ 1), V the ND velocity components
+jrx_status go_velocity2vertex(jrx_handle *h, int ND, double *const *out, const double *const *V, const int64_t n[3], const int64_t m[3])
 {
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    if (!h) return JRX_ERR_ARG;
+    bool bad = false;
+    for (int d = 0; d < ND; d++) bad = bad || !out[d] || !V[d] || n[d] < 1 || m[d] < 1 || m[d] > n[d] + 1;
+    if (bad) return jrx_fail(h, JRX_ERR_ARG, "velocity2vertex!: bad argument (outputs at most ni .+ 1)");
+    JRX_TRY(jrx_check_device(h));
+    if (ND == 2) hipLaunchKernelGGL(k_vel2vertex2d, OUT_GRID(m[0], m[1], 1), dim3(256), 0, h->stream, out[0], out[1], V[0], V[1], (int)n[0], (int)m[0], (int)m[1]);
+    else
+        hipLaunchKernelGGL(k_vel2vertex3d, OUT_GRID(m[0], m[1], m[2]), dim3(256), 0, h->stream, out[0], out[1], out[2], V[0], V[1], V[2], (int)n[0], (int)n[1], (int)m[0],
+                           (int)m[1]);
+    return op_finish(h);
+}
+
+// velocity2center!: out the ND outputs at the cell centres
+jrx_status go_velocity2center(jrx_handle *h, int ND, double *const *out, const double *const *V, const int64_t n[3])
+{
+    if (!h) return JRX_ERR_ARG;
+    bool bad = false;
+    for (int d = 0; d < ND; d++) bad = bad || !out[d] || !V[d] || n[d] < 1;
+    if (bad) return jrx_fail(h, JRX_ERR_ARG, "velocity2center!: bad argument");
+    JRX_TRY(jrx_check_device(h));
+    if (ND == 2) hipLaunchKernelGGL(k_vel2center2d, OUT_GRID(n[0], n[1], 1), dim3(256), 0, h->stream, out[0], out[1], V[0], V[1], (int)n[0], (int)n[1]);
+    else hipLaunchKernelGGL(k_vel2center3d, OUT_GRID(n[0], n[1], n[2]), dim3(256), 0, h->stream, out[0], out[1], out[2], V[0], V[1], V[2], (int)n[0], (int)n[1]);
+    return op_finish(h);
 }
 
 }  // namespace
@@ -214,90 +235,83 @@ extern "C" {
 
 jrx_status jrx_velocity2vertex2d(jrx_handle *h, double *Vx_v, double *Vy_v, const double *Vx, const double *Vy, int64_t nx, int64_t ny, int64_t mx, int64_t my)
 {
-    if (!h) return JRX_ERR_ARG;
-    JRX_TRY(jrx_check_device(h));
-    if (!Vx_v || !Vy_v || !Vx || !Vy || nx < 1 || ny < 1 || mx < 1 || my < 1 || mx > nx + 1 || my > ny + 1)
-        return jrx_fail(h, JRX_ERR_ARG, "velocity2vertex!: bad argument (outputs at most ni .+ 1)");
-    hipLaunchKernelGGL(k_vel2vertex2d, OUT_GRID(mx, my, 1), dim3(256), 0, h->stream, Vx_v, Vy_v, Vx, Vy, (int)nx, (int)mx, (int)my);
-    return done(h);
+    double *const out[2] = {Vx_v, Vy_v};
+    const double *const V[2] = {Vx, Vy};
+    const int64_t n[3] = {nx, ny, 1}, m[3] = {mx, my, 1};
+    return go_velocity2vertex(h, 2, out, V, n, m);
 }
 
 jrx_status jrx_velocity2vertex3d(jrx_handle *h, double *Vx_v, double *Vy_v, double *Vz_v, const double *Vx, const double *Vy, const double *Vz, int64_t nx,
                                  int64_t ny, int64_t nz, int64_t mx, int64_t my, int64_t mz)
 {
-    if (!h) return JRX_ERR_ARG;
-    JRX_TRY(jrx_check_device(h));
-    if (!Vx_v || !Vy_v || !Vz_v || !Vx || !Vy || !Vz || nx < 1 || ny < 1 || nz < 1 || mx < 1 || my < 1 || mz < 1 || mx > nx + 1 || my > ny + 1 || mz > nz + 1)
-        return jrx_fail(h, JRX_ERR_ARG, "velocity2vertex!: bad argument (outputs at most ni .+ 1)");
-    hipLaunchKernelGGL(k_vel2vertex3d, OUT_GRID(mx, my, mz), dim3(256), 0, h->stream, Vx_v, Vy_v, Vz_v, Vx, Vy, Vz, (int)nx, (int)ny, (int)mx, (int)my);
-    return done(h);
+    double *const out[3] = {Vx_v, Vy_v, Vz_v};
+    const double *const V[3] = {Vx, Vy, Vz};
+    const int64_t n[3] = {nx, ny, nz}, m[3] = {mx, my, mz};
+    return go_velocity2vertex(h, 3, out, V, n, m);
 }
 
 jrx_status jrx_velocity2center2d(jrx_handle *h, double *Vx_c, double *Vy_c, const double *Vx, const double *Vy, int64_t nx, int64_t ny)
 {
-    if (!h) return JRX_ERR_ARG;
-    JRX_TRY(jrx_check_device(h));
-    if (!Vx_c || !Vy_c || !Vx || !Vy || nx < 1 || ny < 1) return jrx_fail(h, JRX_ERR_ARG, "velocity2center!: bad argument");
-    hipLaunchKernelGGL(k_vel2center2d, OUT_GRID(nx, ny, 1), dim3(256), 0, h->stream, Vx_c, Vy_c, Vx, Vy, (int)nx, (int)ny);
-    return done(h);
+    double *const out[2] = {Vx_c, Vy_c};
+    const double *const V[2] = {Vx, Vy};
+    const int64_t n[3] = {nx, ny, 1};
+    return go_velocity2center(h, 2, out, V, n);
 }
 
 jrx_status jrx_velocity2center3d(jrx_handle *h, double *Vx_c, double *Vy_c, double *Vz_c, const double *Vx, const double *Vy, const double *Vz, int64_t nx,
                                  int64_t ny, int64_t nz)
 {
-    if (!h) return JRX_ERR_ARG;
-    JRX_TRY(jrx_check_device(h));
-    if (!Vx_c || !Vy_c || !Vz_c || !Vx || !Vy || !Vz || nx < 1 || ny < 1 || nz < 1) return jrx_fail(h, JRX_ERR_ARG, "velocity2center!: bad argument");
-    hipLaunchKernelGGL(k_vel2center3d, OUT_GRID(nx, ny, nz), dim3(256), 0, h->stream, Vx_c, Vy_c, Vz_c, Vx, Vy, Vz, (int)nx, (int)ny);
-    return done(h);
+    double *const out[3] = {Vx_c, Vy_c, Vz_c};
+    const double *const V[3] = {Vx, Vy, Vz};
+    const int64_t n[3] = {nx, ny, nz};
+    return go_velocity2center(h, 3, out, V, n);
 }
 
 jrx_status jrx_vertex2center(jrx_handle *h, double *center, const double *vertex, const int64_t vdim[3], const int64_t cdim[3], int32_t ndim, int32_t ghost_x,
                              int32_t ghost_y, int32_t ghost_z)
 {
     if (!h) return JRX_ERR_ARG;
-    JRX_TRY(jrx_check_device(h));
     if (!center || !vertex || !vdim || !cdim || (ndim != 2 && ndim != 3)) return jrx_fail(h, JRX_ERR_ARG, "vertex2center!: bad argument");
     const int g[3] = {ghost_x != 0, ghost_y != 0, ndim == 3 && ghost_z != 0};
     for (int d = 0; d < ndim; d++)
         if (vdim[d] < 2 || vdim[d] - 1 + g[d] > cdim[d])
             return jrx_fail(h, JRX_ERR_ARG, "vertex2center!: the centre array is too small along dimension %d (size(vertex) - 1 + ghost = %lld > %lld)", d + 1,
                             (long long)(vdim[d] - 1 + g[d]), (long long)cdim[d]);
+    JRX_TRY(jrx_check_device(h));
     if (ndim == 3)
         hipLaunchKernelGGL(k_vertex2center<true>, OUT_GRID(vdim[0] - 1, vdim[1] - 1, vdim[2] - 1), dim3(256), 0, h->stream, center, vertex, (int)vdim[0],
                            (int)vdim[1], (int)cdim[0], (int)cdim[1], g[0], g[1], g[2]);
     else
         hipLaunchKernelGGL(k_vertex2center<false>, OUT_GRID(vdim[0] - 1, vdim[1] - 1, 1), dim3(256), 0, h->stream, center, vertex, (int)vdim[0], (int)vdim[1],
                            (int)cdim[0], (int)cdim[1], g[0], g[1], 0);
-    return done(h);
+    return op_finish(h);
 }
 
 jrx_status jrx_center2vertex_harm2d(jrx_handle *h, double *vertex, const double *center, int64_t nx, int64_t ny)
 {
     if (!h) return JRX_ERR_ARG;
-    JRX_TRY(jrx_check_device(h));
     if (!vertex || !center || nx < 1 || ny < 1) return jrx_fail(h, JRX_ERR_ARG, "center2vertex_harm!: bad argument");
+    JRX_TRY(jrx_check_device(h));
     hipLaunchKernelGGL(k_center2vertex_harm2d, OUT_GRID(nx + 1, ny + 1, 1), dim3(256), 0, h->stream, vertex, center, (int)nx, (int)ny);
-    return done(h);
+    return op_finish(h);
 }
 
 jrx_status jrx_center2vertex3d(jrx_handle *h, double *vertex_yz, double *vertex_xz, double *vertex_xy, const double *center_yz, const double *center_xz,
                                const double *center_xy, int64_t nx, int64_t ny, int64_t nz)
 {
     if (!h) return JRX_ERR_ARG;
-    JRX_TRY(jrx_check_device(h));
     if (!vertex_yz || !vertex_xz || !vertex_xy || !center_yz || !center_xz || !center_xy || nx < 1 || ny < 1 || nz < 1)
         return jrx_fail(h, JRX_ERR_ARG, "center2vertex!: bad argument");
+    JRX_TRY(jrx_check_device(h));
     hipLaunchKernelGGL(k_center2vertex3d, OUT_GRID(nx, ny, nz), dim3(256), 0, h->stream, vertex_yz, vertex_xz, vertex_xy, center_yz, center_xz, center_xy,
                        (int)nx, (int)ny, (int)nz);
-    return done(h);
+    return op_finish(h);
 }
 
 jrx_status jrx_compute_rhog(jrx_handle *h, double *rhog, const jrx_rheology *rh, const double *phase_c, const double *T, const double *P, const int64_t n[3],
                             const int64_t tdim[3], int32_t ndim)
 {
     if (!h) return JRX_ERR_ARG;
-    JRX_TRY(jrx_check_device(h));
     if (!rhog || !rh || !n || (ndim != 2 && ndim != 3) || rh->nphase < 1 || rh->nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "compute_ρg!: bad argument");
     if (!rh->has_density) return jrx_fail(h, JRX_ERR_ARG, "compute_ρg!: the rheology table carries no density law (has_density = 0)");
     const int nx = (int)n[0], ny = (int)n[1], nz = ndim == 3 ? (int)n[2] : 1;
@@ -308,31 +322,31 @@ jrx_status jrx_compute_rhog(jrx_handle *h, double *rhog, const jrx_rheology *rh,
             if (tdim[d] < n[d]) return jrx_fail(h, JRX_ERR_ARG, "compute_ρg!: args.T is smaller than ρg along dimension %d", d + 1);
         t1 = (int)tdim[0]; t2 = (int)tdim[1];
     }
+    JRX_TRY(jrx_check_device(h));
     if (phase_c) hipLaunchKernelGGL(k_compute_rhog<true>, OUT_GRID(nx, ny, nz), dim3(256), 0, h->stream, rhog, *rh, phase_c, T, P, nx, ny, t1, t2);
     else hipLaunchKernelGGL(k_compute_rhog<false>, OUT_GRID(nx, ny, nz), dim3(256), 0, h->stream, rhog, *rh, phase_c, T, P, nx, ny, t1, t2);
-    return done(h);
+    return op_finish(h);
 }
 
 jrx_status jrx_compute_lithostatic_pressure(jrx_handle *h, double *P, const double *rhog, double dz, const double *dz_cells, const int64_t n[3], int32_t ndim)
 {
     if (!h) return JRX_ERR_ARG;
-    JRX_TRY(jrx_check_device(h));
     if (!P || !rhog || !n || (ndim != 2 && ndim != 3)) return jrx_fail(h, JRX_ERR_ARG, "compute_lithostatic_pressure!: bad argument");
     for (int d = 0; d < ndim; d++)
         if (n[d] < 1) return jrx_fail(h, JRX_ERR_ARG, "compute_lithostatic_pressure!: bad size");
     if (jrx_comm_active(h) && (jrx_comm_has_neighbor(h, ndim - 1, 0) || jrx_comm_has_neighbor(h, ndim - 1, 1)))
         return jrx_fail(h, JRX_ERR_UNSUPPORTED, "compute_lithostatic_pressure!: the vertical direction is split across ranks (the IGG form that gathers the weight of the "
                                                 "ranks above is not built)");
+    JRX_TRY(jrx_check_device(h));
     const i64 ncol = ndim == 3 ? (i64)n[0] * n[1] : (i64)n[0];
     hipLaunchKernelGGL(k_lithostatic, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, h->stream, P, rhog, dz_cells, dz, ncol, (int)n[ndim - 1]);
-    return done(h);
+    return op_finish(h);
 }
 
 jrx_status jrx_compute_viscosity_single(jrx_handle *h, double *eta, const jrx_rheology *rh, const double *T, const double *P, const int64_t n[3],
                                         const int64_t tdim[3], int32_t ndim, double nu, double cutoff_lo, double cutoff_hi, const double *AII, int32_t tau_form)
 {
     if (!h) return JRX_ERR_ARG;
-    JRX_TRY(jrx_check_device(h));
     if (!eta || !rh || !n || (ndim != 2 && ndim != 3) || rh->nphase < 1) return jrx_fail(h, JRX_ERR_ARG, "compute_viscosity!: bad argument");
     const int nx = (int)n[0], ny = (int)n[1], nz = ndim == 3 ? (int)n[2] : 1;
     if (nx < 1 || ny < 1 || nz < 1) return jrx_fail(h, JRX_ERR_ARG, "compute_viscosity!: bad size");
@@ -345,16 +359,16 @@ jrx_status jrx_compute_viscosity_single(jrx_handle *h, double *eta, const jrx_rh
     }
     if (rh->visc_kind[0] == 2 && !AII)
         return jrx_fail(h, JRX_ERR_ARG, "compute_viscosity!: a power-law creep needs the invariant array (compute_viscosity_εII!(η, ν, εII, args, rheology, cutoff))");
+    JRX_TRY(jrx_check_device(h));
     hipLaunchKernelGGL(k_viscosity_single, OUT_GRID(nx, ny, nz), dim3(256), 0, h->stream, eta, *rh, T, P, nx, ny, t1, t2, sh, ndim == 3 ? sh : 0, nu, cutoff_lo,
                        cutoff_hi, AII, tau_form != 0);
-    return done(h);
+    return op_finish(h);
 }
 
 jrx_status jrx_compute_shear_heating(jrx_handle *h, double *shear_heating, const double *const *tau, const double *const *tau_o, const double *const *eps,
                                      const double *phase_c, const jrx_rheology *rh, const double *chi, double dt, const int64_t n[3], int32_t ndim)
 {
     if (!h) return JRX_ERR_ARG;
-    JRX_TRY(jrx_check_device(h));
     if (!shear_heating || !tau || !tau_o || !eps || !rh || !chi || !n || (ndim != 2 && ndim != 3) || rh->nphase < 1 || rh->nphase > JRX_MAXPHASE)
         return jrx_fail(h, JRX_ERR_ARG, "compute_shear_heating!: bad argument");
     const int N = ndim == 3 ? 6 : 3;
@@ -367,9 +381,10 @@ jrx_status jrx_compute_shear_heating(jrx_handle *h, double *shear_heating, const
         a.t[q] = tau[q]; a.to[q] = tau_o[q]; a.e[q] = eps[q];
     }
     for (int q = 0; q < rh->nphase; q++) { a.G[q] = rh->G[q]; a.chi[q] = chi[q]; }
+    JRX_TRY(jrx_check_device(h));
     if (ndim == 3) hipLaunchKernelGGL(k_shear_heating<true>, OUT_GRID(a.nx, a.ny, a.nz), dim3(256), 0, h->stream, a);
     else hipLaunchKernelGGL(k_shear_heating<false>, OUT_GRID(a.nx, a.ny, 1), dim3(256), 0, h->stream, a);
-    return done(h);
+    return op_finish(h);
 }
 
 }  // extern "C"

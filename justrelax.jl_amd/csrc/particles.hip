@@ -885,11 +885,11 @@ jrx_status pt_field_op(jrx_handle *h, const char *fn, K kernel, double *pF, doub
     PtGeom g;
     JRX_TRY(pt_geom(h, fn, "particles", part, &S, &g));
     if (centres) JRX_TRY(pt_centres(h, fn, g));
-    const PtArr ap = {pF, 8 * pt_slots(S), "pF"}, af = {F, 8 * (i64)(g.nx + e) * (g.ny + e), "F"};
+    const OpArr ap = {pF, 8 * pt_slots(S), "pF"}, af = {F, 8 * (i64)(g.nx + e) * (g.ny + e), "F"};
     JRX_TRY(to_particles ? pt_disjoint(h, fn, &ap, 1, &af, 1, S) : pt_disjoint(h, fn, &af, 1, &ap, 1, S));
     JRX_TRY(jrx_check_device(h));
     pt_launch_field(h, kernel, to_particles ? 0 : e, g, pF, F);
-    return pt_finish(h);
+    return op_finish(h);
 }
 
 // fused = false: operator 8 alone on a.pxx, pyy, pxy, pw; true: the one-launch rotate_stress!
@@ -917,8 +917,8 @@ jrx_status pt_subgrid(jrx_handle *h, const char *fn, bool vertex, double *pT, co
     const PtGeom &g = a.g;
     const int e = vertex ? 1 : 0, ex = g.nx + e, ey = g.ny + e, gh = dT_extent == JRX_SUBGRID_DT_GHOSTED ? 1 : 0;          // (ex, ey): the node box of the form
     const i64 ns = 8 * pt_slots(S), nn = 8 * (i64)ex * ey, nd = 8 * (i64)(ex + 2 * gh) * (ey + 2 * gh);
-    const PtArr out[4] = {{pT, ns, "pT"}, {pT0, ns, "subgrid_arrays.pT0"}, {pdT, ns, "subgrid_arrays.pΔT"}, {dT_subgrid, nn, "subgrid_arrays.ΔT_subgrid"}};
-    const PtArr in[3] = {{T_grid, nn, "T_grid"}, {dT_grid, nd, "ΔT_grid"}, {pdt0, ns, "subgrid_arrays.dt₀"}};
+    const OpArr out[4] = {{pT, ns, "pT"}, {pT0, ns, "subgrid_arrays.pT0"}, {pdT, ns, "subgrid_arrays.pΔT"}, {dT_subgrid, nn, "subgrid_arrays.ΔT_subgrid"}};
+    const OpArr in[3] = {{T_grid, nn, "T_grid"}, {dT_grid, nd, "ΔT_grid"}, {pdt0, ns, "subgrid_arrays.dt₀"}};
     JRX_TRY(pt_disjoint(h, fn, out, 4, in, 3, S));
     JRX_TRY(jrx_check_device(h));
     a.pT = pT, a.pT0 = pT0, a.pdT = pdT, a.pdt0 = pdt0, a.T = T_grid, a.dTg = dT_grid, a.dTs = dT_subgrid;
@@ -934,7 +934,7 @@ jrx_status pt_subgrid(jrx_handle *h, const char *fn, bool vertex, double *pT, co
             pt_launch(h, k_pt_sg_cell<false>, g.nx, g.ny, a);
             pt_launch(h, k_pt_sg_back<false>, g.nx, g.ny, a);
         }
-        return pt_finish(h);
+        return op_finish(h);
     }
     auto to_particles = [&](double *pF, const double *F) {          // operator 3 from vertices, 6 from centres
         if (vertex) pt_launch_field(h, k_pt_grid2particle, 0, g, pF, F);
@@ -949,7 +949,7 @@ jrx_status pt_subgrid(jrx_handle *h, const char *fn, bool vertex, double *pT, co
     pt_launch(h, k_pt_sg_remainder, ex, ey, a, ex, ey);                                       // 5
     to_particles(pdT, dT_subgrid);                                                            // 6
     pt_launch(h, k_pt_sg_add, g.nx, g.ny, a);                                                 // 7
-    return pt_finish(h);
+    return op_finish(h);
 }
 
 }  // namespace
@@ -973,7 +973,7 @@ jrx_status jrx_particles2d_advect_rk2(jrx_handle *h, const jrx_particles2d *part
     a.oyx = part->y0 - 0.5 * part->dy, a.oxy = part->x0 - 0.5 * part->dx;
     a.dt = dt, a.hdt = 0.5 * dt;
     pt_launch(h, k_pt_advect_rk2, g.nx, g.ny, a);
-    return pt_finish(h);
+    return op_finish(h);
 }
 
 jrx_status jrx_particles2d_move(jrx_handle *h, const jrx_particles2d *src, const jrx_particles2d *dst, const double *const *args_src, double *const *args_dst,
@@ -1049,12 +1049,12 @@ jrx_status jrx_particles2d_rotate(jrx_handle *h, double *const ptau[3], const do
     if (!ptau) return jrx_fail(h, JRX_ERR_ARG, "%s: ptau is NULL", fn);
     JRX_TRY(pt_method(h, fn, dt, method));
     const i64 ns = 8 * pt_slots(S);
-    const PtArr out[3] = {{ptau[0], ns, "pτxx"}, {ptau[1], ns, "pτyy"}, {ptau[2], ns, "pτxy"}}, in[1] = {{pomega, ns, "pω"}};
+    const OpArr out[3] = {{ptau[0], ns, "pτxx"}, {ptau[1], ns, "pτyy"}, {ptau[2], ns, "pτxy"}}, in[1] = {{pomega, ns, "pω"}};
     JRX_TRY(pt_disjoint(h, fn, out, 3, in, 1, S));
     JRX_TRY(jrx_check_device(h));
     a.pxx = ptau[0], a.pyy = ptau[1], a.pxy = ptau[2], a.pw = const_cast<double *>(pomega), a.dt = dt;
     pt_launch_rotate(h, a, method, false);
-    return pt_finish(h);
+    return op_finish(h);
 }
 
 jrx_status jrx_particles2d_rotate_stress(jrx_handle *h, double *const ptau[3], double *pomega, const double *tau_xx, const double *tau_yy, const double *tau_xy,
@@ -1070,8 +1070,8 @@ jrx_status jrx_particles2d_rotate_stress(jrx_handle *h, double *const ptau[3], d
     JRX_TRY(pt_method(h, fn, dt, method));
     const PtGeom &g = a.g;
     const i64 ns = 8 * pt_slots(S), nc = 8 * (i64)g.nx * g.ny, nv = 8 * (i64)(g.nx + 1) * (g.ny + 1);
-    const PtArr out[4] = {{ptau[0], ns, "pτxx"}, {ptau[1], ns, "pτyy"}, {ptau[2], ns, "pτxy"}, {pomega, ns, "pω"}};
-    const PtArr in[4] = {{tau_xx, nc, "τ.xx"}, {tau_yy, nc, "τ.yy"}, {tau_xy, nv, "τ.xy"}, {omega_xy, nv, "ω.xy"}};
+    const OpArr out[4] = {{ptau[0], ns, "pτxx"}, {ptau[1], ns, "pτyy"}, {ptau[2], ns, "pτxy"}, {pomega, ns, "pω"}};
+    const OpArr in[4] = {{tau_xx, nc, "τ.xx"}, {tau_yy, nc, "τ.yy"}, {tau_xy, nv, "τ.xy"}, {omega_xy, nv, "ω.xy"}};
     JRX_TRY(pt_disjoint(h, fn, out, 4, in, 4, S));
     JRX_TRY(jrx_check_device(h));
     a.pxx = ptau[0], a.pyy = ptau[1], a.pxy = ptau[2], a.pw = pomega, a.dt = dt;
@@ -1086,7 +1086,7 @@ jrx_status jrx_particles2d_rotate_stress(jrx_handle *h, double *const ptau[3], d
         pt_launch_field(h, k_pt_grid2particle, 0, g, pomega, omega_xy);
         pt_launch_rotate(h, a, method, false);
     }
-    return pt_finish(h);
+    return op_finish(h);
 }
 
 jrx_status jrx_particles2d_stress2grid(jrx_handle *h, double *const tau_o[6], const double *const ptau[3], const jrx_particles2d *part)
@@ -1099,9 +1099,9 @@ jrx_status jrx_particles2d_stress2grid(jrx_handle *h, double *const tau_o[6], co
     if (!tau_o || !ptau) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, !tau_o ? "tau_o" : "ptau");
     const PtGeom &g = a.g;
     const i64 ns = 8 * pt_slots(S), nc = 8 * (i64)g.nx * g.ny, nv = 8 * (i64)(g.nx + 1) * (g.ny + 1);
-    const PtArr out[6] = {{tau_o[0], nc, "τ_o.xx"}, {tau_o[1], nc, "τ_o.yy"}, {tau_o[2], nc, "τ_o.xy_c"}, {tau_o[3], nv, "τ_o.xy"}, {tau_o[4], nv, "τ_o.xx_v"},
+    const OpArr out[6] = {{tau_o[0], nc, "τ_o.xx"}, {tau_o[1], nc, "τ_o.yy"}, {tau_o[2], nc, "τ_o.xy_c"}, {tau_o[3], nv, "τ_o.xy"}, {tau_o[4], nv, "τ_o.xx_v"},
                           {tau_o[5], nv, "τ_o.yy_v"}};
-    const PtArr in[3] = {{ptau[0], ns, "pτxx"}, {ptau[1], ns, "pτyy"}, {ptau[2], ns, "pτxy"}};
+    const OpArr in[3] = {{ptau[0], ns, "pτxx"}, {ptau[1], ns, "pτyy"}, {ptau[2], ns, "pτxy"}};
     JRX_TRY(pt_disjoint(h, fn, out, 6, in, 3, S));
     JRX_TRY(jrx_check_device(h));
     if (h->particles_stress_fused) {
@@ -1114,7 +1114,7 @@ jrx_status jrx_particles2d_stress2grid(jrx_handle *h, double *const tau_o[6], co
         pt_launch_field(h, k_pt_particle2grid, 1, g, ptau[1], tau_o[5]);
         pt_launch_field(h, k_pt_particle2grid, 1, g, ptau[2], tau_o[3]);
     }
-    return pt_finish(h);
+    return op_finish(h);
 }
 
 jrx_status jrx_particles2d_subgrid_diffusion_centroid(jrx_handle *h, double *pT, const double *T_grid, const double *dT_grid, int32_t dT_extent, double *pT0,
@@ -1159,17 +1159,17 @@ jrx_status jrx_particles2d_inject(jrx_handle *h, const jrx_particles2d *part, in
     }
     // everything written -- the mask's copy, the phases, the particle fields, and the coordinates in place -- apart from the mask that is read and from each other
     const i64 ns = pt_slots(S);
-    if (pt_overlaps(active_out, 4 * ns, g.active, 4 * ns)) return jrx_fail(h, JRX_ERR_ARG, "%s: active_out overlaps the mask (the mask is written out of place)", fn);
-    PtArr out[2 + JRX_MAXPHASE] = {{active_out, 4 * ns, "active_out"}, {pPhases, 8 * ns, "pPhases"}};
+    if (op_overlaps(active_out, 4 * ns, g.active, 4 * ns)) return jrx_fail(h, JRX_ERR_ARG, "%s: active_out overlaps the mask (the mask is written out of place)", fn);
+    OpArr out[2 + JRX_MAXPHASE] = {{active_out, 4 * ns, "active_out"}, {pPhases, 8 * ns, "pPhases"}};
     static const char *const names[JRX_MAXPHASE] = {"particle field 1", "particle field 2", "particle field 3", "particle field 4",
                                                     "particle field 5", "particle field 6", "particle field 7", "particle field 8"};
-    for (int k = 0; k < nargs; k++) out[2 + k] = PtArr{args[k], 8 * ns, names[k]};
-    PtArr in[JRX_MAXPHASE];
+    for (int k = 0; k < nargs; k++) out[2 + k] = OpArr{args[k], 8 * ns, names[k]};
+    OpArr in[JRX_MAXPHASE];
     int nin = 0;
     for (int k = 0; k < nargs; k++) {
         if (field_loc[k] == JRX_INJECT_DONOR) continue;
         const bool v = field_loc[k] == JRX_INJECT_VERTEX;
-        in[nin++] = PtArr{fields[k], 8 * (i64)(g.nx + (v ? 1 : 0)) * (g.ny + (v ? 1 : 0)), v ? "a vertex field" : "a centre field"};
+        in[nin++] = OpArr{fields[k], 8 * (i64)(g.nx + (v ? 1 : 0)) * (g.ny + (v ? 1 : 0)), v ? "a vertex field" : "a centre field"};
     }
     JRX_TRY(pt_disjoint(h, fn, out, 2 + nargs, in, nin, S));
     for (int k = 0; k < nin; k++) JRX_TRY(pt_apart(h, fn, in[k], S));          // px, py are written too

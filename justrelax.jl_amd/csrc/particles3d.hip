@@ -497,7 +497,7 @@ jrx_status p3_field_op(jrx_handle *h, const char *fn, K kernel, double *pF, doub
     const P3Geom &g = a.g;
     if (centres && (g.nx < 2 || g.ny < 2 || g.nz < 2))
         return jrx_fail(h, JRX_ERR_ARG, "%s: %d x %d x %d cells (interpolation between centres needs every extent >= 2)", fn, g.nx, g.ny, g.nz);
-    const PtArr ap = {pF, 8 * pt_slots(S), "pF"}, af = {F, 8 * (i64)(g.nx + e) * (g.ny + e) * (g.nz + e), "F"};
+    const OpArr ap = {pF, 8 * pt_slots(S), "pF"}, af = {F, 8 * (i64)(g.nx + e) * (g.ny + e) * (g.nz + e), "F"};
     JRX_TRY(to_particles ? pt_disjoint(h, fn, &ap, 1, &af, 1, S) : pt_disjoint(h, fn, &af, 1, &ap, 1, S));
     JRX_TRY(jrx_check_device(h));
     a.pF = pF, a.F = F;
@@ -505,7 +505,7 @@ jrx_status p3_field_op(jrx_handle *h, const char *fn, K kernel, double *pF, doub
     const int n = to_particles ? 0 : e;          // a thread per cell, or per node of the field that is written
     h->stat_particles_launches++;
     hipLaunchKernelGGL(kernel, p3_grid(g.nx + n, g.ny + n, g.nz + n), kP3Block, 0, h->stream, a);
-    return pt_finish(h);
+    return op_finish(h);
 }
 
 }  // namespace
@@ -531,7 +531,7 @@ jrx_status jrx_particles3d_advect_rk2(jrx_handle *h, const jrx_particles3d *part
     a.dt = dt, a.hdt = 0.5 * dt;
     h->stat_particles_launches++;
     hipLaunchKernelGGL(k_p3_advect_rk2, p3_grid(g.nx, g.ny, g.nz), kP3Block, 0, h->stream, a);
-    return pt_finish(h);
+    return op_finish(h);
 }
 
 jrx_status jrx_particles3d_move(jrx_handle *h, const jrx_particles3d *src, const jrx_particles3d *dst, const double *const *args_src, double *const *args_dst,

@@ -1,12 +1,12 @@
 // particles_common.hpp -- what the 2D (particles.hip) and the 3D (particles3d.hip) particle operators share.  Device side: the per-axis pieces of every definition
 // of include/jrx.h (the finite test, the clamped pair index, the bilinear form, the node weight) and the per-wave counting into the library's counter words.
 // Host side, dimension-free: PtSet, a particle set in 2 or 3 axes (each file converts its jrx_particles2d / jrx_particles3d to it in one place, pt_geom / p3_geom);
-// the checks of a set (pt_check_set); the overlap rules (pt_slots, pt_apart, pt_disjoint); the checks move_particles! and update_phase_ratios! make after the
-// geometry (pt_move_checks, pt_ratio_checks); the counter read-back.  A file includes it inside no namespace of its own.
+// the checks of a set (pt_check_set); the overlap rules (pt_slots, pt_apart, pt_disjoint) on the primitives of op_args.hpp; the checks move_particles! and
+// update_phase_ratios! make after the geometry (pt_move_checks, pt_ratio_checks); the counter read-back.  A file includes it inside no namespace of its own.
 #ifndef JRX_PARTICLES_COMMON_HPP
 #define JRX_PARTICLES_COMMON_HPP
 #include <cfloat>
-#include "jrx_internal.hpp"
+#include "op_args.hpp"
 
 namespace {
 
@@ -53,20 +53,6 @@ struct PtSet {
     double o[3], d[3], id[3];         // origin, spacing, inverse spacing
 };
 
-// the first nd entries of v as text: "7 x 5" or "0.25, -0.5"
-struct PtText {
-    char s[112];
-};
-template <typename T>
-PtText pt_list(const T *v, int nd, const char *sep)
-{
-    PtText t = {};
-    for (int a = 0, at = 0; a < nd; a++)
-        at += std::is_integral<T>::value ? snprintf(t.s + at, sizeof t.s - at, "%s%lld", a ? sep : "", (long long)v[a])
-                                         : snprintf(t.s + at, sizeof t.s - at, "%s%g", a ? sep : "", (double)v[a]);
-    return t;
-}
-
 // the checks every entry point shares
 jrx_status pt_check_set(jrx_handle *h, const char *fn, const char *what, const PtSet &S)
 {
@@ -85,18 +71,18 @@ jrx_status pt_check_set(jrx_handle *h, const char *fn, const char *what, const P
         pos = pos && S.d[a] > 0.0 && std::isfinite(S.d[a]);
         inv = inv && S.id[a] == 1.0 / S.d[a];
     }
-    if (!ok) return jrx_fail(h, JRX_ERR_ARG, "%s: %s has %s cells", fn, what, pt_list(S.n, nd, " x ").s);
+    if (!ok) return jrx_fail(h, JRX_ERR_ARG, "%s: %s has %s cells", fn, what, op_list(S.n, nd, " x ").s);
     if (S.mx < 1) return jrx_fail(h, JRX_ERR_ARG, "%s: %s.max_xcell = %d", fn, what, S.mx);
     // 32-bit offsets: into the particle arrays, and into the largest grid field (2D: a phase-ratio member, JRX_MAXPHASE values per node; 3D: a ghosted velocity)
-    if (slots * (double)S.mx >= 2147483648.0 || (nd == 2 ? nodes * JRX_MAXPHASE : nodes) >= 2147483648.0)
+    if (op_2g(slots * (double)S.mx) || op_2g(nd == 2 ? nodes * JRX_MAXPHASE : nodes))
         return jrx_fail(h, JRX_ERR_ARG, "%s: %s has 2^31 or more slots or nodes (32-bit offsets)", fn, what);
     // 3D launches put y and z on blockIdx.y and .z, two cells (or nodes) per block; the 2D launch grid is one-dimensional
     if (nd == 3 && (S.n[1] > 2 * 65535 - 2 || S.n[2] > 2 * 65535 - 2))
         return jrx_fail(h, JRX_ERR_ARG, "%s: %s has more than %d cells along y or z (the launch grid)", fn, what, 2 * 65535 - 2);
-    if (!fin) return jrx_fail(h, JRX_ERR_ARG, "%s: %s has origin (%s) (must be finite)", fn, what, pt_list(S.o, nd, ", ").s);
-    if (!pos) return jrx_fail(h, JRX_ERR_ARG, "%s: %s has spacings (%s) (must be positive and finite: a uniform grid)", fn, what, pt_list(S.d, nd, ", ").s);
+    if (!fin) return jrx_fail(h, JRX_ERR_ARG, "%s: %s has origin (%s) (must be finite)", fn, what, op_list(S.o, nd, ", ").s);
+    if (!pos) return jrx_fail(h, JRX_ERR_ARG, "%s: %s has spacings (%s) (must be positive and finite: a uniform grid)", fn, what, op_list(S.d, nd, ", ").s);
     if (!inv)
-        return jrx_fail(h, JRX_ERR_ARG, "%s: %s.%s = (%s) are not %s", fn, what, nd == 2 ? "_dx, ._dy" : "_dx, ._dy, ._dz", pt_list(S.id, nd, ", ").s,
+        return jrx_fail(h, JRX_ERR_ARG, "%s: %s.%s = (%s) are not %s", fn, what, nd == 2 ? "_dx, ._dy" : "_dx, ._dy, ._dz", op_list(S.id, nd, ", ").s,
                         nd == 2 ? "1 / dx, 1 / dy" : "1 / dx, 1 / dy, 1 / dz");
     if (jrx_comm_active(h)) return jrx_fail(h, JRX_ERR_ARG, "%s: a handle with a communicator (particles are built for one block)", fn);
     return JRX_OK;
@@ -109,51 +95,27 @@ i64 pt_slots(const PtSet &S)
     return ns;
 }
 
-bool pt_overlaps(const void *a, i64 abytes, const void *b, i64 bbytes)
-{
-    const char *pa = (const char *)a, *pb = (const char *)b;
-    return pa < pb + bbytes && pb < pa + abytes;
-}
-
-struct PtArr {
-    const void *p;
-    i64 bytes;
-    const char *name;
-};
-
 // an array must not share memory with the coordinates or the mask of S
-jrx_status pt_apart(jrx_handle *h, const char *fn, const PtArr &x, const PtSet &S)
+jrx_status pt_apart(jrx_handle *h, const char *fn, const OpArr &x, const PtSet &S)
 {
     const i64 ns = pt_slots(S);
-    bool hit = pt_overlaps(x.p, x.bytes, S.active, 4 * ns);
-    for (int a = 0; a < S.nd; a++) hit = hit || pt_overlaps(x.p, x.bytes, S.coord[a], 8 * ns);
+    bool hit = op_overlaps(x.p, x.bytes, S.active, 4 * ns);
+    for (int a = 0; a < S.nd; a++) hit = hit || op_overlaps(x.p, x.bytes, S.coord[a], 8 * ns);
     if (hit) return jrx_fail(h, JRX_ERR_ARG, "%s: %s overlaps the particle coordinates or the mask", fn, x.name);
-    return JRX_OK;
-}
-
-jrx_status pt_present(jrx_handle *h, const char *fn, const PtArr *x, int n)
-{
-    for (int m = 0; m < n; m++)
-        if (!x[m].p) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL", fn, x[m].name);
     return JRX_OK;
 }
 
 // every array present; no output shares memory with the particles' own arrays, an input or another output.  `two`: the sentence for two outputs that overlap,
 // where the outputs do not carry names of their own
-jrx_status pt_disjoint(jrx_handle *h, const char *fn, const PtArr *out, int nout, const PtArr *in, int nin, const PtSet &S, const char *two = nullptr)
+jrx_status pt_disjoint(jrx_handle *h, const char *fn, const OpArr *out, int nout, const OpArr *in, int nin, const PtSet &S, const char *two = nullptr)
 {
-    JRX_TRY(pt_present(h, fn, out, nout));
-    JRX_TRY(pt_present(h, fn, in, nin));
-    for (int m = 0; m < nout; m++) {
-        JRX_TRY(pt_apart(h, fn, out[m], S));
-        for (int k = 0; k < nin; k++)
-            if (pt_overlaps(out[m].p, out[m].bytes, in[k].p, in[k].bytes)) return jrx_fail(h, JRX_ERR_ARG, "%s: %s overlaps %s", fn, out[m].name, in[k].name);
-        for (int q = m + 1; q < nout; q++) {
-            if (!pt_overlaps(out[m].p, out[m].bytes, out[q].p, out[q].bytes)) continue;
-            return two ? jrx_fail(h, JRX_ERR_ARG, "%s: %s", fn, two) : jrx_fail(h, JRX_ERR_ARG, "%s: %s and %s overlap", fn, out[m].name, out[q].name);
-        }
-    }
-    return JRX_OK;
+    JRX_TRY(op_present(h, fn, out, nout));
+    JRX_TRY(op_present(h, fn, in, nin));
+    for (int m = 0; m < nout; m++) JRX_TRY(pt_apart(h, fn, out[m], S));
+    const OpClash c = op_disjoint(out, nout, in, nin);
+    if (!c) return JRX_OK;
+    if (!c.two) return jrx_fail(h, JRX_ERR_ARG, "%s: %s overlaps %s", fn, out[c.a].name, in[c.b].name);
+    return two ? jrx_fail(h, JRX_ERR_ARG, "%s: %s", fn, two) : jrx_fail(h, JRX_ERR_ARG, "%s: %s and %s overlap", fn, out[c.a].name, out[c.b].name);
 }
 
 // move_particles!, after the two geometries: the counters, the two sets alike, the particle fields, and nothing written -- the destination's arrays, its fields,
@@ -173,12 +135,12 @@ jrx_status pt_move_checks(jrx_handle *h, const char *fn, const PtSet &S, const P
         if (!args_src[k] || !args_dst[k]) return jrx_fail(h, JRX_ERR_ARG, "%s: particle field %d (%s) is NULL", fn, k + 1, !args_src[k] ? "source" : "destination");
     const i64 ns = pt_slots(D);
     const char *dest = "an array of the destination";
-    PtArr out[5 + JRX_MAXPHASE], in[JRX_MAXPHASE];
+    OpArr out[5 + JRX_MAXPHASE], in[JRX_MAXPHASE];
     int nout = 0;
-    for (int a = 0; a < D.nd; a++) out[nout++] = PtArr{D.coord[a], 8 * ns, dest};
-    out[nout++] = PtArr{D.active, 4 * ns, dest};
-    for (int k = 0; k < nargs; k++) out[nout++] = PtArr{args_dst[k], 8 * ns, dest}, in[k] = PtArr{args_src[k], 8 * ns, source[k]};
-    if (work) out[nout++] = PtArr{work, ns, "work"};
+    for (int a = 0; a < D.nd; a++) out[nout++] = OpArr{D.coord[a], 8 * ns, dest};
+    out[nout++] = OpArr{D.active, 4 * ns, dest};
+    for (int k = 0; k < nargs; k++) out[nout++] = OpArr{args_dst[k], 8 * ns, dest}, in[k] = OpArr{args_src[k], 8 * ns, source[k]};
+    if (work) out[nout++] = OpArr{work, ns, "work"};
     return pt_disjoint(h, fn, out, nout, in, nargs, S, "two arrays of the destination overlap");
 }
 
@@ -187,11 +149,11 @@ jrx_status pt_ratio_checks(jrx_handle *h, const char *fn, const PtSet &S, double
                            const double *pPhases, int32_t nphase, const int64_t *n_empty)
 {
     if (!members) return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios is NULL", fn);
-    PtArr out[8];
-    for (int m = 0; m < nm; m++) out[m] = PtArr{members[m], 0, names[m]};
-    const PtArr in[1] = {{pPhases, 8 * pt_slots(S), "pPhases"}};
-    JRX_TRY(pt_present(h, fn, out, nm));
-    JRX_TRY(pt_present(h, fn, in, 1));
+    OpArr out[8];
+    for (int m = 0; m < nm; m++) out[m] = OpArr{members[m], 0, names[m]};
+    const OpArr in[1] = {{pPhases, 8 * pt_slots(S), "pPhases"}};
+    JRX_TRY(op_present(h, fn, out, nm));
+    JRX_TRY(op_present(h, fn, in, 1));
     if (!n_empty) return jrx_fail(h, JRX_ERR_ARG, "%s: n_empty is NULL", fn);
     if (nphase < 1 || nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d phases (1 .. %d are built)", fn, (int)nphase, JRX_MAXPHASE);
     for (int m = 0; m < nm; m++) {
@@ -211,13 +173,6 @@ jrx_status pt_read_words(jrx_handle *h, int first, int n, int64_t *out)
     JRX_HIP(h, hipMemcpyAsync(h->h_sums + kPtWord0 + first, h->d_sums + kPtWord0 + first, sizeof(int64_t) * n, hipMemcpyDeviceToHost, h->stream));
     JRX_HIP(h, hipStreamSynchronize(h->stream));
     memcpy(out, h->h_sums + kPtWord0 + first, sizeof(int64_t) * n);
-    return JRX_OK;
-}
-
-jrx_status pt_finish(jrx_handle *h)
-{
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
     return JRX_OK;
 }
 

@@ -23,7 +23,7 @@
 //     the cells its member reads.
 // fma() stands where the reference has muladd (the 2D vertex weights); the library builds with -ffp-contract=off, so nothing else is contracted.
 // Addressing: 32-bit element offsets (every output below 2^31 entries, checked).
-#include "jrx_internal.hpp"
+#include "op_args.hpp"
 
 namespace {
 
@@ -238,45 +238,33 @@ void pr_launch(jrx_handle *h, const PrArgs<N> &a, bool fused)
     }
 }
 
-bool overlaps(const void *a, i64 na, const void *b, i64 nb)
-{
-    const char *pa = (const char *)a, *pb = (const char *)b;
-    return pa < pb + 8 * nb && pb < pa + 8 * na;
-}
-
 // checks and launch shared by the two entry points; out / names by staggering set S, NULL where ndim has no such member
 jrx_status pr_update(jrx_handle *h, const char *fn, int ND, double *const out[8], const char *const names[8], const double *const *phase_arrays, int32_t nphase,
                      const int64_t n[3], const double *const *xc, const double *const *xv, const double *dx)
 {
+    if (!h) return JRX_ERR_ARG;
     const int NC = 1 << ND;
     if (!phase_arrays || !xc || !xv || !dx) return jrx_fail(h, JRX_ERR_ARG, "%s: NULL argument", fn);
-    for (int S = 0; S < NC; S++)
-        if (!out[S]) return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios.%s is NULL", fn, names[S]);
+    OpArr o[8], in[JRX_MAXPHASE + 6];            // inputs: the phase arrays, then xc and xv of each dimension
+    for (int S = 0; S < NC; S++) o[S] = OpArr{out[S], 0, names[S]};
+    JRX_TRY(op_present(h, fn, o, NC));
     if (nphase < 1 || nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d phase arrays (1 .. %d are built)", fn, (int)nphase, JRX_MAXPHASE);
     for (int k = 0; k < nphase; k++)
         if (!phase_arrays[k]) return jrx_fail(h, JRX_ERR_ARG, "%s: phase array %d is NULL", fn, k + 1);
     for (int d = 0; d < ND; d++) {
         if (!xc[d] || !xv[d]) return jrx_fail(h, JRX_ERR_ARG, "%s: coordinate vector of dimension %d is NULL", fn, d + 1);
         if (n[d] < 1) return jrx_fail(h, JRX_ERR_ARG, "%s: extent %lld along dimension %d", fn, (long long)n[d], d + 1);
-        if (!(dx[d] > 0.0) || !std::isfinite(dx[d])) return jrx_fail(h, JRX_ERR_ARG, "%s: spacing %g along dimension %d (must be positive and finite)", fn, dx[d], d + 1);
+        if (!op_pos_finite(dx[d])) return jrx_fail(h, JRX_ERR_ARG, "%s: spacing %g along dimension %d (must be positive and finite)", fn, dx[d], d + 1);
     }
-    double ent = (double)nphase;                 // entries of the largest output, the vertex array
-    for (int d = 0; d < ND; d++) ent *= (double)(n[d] + 1);
-    if (ent >= 2147483648.0) return jrx_fail(h, JRX_ERR_UNSUPPORTED, "%s: phase_ratios.vertex has 2^31 or more entries (32-bit offsets)", fn);
-    i64 on[8], nc = 1;
-    for (int d = 0; d < ND; d++) nc *= n[d];
-    for (int S = 0; S < NC; S++) {
-        on[S] = nphase;
-        for (int d = 0; d < ND; d++) on[S] *= n[d] + ((S >> d) & 1);
-    }
-    for (int S = 0; S < NC; S++) {
-        for (int T = S + 1; T < NC; T++)
-            if (overlaps(out[S], on[S], out[T], on[T])) return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios.%s and phase_ratios.%s overlap", fn, names[S], names[T]);
-        for (int k = 0; k < nphase; k++)
-            if (overlaps(out[S], on[S], phase_arrays[k], nc)) return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios.%s overlaps phase array %d", fn, names[S], k + 1);
-        for (int d = 0; d < ND; d++)
-            if (overlaps(out[S], on[S], xc[d], n[d]) || overlaps(out[S], on[S], xv[d], n[d] + 1))
-                return jrx_fail(h, JRX_ERR_ARG, "%s: phase_ratios.%s overlaps a coordinate vector of dimension %d", fn, names[S], d + 1);
+    // the largest output is the vertex array
+    if (op_2g((double)nphase * op_count(n, ND, 1))) return jrx_fail(h, JRX_ERR_UNSUPPORTED, "%s: phase_ratios.vertex has 2^31 or more entries (32-bit offsets)", fn);
+    for (int S = 0; S < NC; S++) o[S].bytes = nphase * op_bytes(n, ND, S & 1, (S >> 1) & 1, (S >> 2) & 1);
+    for (int k = 0; k < nphase; k++) in[k] = OpArr{phase_arrays[k], op_bytes(n, ND, 0, 0, 0), nullptr};
+    for (int d = 0; d < ND; d++) in[nphase + 2 * d] = OpArr{xc[d], 8 * n[d], nullptr}, in[nphase + 2 * d + 1] = OpArr{xv[d], 8 * (n[d] + 1), nullptr};
+    if (const OpClash c = op_disjoint(o, NC, in, nphase + 2 * ND)) {
+        if (c.two) return jrx_fail(h, JRX_ERR_ARG, "%s: %s and %s overlap", fn, o[c.a].name, o[c.b].name);
+        return c.b < nphase ? jrx_fail(h, JRX_ERR_ARG, "%s: %s overlaps phase array %d", fn, o[c.a].name, c.b + 1)
+                            : jrx_fail(h, JRX_ERR_ARG, "%s: %s overlaps a coordinate vector of dimension %d", fn, o[c.a].name, (c.b - nphase) / 2 + 1);
     }
     JRX_TRY(jrx_check_device(h));
     const bool fused = h->phase_ratios_fused;
@@ -297,9 +285,7 @@ jrx_status pr_update(jrx_handle *h, const char *fn, int ND, double *const out[8]
         if (ND == 2) pr_launch<N, 2>(h, a, fused);
         else pr_launch<N, 3>(h, a, fused);
     });
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    return op_finish(h);
 }
 
 }  // namespace
@@ -309,9 +295,8 @@ extern "C" {
 jrx_status jrx_update_phase_ratios2d(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, const double *const *phase_arrays, int32_t nphase,
                                      int64_t nx, int64_t ny, const double *const xc[2], const double *const xv[2], const double dx[2])
 {
-    if (!h) return JRX_ERR_ARG;
     double *const out[8] = {center, Vx, Vy, vertex, nullptr, nullptr, nullptr, nullptr};
-    const char *const names[8] = {"center", "Vx", "Vy", "vertex", "", "", "", ""};
+    const char *const names[8] = {"phase_ratios.center", "phase_ratios.Vx", "phase_ratios.Vy", "phase_ratios.vertex", "", "", "", ""};
     const int64_t n[3] = {nx, ny, 1};
     return pr_update(h, "update_phase_ratios_2D!", 2, out, names, phase_arrays, nphase, n, xc, xv, dx);
 }
@@ -320,9 +305,9 @@ jrx_status jrx_update_phase_ratios3d(jrx_handle *h, double *center, double *vert
                                      const double *const *phase_arrays, int32_t nphase, int64_t nx, int64_t ny, int64_t nz, const double *const xc[3],
                                      const double *const xv[3], const double dx[3])
 {
-    if (!h) return JRX_ERR_ARG;
     double *const out[8] = {center, Vx, Vy, xy, Vz, xz, yz, vertex};
-    const char *const names[8] = {"center", "Vx", "Vy", "xy", "Vz", "xz", "yz", "vertex"};
+    const char *const names[8] = {"phase_ratios.center", "phase_ratios.Vx", "phase_ratios.Vy", "phase_ratios.xy",
+                                  "phase_ratios.Vz",     "phase_ratios.xz", "phase_ratios.yz", "phase_ratios.vertex"};
     const int64_t n[3] = {nx, ny, nz};
     return pr_update(h, "update_phase_ratios_3D!", 3, out, names, phase_arrays, nphase, n, xc, xv, dx);
 }

@@ -15,7 +15,7 @@
 // One thread per cell, x fastest across the lanes; per cell 2D reads 24 B and writes 32 B, 3D reads 48 B and writes 72 B (three 8-B writes per output
 // array at a 24-B stride: the three of a wave cover 1,536 contiguous bytes).
 // The library builds with -ffp-contract=off: fma() appears only where written, so the 2D form keeps the reference's roundings.
-#include "jrx_internal.hpp"
+#include "op_args.hpp"
 
 #include <cfloat>
 
@@ -130,10 +130,31 @@ __global__ __launch_bounds__(256) void k_principal3d(double *__restrict__ s1, do
     }
 }
 
-bool overlaps(const void *a, i64 na, const void *b, i64 nb)
+// both entry points: s the ND outputs σ1 .. σND (ND values per cell), t the components of the stress (3 in 2D, 6 in 3D)
+jrx_status ps_compute(jrx_handle *h, int ND, double *const *s, const double *const *t, const int64_t n[3])
 {
-    const char *pa = (const char *)a, *pb = (const char *)b;
-    return pa < pb + 8 * nb && pb < pa + 8 * na;
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "compute_principal_stresses!";
+    const int NT = ND == 2 ? 3 : 6;
+    bool null = false;
+    for (int a = 0; a < ND; a++) null = null || !s[a];
+    for (int q = 0; q < NT; q++) null = null || !t[q];
+    if (null) return jrx_fail(h, JRX_ERR_ARG, "%s: NULL argument", fn);
+    if (!op_extents_ok(n, ND)) return jrx_fail(h, JRX_ERR_ARG, "%s: size(stokes.P) = (%s)", fn, op_list(n, ND, ", ").s);
+    if (op_count(n, ND, 0) >= 2147483648.0 * 256.0) return jrx_fail(h, JRX_ERR_UNSUPPORTED, "%s: 2^39 or more cells", fn);      // 64-bit offsets; 2^31 blocks of 256
+    const i64 bytes = op_bytes(n, ND, 0, 0, 0), cells = bytes / 8;
+    OpArr out[3], in[6];
+    for (int a = 0; a < ND; a++) out[a] = OpArr{s[a], ND * bytes, nullptr};
+    for (int q = 0; q < NT; q++) in[q] = OpArr{t[q], bytes, nullptr};
+    if (const OpClash c = op_disjoint(out, ND, in, NT))
+        return c.two ? jrx_fail(h, JRX_ERR_ARG, "%s: σ%d and σ%d overlap", fn, c.a + 1, c.b + 1)
+                     : jrx_fail(h, JRX_ERR_ARG, "%s: an output overlaps a stress component", fn);
+    JRX_TRY(jrx_check_device(h));
+    h->stat_principal_calls++;
+    const dim3 grid((unsigned)((cells + 255) / 256)), block(256);
+    if (ND == 2) hipLaunchKernelGGL(k_principal2d, grid, block, 0, h->stream, s[0], s[1], t[0], t[1], t[2], cells);
+    else hipLaunchKernelGGL(k_principal3d, grid, block, 0, h->stream, s[0], s[1], s[2], t[0], t[1], t[2], t[3], t[4], t[5], cells);
+    return op_finish(h);
 }
 
 }  // namespace
@@ -142,45 +163,19 @@ extern "C" {
 
 jrx_status jrx_principal_stresses2d(jrx_handle *h, double *s1, double *s2, const double *xx, const double *yy, const double *xy_c, int64_t nx, int64_t ny)
 {
-    if (!h) return JRX_ERR_ARG;
-    if (!s1 || !s2 || !xx || !yy || !xy_c) return jrx_fail(h, JRX_ERR_ARG, "compute_principal_stresses!: NULL argument");
-    if (nx < 1 || ny < 1) return jrx_fail(h, JRX_ERR_ARG, "compute_principal_stresses!: size(stokes.P) = (%lld, %lld)", (long long)nx, (long long)ny);
-    if ((double)nx * (double)ny >= 2147483648.0 * 256.0) return jrx_fail(h, JRX_ERR_UNSUPPORTED, "compute_principal_stresses!: 2^39 or more cells");
-    const i64 n = nx * ny;
-    if (overlaps(s1, 2 * n, s2, 2 * n)) return jrx_fail(h, JRX_ERR_ARG, "compute_principal_stresses!: σ1 and σ2 overlap");
-    for (const double *p : {xx, yy, xy_c})
-        if (overlaps(p, n, s1, 2 * n) || overlaps(p, n, s2, 2 * n))
-            return jrx_fail(h, JRX_ERR_ARG, "compute_principal_stresses!: an output overlaps a stress component");
-    JRX_TRY(jrx_check_device(h));
-    h->stat_principal_calls++;
-    hipLaunchKernelGGL(k_principal2d, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, s1, s2, xx, yy, xy_c, n);
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    double *const s[2] = {s1, s2};
+    const double *const t[3] = {xx, yy, xy_c};
+    const int64_t n[3] = {nx, ny, 1};
+    return ps_compute(h, 2, s, t, n);
 }
 
 jrx_status jrx_principal_stresses3d(jrx_handle *h, double *s1, double *s2, double *s3, const double *xx, const double *yy, const double *zz,
                                     const double *yz_c, const double *xz_c, const double *xy_c, int64_t nx, int64_t ny, int64_t nz)
 {
-    if (!h) return JRX_ERR_ARG;
-    if (!s1 || !s2 || !s3 || !xx || !yy || !zz || !yz_c || !xz_c || !xy_c) return jrx_fail(h, JRX_ERR_ARG, "compute_principal_stresses!: NULL argument");
-    if (nx < 1 || ny < 1 || nz < 1)
-        return jrx_fail(h, JRX_ERR_ARG, "compute_principal_stresses!: size(stokes.P) = (%lld, %lld, %lld)", (long long)nx, (long long)ny, (long long)nz);
-    if ((double)nx * (double)ny * (double)nz >= 2147483648.0 * 256.0) return jrx_fail(h, JRX_ERR_UNSUPPORTED, "compute_principal_stresses!: 2^39 or more cells");
-    const i64 n = nx * ny * nz;
-    double *out[3] = {s1, s2, s3};
-    for (int a = 0; a < 3; a++)
-        for (int b = a + 1; b < 3; b++)
-            if (overlaps(out[a], 3 * n, out[b], 3 * n)) return jrx_fail(h, JRX_ERR_ARG, "compute_principal_stresses!: σ%d and σ%d overlap", a + 1, b + 1);
-    for (const double *p : {xx, yy, zz, yz_c, xz_c, xy_c})
-        for (double *o : out)
-            if (overlaps(p, n, o, 3 * n)) return jrx_fail(h, JRX_ERR_ARG, "compute_principal_stresses!: an output overlaps a stress component");
-    JRX_TRY(jrx_check_device(h));
-    h->stat_principal_calls++;
-    hipLaunchKernelGGL(k_principal3d, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, s1, s2, s3, xx, yy, zz, yz_c, xz_c, xy_c, n);
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    double *const s[3] = {s1, s2, s3};
+    const double *const t[6] = {xx, yy, zz, yz_c, xz_c, xy_c};
+    const int64_t n[3] = {nx, ny, nz};
+    return ps_compute(h, 3, s, t, n);
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 // Every operator is one launch of one thread per output value, x fastest across the lanes of a wave.  pureshear_bc! and free_surface_bcs! touch faces and
 // a few planes (launch-bound); the other two stream the cells once (HBM-bound: the ratios, T[, P] in, one value out).
 // The library builds with -ffp-contract=off: no fma appears here, so every expression keeps the reference's grouping and roundings.
-#include "jrx_internal.hpp"
+#include "op_args.hpp"
 #include "jrx_thermal_phases.hpp"
 
 namespace {
@@ -137,25 +137,7 @@ __global__ __launch_bounds__(256) void k_melt_fraction(double *__restrict__ phi,
     phi[c] = x;
 }
 
-bool overlaps(const void *a, i64 na, const void *b, i64 nb)
-{
-    const char *pa = (const char *)a, *pb = (const char *)b;
-    return pa < pb + 8 * nb && pb < pa + 8 * na;
-}
-
-// an extent product as a double: exact far beyond 2^31, never overflows
-bool too_many(double entries) { return entries >= 2147483648.0; }
-bool pos_finite(double x) { return x > 0.0 && x <= 1.79769313486231570e308; }
-
 unsigned blocks(i64 n) { return (unsigned)((n + 255) / 256); }
-
-jrx_status launched(jrx_handle *h)
-{
-    h->stat_stepops_launches++;
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
-}
 
 jrx_status phase_g(jrx_handle *h, const char *who, const jrx_rheology *rh, PhaseG *g)
 {
@@ -165,153 +147,167 @@ jrx_status phase_g(jrx_handle *h, const char *who, const jrx_rheology *rh, Phase
     return JRX_OK;
 }
 
+// pureshear_bc!: V the ND velocity components, x the ND vertex coordinate vectors
+jrx_status so_pureshear(jrx_handle *h, int ND, double *const *V, const double *const *x, double eps_bg, const int64_t n[3])
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "pureshear_bc!";
+    bool null = false;
+    for (int c = 0; c < ND; c++) null = null || !V[c] || !x[c];
+    if (null) return jrx_fail(h, JRX_ERR_ARG, "%s: NULL argument", fn);
+    if (!op_extents_ok(n, ND)) return jrx_fail(h, JRX_ERR_ARG, "%s: ni = (%s)", fn, op_list(n, ND, ", ").s);
+    if (op_2g(op_count(n, ND, 2))) return jrx_fail(h, JRX_ERR_ARG, "%s: a velocity array of 2^31 or more entries", fn);
+    OpArr out[3], in[3];
+    for (int c = 0; c < ND; c++) out[c] = OpArr{V[c], op_vel_bytes(n, ND, c), nullptr}, in[c] = OpArr{x[c], 8 * (n[c] + 1), nullptr};
+    if (const OpClash c = op_disjoint(out, ND, in, ND))
+        return !c.two ? jrx_fail(h, JRX_ERR_ARG, "%s: a velocity array overlaps a coordinate vector", fn)
+                      : jrx_fail(h, JRX_ERR_ARG, ND == 2 ? "%s: Vx and Vy overlap" : "%s: two velocity arrays overlap", fn);
+    JRX_TRY(jrx_check_device(h));
+    const int nx = (int)n[0], ny = (int)n[1], nz = (int)n[2];
+    if (ND == 2) hipLaunchKernelGGL(k_pureshear2d, dim3(blocks(op_bytes(n, 2, 1, 1) / 8)), dim3(256), 0, h->stream, V[0], V[1], x[0], x[1], eps_bg, nx, ny);
+    else hipLaunchKernelGGL(k_pureshear3d, dim3(blocks(op_bytes(n, 3, 1, 1, 1) / 8)), dim3(256), 0, h->stream, V[0], V[1], V[2], x[0], x[1], x[2], eps_bg, nx, ny, nz);
+    h->stat_stepops_launches++;
+    return op_finish(h);
+}
+
+// free_surface_bcs!: Vtop the vertical velocity component (written), Vside the ND - 1 others; cen = P, P0, τ_o.yy, η at the cell centres; d the ND spacings, of
+// which the 2D kernel reads dx_i / dy_j instead where that array is given
+jrx_status so_free_surface(jrx_handle *h, int ND, double *Vtop, const double *const *Vside, const double *const *cen, const double *phase_c, const jrx_rheology *rh,
+                           double dt, const double *d, const double *dx_i, const double *dy_j, const int64_t n[3], int32_t free_surface)
+{
+    if (!h) return JRX_ERR_ARG;
+    if (!free_surface) return JRX_OK;
+    const char *fn = "free_surface_bcs!";
+    const int top = "xyz"[ND - 1];                    // the component written: Vy in 2D, Vz in 3D
+    bool null = !Vtop || !phase_c || !rh;
+    for (int c = 0; c < ND - 1; c++) null = null || !Vside[c];
+    for (int q = 0; q < 4; q++) null = null || !cen[q];
+    if (null) return jrx_fail(h, JRX_ERR_ARG, "%s: NULL argument", fn);
+    if (!op_extents_ok(n, ND)) return jrx_fail(h, JRX_ERR_ARG, "%s: ni = (%s)", fn, op_list(n, ND, ", ").s);
+    PhaseG g;
+    JRX_TRY(phase_g(h, fn, rh, &g));
+    if (op_2g(op_count(n, ND, 2)) || op_2g((double)g.nphase * op_count(n, ND, 0))) return jrx_fail(h, JRX_ERR_ARG, "%s: an array of 2^31 or more entries", fn);
+    if (!op_pos_finite(dt)) return jrx_fail(h, JRX_ERR_ARG, "%s: dt = %g", fn, dt);
+    const double *const per_cell[3] = {dx_i, dy_j, nullptr};
+    bool spacings = true;
+    for (int a = 0; a < ND; a++) spacings = spacings && (per_cell[a] || op_pos_finite(d[a]));
+    if (!spacings) return jrx_fail(h, JRX_ERR_ARG, "%s: spacings (%s)", fn, op_list(d, ND, ", ").s);
+    const i64 nc = op_bytes(n, ND, 0, 0, 0);              // bytes of a centre array
+    const OpArr out[1] = {{Vtop, op_vel_bytes(n, ND, ND - 1), nullptr}};
+    OpArr in[7];
+    for (int q = 0; q < 4; q++) in[q] = OpArr{cen[q], nc, nullptr};
+    for (int c = 0; c < ND - 1; c++) in[4 + c] = OpArr{Vside[c], op_vel_bytes(n, ND, c), nullptr};
+    in[3 + ND] = OpArr{phase_c, g.nphase * nc, nullptr};
+    if (const OpClash c = op_disjoint(out, 1, in, 4 + ND))
+        return jrx_fail(h, JRX_ERR_ARG, "%s: V%c overlaps %s", fn, top, c.b == 3 + ND ? "the phase ratios" : "an input array");
+    JRX_TRY(jrx_check_device(h));
+    const int nx = (int)n[0], ny = (int)n[1], nz = (int)n[2];
+    if (ND == 2)
+        hipLaunchKernelGGL(k_free_surface2d, dim3(blocks(nx)), dim3(256), 0, h->stream, Vside[0], Vtop, cen[0], cen[1], cen[2], cen[3], phase_c, g, dt, d[0], d[1],
+                           dx_i, dy_j, nx, ny);
+    else
+        hipLaunchKernelGGL(k_free_surface3d, dim3(blocks((i64)nx * ny)), dim3(256), 0, h->stream, Vside[0], Vside[1], Vtop, cen[0], cen[1], cen[2], cen[3], phase_c, g,
+                           dt, d[0], d[1], d[2], nx, ny, nz);
+    h->stat_stepops_launches++;
+    return op_finish(h);
+}
+
 }  // namespace
 
 extern "C" {
 
 jrx_status jrx_pureshear_bc2d(jrx_handle *h, double *Vx, double *Vy, const double *xv, const double *yv, double eps_bg, int64_t nx, int64_t ny)
 {
-    if (!h) return JRX_ERR_ARG;
-    if (!Vx || !Vy || !xv || !yv) return jrx_fail(h, JRX_ERR_ARG, "pureshear_bc!: NULL argument");
-    if (nx < 1 || ny < 1) return jrx_fail(h, JRX_ERR_ARG, "pureshear_bc!: ni = (%lld, %lld)", (long long)nx, (long long)ny);
-    if (too_many(((double)nx + 2) * ((double)ny + 2))) return jrx_fail(h, JRX_ERR_ARG, "pureshear_bc!: a velocity array of 2^31 or more entries");
-    const i64 nvx = (nx + 1) * (ny + 2), nvy = (nx + 2) * (ny + 1);
-    if (overlaps(Vx, nvx, Vy, nvy)) return jrx_fail(h, JRX_ERR_ARG, "pureshear_bc!: Vx and Vy overlap");
-    for (double *o : {Vx, Vy})
-        if (overlaps(o, o == Vx ? nvx : nvy, xv, nx + 1) || overlaps(o, o == Vx ? nvx : nvy, yv, ny + 1))
-            return jrx_fail(h, JRX_ERR_ARG, "pureshear_bc!: a velocity array overlaps a coordinate vector");
-    JRX_TRY(jrx_check_device(h));
-    hipLaunchKernelGGL(k_pureshear2d, dim3(blocks((nx + 1) * (ny + 1))), dim3(256), 0, h->stream, Vx, Vy, xv, yv, eps_bg, (int)nx, (int)ny);
-    return launched(h);
+    double *const V[2] = {Vx, Vy};
+    const double *const x[2] = {xv, yv};
+    const int64_t n[3] = {nx, ny, 1};
+    return so_pureshear(h, 2, V, x, eps_bg, n);
 }
 
 jrx_status jrx_pureshear_bc3d(jrx_handle *h, double *Vx, double *Vy, double *Vz, const double *xv, const double *yv, const double *zv, double eps_bg,
                               int64_t nx, int64_t ny, int64_t nz)
 {
-    if (!h) return JRX_ERR_ARG;
-    if (!Vx || !Vy || !Vz || !xv || !yv || !zv) return jrx_fail(h, JRX_ERR_ARG, "pureshear_bc!: NULL argument");
-    if (nx < 1 || ny < 1 || nz < 1) return jrx_fail(h, JRX_ERR_ARG, "pureshear_bc!: ni = (%lld, %lld, %lld)", (long long)nx, (long long)ny, (long long)nz);
-    if (too_many(((double)nx + 2) * ((double)ny + 2) * ((double)nz + 2)))
-        return jrx_fail(h, JRX_ERR_ARG, "pureshear_bc!: a velocity array of 2^31 or more entries");
-    double *out[3] = {Vx, Vy, Vz};
-    const i64 nout[3] = {(nx + 1) * (ny + 2) * (nz + 2), (nx + 2) * (ny + 1) * (nz + 2), (nx + 2) * (ny + 2) * (nz + 1)};
-    const double *in[3] = {xv, yv, zv};
-    const i64 nin[3] = {nx + 1, ny + 1, nz + 1};
-    for (int a = 0; a < 3; a++) {
-        for (int b = a + 1; b < 3; b++)
-            if (overlaps(out[a], nout[a], out[b], nout[b])) return jrx_fail(h, JRX_ERR_ARG, "pureshear_bc!: two velocity arrays overlap");
-        for (int b = 0; b < 3; b++)
-            if (overlaps(out[a], nout[a], in[b], nin[b])) return jrx_fail(h, JRX_ERR_ARG, "pureshear_bc!: a velocity array overlaps a coordinate vector");
-    }
-    JRX_TRY(jrx_check_device(h));
-    hipLaunchKernelGGL(k_pureshear3d, dim3(blocks((nx + 1) * (ny + 1) * (nz + 1))), dim3(256), 0, h->stream, Vx, Vy, Vz, xv, yv, zv, eps_bg, (int)nx, (int)ny,
-                       (int)nz);
-    return launched(h);
+    double *const V[3] = {Vx, Vy, Vz};
+    const double *const x[3] = {xv, yv, zv};
+    const int64_t n[3] = {nx, ny, nz};
+    return so_pureshear(h, 3, V, x, eps_bg, n);
 }
 
 jrx_status jrx_free_surface_bcs2d(jrx_handle *h, const double *Vx, double *Vy, const double *P, const double *P0, const double *tau_o_yy, const double *eta,
                                   const double *phase_c, const jrx_rheology *rh, double dt, double dx, double dy, const double *dx_i, const double *dy_j,
                                   int64_t nx, int64_t ny, int32_t free_surface)
 {
-    if (!h) return JRX_ERR_ARG;
-    if (!free_surface) return JRX_OK;
-    if (!Vx || !Vy || !P || !P0 || !tau_o_yy || !eta || !phase_c || !rh) return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: NULL argument");
-    if (nx < 1 || ny < 1) return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: ni = (%lld, %lld)", (long long)nx, (long long)ny);
-    PhaseG g;
-    JRX_TRY(phase_g(h, "free_surface_bcs!", rh, &g));
-    if (too_many(((double)nx + 2) * ((double)ny + 2)) || too_many((double)g.nphase * (double)nx * (double)ny))
-        return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: an array of 2^31 or more entries");
-    if (!pos_finite(dt)) return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: dt = %g", dt);
-    if ((!dx_i && !pos_finite(dx)) || (!dy_j && !pos_finite(dy))) return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: spacings (%g, %g)", dx, dy);
-    const i64 nc = nx * ny, nvy = (nx + 2) * (ny + 1);
-    const double *in[5] = {P, P0, tau_o_yy, eta, Vx};
-    const i64 nin[5] = {nc, nc, nc, nc, (nx + 1) * (ny + 2)};
-    for (int q = 0; q < 5; q++)
-        if (overlaps(Vy, nvy, in[q], nin[q])) return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: Vy overlaps an input array");
-    if (overlaps(Vy, nvy, phase_c, g.nphase * nc)) return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: Vy overlaps the phase ratios");
-    JRX_TRY(jrx_check_device(h));
-    hipLaunchKernelGGL(k_free_surface2d, dim3(blocks(nx)), dim3(256), 0, h->stream, Vx, Vy, P, P0, tau_o_yy, eta, phase_c, g, dt, dx, dy, dx_i, dy_j, (int)nx,
-                       (int)ny);
-    return launched(h);
+    const double *const Vside[1] = {Vx};
+    const double *const cen[4] = {P, P0, tau_o_yy, eta};
+    const int64_t n[3] = {nx, ny, 1};
+    const double d[2] = {dx, dy};
+    return so_free_surface(h, 2, Vy, Vside, cen, phase_c, rh, dt, d, dx_i, dy_j, n, free_surface);
 }
 
 jrx_status jrx_free_surface_bcs3d(jrx_handle *h, const double *Vx, const double *Vy, double *Vz, const double *P, const double *P0, const double *tau_o_yy,
                                   const double *eta, const double *phase_c, const jrx_rheology *rh, double dt, double dx, double dy, double dz, int64_t nx,
                                   int64_t ny, int64_t nz, int32_t free_surface)
 {
-    if (!h) return JRX_ERR_ARG;
-    if (!free_surface) return JRX_OK;
-    if (!Vx || !Vy || !Vz || !P || !P0 || !tau_o_yy || !eta || !phase_c || !rh) return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: NULL argument");
-    if (nx < 1 || ny < 1 || nz < 1) return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: ni = (%lld, %lld, %lld)", (long long)nx, (long long)ny, (long long)nz);
-    PhaseG g;
-    JRX_TRY(phase_g(h, "free_surface_bcs!", rh, &g));
-    if (too_many(((double)nx + 2) * ((double)ny + 2) * ((double)nz + 2)) || too_many((double)g.nphase * (double)nx * (double)ny * (double)nz))
-        return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: an array of 2^31 or more entries");
-    if (!pos_finite(dt)) return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: dt = %g", dt);
-    if (!pos_finite(dx) || !pos_finite(dy) || !pos_finite(dz)) return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: spacings (%g, %g, %g)", dx, dy, dz);
-    const i64 nc = nx * ny * nz, nvz = (nx + 2) * (ny + 2) * (nz + 1);
-    const double *in[6] = {P, P0, tau_o_yy, eta, Vx, Vy};
-    const i64 nin[6] = {nc, nc, nc, nc, (nx + 1) * (ny + 2) * (nz + 2), (nx + 2) * (ny + 1) * (nz + 2)};
-    for (int q = 0; q < 6; q++)
-        if (overlaps(Vz, nvz, in[q], nin[q])) return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: Vz overlaps an input array");
-    if (overlaps(Vz, nvz, phase_c, g.nphase * nc)) return jrx_fail(h, JRX_ERR_ARG, "free_surface_bcs!: Vz overlaps the phase ratios");
-    JRX_TRY(jrx_check_device(h));
-    hipLaunchKernelGGL(k_free_surface3d, dim3(blocks(nx * ny)), dim3(256), 0, h->stream, Vx, Vy, Vz, P, P0, tau_o_yy, eta, phase_c, g, dt, dx, dy, dz, (int)nx,
-                       (int)ny, (int)nz);
-    return launched(h);
+    const double *const Vside[2] = {Vx, Vy};
+    const double *const cen[4] = {P, P0, tau_o_yy, eta};
+    const int64_t n[3] = {nx, ny, nz};
+    const double d[3] = {dx, dy, dz};
+    return so_free_surface(h, 3, Vz, Vside, cen, phase_c, rh, dt, d, nullptr, nullptr, n, free_surface);
 }
 
 jrx_status jrx_subgrid_characteristic_time(jrx_handle *h, double *dt0, const double *phase_c, const jrx_thermal_phases *ph, const double *T, const double *P,
                                            const int64_t n[3], int32_t ndim, const double di[3])
 {
     if (!h) return JRX_ERR_ARG;
-    if (!dt0 || !phase_c || !ph || !T || !P || !n || !di) return jrx_fail(h, JRX_ERR_ARG, "subgrid_characteristic_time!: NULL argument");
-    if (ndim != 2 && ndim != 3) return jrx_fail(h, JRX_ERR_ARG, "subgrid_characteristic_time!: ndim = %d", (int)ndim);
-    if (ph->nphase < 1 || ph->nphase > JRX_MAXPHASE)
-        return jrx_fail(h, JRX_ERR_ARG, "subgrid_characteristic_time!: %d phases (1..%d)", (int)ph->nphase, JRX_MAXPHASE);
-    const int64_t nx = n[0], ny = n[1], nz = ndim == 3 ? n[2] : 1;
-    if (nx < 1 || ny < 1 || nz < 1)
-        return jrx_fail(h, JRX_ERR_ARG, "subgrid_characteristic_time!: size(stokes.P) = (%lld, %lld, %lld)", (long long)nx, (long long)ny, (long long)nz);
-    const double tz = ndim == 3 ? (double)nz + 2 : 1.0;
-    if (too_many(((double)nx + 2) * ((double)ny + 2) * tz) || too_many((double)ph->nphase * (double)nx * (double)ny * (double)nz))
-        return jrx_fail(h, JRX_ERR_ARG, "subgrid_characteristic_time!: an array of 2^31 or more entries");
+    const char *fn = "subgrid_characteristic_time!";
+    if (!dt0 || !phase_c || !ph || !T || !P || !n || !di) return jrx_fail(h, JRX_ERR_ARG, "%s: NULL argument", fn);
+    if (ndim != 2 && ndim != 3) return jrx_fail(h, JRX_ERR_ARG, "%s: ndim = %d", fn, (int)ndim);
+    if (ph->nphase < 1 || ph->nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d phases (1..%d)", fn, (int)ph->nphase, JRX_MAXPHASE);
+    const int64_t m[3] = {n[0], n[1], ndim == 3 ? n[2] : 1};
+    if (!op_extents_ok(m, 3)) return jrx_fail(h, JRX_ERR_ARG, "%s: size(stokes.P) = (%s)", fn, op_list(m, 3, ", ").s);
+    if (op_2g(op_count(m, ndim, 2)) || op_2g((double)ph->nphase * op_count(m, 3, 0))) return jrx_fail(h, JRX_ERR_ARG, "%s: an array of 2^31 or more entries", fn);
     double sum_dxi = 0.0;          // mapreduce(x -> inv(x)^2, +, di): left to right
     for (int d = 0; d < ndim; d++) {
-        if (!pos_finite(di[d])) return jrx_fail(h, JRX_ERR_ARG, "subgrid_characteristic_time!: di[%d] = %g", d + 1, di[d]);
+        if (!op_pos_finite(di[d])) return jrx_fail(h, JRX_ERR_ARG, "%s: di[%d] = %g", fn, d + 1, di[d]);
         const double inv = 1.0 / di[d];
         sum_dxi = d == 0 ? inv * inv : sum_dxi + inv * inv;
     }
-    const i64 nc = nx * ny * nz, nt = (nx + 2) * (ny + 2) * (ndim == 3 ? nz + 2 : 1);
-    if (overlaps(dt0, nc, T, nt) || overlaps(dt0, nc, P, nc) || overlaps(dt0, nc, phase_c, ph->nphase * nc))
-        return jrx_fail(h, JRX_ERR_ARG, "subgrid_characteristic_time!: dt₀ overlaps an input array");
+    const i64 bytes = op_bytes(m, 3, 0, 0, 0);
+    const OpArr out[1] = {{dt0, bytes, nullptr}}, in[3] = {{T, op_bytes(m, ndim, 2, 2, 2), nullptr}, {P, bytes, nullptr}, {phase_c, ph->nphase * bytes, nullptr}};
+    if (op_disjoint(out, 1, in, 3)) return jrx_fail(h, JRX_ERR_ARG, "%s: dt₀ overlaps an input array", fn);
     JRX_TRY(jrx_check_device(h));
     const int sk = ndim == 3 ? 1 : 0;
     dispatch_const<0, 1, 2, 3, 4>(ph->nphase <= 4 ? ph->nphase : 0, [&](auto NP) {
-        hipLaunchKernelGGL(k_subgrid_time<NP()>, dim3(blocks(nc)), dim3(256), 0, h->stream, dt0, phase_c, *ph, T, P, sum_dxi, (int)nx, (int)ny, (int)nz, sk);
+        hipLaunchKernelGGL(k_subgrid_time<NP()>, dim3(blocks(bytes / 8)), dim3(256), 0, h->stream, dt0, phase_c, *ph, T, P, sum_dxi, (int)m[0], (int)m[1], (int)m[2], sk);
     });
-    return launched(h);
+    h->stat_stepops_launches++;
+    return op_finish(h);
 }
 
 jrx_status jrx_compute_melt_fraction(jrx_handle *h, double *phi, const double *phase_c, const jrx_melting *m, const double *T, double T_scalar, const double *P,
                                      double P_scalar, const int64_t n[3], int32_t ndim)
 {
     if (!h) return JRX_ERR_ARG;
-    if (!phi || !m || !n) return jrx_fail(h, JRX_ERR_ARG, "compute_melt_fraction!: NULL argument");
-    if (ndim != 2 && ndim != 3) return jrx_fail(h, JRX_ERR_ARG, "compute_melt_fraction!: ndim = %d", (int)ndim);
-    if (m->nphase < 1 || m->nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "compute_melt_fraction!: %d phases (1..%d)", (int)m->nphase, JRX_MAXPHASE);
+    const char *fn = "compute_melt_fraction!";
+    if (!phi || !m || !n) return jrx_fail(h, JRX_ERR_ARG, "%s: NULL argument", fn);
+    if (ndim != 2 && ndim != 3) return jrx_fail(h, JRX_ERR_ARG, "%s: ndim = %d", fn, (int)ndim);
+    if (m->nphase < 1 || m->nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d phases (1..%d)", fn, (int)m->nphase, JRX_MAXPHASE);
     for (int q = 0; q < m->nphase; q++)
         if (m->kind[q] != 0 && m->kind[q] != 1)
-            return jrx_fail(h, JRX_ERR_ARG, "compute_melt_fraction!: melting kind %d of phase %d is not built (0 = none, 1 = MeltingParam_Caricchi: the one law "
-                                            "the reference's tests pin)", (int)m->kind[q], q + 1);
-    const int64_t nx = n[0], ny = n[1], nz = ndim == 3 ? n[2] : 1;
-    if (nx < 1 || ny < 1 || nz < 1)
-        return jrx_fail(h, JRX_ERR_ARG, "compute_melt_fraction!: size(ϕ) = (%lld, %lld, %lld)", (long long)nx, (long long)ny, (long long)nz);
-    if (too_many((phase_c ? (double)m->nphase : 1.0) * (double)nx * (double)ny * (double)nz))
-        return jrx_fail(h, JRX_ERR_ARG, "compute_melt_fraction!: an array of 2^31 or more entries");
+            return jrx_fail(h, JRX_ERR_ARG, "%s: melting kind %d of phase %d is not built (0 = none, 1 = MeltingParam_Caricchi: the one law the reference's tests pin)",
+                            fn, (int)m->kind[q], q + 1);
+    const int64_t e[3] = {n[0], n[1], ndim == 3 ? n[2] : 1};
+    if (!op_extents_ok(e, 3)) return jrx_fail(h, JRX_ERR_ARG, "%s: size(ϕ) = (%s)", fn, op_list(e, 3, ", ").s);
+    if (op_2g((phase_c ? (double)m->nphase : 1.0) * op_count(e, 3, 0))) return jrx_fail(h, JRX_ERR_ARG, "%s: an array of 2^31 or more entries", fn);
     (void)P_scalar;                // neither law reads the pressure
-    const i64 nc = nx * ny * nz;
-    if ((T && overlaps(phi, nc, T, nc)) || (P && overlaps(phi, nc, P, nc)) || (phase_c && overlaps(phi, nc, phase_c, m->nphase * nc)))
-        return jrx_fail(h, JRX_ERR_ARG, "compute_melt_fraction!: ϕ overlaps an input array");
+    const i64 bytes = op_bytes(e, 3, 0, 0, 0), nc = bytes / 8;
+    const OpArr out[1] = {{phi, bytes, nullptr}};
+    OpArr in[3];                   // T, P and the phase ratios: those that are there
+    int nin = 0;
+    if (T) in[nin++] = OpArr{T, bytes, nullptr};
+    if (P) in[nin++] = OpArr{P, bytes, nullptr};
+    if (phase_c) in[nin++] = OpArr{phase_c, m->nphase * bytes, nullptr};
+    if (op_disjoint(out, 1, in, nin)) return jrx_fail(h, JRX_ERR_ARG, "%s: ϕ overlaps an input array", fn);
     JRX_TRY(jrx_check_device(h));
     if (!phase_c)
         hipLaunchKernelGGL((k_melt_fraction<0, false>), dim3(blocks(nc)), dim3(256), 0, h->stream, phi, phase_c, *m, T, T_scalar, nc);
@@ -319,7 +315,8 @@ jrx_status jrx_compute_melt_fraction(jrx_handle *h, double *phi, const double *p
         dispatch_const<0, 1, 2, 3, 4>(m->nphase <= 4 ? m->nphase : 0, [&](auto NP) {
             hipLaunchKernelGGL((k_melt_fraction<NP(), true>), dim3(blocks(nc)), dim3(256), 0, h->stream, phi, phase_c, *m, T, T_scalar, nc);
         });
-    return launched(h);
+    h->stat_stepops_launches++;
+    return op_finish(h);
 }
 
 }  // extern "C"

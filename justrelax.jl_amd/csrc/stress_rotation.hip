@@ -19,7 +19,7 @@
 // lanes of a wave and the rows of a block share almost every operand.  method and advection are template arguments.  No fma (the library builds with
 // -ffp-contract=off): every product and sum is rounded once, in the order written, which is the order of tests/_stress_rotation.py.
 // Addressing: 32-bit element offsets (every array below 2^31 entries, checked).
-#include "jrx_internal.hpp"
+#include "op_args.hpp"
 #include "rotate_point.hpp"
 
 namespace {
@@ -314,23 +314,12 @@ __global__ __launch_bounds__(256) void k_rotate_stress3d(const RsArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------ host
-bool overlaps(const void *a, i64 na, const void *b, i64 nb)
-{
-    const char *pa = (const char *)a, *pb = (const char *)b;
-    return pa < pb + 8 * nb && pb < pa + 8 * na;
-}
-
-struct RsArray {
-    const void *p;
-    i64 n;
-    const char *name;
-};
-
 // checks and launch shared by the two entry points.  tau / tau_o: NT members with the staggering sets stag[]; the first `req` are required
 jrx_status rs_rotate(jrx_handle *h, const char *fn, int ND, double *const *tau_o, const double *const *tau, const char *const *names, const int *stag, int NT, int req,
                      const double *const *omega, const char *const *wnames, const int *wstag, int NW, const double *const *V, const int64_t n[3], const double *_di,
                      double dt, int32_t method, int32_t advection)
 {
+    if (!h) return JRX_ERR_ARG;
     if (!tau_o || !tau || !omega || !_di) return jrx_fail(h, JRX_ERR_ARG, "%s: NULL argument", fn);
     if (method != JRX_ROTATE_MATRIX && method != JRX_ROTATE_JAUMANN)
         return jrx_fail(h, JRX_ERR_ARG, "%s: unknown method %d (%d = matrix, %d = jaumann)", fn, (int)method, JRX_ROTATE_MATRIX, JRX_ROTATE_JAUMANN);
@@ -338,19 +327,14 @@ jrx_status rs_rotate(jrx_handle *h, const char *fn, int ND, double *const *tau_o
         return jrx_fail(h, JRX_ERR_ARG, "%s: unknown advection kind %d (%d = none, %d = upwind)", fn, (int)advection, JRX_ADVECT_NONE, JRX_ADVECT_UPWIND);
     for (int d = 0; d < ND; d++)
         if (n[d] < 1) return jrx_fail(h, JRX_ERR_ARG, "%s: extent %lld along dimension %d", fn, (long long)n[d], d + 1);
-    double ent = 1.0;                            // entries of a box that holds every array: the velocities have n + 2 along their transverse axes
-    for (int d = 0; d < ND; d++) ent *= (double)(n[d] + 2);
-    if (ent >= 2147483648.0) return jrx_fail(h, JRX_ERR_ARG, "%s: the velocity box (ni .+ 2) has 2^31 or more entries (32-bit offsets)", fn);
+    // a box that holds every array: the velocities have n + 2 along their transverse axes
+    if (op_2g(op_count(n, ND, 2))) return jrx_fail(h, JRX_ERR_ARG, "%s: the velocity box (ni .+ 2) has 2^31 or more entries (32-bit offsets)", fn);
     const bool adv = advection == JRX_ADVECT_UPWIND;
     if (adv && !V) return jrx_fail(h, JRX_ERR_ARG, "%s: V is NULL (only advection = none takes no velocities)", fn);
-    auto count = [&](int S, int ghostC) {        // entries of an array at location S; ghostC >= 0: velocity component ghostC
-        i64 c = 1;
-        for (int d = 0; d < ND; d++) c *= ghostC < 0 ? n[d] + ((S >> d) & 1) : n[d] + (d == ghostC ? 1 : 2);
-        return c;
-    };
+    auto at = [&](int S) { return op_bytes(n, ND, S & 1, (S >> 1) & 1, (S >> 2) & 1); };       // bytes of an array at location S
     bool present[9] = {};
     const bool opt = NT > req && tau[req] && tau[req + 1] && tau_o[req] && tau_o[req + 1];       // the 2D vertex normals: all four or none
-    RsArray in[16], out[9];
+    OpArr in[16], out[9];
     int nin = 0, nout = 0;
     for (int m = 0; m < NT; m++) {
         if (m >= req) {
@@ -361,26 +345,22 @@ jrx_status rs_rotate(jrx_handle *h, const char *fn, int ND, double *const *tau_o
             if (!tau_o[m]) return jrx_fail(h, JRX_ERR_ARG, "%s: τ_o.%s is NULL", fn, names[m]);
             present[m] = true;
         }
-        in[nin++] = {tau[m], count(stag[m], -1), names[m]};
-        out[nout++] = {tau_o[m], count(stag[m], -1), names[m]};
+        in[nin++] = {tau[m], at(stag[m]), names[m]};
+        out[nout++] = {tau_o[m], at(stag[m]), names[m]};
     }
     static const char *const vnames[3] = {"V.Vx", "V.Vy", "V.Vz"};
     for (int c = 0; c < NW; c++) {
         if (!omega[c]) return jrx_fail(h, JRX_ERR_ARG, "%s: ω.%s is NULL", fn, wnames[c]);
-        in[nin++] = {omega[c], count(wstag[c], -1), wnames[c]};
+        in[nin++] = {omega[c], at(wstag[c]), wnames[c]};
     }
     if (adv)
         for (int c = 0; c < ND; c++) {
             if (!V[c]) return jrx_fail(h, JRX_ERR_ARG, "%s: %s is NULL (only advection = none takes no velocities)", fn, vnames[c]);
-            in[nin++] = {V[c], count(0, c), vnames[c]};
+            in[nin++] = {V[c], op_vel_bytes(n, ND, c), vnames[c]};
         }
-    for (int i = 0; i < nout; i++) {
-        for (int j = 0; j < nin; j++)
-            if (overlaps(out[i].p, out[i].n, in[j].p, in[j].n))
-                return jrx_fail(h, JRX_ERR_ARG, "%s: output τ_o.%s overlaps input %s (the step is out of place)", fn, out[i].name, in[j].name);
-        for (int j = i + 1; j < nout; j++)
-            if (overlaps(out[i].p, out[i].n, out[j].p, out[j].n)) return jrx_fail(h, JRX_ERR_ARG, "%s: outputs τ_o.%s and τ_o.%s overlap", fn, out[i].name, out[j].name);
-    }
+    if (const OpClash c = op_disjoint(out, nout, in, nin))
+        return c.two ? jrx_fail(h, JRX_ERR_ARG, "%s: outputs τ_o.%s and τ_o.%s overlap", fn, out[c.a].name, out[c.b].name)
+                     : jrx_fail(h, JRX_ERR_ARG, "%s: output τ_o.%s overlaps input %s (the step is out of place)", fn, out[c.a].name, in[c.b].name);
     JRX_TRY(jrx_check_device(h));
     RsArgs a = {};
     for (int m = 0; m < NT; m++)
@@ -406,9 +386,7 @@ jrx_status rs_rotate(jrx_handle *h, const char *fn, int ND, double *const *tau_o
             else hipLaunchKernelGGL((k_rotate_stress2d<M, A, 0>), dim3((unsigned)nb), dim3(kRsTX, ty, tz), 0, h->stream, a);
         });
     });
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    return op_finish(h);
 }
 
 }  // namespace
@@ -418,7 +396,6 @@ extern "C" {
 jrx_status jrx_rotate_stress2d(jrx_handle *h, double *const tau_o[6], const double *const tau[6], const double *omega_xy, const double *const V[2], int64_t nx,
                                int64_t ny, const double _di[2], double dt, int32_t method, int32_t advection)
 {
-    if (!h) return JRX_ERR_ARG;
     static const char *const names[6] = {"xx", "yy", "xy_c", "xy", "xx_v", "yy_v"};
     static const int stag[6] = {0, 0, 0, 3, 3, 3};
     static const char *const wnames[1] = {"xy"};
@@ -431,7 +408,6 @@ jrx_status jrx_rotate_stress2d(jrx_handle *h, double *const tau_o[6], const doub
 jrx_status jrx_rotate_stress3d(jrx_handle *h, double *const tau_o[9], const double *const tau[9], const double *const omega[3], const double *const V[3],
                                int64_t nx, int64_t ny, int64_t nz, const double _di[3], double dt, int32_t method, int32_t advection)
 {
-    if (!h) return JRX_ERR_ARG;
     static const char *const names[9] = {"xx", "yy", "zz", "yz_c", "xz_c", "xy_c", "yz", "xz", "xy"};
     static const int stag[9] = {0, 0, 0, 0, 0, 0, 6, 5, 3};
     static const char *const wnames[3] = {"yz", "xz", "xy"};

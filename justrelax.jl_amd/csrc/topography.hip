@@ -19,7 +19,7 @@
 // by measurement) writes the eight members that node owns; its only loads are the nine heights around (i, j); rows the surface does not cross are 1 or 0 by the
 // shortcuts of the definition without evaluating a triangle.  k_advect_topography3d: a thread per vertex.  k_phases_topography3d<N>: a thread per column (i, j)
 // marches k by the 2D rule.
-#include "jrx_internal.hpp"
+#include "op_args.hpp"
 
 namespace {
 
@@ -352,27 +352,126 @@ __global__ __launch_bounds__(256) void k_phases_topography3d(const Ph3Args a)
     }
 }
 
-bool tp_overlaps(const void *a, i64 na, const void *b, i64 nb)
-{
-    const char *pa = (const char *)a, *pb = (const char *)b;
-    return pa < pb + 8 * nb && pb < pa + 8 * na;
-}
-
+// ------------------------------------------------------------------------------------------------ host: one body per operator, ND = 2 or 3
 // extents >= 1 and every array (the largest is the ni .+ 2 box of the velocities) below 2^31 entries
-jrx_status tp_extents(jrx_handle *h, const char *fn, int64_t nx, int64_t ny)
+jrx_status tp_extents(jrx_handle *h, const char *fn, const int64_t *n, int ND)
 {
-    if (nx < 1 || ny < 1) return jrx_fail(h, JRX_ERR_ARG, "%s: extents %lld x %lld (each must be >= 1)", fn, (long long)nx, (long long)ny);
-    if ((double)(nx + 2) * (double)(ny + 2) >= 2147483648.0) return jrx_fail(h, JRX_ERR_ARG, "%s: the ni .+ 2 box has 2^31 or more entries (32-bit offsets)", fn);
+    if (!op_extents_ok(n, ND)) return jrx_fail(h, JRX_ERR_ARG, "%s: extents %s (each must be >= 1)", fn, op_list(n, ND, " x ").s);
+    if (op_2g(op_count(n, ND, 2))) return jrx_fail(h, JRX_ERR_ARG, "%s: the ni .+ 2 box has 2^31 or more entries (32-bit offsets)", fn);
     return JRX_OK;
 }
 
-jrx_status tp_extents3(jrx_handle *h, const char *fn, int64_t nx, int64_t ny, int64_t nz)
+// compute_rock_fraction!: the members of ϕ in the order of the 3D entry point, of which 2D has the first four; u0, _du: origin and inverse spacing of the
+// vertical axis (y in 2D, z in 3D)
+jrx_status tp_rock_fraction(jrx_handle *h, int ND, double *const *out, const double *topo_h, const int64_t n[3], double u0, double _du)
 {
-    if (nx < 1 || ny < 1 || nz < 1)
-        return jrx_fail(h, JRX_ERR_ARG, "%s: extents %lld x %lld x %lld (each must be >= 1)", fn, (long long)nx, (long long)ny, (long long)nz);
-    if ((double)(nx + 2) * (double)(ny + 2) * (double)(nz + 2) >= 2147483648.0)
-        return jrx_fail(h, JRX_ERR_ARG, "%s: the ni .+ 2 box has 2^31 or more entries (32-bit offsets)", fn);
-    return JRX_OK;
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "compute_rock_fraction!";
+    static const char *const names[8] = {"ϕ.center", "ϕ.vertex", "ϕ.Vx", "ϕ.Vy", "ϕ.Vz", "ϕ.yz", "ϕ.xz", "ϕ.xy"};
+    static const int stag[8][3] = {{0, 0, 0}, {1, 1, 1}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {0, 1, 1}, {1, 0, 1}, {1, 1, 0}};
+    const int NM = ND == 2 ? 4 : 8, ax = "xyz"[ND - 1];
+    OpArr o[8], in[1] = {{topo_h, 0, "topo.h"}};
+    for (int m = 0; m < NM; m++) o[m] = OpArr{out[m], 0, names[m]};
+    JRX_TRY(op_present(h, fn, o, NM));
+    JRX_TRY(op_present(h, fn, in, 1));
+    JRX_TRY(tp_extents(h, fn, n, ND));
+    if (!op_finite({u0, _du})) return jrx_fail(h, JRX_ERR_ARG, "%s: %c0 = %g, _d%c = %g (both must be finite)", fn, ax, u0, ax, _du);
+    for (int m = 0; m < NM; m++) o[m].bytes = op_bytes(n, ND, stag[m][0], stag[m][1], stag[m][2]);
+    in[0].bytes = op_bytes(n, ND - 1, 1, 1);          // the height field: a value per vertex of the ND - 1 horizontal axes
+    if (const OpClash c = op_disjoint(o, NM, in, 1))
+        return c.two ? jrx_fail(h, JRX_ERR_ARG, "%s: outputs %s and %s overlap", fn, o[c.a].name, o[c.b].name)
+                     : jrx_fail(h, JRX_ERR_ARG, "%s: output %s overlaps topo.h", fn, o[c.a].name);
+    JRX_TRY(jrx_check_device(h));
+    const int64_t nx = n[0], ny = n[1], nz = n[2];
+    h->stat_rock_fraction_calls++;
+    if (ND == 2) {
+        RfArgs a = {topo_h, out[0], out[1], out[2], out[3], u0, _du, (int)nx, (int)ny, (int)((nx + 1 + kTpTX - 1) / kTpTX)};
+        const int64_t nb = (int64_t)a.nbx * ((ny + 1 + kTpTY - 1) / kTpTY);      // below 2^31: the box is
+        hipLaunchKernelGGL(k_rock_fraction2d, dim3((unsigned)nb), dim3(kTpTX, kTpTY), 0, h->stream, a);
+        return op_finish(h);
+    }
+    int rows = h->rock_fraction3d_rows > 0 ? h->rock_fraction3d_rows : kTpRows3;
+    if (rows > nz + 1) rows = (int)(nz + 1);      // a deeper march is the whole column; keeps k0 + rows inside an int
+    Rf3Args a = {topo_h, out[0], out[1], out[2], out[3], out[4], out[5], out[6], out[7], u0, _du, (int)nx, (int)ny, (int)nz, (int)((nx + 1 + kTpTX - 1) / kTpTX),
+                 (int)((ny + 1 + kTpTY - 1) / kTpTY), rows};
+    const int64_t nb = (int64_t)a.nbx * a.nby * ((nz + 1 + rows - 1) / rows);      // below 2^31: no more blocks than nodes of the ni .+ 1 box
+    hipLaunchKernelGGL(k_rock_fraction3d, dim3((unsigned)nb), dim3(kTpTX, kTpTY), 0, h->stream, a);
+    return op_finish(h);
+}
+
+// advect_topography!: V the ND velocity components with their ghost layers, _di the ND inverse spacings
+jrx_status tp_advect(jrx_handle *h, int ND, double *topo_h, double *topo_h_old, const double *const *V, const int64_t n[3], double u0, const double *_di, double dt)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "advect_topography!";
+    static const char *const vnames[3] = {"V.Vx", "V.Vy", "V.Vz"};
+    OpArr o[2] = {{topo_h, 0, "topo.h"}, {topo_h_old, 0, "topo.h_old"}}, in[3];
+    for (int c = 0; c < ND; c++) in[c] = OpArr{V[c], 0, vnames[c]};
+    JRX_TRY(op_present(h, fn, o, 2));
+    JRX_TRY(op_present(h, fn, in, ND));
+    JRX_TRY(tp_extents(h, fn, n, ND));
+    if (ND == 2 && !op_finite({dt, _di[0], _di[1], u0}))
+        return jrx_fail(h, JRX_ERR_ARG, "%s: dt = %g, _dx = %g, _dy = %g, y0 = %g (all must be finite)", fn, dt, _di[0], _di[1], u0);
+    if (ND == 3 && !op_finite({dt, _di[0], _di[1], _di[2], u0}))
+        return jrx_fail(h, JRX_ERR_ARG, "%s: dt = %g, _dx = %g, _dy = %g, _dz = %g, z0 = %g (all must be finite)", fn, dt, _di[0], _di[1], _di[2], u0);
+    const i64 nh = op_bytes(n, ND - 1, 1, 1);          // bytes of a height field
+    o[0].bytes = o[1].bytes = nh;
+    for (int c = 0; c < ND; c++) in[c].bytes = op_vel_bytes(n, ND, c);
+    if (const OpClash c = op_disjoint(o, 2, in, ND)) return jrx_fail(h, JRX_ERR_ARG, "%s: output %s overlaps %s", fn, o[c.a].name, (c.two ? o : in)[c.b].name);
+    JRX_TRY(jrx_check_device(h));
+    const int64_t nx = n[0], ny = n[1], nz = n[2];
+    h->stat_topography_advect_calls++;
+    JRX_HIP(h, hipMemcpyAsync(topo_h_old, topo_h, (size_t)nh, hipMemcpyDeviceToDevice, h->stream));
+    if (ND == 2) {
+        AdvArgs a = {topo_h, topo_h_old, V[0], V[1], u0, _di[0], _di[1], dt, (int)nx, (int)ny};
+        hipLaunchKernelGGL(k_advect_topography2d, dim3((unsigned)((nx + 1 + kTpCols - 1) / kTpCols)), dim3(kTpCols), 0, h->stream, a);
+    } else {
+        Adv3Args a = {topo_h, topo_h_old, V[0], V[1], V[2], u0, _di[0], _di[1], _di[2], dt, (int)nx, (int)ny, (int)nz, (int)((nx + 1 + kTpTX - 1) / kTpTX)};
+        hipLaunchKernelGGL(k_advect_topography3d, dim3((unsigned)((int64_t)a.nbx * ((ny + 1 + kTpTY - 1) / kTpTY))), dim3(kTpTX, kTpTY), 0, h->stream, a);
+    }
+    return op_finish(h);
+}
+
+// update_phases_given_topography!
+jrx_status tp_phases(jrx_handle *h, int ND, double *const *phases, int32_t nphase, const double *topo_h, const int64_t n[3], double u0, double _du, int32_t air_phase)
+{
+    if (!h) return JRX_ERR_ARG;
+    const char *fn = "update_phases_given_topography!";
+    const int ax = "xyz"[ND - 1];
+    if (!phases) return jrx_fail(h, JRX_ERR_ARG, "%s: phases is NULL", fn);
+    if (nphase < 1 || nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d phase fields (1 .. %d are built)", fn, (int)nphase, JRX_MAXPHASE);
+    if (air_phase < 1 || air_phase > nphase) return jrx_fail(h, JRX_ERR_ARG, "%s: air_phase %d outside 1 .. %d", fn, (int)air_phase, (int)nphase);
+    for (int k = 0; k < nphase; k++)
+        if (!phases[k]) return jrx_fail(h, JRX_ERR_ARG, "%s: phase field %d is NULL", fn, k + 1);
+    if (!topo_h) return jrx_fail(h, JRX_ERR_ARG, "%s: topo.h is NULL", fn);
+    JRX_TRY(tp_extents(h, fn, n, ND));
+    if (!op_finite({u0, _du})) return jrx_fail(h, JRX_ERR_ARG, "%s: %c0 = %g, _d%c = %g (both must be finite)", fn, ax, u0, ax, _du);
+    OpArr o[JRX_MAXPHASE];
+    for (int k = 0; k < nphase; k++) o[k] = OpArr{phases[k], op_bytes(n, ND, 0, 0, 0), nullptr};
+    const OpArr in[1] = {{topo_h, op_bytes(n, ND - 1, 1, 1), nullptr}};
+    if (const OpClash c = op_disjoint(o, nphase, in, 1))
+        return c.two ? jrx_fail(h, JRX_ERR_ARG, "%s: phase fields %d and %d overlap", fn, c.a + 1, c.b + 1)
+                     : jrx_fail(h, JRX_ERR_ARG, "%s: phase field %d overlaps topo.h", fn, c.a + 1);
+    JRX_TRY(jrx_check_device(h));
+    const int64_t nx = n[0], ny = n[1], nz = n[2];
+    h->stat_topography_phase_calls++;
+    if (ND == 2) {
+        PhArgs a = {};
+        for (int k = 0; k < nphase; k++) a.c[k] = phases[k];
+        a.h = topo_h, a.y0 = u0, a.idy = _du, a.nx = (int)nx, a.ny = (int)ny, a.air = (int)air_phase - 1;
+        dispatch_const<1, 2, 3, 4, 5, 6, 7, 8>((int)nphase, [&](auto NN) {
+            hipLaunchKernelGGL((k_phases_topography2d<NN()>), dim3((unsigned)((nx + kTpCols - 1) / kTpCols)), dim3(kTpCols), 0, h->stream, a);
+        });
+        return op_finish(h);
+    }
+    Ph3Args a = {};
+    for (int k = 0; k < nphase; k++) a.c[k] = phases[k];
+    a.h = topo_h, a.z0 = u0, a.idz = _du, a.nx = (int)nx, a.ny = (int)ny, a.nz = (int)nz, a.nbx = (int)((nx + kTpTX - 1) / kTpTX), a.air = (int)air_phase - 1;
+    const unsigned nb = (unsigned)((int64_t)a.nbx * ((ny + kTpTY - 1) / kTpTY));
+    dispatch_const<1, 2, 3, 4, 5, 6, 7, 8>((int)nphase, [&](auto NN) {
+        hipLaunchKernelGGL((k_phases_topography3d<NN()>), dim3(nb), dim3(kTpTX, kTpTY), 0, h->stream, a);
+    });
+    return op_finish(h);
 }
 
 }  // namespace
@@ -382,184 +481,49 @@ extern "C" {
 jrx_status jrx_compute_rock_fraction2d(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, const double *topo_h, int64_t nx, int64_t ny, double y0,
                                        double _dy)
 {
-    if (!h) return JRX_ERR_ARG;
-    const char *fn = "compute_rock_fraction!";
     double *const out[4] = {center, vertex, Vx, Vy};
-    static const char *const names[4] = {"center", "vertex", "Vx", "Vy"};
-    for (int m = 0; m < 4; m++)
-        if (!out[m]) return jrx_fail(h, JRX_ERR_ARG, "%s: ϕ.%s is NULL", fn, names[m]);
-    if (!topo_h) return jrx_fail(h, JRX_ERR_ARG, "%s: topo.h is NULL", fn);
-    JRX_TRY(tp_extents(h, fn, nx, ny));
-    if (!std::isfinite(y0) || !std::isfinite(_dy)) return jrx_fail(h, JRX_ERR_ARG, "%s: y0 = %g, _dy = %g (both must be finite)", fn, y0, _dy);
-    const i64 cnt[4] = {nx * ny, (nx + 1) * (ny + 1), (nx + 1) * ny, nx * (ny + 1)};
-    for (int m = 0; m < 4; m++) {
-        if (tp_overlaps(out[m], cnt[m], topo_h, nx + 1)) return jrx_fail(h, JRX_ERR_ARG, "%s: output ϕ.%s overlaps topo.h", fn, names[m]);
-        for (int q = m + 1; q < 4; q++)
-            if (tp_overlaps(out[m], cnt[m], out[q], cnt[q])) return jrx_fail(h, JRX_ERR_ARG, "%s: outputs ϕ.%s and ϕ.%s overlap", fn, names[m], names[q]);
-    }
-    JRX_TRY(jrx_check_device(h));
-    RfArgs a = {topo_h, center, vertex, Vx, Vy, y0, _dy, (int)nx, (int)ny, (int)((nx + 1 + kTpTX - 1) / kTpTX)};
-    const int64_t nb = (int64_t)a.nbx * ((ny + 1 + kTpTY - 1) / kTpTY);      // below 2^31: the box is
-    h->stat_rock_fraction_calls++;
-    hipLaunchKernelGGL(k_rock_fraction2d, dim3((unsigned)nb), dim3(kTpTX, kTpTY), 0, h->stream, a);
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
-}
-
-jrx_status jrx_advect_topography2d(jrx_handle *h, double *topo_h, double *topo_h_old, const double *Vx, const double *Vy, int64_t nx, int64_t ny, double y0,
-                                   double _dx, double _dy, double dt)
-{
-    if (!h) return JRX_ERR_ARG;
-    const char *fn = "advect_topography!";
-    if (!topo_h) return jrx_fail(h, JRX_ERR_ARG, "%s: topo.h is NULL", fn);
-    if (!topo_h_old) return jrx_fail(h, JRX_ERR_ARG, "%s: topo.h_old is NULL", fn);
-    if (!Vx) return jrx_fail(h, JRX_ERR_ARG, "%s: V.Vx is NULL", fn);
-    if (!Vy) return jrx_fail(h, JRX_ERR_ARG, "%s: V.Vy is NULL", fn);
-    JRX_TRY(tp_extents(h, fn, nx, ny));
-    if (!std::isfinite(dt) || !std::isfinite(_dx) || !std::isfinite(_dy) || !std::isfinite(y0))
-        return jrx_fail(h, JRX_ERR_ARG, "%s: dt = %g, _dx = %g, _dy = %g, y0 = %g (all must be finite)", fn, dt, _dx, _dy, y0);
-    const void *const in[3] = {topo_h_old, Vx, Vy};
-    static const char *const names[3] = {"topo.h_old", "V.Vx", "V.Vy"};
-    const i64 cnt[3] = {nx + 1, (nx + 1) * (ny + 2), (nx + 2) * (ny + 1)};
-    for (int m = 0; m < 3; m++)
-        if (tp_overlaps(topo_h, nx + 1, in[m], cnt[m])) return jrx_fail(h, JRX_ERR_ARG, "%s: output topo.h overlaps %s", fn, names[m]);
-    for (int m = 1; m < 3; m++)
-        if (tp_overlaps(topo_h_old, nx + 1, in[m], cnt[m])) return jrx_fail(h, JRX_ERR_ARG, "%s: output topo.h_old overlaps %s", fn, names[m]);
-    JRX_TRY(jrx_check_device(h));
-    h->stat_topography_advect_calls++;
-    JRX_HIP(h, hipMemcpyAsync(topo_h_old, topo_h, (size_t)(nx + 1) * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    AdvArgs a = {topo_h, topo_h_old, Vx, Vy, y0, _dx, _dy, dt, (int)nx, (int)ny};
-    hipLaunchKernelGGL(k_advect_topography2d, dim3((unsigned)((nx + 1 + kTpCols - 1) / kTpCols)), dim3(kTpCols), 0, h->stream, a);
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
-}
-
-jrx_status jrx_update_phases_topography2d(jrx_handle *h, double *const *phases, int32_t nphase, const double *topo_h, int64_t nx, int64_t ny, double y0, double _dy,
-                                          int32_t air_phase)
-{
-    if (!h) return JRX_ERR_ARG;
-    const char *fn = "update_phases_given_topography!";
-    if (!phases) return jrx_fail(h, JRX_ERR_ARG, "%s: phases is NULL", fn);
-    if (nphase < 1 || nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d phase fields (1 .. %d are built)", fn, (int)nphase, JRX_MAXPHASE);
-    if (air_phase < 1 || air_phase > nphase) return jrx_fail(h, JRX_ERR_ARG, "%s: air_phase %d outside 1 .. %d", fn, (int)air_phase, (int)nphase);
-    for (int k = 0; k < nphase; k++)
-        if (!phases[k]) return jrx_fail(h, JRX_ERR_ARG, "%s: phase field %d is NULL", fn, k + 1);
-    if (!topo_h) return jrx_fail(h, JRX_ERR_ARG, "%s: topo.h is NULL", fn);
-    JRX_TRY(tp_extents(h, fn, nx, ny));
-    if (!std::isfinite(y0) || !std::isfinite(_dy)) return jrx_fail(h, JRX_ERR_ARG, "%s: y0 = %g, _dy = %g (both must be finite)", fn, y0, _dy);
-    for (int k = 0; k < nphase; k++) {
-        if (tp_overlaps(phases[k], nx * ny, topo_h, nx + 1)) return jrx_fail(h, JRX_ERR_ARG, "%s: phase field %d overlaps topo.h", fn, k + 1);
-        for (int q = k + 1; q < nphase; q++)
-            if (tp_overlaps(phases[k], nx * ny, phases[q], nx * ny)) return jrx_fail(h, JRX_ERR_ARG, "%s: phase fields %d and %d overlap", fn, k + 1, q + 1);
-    }
-    JRX_TRY(jrx_check_device(h));
-    PhArgs a = {};
-    for (int k = 0; k < nphase; k++) a.c[k] = phases[k];
-    a.h = topo_h, a.y0 = y0, a.idy = _dy, a.nx = (int)nx, a.ny = (int)ny, a.air = (int)air_phase - 1;
-    h->stat_topography_phase_calls++;
-    dispatch_const<1, 2, 3, 4, 5, 6, 7, 8>((int)nphase, [&](auto NN) {
-        hipLaunchKernelGGL((k_phases_topography2d<NN()>), dim3((unsigned)((nx + kTpCols - 1) / kTpCols)), dim3(kTpCols), 0, h->stream, a);
-    });
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    const int64_t n[3] = {nx, ny, 1};
+    return tp_rock_fraction(h, 2, out, topo_h, n, y0, _dy);
 }
 
 jrx_status jrx_compute_rock_fraction3d(jrx_handle *h, double *center, double *vertex, double *Vx, double *Vy, double *Vz, double *yz, double *xz, double *xy,
                                        const double *topo_h, int64_t nx, int64_t ny, int64_t nz, double z0, double _dz)
 {
-    if (!h) return JRX_ERR_ARG;
-    const char *fn = "compute_rock_fraction!";
     double *const out[8] = {center, vertex, Vx, Vy, Vz, yz, xz, xy};
-    static const char *const names[8] = {"center", "vertex", "Vx", "Vy", "Vz", "yz", "xz", "xy"};
-    for (int m = 0; m < 8; m++)
-        if (!out[m]) return jrx_fail(h, JRX_ERR_ARG, "%s: ϕ.%s is NULL", fn, names[m]);
-    if (!topo_h) return jrx_fail(h, JRX_ERR_ARG, "%s: topo.h is NULL", fn);
-    JRX_TRY(tp_extents3(h, fn, nx, ny, nz));
-    if (!std::isfinite(z0) || !std::isfinite(_dz)) return jrx_fail(h, JRX_ERR_ARG, "%s: z0 = %g, _dz = %g (both must be finite)", fn, z0, _dz);
-    const i64 cnt[8] = {nx * ny * nz,       (nx + 1) * (ny + 1) * (nz + 1), (nx + 1) * ny * nz,       nx * (ny + 1) * nz,
-                        nx * ny * (nz + 1), nx * (ny + 1) * (nz + 1),       (nx + 1) * ny * (nz + 1), (nx + 1) * (ny + 1) * nz};
-    for (int m = 0; m < 8; m++) {
-        if (tp_overlaps(out[m], cnt[m], topo_h, (nx + 1) * (ny + 1))) return jrx_fail(h, JRX_ERR_ARG, "%s: output ϕ.%s overlaps topo.h", fn, names[m]);
-        for (int q = m + 1; q < 8; q++)
-            if (tp_overlaps(out[m], cnt[m], out[q], cnt[q])) return jrx_fail(h, JRX_ERR_ARG, "%s: outputs ϕ.%s and ϕ.%s overlap", fn, names[m], names[q]);
-    }
-    JRX_TRY(jrx_check_device(h));
-    int rows = h->rock_fraction3d_rows > 0 ? h->rock_fraction3d_rows : kTpRows3;
-    if (rows > nz + 1) rows = (int)(nz + 1);      // a deeper march is the whole column; keeps k0 + rows inside an int
-    Rf3Args a = {topo_h, center, vertex, Vx, Vy, Vz, yz, xz, xy, z0, _dz, (int)nx, (int)ny, (int)nz, (int)((nx + 1 + kTpTX - 1) / kTpTX), (int)((ny + 1 + kTpTY - 1) / kTpTY), rows};
-    const int64_t nb = (int64_t)a.nbx * a.nby * ((nz + 1 + rows - 1) / rows);      // below 2^31: no more blocks than nodes of the ni .+ 1 box
-    h->stat_rock_fraction_calls++;
-    hipLaunchKernelGGL(k_rock_fraction3d, dim3((unsigned)nb), dim3(kTpTX, kTpTY), 0, h->stream, a);
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    const int64_t n[3] = {nx, ny, nz};
+    return tp_rock_fraction(h, 3, out, topo_h, n, z0, _dz);
+}
+
+jrx_status jrx_advect_topography2d(jrx_handle *h, double *topo_h, double *topo_h_old, const double *Vx, const double *Vy, int64_t nx, int64_t ny, double y0,
+                                   double _dx, double _dy, double dt)
+{
+    const double *const V[2] = {Vx, Vy};
+    const int64_t n[3] = {nx, ny, 1};
+    const double _di[2] = {_dx, _dy};
+    return tp_advect(h, 2, topo_h, topo_h_old, V, n, y0, _di, dt);
 }
 
 jrx_status jrx_advect_topography3d(jrx_handle *h, double *topo_h, double *topo_h_old, const double *Vx, const double *Vy, const double *Vz, int64_t nx, int64_t ny,
                                    int64_t nz, double z0, double _dx, double _dy, double _dz, double dt)
 {
-    if (!h) return JRX_ERR_ARG;
-    const char *fn = "advect_topography!";
-    if (!topo_h) return jrx_fail(h, JRX_ERR_ARG, "%s: topo.h is NULL", fn);
-    if (!topo_h_old) return jrx_fail(h, JRX_ERR_ARG, "%s: topo.h_old is NULL", fn);
-    if (!Vx) return jrx_fail(h, JRX_ERR_ARG, "%s: V.Vx is NULL", fn);
-    if (!Vy) return jrx_fail(h, JRX_ERR_ARG, "%s: V.Vy is NULL", fn);
-    if (!Vz) return jrx_fail(h, JRX_ERR_ARG, "%s: V.Vz is NULL", fn);
-    JRX_TRY(tp_extents3(h, fn, nx, ny, nz));
-    if (!std::isfinite(dt) || !std::isfinite(_dx) || !std::isfinite(_dy) || !std::isfinite(_dz) || !std::isfinite(z0))
-        return jrx_fail(h, JRX_ERR_ARG, "%s: dt = %g, _dx = %g, _dy = %g, _dz = %g, z0 = %g (all must be finite)", fn, dt, _dx, _dy, _dz, z0);
-    const i64 nh = (nx + 1) * (ny + 1);
-    const void *const in[4] = {topo_h_old, Vx, Vy, Vz};
-    static const char *const names[4] = {"topo.h_old", "V.Vx", "V.Vy", "V.Vz"};
-    const i64 cnt[4] = {nh, (nx + 1) * (ny + 2) * (nz + 2), (nx + 2) * (ny + 1) * (nz + 2), (nx + 2) * (ny + 2) * (nz + 1)};
-    for (int m = 0; m < 4; m++)
-        if (tp_overlaps(topo_h, nh, in[m], cnt[m])) return jrx_fail(h, JRX_ERR_ARG, "%s: output topo.h overlaps %s", fn, names[m]);
-    for (int m = 1; m < 4; m++)
-        if (tp_overlaps(topo_h_old, nh, in[m], cnt[m])) return jrx_fail(h, JRX_ERR_ARG, "%s: output topo.h_old overlaps %s", fn, names[m]);
-    JRX_TRY(jrx_check_device(h));
-    h->stat_topography_advect_calls++;
-    JRX_HIP(h, hipMemcpyAsync(topo_h_old, topo_h, (size_t)nh * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    Adv3Args a = {topo_h, topo_h_old, Vx, Vy, Vz, z0, _dx, _dy, _dz, dt, (int)nx, (int)ny, (int)nz, (int)((nx + 1 + kTpTX - 1) / kTpTX)};
-    hipLaunchKernelGGL(k_advect_topography3d, dim3((unsigned)((int64_t)a.nbx * ((ny + 1 + kTpTY - 1) / kTpTY))), dim3(kTpTX, kTpTY), 0, h->stream, a);
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    const double *const V[3] = {Vx, Vy, Vz};
+    const int64_t n[3] = {nx, ny, nz};
+    const double _di[3] = {_dx, _dy, _dz};
+    return tp_advect(h, 3, topo_h, topo_h_old, V, n, z0, _di, dt);
+}
+
+jrx_status jrx_update_phases_topography2d(jrx_handle *h, double *const *phases, int32_t nphase, const double *topo_h, int64_t nx, int64_t ny, double y0, double _dy,
+                                          int32_t air_phase)
+{
+    const int64_t n[3] = {nx, ny, 1};
+    return tp_phases(h, 2, phases, nphase, topo_h, n, y0, _dy, air_phase);
 }
 
 jrx_status jrx_update_phases_topography3d(jrx_handle *h, double *const *phases, int32_t nphase, const double *topo_h, int64_t nx, int64_t ny, int64_t nz, double z0,
                                           double _dz, int32_t air_phase)
 {
-    if (!h) return JRX_ERR_ARG;
-    const char *fn = "update_phases_given_topography!";
-    if (!phases) return jrx_fail(h, JRX_ERR_ARG, "%s: phases is NULL", fn);
-    if (nphase < 1 || nphase > JRX_MAXPHASE) return jrx_fail(h, JRX_ERR_ARG, "%s: %d phase fields (1 .. %d are built)", fn, (int)nphase, JRX_MAXPHASE);
-    if (air_phase < 1 || air_phase > nphase) return jrx_fail(h, JRX_ERR_ARG, "%s: air_phase %d outside 1 .. %d", fn, (int)air_phase, (int)nphase);
-    for (int k = 0; k < nphase; k++)
-        if (!phases[k]) return jrx_fail(h, JRX_ERR_ARG, "%s: phase field %d is NULL", fn, k + 1);
-    if (!topo_h) return jrx_fail(h, JRX_ERR_ARG, "%s: topo.h is NULL", fn);
-    JRX_TRY(tp_extents3(h, fn, nx, ny, nz));
-    if (!std::isfinite(z0) || !std::isfinite(_dz)) return jrx_fail(h, JRX_ERR_ARG, "%s: z0 = %g, _dz = %g (both must be finite)", fn, z0, _dz);
-    const i64 nc = nx * ny * nz;
-    for (int k = 0; k < nphase; k++) {
-        if (tp_overlaps(phases[k], nc, topo_h, (nx + 1) * (ny + 1))) return jrx_fail(h, JRX_ERR_ARG, "%s: phase field %d overlaps topo.h", fn, k + 1);
-        for (int q = k + 1; q < nphase; q++)
-            if (tp_overlaps(phases[k], nc, phases[q], nc)) return jrx_fail(h, JRX_ERR_ARG, "%s: phase fields %d and %d overlap", fn, k + 1, q + 1);
-    }
-    JRX_TRY(jrx_check_device(h));
-    Ph3Args a = {};
-    for (int k = 0; k < nphase; k++) a.c[k] = phases[k];
-    a.h = topo_h, a.z0 = z0, a.idz = _dz, a.nx = (int)nx, a.ny = (int)ny, a.nz = (int)nz, a.nbx = (int)((nx + kTpTX - 1) / kTpTX), a.air = (int)air_phase - 1;
-    const unsigned nb = (unsigned)((int64_t)a.nbx * ((ny + kTpTY - 1) / kTpTY));
-    h->stat_topography_phase_calls++;
-    dispatch_const<1, 2, 3, 4, 5, 6, 7, 8>((int)nphase, [&](auto NN) {
-        hipLaunchKernelGGL((k_phases_topography3d<NN()>), dim3(nb), dim3(kTpTX, kTpTY), 0, h->stream, a);
-    });
-    JRX_LAUNCH_CHECK(h);
-    JRX_HIP(h, hipStreamSynchronize(h->stream));
-    return JRX_OK;
+    const int64_t n[3] = {nx, ny, nz};
+    return tp_phases(h, 3, phases, nphase, topo_h, n, z0, _dz, air_phase);
 }
 
 }  // extern "C"
