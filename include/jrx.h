@@ -128,6 +128,14 @@ jrx_status jrx_field_stats(jrx_handle *h, int64_t out[6]);
  *   "stat_visc_fallbacks" = operand checks run / failed (general kernels used), "stat_operand_cache_hits" = driver calls that reused the operand verdict, "stat_graph_replays" = hipGraphLaunch calls,
  *   "stat_sweeps3d" = launches of the 3D z-marching stress and velocity sweeps (k_stress3d_zb, k_velocity3d_zb),
  *   "stat_fused2d_b" = those of "stat_fused2d" that ran the batch form k_fused2d_b (32-bit byte offsets: only below 2^29 nodes, see "fused2d_batch" in jrx_tuning.h),
+ *   "stat_fused3d_shfl" / "stat_fused3d_visc_nofold" / "stat_fused3d_visc_nohif" / "stat_fused3d_visc_plain" = those of "stat_fused3d" that ran a form only a tuning switch selects (jrx_tuning.h:
+ *   "fused_ylds" = 0; "visc_fold" = 0; "fused_hiface" = 0; both, or a high-face box of "fused_split"), "stat_fused3d_kz12" = those in 12-plane chunks of the 64 x 8 tile ("fused_kz"),
+ *   "stat_fused3d_first_none" / "stat_fused3d_first_all" = those of "stat_fused3d_inkernel" that launched no tile / every interior z chunk beside the exchange ("fused_first_pct" = 0 / 100),
+ *   "stat_fused3d_split" = fused iterations forked by "fused_split" (four launches each), "stat_hidden3d_bwidth" = split velocity sweeps whose slab widths came from "b_width_x/y/z",
+ *   "stat_vep3_edges_kz16" / "_kz8" / "_kz4" = launches of the z-marching 3D VEP edge kernels by chunk depth ("vep3_cfg", or the depth the grid picks), "stat_vep3_edges_mb3" = those of form 1 built
+ *   for three blocks per CU, "stat_vep3_edges_peel" = peel launches behind them ("vep3_peel"), "stat_vep3_edges_node" = edge passes run by the one-node-per-thread kernel, of which
+ *   "stat_vep3_edges_node_nomap" / "_noxcd" with the plain thread map ("vep3_map" = 0) / without XCD slabs ("vep3_xcd" = 0),
+ *   "stat_vep_store_all" = iterations of the VEP and variational loops enqueued with the stores of their output-only arrays only because "vep_store_all" is set,
  *   "stat_weno_calls" / "stat_weno_fused" = jrx_weno5_advection2d calls / those that ran the fused three-launch form,
  *   "stat_weno3d_calls" / "stat_weno3d_fused" = the same for jrx_weno5_advection3d (the 2D pair counts 2D calls only),
  *   "stat_phase_ratios_calls" / "stat_phase_ratios_fused" = jrx_update_phase_ratios2d / 3d calls that launched / those that ran the one-launch form,

@@ -1,11 +1,13 @@
 /* jrx_tuning.h -- tuning / A-B / test switches of libjrx_hip.  NOT part of the drop-in ABI (include/jrx.h): nothing a caller of
  * solve! needs is here, results never depend on any of these, and keys may change between builds.  They exist so that the
- * measurements under profiles/ and the parity tests can select a kernel form at run time instead of rebuilding.
+ * measurements under profiles/ and the parity tests can select a kernel form at run time instead of rebuilding.  tests/test_tuning_keys_covered.py lists, for every key,
+ * the parity tests that run a non-default value of it.
  *
  * Keys (int64 values):
- *   "fused_ylds" (default 1)      3D fused kernel: y-neighbour operands through LDS (0: lane-shuffle-only form)
+ *   "fused_ylds" (default 1)      3D fused kernel: y-neighbour operands through LDS (0: lane-shuffle-only form, which also switches the viscous-limit form off; bit-identical;
+ *                                 "stat_fused3d_shfl" counts its launches)
  *   "visc_fold" (1)               3D fused kernel, viscous-limit form: the arithmetic with its exact zeros folded away for finite η (dτ_r = 1 / (θ_dτ + 1) once per thread, Δτ = dτ_r fma(2η, ε, -τ),
- *                                 no division by 1 + 0 ψ); same bits (0: the general expressions with zero operands)
+ *                                 no division by 1 + 0 ψ); same bits (0: the general expressions with zero operands; "stat_fused3d_visc_nofold")
  *   "zero_forces" (1)             3D fused kernel (one-launch viscous-limit form and general form) and z-marching velocity sweep (3D Stokes and 3D VEP drivers): ρg arrays whose every entry
  *                                 is +0.0 (all 64 bits zero; a pass of the driver call looks at them) are not loaded -- ρg_x and ρg_y (gravity along z), or all three (SolVi3D, ShearBand3D);
  *                                 x - (+0.0) = x for every x, so the bits are the same (0: always loaded)
@@ -16,21 +18,24 @@
  *   "scratch_contiguous" (0)      the library's second 3D state set in physically contiguous device memory (hipExtMallocWithFlags, hipDeviceMallocContiguous): the probe of
  *                                 profiles/r04_alloc_stagger.txt -- a process whose arrays are ALL physically contiguous runs the 512^3 kernel at the slow rate, every time
  *   "fused_hiface" (1)            3D fused kernel, viscous-limit form, no neighbours: the stress nodes on the high faces i = nx, j = ny, k = nz are updated inside the kernel
- *                                 (0: by the boundary-layer launch behind it)
+ *                                 (0: by the boundary-layer launch behind it; bit-identical; "stat_fused3d_visc_nohif", and "stat_fused3d_visc_plain" with "visc_fold" = 0 as well)
  *   "fused_first_pct" (15)        multi-rank fused pipeline with the neighbour faces inside the kernel (fused_overlap = 3): share (%) of the interior z chunks whose tiles are launched
- *                                 beside update_halo!(V); the rest of the block -- shell tiles among their row neighbours -- follows behind it
+ *                                 beside update_halo!(V); the rest of the block -- shell tiles among their row neighbours -- follows behind it (bit-identical at 0 and 100;
+ *                                 "stat_fused3d_first_none" / "stat_fused3d_first_all" count the iterations whose first launch held no tile / every interior chunk)
  *   "comm_bcs_lazy" (0)           multi-rank fused pipeline: 1 = flow_bcs! of the physical faces applied lazily (before anything reads those entries from memory) instead of twice per
  *                                 iteration; the fix-up next to the received planes derives them by rule (measured 2 % slower than the two launches: off)
  *   "fused_tile" (2)              3D fused kernel tile: 0 = 64 x 4 threads, 1 = 32 x 8, 3 = 64 x 8 (two 8-wave blocks per CU, XCD bands of four tile rows), 2 = chosen by the grid (32 x 8 for nx = 63 .. 90,
  *                                 where three 32-lane tiles replace two 64-lane ones; 64 x 8 where the launch keeps >= 4,096 blocks, i.e. from ~230^3 on)
- *   "fused_split" (0)             no neighbours: high-face tiles + boundary stress layers forked onto the halo stream
- *   "b_width_x/y/z" (0)           > 0 overrides jrx_stokes3d_params.b_width of the split sweeps
+ *   "fused_split" (0)             no neighbours: high-face tiles + boundary stress layers forked onto the halo stream (bit-identical; no effect on a rank with neighbours; "stat_fused3d_split")
+ *   "b_width_x/y/z" (0)           > 0 overrides jrx_stokes3d_params.b_width of the split sweeps, which only ranks with neighbours run (bit-identical; "stat_hidden3d_bwidth")
  *   "fused2d" (1)                 2D visco-elastic loop: one-launch iterations on launch-bound grids
  *   "vep3_edges" (4)              3D VEP edge pass: 4 = z-marching kernel, the three family waves of a row share the centre and shear operands through LDS;
  *                                 6 = the same with a fourth wave per workgroup that loads and publishes every operand (phase ratios and λv included) one plane step ahead of the
  *                                 family waves, which then have no load of their own (bit-identical; measured equal to 4, profiles/r04_vep3d_fused_pre_centre.txt);
  *                                 3 = centre operands only; 1 = no LDS, one family per block; 2 = one launch per family; 0 = one node per thread
- *   "vep3_cfg", "vep3_peel", "vep3_map", "vep3_xcd"     z-marching edge kernel: chunk depth / occupancy, peeling of a thin last segment, thread map, XCD slabs
+ *   "vep3_cfg", "vep3_peel", "vep3_map", "vep3_xcd"     z-marching edge kernel: chunk depth * 10 + min blocks per CU (built: form 4 at 162, 82, 42; form 1 at 162, 163, 82; 0 = form 4 picks
+ *                                 16, 8 or 4 planes by the number of blocks), peeling of a thin last segment; node kernel: thread map, XCD slabs.  All bit-identical
+ *                                 (read-only counters "stat_vep3_edges_kz16" / "_kz8" / "_kz4" / "_mb3" / "_peel" / "_node" / "_node_nomap" / "_node_noxcd")
  *   "vep3_nt" (0), "vep3_prekz" (0)   3D VEP: non-temporal stores of the edge pass; planes per thread of the z-marching pre kernel (0 = chosen by the grid size; 1, 2, 4, 8, 16, 32)
  *   "vep3_hide_comm" (0)          multi-rank 3D VEP driver: 2 = ητ, edge-stress and V exchanges on the halo stream beside independent kernels; 1 = the first two only, update_halo!(V) behind the
  *                                 whole velocity sweep; 0 (default: the fastest on one device since the pre / centre kernels are fused) = everything on the compute stream, in order
@@ -47,7 +52,8 @@
  *   "fused2d_max_nodes" (1200000)  ... on grids of up to this many nodes (larger: the two-kernel iteration)
  *   "vep3_prec_tile" (2)          thread map of the fused 3D VEP pre / centre kernel: 1 = 64 x 4 tiles of node columns, 0 = 256 consecutive nodes of the flattened plane, 2 = tiles from 16,384 node columns per plane
  *   "thermal_fused_ph" (1)        3D heat diffusion, phase-ratio form (phase count 1..4): 1 = unobserved iterations as one launch (flux + update + BCs + next PT coefficients; θr_dτ ping-pongs), 0 = two kernels
- *   "vep_store_all" (0)           VEP loops (2D and 3D): 1 = every iteration stores ∇V, RP, ε_pl, ε_vol_pl, τII, η_vep (default: only iterations whose results can be observed)
+ *   "vep_store_all" (0)           VEP loops (2D and 3D) and the 2D variational loop: 1 = every iteration stores ∇V, RP, ε_pl, ε_vol_pl, τII, η_vep (default: only iterations whose results
+ *                                 can be observed; the same bits at the end; "stat_vep_store_all")
  *   "thermal_cfg", "thermal_xg"   fused 3D heat-diffusion tile shape / XCD band
  *   "thermal_tile" (0), "thermal_nt" (0)   round 6 A/Bs of the fused 3D heat-diffusion iteration: 4 / 8 = 64 x TY tiles whose rows exchange (T, K, θ) and the y flux through LDS (bit-identical, 9 - 16 %
  *                                 slower); 1 = non-temporal stores of the new (T, qT) set (neutral) -- profiles/r06_thermal3d_tile.txt
@@ -63,7 +69,8 @@
  *   "fused_ym" (0)               one-launch viscous-limit kernel, 64 x 8 tile: 2 / 4 = a block marches that many tile rows in y and hands the halo row on in LDS (round 6; bit-identical, measured
  *                                 4 - 8 % slower at 512^3 and fetching more, not less: the march loses the L2 sharing between concurrent y neighbours -- profiles/r06_y_halo.txt); 0 = one tile per block.
  *                                 "stat_fused3d_ym" (read-only) counts its launches.  "fused_tile" = 4: a 64 x 16 tile, one 16-wave block per CU (6 % fewer bytes fetched, 8 % slower)
- *   "fused_kz" (0)               chunk depth of the 64 x 8 tile of k_fused3d: 0 = 12 planes from nz = 384 on, 8 below (scripts/kbench_kz.hip); 8 / 12 force a depth
+ *   "fused_kz" (0)               chunk depth of the 64 x 8 tile of k_fused3d: 0 = 12 planes from nz = 384 on, 8 below (scripts/kbench_kz.hip); 8 / 12 force a depth (bit-identical;
+ *                                 "stat_fused3d_kz12")
  *   "field_pool_pct" (70)         "field_placement" = 1 with chunks of >= 128 MiB: the first allocation of a chunk size creates chunks for this share of the free memory (less 6 GiB), and every
  *                                 array takes random chunks of that pool -- chunks from all over the device's memory are what makes a placement good (profiles/r05_placement_search.txt,
  *                                 section 13); jrx_field_trim releases what nobody took; 0 = no pool (chunks are created as needed)

@@ -119,6 +119,11 @@ int find_opt(jrx_handle *h, const char *key, bool tuning, OptRef *out)
         {"stat_fused3d", 2, &h->stat_fused3d}, {"stat_fused2d", 2, &h->stat_fused2d}, {"stat_fused2d_b", 2, &h->stat_fused2d_b}, {"stat_sweeps3d", 2, &h->stat_sweeps3d}, {"stat_thermal_fused", 2, &h->stat_thermal_fused},
         {"stat_vep3_fused", 2, &h->stat_vep3_fused}, {"stat_graph_replays", 2, &h->stat_graph_replays},
         {"stat_fused3d_visc", 2, &h->stat_fused3d_visc}, {"stat_fused3d_inkernel", 2, &h->stat_fused3d_inkernel}, {"stat_visc_checks", 2, &h->stat_visc_checks}, {"stat_visc_fallbacks", 2, &h->stat_visc_fallbacks}, {"stat_fused3d_nof1", 2, &h->stat_fused3d_nof1}, {"stat_fused3d_nof2", 2, &h->stat_fused3d_nof2},
+        {"stat_fused3d_shfl", 2, &h->stat_fused3d_shfl}, {"stat_fused3d_visc_nofold", 2, &h->stat_fused3d_visc_nofold}, {"stat_fused3d_visc_nohif", 2, &h->stat_fused3d_visc_nohif}, {"stat_fused3d_visc_plain", 2, &h->stat_fused3d_visc_plain},
+        {"stat_fused3d_first_none", 2, &h->stat_fused3d_first_none}, {"stat_fused3d_first_all", 2, &h->stat_fused3d_first_all}, {"stat_fused3d_split", 2, &h->stat_fused3d_split}, {"stat_fused3d_kz12", 2, &h->stat_fused3d_kz12}, {"stat_hidden3d_bwidth", 2, &h->stat_hidden3d_bwidth},
+        {"stat_vep3_edges_kz16", 2, &h->stat_vep3_edges_kz16}, {"stat_vep3_edges_kz8", 2, &h->stat_vep3_edges_kz8}, {"stat_vep3_edges_kz4", 2, &h->stat_vep3_edges_kz4}, {"stat_vep3_edges_mb3", 2, &h->stat_vep3_edges_mb3},
+        {"stat_vep3_edges_peel", 2, &h->stat_vep3_edges_peel}, {"stat_vep3_edges_node", 2, &h->stat_vep3_edges_node}, {"stat_vep3_edges_node_nomap", 2, &h->stat_vep3_edges_node_nomap}, {"stat_vep3_edges_node_noxcd", 2, &h->stat_vep3_edges_node_noxcd},
+        {"stat_vep_store_all", 2, &h->stat_vep_store_all},
         {"stat_weno_calls", 2, &h->stat_weno_calls}, {"stat_weno_fused", 2, &h->stat_weno_fused}, {"stat_weno3d_calls", 2, &h->stat_weno3d_calls}, {"stat_weno3d_fused", 2, &h->stat_weno3d_fused},
         {"stat_principal_calls", 2, &h->stat_principal_calls},
         {"stat_phase_ratios_calls", 2, &h->stat_phase_ratios_calls}, {"stat_phase_ratios_fused", 2, &h->stat_phase_ratios_fused},

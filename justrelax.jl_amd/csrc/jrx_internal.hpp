@@ -124,7 +124,19 @@ struct jrx_handle {
     // ---- read-only counters (jrx_get_option "stat_*"): launches of the fused kernels since jrx_create, so that tests and the bench can
     //      prove which kernel path ran
     int64_t stat_fused3d_inkernel = 0;   // launches of k_fused3d that finished the neighbour faces themselves (fused_overlap = 3)
+    int64_t stat_fused3d_first_none = 0, stat_fused3d_first_all = 0;     // ... of them: no tile launched beside the exchange (box 0 empty) / every interior z chunk launched beside it ("fused_first_pct" = 0 / 100)
     int64_t stat_fused3d_visc = 0, stat_visc_checks = 0, stat_visc_fallbacks = 0, stat_fused3d_nof1 = 0, stat_fused3d_nof2 = 0;     // launches of the viscous-limit form of k_fused3d; operand checks run / failed
+    // ... of them (one of these at most per launch of a single-rank iteration): the lane-shuffle-only form ("fused_ylds" = 0), the one-launch viscous-limit form without the folded
+    // arithmetic ("visc_fold" = 0), the viscous-limit form with the folded arithmetic and the high-face layers left to the boundary-layer launch ("fused_hiface" = 0), the
+    // viscous-limit form with neither (both switches off)
+    int64_t stat_fused3d_shfl = 0, stat_fused3d_visc_nofold = 0, stat_fused3d_visc_nohif = 0, stat_fused3d_visc_plain = 0;
+    int64_t stat_fused3d_split = 0;          // fused iterations forked into interior tiles / high-face tiles + boundary layers ("fused_split" = 1)
+    int64_t stat_fused3d_kz12 = 0;           // launches of the 64 x 8 tile in 12-plane chunks ("fused_kz")
+    int64_t stat_hidden3d_bwidth = 0;        // split velocity sweeps (jrx3d_velocity_hidden) whose slab widths came from "b_width_x/y/z"
+    // launches of the 3D VEP edge pass: the z-marching kernels by chunk depth, those of form 1 built for three blocks per CU, the peel launch, the node kernel as the whole pass
+    int64_t stat_vep3_edges_kz16 = 0, stat_vep3_edges_kz8 = 0, stat_vep3_edges_kz4 = 0, stat_vep3_edges_mb3 = 0, stat_vep3_edges_peel = 0, stat_vep3_edges_node = 0;
+    int64_t stat_vep3_edges_node_nomap = 0, stat_vep3_edges_node_noxcd = 0;      // ... of the node-kernel passes: the plain thread map ("vep3_map" = 0), the tile map without XCD slabs ("vep3_xcd" = 0)
+    int64_t stat_vep_store_all = 0;          // iterations of the VEP / variational loops that stored their output-only arrays only because "vep_store_all" is set (as enqueued: a captured run counts once)
     int64_t stat_sweeps3d = 0;               // launches of the 3D z-marching sweeps (k_stress3d_zb, k_velocity3d_zb; 32-bit byte offsets)
     int64_t stat_fused2d_b = 0;              // ... of them the batch form k_fused2d_b (32-bit byte offsets)
     int64_t stat_fused3d = 0, stat_fused2d = 0, stat_thermal_fused = 0, stat_vep3_fused = 0, stat_graph_replays = 0;

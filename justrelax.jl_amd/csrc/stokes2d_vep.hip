@@ -1016,6 +1016,7 @@ jrx_status jrx_stokes2d_vep_solve(jrx_handle *h, const jrx_vep2d_fields *f, cons
     auto enqueue_iteration = [&](Vep2Iter &it, int64_t iter, bool diag) -> jrx_status {
         VepArgs &A = it.a;
         A.obs = diag || h->vep_store_all;
+        if (!diag && h->vep_store_all) h->stat_vep_store_all++;
         if (comm) {
             hipLaunchKernelGGL(k_maxloc, dim3(gc, 1), dim3(256), 0, s, etatau, (const double *)f->eta, nx, ny, 1);
             JRX_LAUNCH_CHECK(h);

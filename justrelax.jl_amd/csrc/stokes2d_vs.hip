@@ -691,6 +691,7 @@ jrx_status jrx_stokes2d_vs_solve(jrx_handle *h, const jrx_vep2d_fields *f, const
         // can the loop stop after this iteration (a check, the last allowed one, or already converged)?  Only then are its output-only arrays stored
         const bool last = check || it1 > p->iterMax || (p->iterMin < it1 && done());
         a.obs = last || h->vep_store_all;
+        if (!last && h->vep_store_all) h->stat_vep_store_all++;
         hipLaunchKernelGGL(k_vs_pre<true>, dim3(gv), dim3(256), 0, s, a, theta);
         JRX_LAUNCH_CHECK(h);
         { double *t_ = a.f.eta; a.f.eta = a.eta_out; a.eta_out = t_; }

@@ -426,6 +426,7 @@ jrx_status jrx3d_velocity_hidden(jrx_handle *h, const jrx_stokes3d_fields *f, co
     if (h->b_width_opt[0] > 0) bx = h->b_width_opt[0];       // tuning switches "b_width_x/y/z" (the split does not change results)
     if (h->b_width_opt[1] > 0) by = h->b_width_opt[1];
     if (h->b_width_opt[2] > 0) bz = h->b_width_opt[2];
+    if (h->b_width_opt[0] > 0 || h->b_width_opt[1] > 0 || h->b_width_opt[2] > 0) h->stat_hidden3d_bwidth++;
     const int xa = bx < nx / 2 ? bx : nx / 2, ya = by < ny / 2 ? by : ny / 2, za = bz < nz / 2 ? bz : nz / 2;
     hipStream_t hs = h->halo_stream;
     JRX_HIP(h, hipEventRecord(h->ev[0], s));
@@ -805,14 +806,19 @@ static jrx_status launch_fused_t(jrx_handle *h, hipStream_t s, const SweepArgs &
         } else
             hipLaunchKernelGGL((k_fused3d<TX, TY, KZ, MW, 1, false, XGV, false, true, 3, 1, 0, true, true, true>), dim3((unsigned)(ntx * nty * ntz)), dim3(TX * TY), 0, s, a, bc, ntx, nty, b[0], b[2], b[4]);
     }
-    else if (visc && fold)
+    else if (visc && fold) {
         hipLaunchKernelGGL((k_fused3d<TX, TY, KZ, MW, 1, false, XGV, false, true, 3, 1, 0, true, true>), dim3((unsigned)(ntx * nty * ntz)), dim3(TX * TY), 0, s, a, bc, ntx, nty, b[0], b[2], b[4]);
-    else if (visc && !hiface && vf)
+        h->stat_fused3d_visc_nofold++;
+    } else if (visc && !hiface && vf) {
         hipLaunchKernelGGL((k_fused3d<TX, TY, KZ, MW, 1, false, XGV, false, true, 3, 1, 0, true, false, true>), dim3((unsigned)(ntx * nty * ntz)), dim3(TX * TY), 0, s, a, bc, ntx, nty, b[0], b[2], b[4]);
-    else if (visc && hiface)
+        h->stat_fused3d_visc_nohif++;
+    } else if (visc && hiface) {
         hipLaunchKernelGGL((k_fused3d<TX, TY, KZ, MW, 1, false, XGV, false, true, 3, 1, 1, true>), dim3((unsigned)(ntx * nty * ntz)), dim3(TX * TY), 0, s, a, bc, ntx, nty, b[0], b[2], b[4]);
-    else if (visc)
+        h->stat_fused3d_visc_plain++;
+    } else if (visc) {
         hipLaunchKernelGGL((k_fused3d<TX, TY, KZ, MW, 1, false, XGV, false, true, 3, 1, 0, true>), dim3((unsigned)(ntx * nty * ntz)), dim3(TX * TY), 0, s, a, bc, ntx, nty, b[0], b[2], b[4]);
+        h->stat_fused3d_visc_plain++;
+    }
     else if (h->fused_ylds && hiface) {
         if (nof == 2)
             hipLaunchKernelGGL((k_fused3d<TX, TY, KZ, MW, 1, true, XGV, false, true, 3, 1, 1, false, false, false, false, 2>), dim3((unsigned)(ntx * nty * ntz)), dim3(TX * TY), 0, s, a, bc, ntx, nty, b[0], b[2], b[4]);
@@ -834,10 +840,13 @@ static jrx_status launch_fused_t(jrx_handle *h, hipStream_t s, const SweepArgs &
         // + 8-plane chunks and tile rows dealt round-robin to the XCDs (XG = 1: the eight XCDs work on eight adjacent tile rows at a time;
         //   kbench 512^3, same box: 8.65 ms with 16 planes / 8-row bands -> 8.04 ms; 256^3: 1.106 -> 1.04 ms)
         hipLaunchKernelGGL((k_fused3d<TX, TY, KZ, MW, 1, true, XGV, false, true, 3, 1>), dim3((unsigned)(ntx * nty * ntz)), dim3(TX * TY), 0, s, a, bc, ntx, nty, b[0], b[2], b[4]);
-    else
+    else {
         hipLaunchKernelGGL((k_fused3d<TX, TY, KZ, 2, 1, false, 8, false, true>), dim3((unsigned)(ntx * nty * ntz)), dim3(TX * TY), 0, s, a, bc, ntx, nty, b[0], b[2], b[4]);
+        h->stat_fused3d_shfl++;
+    }
     JRX_LAUNCH_CHECK(h);
     h->stat_fused3d++;
+    if (TY == 8 && KZ == 12) h->stat_fused3d_kz12++;
     if (visc) h->stat_fused3d_visc++;
     return JRX_OK;
 }
@@ -972,6 +981,7 @@ static jrx_status iter_step(Iter3D &I, bool diag, bool fuse_next, hipEvent_t *te
             // 256^3 822 / 819 vs 847 / 862 -- the interior launch alone takes as long as the launch over all tiles (the high-face column of
             // tiles sweeps every plane of every array beside it and breaks the DRAM page locality of the sweep): option "fused_split", off.
             bs = h->halo_stream;
+            h->stat_fused3d_split++;
             JRX_HIP(h, hipEventRecord(h->ev[0], s));
             JRX_HIP(h, hipStreamWaitEvent(bs, h->ev[0], 0));
             const int inner[6] = {0, nt[0] - 1, 0, nt[1] - 1, 0, nt[2] - 1};
@@ -1030,6 +1040,7 @@ static jrx_status iter_step(Iter3D &I, bool diag, bool fuse_next, hipEvent_t *te
             int zs = lo[2] + ((hi[2] - lo[2]) * h->fused_first_pct + 99) / 100;
             if (zs > hi[2]) zs = hi[2];
             if (hi[0] <= lo[0] || hi[1] <= lo[1]) zs = lo[2];
+            if (zs == lo[2]) h->stat_fused3d_first_none++; else if (zs == hi[2]) h->stat_fused3d_first_all++;
             {
                 const int boxes[7][6] = {{lo[0], hi[0], lo[1], hi[1], lo[2], zs},                                  // class 1
                                          {0, nt[0], 0, nt[1], zs, nt[2]},                                          // class 2: the rest of the block, natural order

@@ -1177,9 +1177,10 @@ jrx_status launch_vep3_edges(jrx_handle *h, hipStream_t s, const Vep3Args &a, co
         const dim3 g4 = GRID_IJK4(nx + 1, ny + 1, nz + 1);
         if (a.soft) hipLaunchKernelGGL((k_vep3_edges<true, true, true>), g4, dim3(256), 0, s, a, 0, nx + 1);
         else if (p4 && xs) dispatch_const<0, 1, 2, 3, 4>(npc, [&](auto NP) { hipLaunchKernelGGL((k_vep3_edges<true, true, false, decltype(NP)::value>), g4, dim3(256), 0, s, a, 0, nx + 1); });
-        else if (p4) hipLaunchKernelGGL(k_vep3_edges<true>, g4, dim3(256), 0, s, a, 0, nx + 1);
-        else hipLaunchKernelGGL(k_vep3_edges<false>, GRID_IJK(nx + 1, ny + 1, nz + 1), dim3(256), 0, s, a, 0, nx + 1);
+        else if (p4) { hipLaunchKernelGGL(k_vep3_edges<true>, g4, dim3(256), 0, s, a, 0, nx + 1); h->stat_vep3_edges_node_noxcd++; }
+        else { hipLaunchKernelGGL(k_vep3_edges<false>, GRID_IJK(nx + 1, ny + 1, nz + 1), dim3(256), 0, s, a, 0, nx + 1); h->stat_vep3_edges_node_nomap++; }
         JRX_LAUNCH_CHECK(h);
+        h->stat_vep3_edges_node++;
         return JRX_OK;
     }
     const int nseg = pl.nseg, ilim = pl.ilim;
@@ -1187,6 +1188,7 @@ jrx_status launch_vep3_edges(jrx_handle *h, hipStream_t s, const Vep3Args &a, co
         const dim3 gp(pl.peel_gx, pl.peel_gy);
         if (a.soft) hipLaunchKernelGGL((k_vep3_edges<true, false, true>), gp, dim3(256), 0, s, a, ilim, pl.rem);
         else dispatch_const<0, 1, 2, 3, 4>(npc, [&](auto NP) { hipLaunchKernelGGL((k_vep3_edges<true, false, false, decltype(NP)::value>), gp, dim3(256), 0, s, a, ilim, pl.rem); });
+        h->stat_vep3_edges_peel++;
     }
     // the z-marching kernels are built for 1..4 phases (more take form 0) and for the (form, KZ, min blocks) the plan admits
     dispatch_const<1, 2, 3, 4>(np, [&](auto NP_) {
@@ -1207,6 +1209,10 @@ jrx_status launch_vep3_edges(jrx_handle *h, hipStream_t s, const Vep3Args &a, co
             });
     });
     JRX_LAUNCH_CHECK(h);
+    // what ran, for the parity tests: the depth of the z-marching kernel (softening laws: k_vep3_edges_zf<16, NP, 2, true>) and form 1 built for three blocks per CU
+    const int kz_run = a.soft ? 16 : pl.kz;
+    if (kz_run == 16) h->stat_vep3_edges_kz16++; else if (kz_run == 8) h->stat_vep3_edges_kz8++; else h->stat_vep3_edges_kz4++;
+    if (!a.soft && pl.form == 1 && pl.mb == 3) h->stat_vep3_edges_mb3++;
     return JRX_OK;
 }
 
@@ -1573,6 +1579,7 @@ jrx_status jrx_stokes3d_vep_solve(jrx_handle *h, const jrx_vep3d_fields *f, cons
     auto enqueue_iteration = [&](Vep3Iter &it, bool first, bool diag, bool ordered) -> jrx_status {
         Vep3Args &A = it.a;
         A.obs = diag || h->vep_store_all;
+        if (!diag && h->vep_store_all) h->stat_vep_store_all++;
         if (comm && first) {        // ητ of the first iteration: nothing to hide it behind
             double *cur = const_cast<double *>(A.etatau);
             hipLaunchKernelGGL(k_maxloc, gml, dim3(256), 0, s, cur, (const double *)f->eta, nx, ny, nz);

@@ -108,3 +108,49 @@ def test_thermal3d_graph_replay_changes_nothing(jr):
     assert list(ra.iter_count) == list(rb.iter_count) == [50, 100, 150] and list(ra.norm_ResT) == list(rb.norm_ResT)
     for k in a:
         assert np.array_equal(a[k], b[k]), k
+
+
+@pytest.mark.parametrize("ni,bcs,dt", [((70, 33), "free_slip", 0.25), ((33, 70), "no_slip", np.inf)])
+def test_2d_iteration_on_either_side_of_fused2d_max_nodes_keeps_the_bits(jr, oracle, ni, bcs, dt):
+    """tuning switch "fused2d_max_nodes": the auto rule of the 2D visco-elastic loop (kernel_variant = 0) runs the one-launch iteration on grids of up to that many nodes and the
+    two-kernel iteration above.  With the bound one below and exactly at the node count of a small grid ((nx + 1)(ny + 1) = 2,414) the same solve runs on either side: every field
+    and the norm history agree in every bit, stat_fused2d_b counts launches on the one-launch side only, and the two-kernel side is within 1e-9 of the oracle.  Tuning switch
+    "fused2d" = 0 with the bound at the node count is the third run: the switch alone keeps the two-kernel iteration (no one-launch iteration counted), same bits."""
+    from justrelax_jl_amd import _lib, checks
+    from justrelax_jl_amd.miniapps.common import download_stokes, upload_stokes
+    h = _lib.default_handle()
+    nodes = (ni[0] + 1) * (ni[1] + 1)
+    bound0 = h.get_option("fused2d_max_nodes")
+    s = jr.miniapps.random_fields2d(ni, bcs=bcs, dt=dt, iterMax=23, nout=7)
+    s.pt.ϵ_rel = s.pt.ϵ_abs = 1e-30
+    runs = []
+    try:
+        for bound, one_launch in ((nodes - 1, 1), (nodes, 1), (nodes, 0)):
+            h.set_option("fused2d_max_nodes", bound)
+            h.set_option("fused2d", one_launch)
+            stokes, ρg, K, G = upload_stokes(s, jr.AMDGPUBackend)
+            c0 = (h.get_option("stat_fused2d"), h.get_option("stat_fused2d_b"))
+            r = jr.solve_(stokes, s.pt, s.grid, s.flow_bcs, ρg, G, K, s.dt, None, kwargs=s.kwargs)
+            runs.append(((r.iter, tuple(r.err_evo1)), download_stokes(stokes), (h.get_option("stat_fused2d") - c0[0], h.get_option("stat_fused2d_b") - c0[1])))
+    finally:
+        h.set_option("fused2d_max_nodes", bound0)
+        h.set_option("fused2d", 1)
+    (ita, a, ca), (itb, b, cb), (itc, c_, cc) = runs
+    assert ca == (0, 0) and cb[0] > 0 and cb[1] == cb[0] and cc == (0, 0), (ca, cb, cc)
+    assert ita == itb == itc and ita[0] == 24
+    for other in (b, c_):
+        for k in a:
+            x, y = a[k].copy(), other[k].copy()
+            if k in ("Vx", "Vy", "Ux", "Uy"):      # the four ghost corners are not read by any stencil
+                for c in ((0, 0), (0, -1), (-1, 0), (-1, -1)):
+                    x[c] = y[c]
+            assert np.array_equal(x, y, equal_nan=True), k
+    ref = {k: v.copy(order="F") for k, v in s.arrays.items()}
+    r_ref = oracle.stokes2d_solve(ref, checks.oracle_params2d(oracle, s))
+    assert r_ref["iter"] == 24
+    for k in ("P", "Vx", "Vy", "txx", "tyy", "txy"):
+        x, y = a[k].copy(), ref[k]
+        if k in ("Vx", "Vy"):
+            for c in ((0, 0), (0, -1), (-1, 0), (-1, -1)):
+                x[c] = y[c]
+        assert checks.max_rel_diff(x, y) <= 1e-9, k

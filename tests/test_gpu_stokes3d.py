@@ -638,6 +638,140 @@ def test_general_form_folds_its_high_face_layers(env, ni, bcs, zero, gh):
         assert np.array_equal(outs[0][k][m], outs[1][k][m], equal_nan=True), (gh, k)
 
 
+FORM_COUNTERS = ("stat_fused3d", "stat_fused3d_visc", "stat_fused3d_shfl", "stat_fused3d_visc_nofold", "stat_fused3d_visc_nohif", "stat_fused3d_visc_plain", "stat_fused3d_split",
+                 "stat_fused3d_kz12", "stat_fused3d_nof1", "stat_fused3d_nof2")
+FORM_DEFAULTS = dict(kernel_variant=0, fused_ylds=1, fused_tile=2, visc_fold=1, fused_hiface=1, fused_split=0, fused_kz=0)
+
+
+def _form_setup(jr, ni, bcs, dt, zero):
+    s = jr.miniapps.random_fields3d(ni, bcs=bcs, dt=dt, iterMax=23, nout=7)
+    s.pt.ϵ_rel = s.pt.ϵ_abs = 1e-30
+    for c in zero:
+        s.arrays["f" + c][...] = 0.0
+    return s
+
+
+def _run_form(env, s, **opts):
+    """one solve with the given switches (kernel_variant = 3 unless named); returns (iterations and error history, downloaded arrays, deltas of FORM_COUNTERS by name)"""
+    jr = env["jr"]
+    from justrelax_jl_amd import _lib
+    h = _lib.default_handle()
+    try:
+        for k, v in dict(dict(kernel_variant=3), **opts).items():
+            h.set_option(k, v)
+        stokes, ρg, K, G = env["up"](s, jr.AMDGPUBackend)
+        c0 = [h.get_option(k) for k in FORM_COUNTERS]
+        r = jr.solve_(stokes, s.pt, s.grid, s.flow_bcs, ρg, K, G, s.dt, None, kwargs=s.kwargs)
+        d = {k: h.get_option(k) - c for k, c in zip(FORM_COUNTERS, c0)}
+    finally:
+        for k, v in FORM_DEFAULTS.items():
+            h.set_option(k, v)
+    return (r.iter, tuple(r.err_evo1)), env["down"](stokes), d
+
+
+def _anchor_and_oracle(env, s):
+    """the anchor of the bit comparisons -- the per-node general kernels (kernel_variant = 1) -- itself compared with the oracle at this shape, at the file's bound over iterations"""
+    orc, ck = env["orc"], env["checks"]
+    ref = _cp(s.arrays)
+    r_ref = orc.stokes3d_solve(ref, ck.oracle_params3d(orc, s))
+    it, out, d = _run_form(env, s, kernel_variant=1)
+    assert d["stat_fused3d"] == 0 and it[0] == r_ref["iter"] == 24
+    names = [k for k in ref if not (k[0] == "U" and np.isinf(s.dt))]          # U = V dt = ±Inf, NaN where V = 0
+    diffs = ck.compare_stokes(out, ref, names)
+    assert max(diffs.values()) <= TOL_ITERS, diffs
+    return it, out
+
+
+def _form_mismatches(env, tag, it, out, it0, out0):
+    """the arrays of a run that are not np.array_equal to the anchor's outside the ghost edges of V, as test_kernel_variants_are_bit_identical compares them (collected, not
+    raised: one test runs several forms); U = V dt is ±Inf, NaN where V = 0, when dt = Inf"""
+    bad = [] if it == it0 else [(tag, "iterations / error history")]
+    for k in out0:
+        m = env["checks"].interior_mask3d(k, out0[k].shape)
+        if not ((k[0] == "U" or np.isfinite(out0[k][m]).all()) and np.array_equal(out[k][m], out0[k][m], equal_nan=True)):
+            bad.append((tag, k))
+    return bad
+
+
+# the non-default forms of the fused kernel a tuning switch selects, with what the counters must show for `fused` launches of k_fused3d (dt = Inf | finite dt)
+FUSED_FORMS = {"ylds0_tile0": dict(fused_ylds=0, fused_tile=0), "ylds0_tile1": dict(fused_ylds=0, fused_tile=1), "visc_fold0": dict(visc_fold=0), "hiface0": dict(fused_hiface=0),
+               "visc_fold0_hiface0": dict(visc_fold=0, fused_hiface=0), "split": dict(fused_split=1), "split_visc_fold0": dict(fused_split=1, visc_fold=0)}
+
+
+@pytest.mark.parametrize("zero", ["", "xy", "xyz"])
+@pytest.mark.parametrize("dt", [np.inf, 0.25])
+@pytest.mark.parametrize("ni,bcs", [((130, 20, 17), "free_slip"), ((97, 9, 33), "none"), ((66, 9, 35), "slip_mix"), ((130, 17, 20), "no_slip")])
+def test_every_switch_selected_form_of_the_fused_kernel_keeps_the_bits(env, ni, bcs, dt, zero):
+    """include/jrx_tuning.h: "results never depend on any of these".  The forms of k_fused3d that only a non-default switch reaches -- the lane-shuffle-only form (fused_ylds = 0,
+    both tiles; it also switches the viscous-limit form off), the one-launch viscous-limit form without the folded arithmetic (visc_fold = 0), the viscous-limit form with the
+    high-face layers left to the boundary-layer launch (fused_hiface = 0), the plain viscous-limit form (both off), the forked iteration (fused_split = 1: interior tiles beside
+    high-face tiles + boundary layers; with visc_fold = 0 its high-face boxes run the plain form with HIF) -- on grids of two or three tiles in x, a ragged last tile in every
+    direction and every body-force class.  Every array equals the per-node general kernels' (kernel_variant = 1) in every bit, fused_ylds = 0 and fused_hiface = 0 -- which the
+    header does not call bit-identical -- included: both held.  The anchor is compared with the oracle at the same shape, and the counters show that each form ran."""
+    jr = env["jr"]
+    s = _form_setup(jr, ni, bcs, dt, zero)
+    it0, out0 = _anchor_and_oracle(env, s)
+    visc = np.isinf(dt)
+    bad = []
+    for tag, opts in FUSED_FORMS.items():
+        it, out, d = _run_form(env, s, **opts)
+        F, sp = d["stat_fused3d"], d["stat_fused3d_split"]
+        assert F > 0, (tag, d)
+        want = dict(stat_fused3d_shfl=0, stat_fused3d_visc_nofold=0, stat_fused3d_visc_nohif=0, stat_fused3d_visc_plain=0, stat_fused3d_split=0, stat_fused3d_visc=F if visc else 0)
+        if tag.startswith("ylds0"):
+            want.update(stat_fused3d_shfl=F, stat_fused3d_visc=0)
+        elif tag.startswith("split"):
+            assert sp > 0 and F == 4 * sp, (tag, d)      # interior box + three high-face boxes per iteration, none empty on these grids
+            want.update(stat_fused3d_split=sp)
+            if visc:
+                want.update(stat_fused3d_visc_nohif=sp if tag == "split" else 0, stat_fused3d_visc_plain=3 * sp if tag == "split" else 4 * sp)
+        elif visc:
+            want.update({"visc_fold0": dict(stat_fused3d_visc_nofold=F), "hiface0": dict(stat_fused3d_visc_nohif=F), "visc_fold0_hiface0": dict(stat_fused3d_visc_plain=F)}[tag])
+        assert {k: d[k] for k in want} == want, (tag, d)
+        bad += _form_mismatches(env, tag, it, out, it0, out0)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("zero", ["", "xy", "xyz"])
+@pytest.mark.parametrize("dt", [np.inf, 0.25])
+@pytest.mark.parametrize("ni,bcs", [((130, 20, 9), "free_slip"), ((130, 17, 17), "no_slip"), ((97, 9, 25), "none"), ((66, 9, 35), "slip_mix")])
+def test_chunk_depths_of_the_tall_tile_keep_the_bits(env, ni, bcs, dt, zero):
+    """fused_tile = 3 with fused_kz = 8 and 12 (12 is what blocks with nz >= 384 run by default): nz = 9, 17, 25, 35 are one, two and three chunks with a ragged last one at
+    both depths (9 = 8 + 1 | 9; 17 = 2 x 8 + 1 | 12 + 5; 25 = 3 x 8 + 1 | 2 x 12 + 1; 35 = 4 x 8 + 3 | 2 x 12 + 11).  Every array equals the per-node general kernels' in every
+    bit; the anchor is compared with the oracle at the same shape; stat_fused3d_kz12 counts the launches in 12-plane chunks."""
+    jr = env["jr"]
+    s = _form_setup(jr, ni, bcs, dt, zero)
+    it0, out0 = _anchor_and_oracle(env, s)
+    bad = []
+    for kz in (8, 12):
+        it, out, d = _run_form(env, s, fused_tile=3, fused_kz=kz)
+        F = d["stat_fused3d"]
+        assert F > 0 and d["stat_fused3d_kz12"] == (F if kz == 12 else 0) and d["stat_fused3d_visc"] == (F if np.isinf(dt) else 0) and d["stat_fused3d_shfl"] == 0, (kz, d)
+        nof = {"": 0, "xy": 1, "xyz": 2}[zero]
+        assert d["stat_fused3d_nof1"] == (F if nof == 1 else 0) and d["stat_fused3d_nof2"] == (F if nof == 2 else 0), (kz, d)
+        bad += _form_mismatches(env, "kz%d" % kz, it, out, it0, out0)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("dt", [np.inf, 0.25])
+def test_without_a_second_state_set_the_sweeps_run_and_the_bits_stay(env, dt):
+    """option scratch_sets = 0 refuses the library-owned second state set the fused pipeline ping-pongs with: kernel_variant = 3 then runs the two sweeps of every iteration in
+    the caller's arrays -- no launch of k_fused3d -- and every array equals the per-node kernels', which are compared with the oracle at the same shape"""
+    jr = env["jr"]
+    from justrelax_jl_amd import _lib
+    s = _form_setup(jr, (130, 20, 17), "free_slip", dt, "")
+    it0, out0 = _anchor_and_oracle(env, s)
+    h = _lib.default_handle()
+    try:
+        h.set_option("scratch_sets", 0)
+        it, out, d = _run_form(env, s)
+    finally:
+        h.set_option("scratch_sets", 1)
+    assert d["stat_fused3d"] == 0, d
+    bad = _form_mismatches(env, "scratch_sets0", it, out, it0, out0)
+    assert not bad, bad
+
+
 def test_operand_cache_reuses_the_verdict_until_the_fields_are_declared_dirty(env):
     """option operand_cache = 1: the operand pass of the 3D visco-elastic drivers runs once per (operand pointers, extents, dt); the next driver call on the
     same arrays reuses its verdict -- same bits as a call that looks again -- until jrx_fields_dirty, after which a poisoned operand is found and the general kernels report the

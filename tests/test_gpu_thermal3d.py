@@ -159,3 +159,89 @@ def test_tiled_fused_iteration_keeps_the_bits(jr, form, ni, tile):
         assert outs[0][0] == outs[v][0] == [20, 40, 60] and outs[0][1] == outs[v][1]
         for k in outs[0][2]:
             assert np.array_equal(outs[0][2][k], outs[v][2][k]), (v, k)
+
+
+def _run_60(jr, h, s, rheo, **opts):
+    """60 iterations, checks every 20, with the given switches set (the caller restores them); returns (iter_count, norm history, fields, launches of the one-launch iteration)"""
+    for k, v in opts.items():
+        h.set_option(k, v)
+    thermal, pt, K, ρCp = _setup(jr, s)
+    pt.ϵ = 1e-30
+    A, B = (rheo, None) if rheo is not None else (K, ρCp)
+    n0 = h.get_option("stat_thermal_fused")
+    r = jr.heatdiffusion_PT_(thermal, pt, s.flow_bcs, A, B, s.dt, s.grid, kwargs=dict(iterMax=60, nout=20, verbose=False))
+    return (list(r.iter_count), list(r.norm_ResT), {k: jr.to_numpy(getattr(thermal, k)) for k in ("T", "Told", "ΔT", "qTx", "qTy", "qTz", "qTz2", "ResT")},
+            h.get_option("stat_thermal_fused") - n0)
+
+
+def _assert_run_matches_oracle(oracle, s, rheo, run):
+    """a run of _run_60 against the oracle's loop, with the bounds of test_thermal3d_iterations_match_oracle"""
+    from justrelax_jl_amd.checks import max_rel_diff
+    ref = {k: v.copy(order="F") for k, v in s.arrays.items()}
+    r_ref = oracle.heatdiffusion_PT3d(ref, _params(oracle, s, 1e-30, iterMax=60, nout=20, rheology=rheo))
+    it, norms, got = run[:3]
+    assert it == list(r_ref["iter_count"]) == [20, 40, 60] and np.allclose(norms, r_ref["norm_ResT"], rtol=1e-9)
+    for name, key in (("T", "T"), ("Told", "Told"), ("dT", "ΔT")):
+        assert np.abs(got[key] - ref[name]).max() <= TOL_ITERS * np.abs(ref[name]).max(), name
+    for name in ("qTx", "qTy", "qTz", "qTz2"):
+        assert max_rel_diff(got[name], ref[name]) <= TOL_ITERS, name
+    assert np.abs(got["ResT"] - ref["ResT"]).max() <= TOL_ITERS * max(np.abs(ref["ResT"]).max(), 1e-6)
+
+
+@pytest.mark.parametrize("form,ni,xg,cfg", [("array", (64, 21, 13), 1, 0), ("rheology", (70, 17, 20), 1, 0), ("array", (130, 9, 35), 1, 0), ("rheology", (130, 9, 35), 2, 0),
+                                            ("array", (130, 9, 35), 4, 0), ("array", (130, 9, 35), 1, 10402), ("rheology", (130, 9, 35), 2, 10402), ("array", (130, 9, 35), 1, 10408)])
+def test_xcd_bands_of_the_fused_iteration_keep_the_bits(jr, oracle, form, ni, xg, cfg):
+    """tuning switch "thermal_xg": tile rows per XCD band of the one-launch iteration (default 8; 1 is built for every default tile width at 4 planes, 2 and 4 for 256-cell
+    segments, and with "thermal_cfg" for 256-cell segments 2 and 8 planes deep -- heat_plan.hpp, HEAT3_FUSED_SHAPES).  With another band than 8 the depth stays 4 planes on small
+    grids too.  Each equals the two-kernel iteration (thermal_fused = 0), which is compared with the oracle at the same shape, bit for bit, and ran as one launch 57 times."""
+    from justrelax_jl_amd import _lib
+    s = jr.miniapps.diffusion3d(ni, iterMax=60, nout=20)
+    rheo = s.extra["rheology"] if form == "rheology" else None
+    h = _lib.default_handle()
+    try:
+        anchor = _run_60(jr, h, s, rheo, thermal_fused=0)
+        run = _run_60(jr, h, s, rheo, thermal_fused=1, thermal_xg=xg, thermal_cfg=cfg)
+    finally:
+        for k, v in dict(thermal_fused=1, thermal_xg=8, thermal_cfg=0).items():
+            h.set_option(k, v)
+    assert anchor[3] == 0 and run[3] == 57
+    _assert_run_matches_oracle(oracle, s, rheo, anchor)
+    assert run[0] == anchor[0] and run[1] == anchor[1]
+    for k in anchor[2]:
+        assert np.array_equal(run[2][k], anchor[2][k]), k
+
+
+@pytest.mark.parametrize("form,ni", [("array", (70, 17, 20)), ("rheology", (130, 9, 35)), ("rheology", (70, 17, 20)), ("array", (130, 9, 35))])
+def test_non_temporal_stores_of_the_fused_iteration_keep_the_bits(jr, oracle, form, ni):
+    """tuning switch "thermal_nt" = 1: the one-launch iteration stores the new (T, qT) set with non-temporal stores -- the row-segment form and the 64 x 4 / 64 x 8 tiles of
+    "thermal_tile".  Two and three row segments with a ragged last one, ragged z chunks and partial tiles in y.  Each run equals the two-kernel iteration (thermal_fused = 0) in
+    T, the fluxes, the residual and the norm history bit for bit, stat_thermal_fused counts its 57 unobserved iterations, and the plain nt run is compared with the oracle as
+    test_thermal3d_iterations_match_oracle does"""
+    from justrelax_jl_amd import _lib
+    from justrelax_jl_amd.checks import max_rel_diff
+    s = jr.miniapps.diffusion3d(ni, iterMax=60, nout=20)
+    rheo = s.extra["rheology"] if form == "rheology" else None
+    h = _lib.default_handle()
+    outs = []
+    try:
+        for fused, nt, tl in ((0, 0, 0), (1, 1, 0), (1, 1, 4), (1, 1, 8)):
+            h.set_option("thermal_fused", fused)
+            h.set_option("thermal_nt", nt)
+            h.set_option("thermal_tile", tl)
+            thermal, pt, K, ρCp = _setup(jr, s)
+            pt.ϵ = 1e-30
+            A, B = (rheo, None) if form == "rheology" else (K, ρCp)
+            n0 = h.get_option("stat_thermal_fused")
+            r = jr.heatdiffusion_PT_(thermal, pt, s.flow_bcs, A, B, s.dt, s.grid, kwargs=dict(iterMax=60, nout=20, verbose=False))
+            assert h.get_option("stat_thermal_fused") - n0 == (57 if fused else 0)
+            outs.append((list(r.iter_count), list(r.norm_ResT), {k: jr.to_numpy(getattr(thermal, k)) for k in ("T", "Told", "ΔT", "qTx", "qTy", "qTz", "qTz2", "ResT")}))
+            del thermal, pt, K, ρCp
+    finally:
+        h.set_option("thermal_fused", 1)
+        h.set_option("thermal_nt", 0)
+        h.set_option("thermal_tile", 0)
+    for v in (1, 2, 3):
+        assert outs[0][0] == outs[v][0] == [20, 40, 60] and outs[0][1] == outs[v][1]
+        for k in outs[0][2]:
+            assert np.array_equal(outs[0][2][k], outs[v][2][k]), (v, k)
+    _assert_run_matches_oracle(oracle, s, rheo, outs[1])

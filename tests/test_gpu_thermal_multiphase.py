@@ -21,7 +21,7 @@ def _device_setup(jr, s, *, eps=None):
     thermal = jr.ThermalArrays(jr.AMDGPUBackend, s.ni)
     for name in ("T", "Told", "H", "qTx", "qTy", "qTx2", "qTy2", "shear_heating") + (("qTz", "qTz2") if nd == 3 else ()):
         getattr(thermal, name).copy_(from_numpy(s.arrays[name], dev))
-    pr = jr.PhaseRatios(jr.AMDGPUBackend, 2, s.ni)
+    pr = jr.PhaseRatios(jr.AMDGPUBackend, s.extra["phase_ratios"]["center"].shape[0], s.ni)
     for k, v in s.extra["phase_ratios"].items():
         getattr(pr, k).copy_(from_numpy(v, dev))
     args = SimpleNamespace(P=from_numpy(s.arrays["P"], dev), T=thermal.T)
@@ -350,3 +350,78 @@ def test_fused_3d_phase_form_in_graphs_equals_plain_launches_and_the_two_kernels
         assert o[0] == outs[0][0] and o[1] == outs[0][1]
         for a, b in zip(outs[0][2], o[2]):
             assert np.array_equal(a, b)
+
+
+def _randomise_phases(s, seed, nphase):
+    """_randomise for any phase count: ratios that sum to one with pure cells of every phase among them, phases that differ in k, Cp, ρ0, radioactive heat and the density law"""
+    _randomise(s, seed)
+    rng = np.random.default_rng(seed + 100 * nphase)
+    for k, v in list(s.extra["phase_ratios"].items()):
+        shp = v.shape[1:]
+        r = rng.dirichlet(np.ones(nphase), size=shp)
+        pure = rng.random(shp) < 0.3
+        r[pure] = np.eye(nphase)[rng.integers(nphase, size=int(pure.sum()))]
+        s.extra["phase_ratios"][k] = np.asfortranarray(np.moveaxis(r, -1, 0))
+    base = s.extra["rheology"]
+    rheo = []
+    for q in range(nphase):
+        ph = dict(base[q % 2], density=dict(base[q % 2]["density"]))
+        ph["k"], ph["Cp"], ph["Hr"] = ph["k"] * (1.0 + 0.2 * q), ph["Cp"] * (1.0 + 0.1 * q), ph["Hr"] * (1.0 + 0.5 * q)
+        ph["density"]["rho0"] = ph["density"]["rho0"] * (1.0 + 0.05 * q)
+        rheo.append(ph)
+    s.extra["rheology"] = tuple(rheo)
+
+
+@pytest.mark.parametrize("nphase", [1, 2, 3, 4])
+@pytest.mark.parametrize("ni", [(70, 17, 20), (130, 9, 35)])
+def test_3d_phase_form_with_a_constant_phase_count_in_every_launch_pipeline(jr, oracle, ni, nphase):
+    """The 3D phase-ratio kernels are instantiated per phase count (1 .. 4; thermal_np_const).  By default unobserved iterations run as one launch (k_thermal3d_fused_ph);
+    thermal_fused_ph = 0 runs the constant-phase-count flux and update kernels as two launches instead, thermal_nt = 1 the one launch with non-temporal stores of the new
+    (T, qT) set.  Anchor: the two kernels with run-time phase loops (thermal_fused = 0, thermal_np_const = 0).  (70, 17, 20) and (130, 9, 35) are two and three row segments with a
+    ragged last one and ragged z chunks.  The default run is compared with the oracle as test_multiphase_iterations_match_oracle does; every pipeline equals the anchor in
+    temperature, fluxes, residual and PT coefficients bit for bit; stat_thermal_fused shows the one-launch pipelines from the two-kernel ones."""
+    from justrelax_jl_amd import _lib
+    from justrelax_jl_amd.checks import max_rel_diff
+    h = _lib.default_handle()
+    paths = {"anchor": dict(thermal_fused=0, thermal_np_const=0), "default": {}, "two_kernels": dict(thermal_fused_ph=0, thermal_np_const=1), "nt": dict(thermal_nt=1)}
+    defaults = dict(thermal_fused=1, thermal_np_const=1, thermal_fused_ph=1, thermal_nt=0)
+    outs = {}
+    try:
+        for tag, opts in paths.items():
+            for k, v in opts.items():
+                h.set_option(k, v)
+            s = jr.miniapps.diffusion3d_multiphase(ni, iterMax=60, nout=20)
+            _randomise_phases(s, 14, nphase)
+            thermal, pt, pr, args = _device_setup(jr, s, eps=1e-30)
+            f0 = h.get_option("stat_thermal_fused")
+            r = jr.heatdiffusion_PT_(thermal, pt, s.flow_bcs, s.extra["rheology"], args, s.dt, s.grid, kwargs=dict(phase=pr, iterMax=60, nout=20, verbose=False))
+            fused = h.get_option("stat_thermal_fused") - f0
+            assert fused == (57 if tag in ("default", "nt") else 0), (tag, fused)          # 60 iterations, three of them observed
+            names = ("T", "Told", "dT", "qTx", "qTy", "qTz", "qTx2", "qTy2", "qTz2", "ResT", "thetar_dtau", "dtau_rho")
+            fields = [thermal.T, thermal.Told, thermal.ΔT, thermal.qTx, thermal.qTy, thermal.qTz, thermal.qTx2, thermal.qTy2, thermal.qTz2, thermal.ResT, pt.θr_dτ, pt.dτ_ρ]
+            outs[tag] = (list(r.iter_count), list(r.norm_ResT), {k: jr.to_numpy(t) for k, t in zip(names, fields)})
+            for k, v in defaults.items():
+                h.set_option(k, v)
+    finally:
+        for k, v in defaults.items():
+            h.set_option(k, v)
+    # the oracle on the same input
+    p, m, ph = _oracle_inputs(oracle, s, 1e-30, iterMax=60, nout=20)
+    ref = {k: v.copy(order="F") for k, v in s.arrays.items()}
+    ph["P"] = ref["P"]
+    r_ref = oracle.heatdiffusion_PT_phases(ref, p, m, ph)
+    it, norms, got = outs["default"]
+    assert it == list(r_ref["iter_count"]) == [20, 40, 60]
+    assert np.allclose(norms, r_ref["norm_ResT"], rtol=1e-9)
+    for name in ("T", "Told", "dT"):
+        assert np.abs(got[name] - ref[name]).max() <= TOL * np.abs(ref[name]).max(), name
+    for name in ("qTx", "qTy", "qTz", "qTx2", "qTy2", "qTz2"):
+        assert max_rel_diff(got[name], ref[name]) <= TOL, name
+    for name in ("thetar_dtau", "dtau_rho"):
+        assert max_rel_diff(got[name], ref[name]) <= 1e-13, name
+    scale = max(np.abs(ref["ResT"]).max(), 1e-7)
+    assert np.abs(got["ResT"] - ref["ResT"]).max() <= 1e-7 * scale + TOL * scale
+    for tag in ("default", "two_kernels", "nt"):
+        assert outs[tag][0] == outs["anchor"][0] and outs[tag][1] == outs["anchor"][1], tag
+        for k, a in outs["anchor"][2].items():
+            assert np.array_equal(a, outs[tag][2][k]), (tag, k)

@@ -36,7 +36,15 @@ PIPELINES = {"fused": dict(kernel_variant=3, fused_overlap=0, fused_comm=1), "fu
              "fused_early_tall": dict(kernel_variant=3, fused_overlap=2, fused_comm=1, comm_bcs_lazy=0, fused_tile=3),
              "fused_tall": dict(kernel_variant=3, fused_overlap=0, fused_comm=1, fused_tile=3),
              "fused_early_lazy_bcs": dict(kernel_variant=3, fused_overlap=2, fused_comm=1, comm_bcs_lazy=1),
-             "split_sweeps": dict(kernel_variant=3, fused_overlap=0, fused_comm=0)}
+             "split_sweeps": dict(kernel_variant=3, fused_overlap=0, fused_comm=0),
+             # the share of the interior z chunks launched beside the exchange (default 15 %): none of them (box 0 empty) and all of them (the second class is the shell alone)
+             "fused_inkernel_first0": dict(kernel_variant=3, fused_overlap=4, fused_comm=1, comm_bcs_lazy=0, fused_first_pct=0),
+             "fused_inkernel_first100": dict(kernel_variant=3, fused_overlap=4, fused_comm=1, comm_bcs_lazy=0, fused_first_pct=100),
+             "fused_inkernel_split": dict(kernel_variant=3, fused_overlap=4, fused_comm=1, comm_bcs_lazy=0, fused_split=1),      # the fork of a block WITHOUT neighbours: no effect here
+             # slab widths of the split sweeps (@hide_communication b_width; the parameter's default is 4): 1, 2 and wider than half of any extent (clamped to n / 2: no interior left)
+             "split_sweeps_b1": dict(kernel_variant=3, fused_overlap=0, fused_comm=0, b_width_x=1, b_width_y=1, b_width_z=1),
+             "split_sweeps_b2": dict(kernel_variant=3, fused_overlap=0, fused_comm=0, b_width_x=2, b_width_y=2, b_width_z=2),
+             "split_sweeps_bwide": dict(kernel_variant=3, fused_overlap=0, fused_comm=0, b_width_x=200, b_width_y=200, b_width_z=200)}
 
 
 def _set(h, **opts):
@@ -91,7 +99,8 @@ def _solve_blocks(jr, tb, S, pipeline, iters_kw):
         g.finalize_global_grid()
 
 
-@pytest.mark.parametrize("pipeline", ["fused", "fused_overlap", "fused_early", "fused_early_lazy_bcs", "split_sweeps", "fused_tall", "fused_early_tall"])
+@pytest.mark.parametrize("pipeline", ["fused", "fused_overlap", "fused_early", "fused_early_lazy_bcs", "split_sweeps", "fused_tall", "fused_early_tall",
+                                      "split_sweeps_b1", "split_sweeps_b2", "split_sweeps_bwide"])
 @pytest.mark.parametrize("dims,n", [((2, 1, 1), (70, 13, 12)), ((1, 2, 1), (70, 13, 12)), ((1, 1, 2), (70, 13, 12)),
                                     # 3 x 5 x 5 tiles of the fused kernel per block: every shell box and an interior box
                                     ((2, 1, 1), (130, 14, 40)), ((1, 1, 2), (130, 14, 40))])
@@ -114,9 +123,12 @@ def test_two_blocks_equal_the_undecomposed_run_bit_for_bit(jr, dims, n, pipeline
             _set(h0, kernel_variant=0)
         res, outs = _solve_blocks(jr, tb, S, pipeline, kw)
         fused_launches = [_get(h, "stat_fused3d") for h in tb.handles]
+        widths_set = [_get(h, "stat_hidden3d_bwidth") for h in tb.handles]
     assert rg.iter == 24 and all(r.iter == 24 for r in res)
-    if pipeline == "split_sweeps":
+    if pipeline.startswith("split_sweeps"):
         assert fused_launches == [0, 0]
+        # tuning switches b_width_x/y/z: every velocity sweep of the 24 iterations took its slab widths from them (or none did)
+        assert widths_set == ([24, 24] if "b_width_x" in PIPELINES[pipeline] else [0, 0]), widths_set
     else:
         assert min(fused_launches) >= 12, fused_launches       # the fused kernel really ran on both ranks
     for r, out in enumerate(outs):
@@ -143,7 +155,8 @@ def test_two_blocks_equal_the_undecomposed_run_bit_for_bit(jr, dims, n, pipeline
     assert getattr(res[0], "norm_∇V")[-1] != getattr(rg, "norm_∇V")[-1]          # ... which are not the undecomposed norm (RP: overlap counted twice)
 
 
-@pytest.mark.parametrize("pipeline", ["fused", "fused_overlap", "fused_early", "fused_early_lazy_bcs", "fused_inkernel", "fused_inkernel_no_feeder", "split_sweeps"])
+@pytest.mark.parametrize("pipeline", ["fused", "fused_overlap", "fused_early", "fused_early_lazy_bcs", "fused_inkernel", "fused_inkernel_no_feeder", "split_sweeps",
+                                      "fused_inkernel_first0", "fused_inkernel_first100", "fused_inkernel_split"])
 @pytest.mark.parametrize("dims,n", [((2, 1, 1), (70, 13, 12)), ((1, 1, 2), (130, 14, 40))])
 def test_two_blocks_in_the_viscous_limit_equal_the_undecomposed_general_kernels(jr, dims, n, pipeline):
     """dt = Inf: every rank runs the viscous-limit forms (fused kernel, z-marching sweep, fix-up layers next to received planes), which do not load τ_o, P0, K, G, Q
@@ -166,6 +179,12 @@ def test_two_blocks_in_the_viscous_limit_equal_the_undecomposed_general_kernels(
         res, outs = _solve_blocks(jr, tb, S, pipeline, kw)
         assert all(_get(h, "viscous_limit") == 1 for h in tb.handles)
         assert all((_get(h, "stat_fused3d_inkernel") >= 12) == pipeline.startswith("fused_inkernel") for h in tb.handles)
+        # fused_first_pct: with 0 no tile is launched beside the exchange (box 0 empty), with 100 every interior z chunk is, with the default 15 one chunk of six / three of nineteen
+        first = {0: (1, 0), 100: (0, 1)}.get(PIPELINES[pipeline].get("fused_first_pct"), (0, 0))
+        for h in tb.handles:
+            ik = _get(h, "stat_fused3d_inkernel")
+            assert (_get(h, "stat_fused3d_first_none"), _get(h, "stat_fused3d_first_all")) == (first[0] * ik, first[1] * ik), (pipeline, ik)
+        assert all(_get(h, "stat_fused3d_split") == 0 for h in tb.handles)          # fused_split = 1 forks nothing on a rank with neighbours: the same launches, the same bits
     assert rg.iter == 24 and all(r.iter == 24 for r in res)
     for r, out in enumerate(outs):
         co = B.coords_of(tb.carts[r])

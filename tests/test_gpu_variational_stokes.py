@@ -367,3 +367,32 @@ def test_nan_exit_leaves_the_current_stresses_in_the_callers_arrays(jr):
     for k in ("txx", "tyy", "txy", "txy_c", "eta"):
         assert np.array_equal(outs[0][k], outs[1][k], equal_nan=True), k
         assert np.isfinite(outs[0][k]).any(), k
+
+
+def test_full_solve_that_stores_every_iteration_keeps_the_bits(jr):
+    """tuning switch "vep_store_all" = 1: every iteration of solve_VariationalStokes! stores its output-only arrays (default: only the iterations after which the loop can stop).
+    The solve of test_full_solve_with_air_matches_restatement (n = 32) with the switch off and on: every field of VEP_MAP is the same in every bit at the end, both runs match
+    the restatement at that test's 1e-9, and stat_vep_store_all counts the iterations that stored because of the switch."""
+    from justrelax_jl_amd import _lib
+    from justrelax_jl_amd.checks import max_rel_diff
+    h = _lib.default_handle()
+    runs = []
+    try:
+        for store in (0, 1):
+            h.set_option("vep_store_all", store)
+            s = jr.miniapps.shearband2d_variational(32, air_rows=3, iterMax=59, nout=20)
+            s.kwargs.update(iterMin=10)
+            s.pt.ϵ_rel = s.pt.ϵ_abs = 1e-30
+            c0 = h.get_option("stat_vep_store_all")
+            r, r_ref, out, phi = _solve_both(jr, s)
+            runs.append((r, out, h.get_option("stat_vep_store_all") - c0))
+            assert r.iter == r_ref["iter"] == 60
+            assert np.allclose(r.err_evo1, r_ref["err_evo1"], rtol=1e-9) and np.allclose(r.norm_Rx, r_ref["norm_Rx"], rtol=1e-9)
+            for k in out:
+                assert max_rel_diff(out[k], s.arrays[k]) <= 1e-9, k
+    finally:
+        h.set_option("vep_store_all", 0)
+    assert runs[0][2] == 0 and runs[1][2] > 0
+    assert list(runs[0][0].err_evo1) == list(runs[1][0].err_evo1)
+    for k in runs[0][1]:
+        assert np.array_equal(runs[0][1][k], runs[1][1][k]), k

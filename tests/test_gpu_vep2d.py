@@ -244,3 +244,36 @@ def test_vep2d_batched_kernels_equal_the_control_flow_kernels(jr, ni, iters, nou
                 for c in ((0, 0), (0, -1), (-1, 0), (-1, -1)):
                     a[c] = b[c]
             assert np.array_equal(a, b, equal_nan=True), (v, k)
+
+
+def test_vep2d_solve_that_stores_every_iteration_keeps_the_bits(jr, oracle):
+    """tuning switch "vep_store_all" = 1: every iteration of the 2D VEP loop stores ∇V, RP, ε_pl, ε_vol_pl, τII, η_vep; by default only the iterations whose results can be
+    observed do.  The solve of test_vep_solve_matches_oracle_over_iterations with the switch off and on: the last iteration is observed, so every array of VEP_MAP -- the
+    output-only ones included -- is the same in every bit, both runs are within 1e-9 of the oracle, and stat_vep_store_all counts the unobserved iterations that stored."""
+    from justrelax_jl_amd import _lib
+    from justrelax_jl_amd.checks import max_rel_diff
+    h = _lib.default_handle()
+    s = jr.miniapps.shearband2d(24, iterMax=60, nout=20)
+    s.kwargs.update(iterMin=10)
+    s.pt.ϵ_rel = s.pt.ϵ_abs = 1e-30
+    ref = {k: v.copy(order="F") for k, v in s.arrays.items()}
+    r_ref = oracle.stokes2d_vep_solve(ref, oracle.rheology_struct(s.extra["phases"]), _vep_params(oracle, s, iterMin=10))
+    runs = []
+    try:
+        for store in (0, 1):
+            h.set_option("vep_store_all", store)
+            stokes, pr, ρg = _upload(jr, s)
+            c0 = h.get_option("stat_vep_store_all")
+            r = jr.solve_(stokes, s.pt, s.grid, s.flow_bcs, ρg, pr, s.extra["phases"], None, s.dt, None, kwargs=s.kwargs)
+            runs.append((r, _download(jr, stokes), h.get_option("stat_vep_store_all") - c0))
+    finally:
+        h.set_option("vep_store_all", 0)
+    assert runs[0][2] == 0 and runs[1][2] > 0
+    for r, out, _ in runs:
+        assert r.iter == r_ref["iter"] == 61
+        assert np.allclose(r.err_evo1, r_ref["err_evo1"], rtol=1e-9)
+        for k in out:
+            assert max_rel_diff(out[k], ref[k]) <= 1e-9, k
+    assert list(runs[0][0].err_evo1) == list(runs[1][0].err_evo1)
+    for k in runs[0][1]:
+        assert np.array_equal(runs[0][1][k], runs[1][1][k]), k

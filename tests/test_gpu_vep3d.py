@@ -77,42 +77,11 @@ def test_update_stresses_3d_matches_oracle(jr, oracle, edges, ni):
     phase ratios, dilatant plasticity with finite bulk modulus.  edges = 1: the z-marching edge kernel, one family per block (grids spanning one, two and three
     62-node lane segments and one to three z chunks), 2: the same as one launch per family, 3: the three family waves of a row as one workgroup sharing the
     centre operands through LDS, 4 (default): the shear operands too, 0: one node per thread."""
-    from justrelax_jl_amd import _lib, stokes as st_mod
-    from justrelax_jl_amd.arrays import from_numpy
     from justrelax_jl_amd.checks import max_rel_diff
-    s = jr.miniapps.shearband3d(ni)
-    phases = _randomize(s)
-    rh = oracle.rheology_struct(phases)
-    p = _params(oracle, s)
-    ref = {k: v.copy(order="F") for k, v in s.arrays.items()}
-    rng = np.random.default_rng(9)
-    theta = np.asfortranarray(rng.uniform(-1, 1, size=s.ni))
-    lam = np.asfortranarray(rng.uniform(0, 0.1, size=s.ni))
-    lamv = [np.asfortranarray(rng.uniform(0, 0.1, size=s.arrays[k].shape)) for k in ("tyz", "txz", "txy")]
-    lam_r, lamv_r = lam.copy(order="F"), [x.copy(order="F") for x in lamv]
-    oracle.vep3d_stress(ref, theta, lam_r, lamv_r, rh, p)
-    stokes, pr, ρg = _upload(jr, s)
-    dev = stokes.P.device
-    th_d, lam_d = from_numpy(theta, dev), from_numpy(lam, dev)
-    lamv_d = [from_numpy(x, dev) for x in lamv]
-    h = _lib.default_handle()
-    fd = st_mod.vep_fields3d(stokes, ρg, pr)
-    pd = st_mod.vep_params3d(stokes, s.pt, s.grid, s.flow_bcs, s.dt)
-    lv = (C.c_void_p * 3)(*[x.data_ptr() for x in lamv_d])
-    h.call("jrx_tuning_set", C.c_char_p(b"vep3_edges"), C.c_int64(edges))
-    try:
-        h.call("jrx_vep3d_update_stresses", C.byref(fd), C.c_void_p(th_d.data_ptr()), C.c_void_p(lam_d.data_ptr()), lv,
-               C.byref(st_mod.rheology_table(phases)), C.byref(pd))
-    finally:
-        h.call("jrx_tuning_set", C.c_char_p(b"vep3_edges"), C.c_int64(4))
-    out = _download(jr, stokes)
-    assert (lam_r != lam).any() and (lam_r == lam).any() and (ref["eplxz"] != 0).any() and (ref["eplxz"] == 0).any()
-    for k in ("txx", "tyy", "tzz", "tyz", "txz", "txy", "tyz_c", "txz_c", "txy_c", "tII", "eta_vep", "P", "eplxx", "eplyy", "eplzz", "eplyz", "eplxz",
-              "eplxy", "evol_pl"):
-        assert max_rel_diff(out[k], ref[k]) <= 1e-12, k
-    assert max_rel_diff(jr.to_numpy(lam_d), lam_r) <= 1e-12
-    for a, b in zip(lamv_d, lamv_r):
-        assert max_rel_diff(jr.to_numpy(a), b) <= 1e-12
+    pb = _stress_problem(jr, oracle, ni)
+    out, _ = _stress_run(jr, pb, vep3_edges=edges)
+    for k in STRESS_OUT:
+        assert max_rel_diff(out[k], pb["ref"][k]) <= 1e-12, k
 
 
 def test_retired_switches_are_unknown_and_edges_5_is_refused_before_anything_runs(jr, oracle):
@@ -198,56 +167,12 @@ def test_vep3d_solve_matches_oracle_over_iterations(jr, oracle):
 @pytest.mark.parametrize("nphase", [1, 3, 4, 5])
 def test_update_stresses_3d_other_phase_counts(jr, oracle, nphase):
     """the z-marching edge kernel is instantiated per phase count (1..4, unrolled phase loops); five phases take the one-node-per-thread kernel"""
-    from justrelax_jl_amd import _lib, stokes as st_mod
-    from justrelax_jl_amd.arrays import from_numpy
     from justrelax_jl_amd.checks import max_rel_diff
-    import torch
-    ni = (66, 7, 19)
-    s = jr.miniapps.shearband3d(ni)
-    _randomize(s)
-    rng = np.random.default_rng(40 + nphase)
-    base = s.extra["phases"]
-    phases = []
-    for q in range(nphase):
-        ph = dict(base[q % 2], Kb=3.0 + 0.5 * q, psi_deg=4.0 + q)
-        ph["eta"] = ph["eta"] * (1.0 + 0.3 * q)
-        ph["C"] = ph["C"] * (1.0 - 0.1 * q)
-        ph["G"] = ph["G"] * (1.0 + 0.2 * q)
-        phases.append(ph)
-    for k in ("phase_c", "phase_yz", "phase_xz", "phase_xy"):
-        shp = s.arrays[k].shape[1:]
-        r = rng.dirichlet(np.ones(nphase), size=shp)                      # ratios sum to 1
-        r[rng.uniform(size=shp) < 0.3] = np.eye(nphase)[rng.integers(nphase)]    # some pure cells
-        s.arrays[k] = np.asfortranarray(np.moveaxis(r, -1, 0))
-    rh = oracle.rheology_struct(phases)
-    p = _params(oracle, s)
-    ref = {k: v.copy(order="F") for k, v in s.arrays.items()}
-    theta = np.asfortranarray(rng.uniform(-1, 1, size=s.ni))
-    lam = np.asfortranarray(rng.uniform(0, 0.1, size=s.ni))
-    lamv = [np.asfortranarray(rng.uniform(0, 0.1, size=s.arrays[k].shape)) for k in ("tyz", "txz", "txy")]
-    lam_r, lamv_r = lam.copy(order="F"), [x.copy(order="F") for x in lamv]
-    oracle.vep3d_stress(ref, theta, lam_r, lamv_r, rh, p)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    stokes = jr.StokesArrays(jr.AMDGPUBackend, s.ni)
-    for k, path in VEP3_MAP.items():
-        _get(stokes, path).copy_(from_numpy(s.arrays[k], dev))
-    pr = jr.PhaseRatios(jr.AMDGPUBackend, nphase, s.ni)
-    for k, name in (("phase_c", "center"), ("phase_yz", "yz"), ("phase_xz", "xz"), ("phase_xy", "xy")):
-        getattr(pr, name).copy_(from_numpy(s.arrays[k], dev))
-    ρg = tuple(from_numpy(s.arrays[k], dev) for k in ("fx", "fy", "fz"))
-    th_d, lam_d = from_numpy(theta, dev), from_numpy(lam, dev)
-    lamv_d = [from_numpy(x, dev) for x in lamv]
-    h = _lib.default_handle()
-    fd = st_mod.vep_fields3d(stokes, ρg, pr)
-    pd = st_mod.vep_params3d(stokes, s.pt, s.grid, s.flow_bcs, s.dt)
-    lv = (C.c_void_p * 3)(*[x.data_ptr() for x in lamv_d])
-    h.call("jrx_vep3d_update_stresses", C.byref(fd), C.c_void_p(th_d.data_ptr()), C.c_void_p(lam_d.data_ptr()), lv, C.byref(st_mod.rheology_table(phases)), C.byref(pd))
-    out = _download(jr, stokes)
-    assert (ref["eplxz"] != 0).any() and (ref["eplxz"] == 0).any()
-    for k in ("txx", "tyy", "tzz", "tyz", "txz", "txy", "tyz_c", "txz_c", "txy_c", "tII", "eta_vep", "P", "eplxx", "eplyz", "eplxz", "eplxy", "evol_pl"):
-        assert max_rel_diff(out[k], ref[k]) <= 1e-12, k
-    for a, b in zip(lamv_d, lamv_r):
-        assert max_rel_diff(jr.to_numpy(a), b) <= 1e-12
+    pb = _stress_problem(jr, oracle, (66, 7, 19), nphase)
+    out, d = _stress_run(jr, pb)
+    assert d["stat_vep3_edges_node"] == (1 if nphase == 5 else 0) and d["stat_vep3_edges_kz4"] == (0 if nphase == 5 else 1), d
+    for k in STRESS_OUT:
+        assert max_rel_diff(out[k], pb["ref"][k]) <= 1e-12, k
 
 
 @pytest.mark.parametrize("ni,iters", [((96, 80, 72), 12), ((160, 160, 160), 6), ((256, 256, 256), 4)])
@@ -333,7 +258,9 @@ def test_epilogue_operators_3d(jr, oracle):
 
 @pytest.mark.parametrize("tile", [0, 1])
 @pytest.mark.parametrize("ni,iters,nout,prekz", [((20, 12, 10), 7, 3, 0), ((20, 12, 10), 40, 10, 0), ((13, 9, 7), 5, 2, 1), ((70, 5, 6), 6, 5, 4), ((64, 64, 17), 4, 2, 8),
-                                                   ((63, 31, 16), 5, 4, 16), ((127, 66, 40), 6, 3, 8), ((127, 66, 40), 5, 10 ** 9, 32), ((96, 80, 72), 35, 17, 0)])
+                                                   ((63, 31, 16), 5, 4, 16), ((127, 66, 40), 6, 3, 8), ((127, 66, 40), 5, 10 ** 9, 32), ((96, 80, 72), 35, 17, 0),
+                                                   # depth 2: what the size rule picks at about 104^3 .. 120^3; odd and even plane counts, one and two lane segments
+                                                   ((70, 5, 6), 6, 3, 2), ((61, 7, 33), 5, 2, 2)])
 def test_vep3d_fused_pre_centre_equals_the_three_kernels(jr, ni, iters, nout, prekz, tile):
     """k_vep3_prec (pre + viscosity relaxation + centre pass in one kernel ahead of the edge pass, second sets of η and τxx/τyy/τzz adopted by pointer swap; the default without
     neighbours) against the three kernels with the centre pass behind the edge pass: every field of the solve bit for bit -- odd and even iteration counts (the copy-back of the
@@ -491,3 +418,206 @@ def test_nan_exit_leaves_the_current_stresses_in_the_callers_arrays(jr):
     for k in ("txx", "tyy", "tzz", "tyz", "txz", "txy", "eta"):
         assert np.array_equal(outs[0][k], outs[1][k], equal_nan=True), k
         assert np.isfinite(outs[0][k]).any(), k
+
+
+# ---- the forms of the 3D VEP kernels that only a tuning switch (or, in production, the size rule of vep3_plan_edges) selects.  Anchor of the bit comparisons: the
+# one-node-per-thread edge kernel (vep3_edges = 0), itself compared with the oracle at the same shape.
+VEP3_COUNTERS = ("stat_vep3_edges_kz16", "stat_vep3_edges_kz8", "stat_vep3_edges_kz4", "stat_vep3_edges_mb3", "stat_vep3_edges_peel", "stat_vep3_edges_node",
+                 "stat_vep3_edges_node_nomap", "stat_vep3_edges_node_noxcd", "stat_vep3_fused", "stat_vep_store_all")
+VEP3_DEFAULTS = dict(vep3_edges=4, vep3_cfg=0, vep3_peel=1, vep3_map=1, vep3_xcd=1, vep3_nt=0, vep3_fuse_pc=1, vep_store_all=0)
+STRESS_OUT = ("txx", "tyy", "tzz", "tyz", "txz", "txy", "tyz_c", "txz_c", "txy_c", "tII", "eta_vep", "P", "eplxx", "eplyy", "eplzz", "eplyz", "eplxz", "eplxy", "evol_pl",
+              "lam", "lamv0", "lamv1", "lamv2")
+
+
+def _stress_problem(jr, oracle, ni, nphase=2):
+    """a random state for one update_stresses_center_vertex_ps! call (as test_update_stresses_3d_matches_oracle builds it; other phase counts as
+    test_update_stresses_3d_other_phase_counts) and the oracle's result, computed once per test"""
+    s = jr.miniapps.shearband3d(ni)
+    phases = _randomize(s)
+    rng = np.random.default_rng(40 + nphase)
+    if nphase != 2:
+        base, phases = s.extra["phases"], []
+        for q in range(nphase):
+            ph = dict(base[q % 2], Kb=3.0 + 0.5 * q, psi_deg=4.0 + q)
+            ph["eta"], ph["C"], ph["G"] = ph["eta"] * (1.0 + 0.3 * q), ph["C"] * (1.0 - 0.1 * q), ph["G"] * (1.0 + 0.2 * q)
+            phases.append(ph)
+        for k in ("phase_c", "phase_yz", "phase_xz", "phase_xy"):
+            shp = s.arrays[k].shape[1:]
+            r = rng.dirichlet(np.ones(nphase), size=shp)                      # ratios sum to 1
+            r[rng.uniform(size=shp) < 0.3] = np.eye(nphase)[rng.integers(nphase)]    # some pure cells
+            s.arrays[k] = np.asfortranarray(np.moveaxis(r, -1, 0))
+    rng = np.random.default_rng(9)
+    theta = np.asfortranarray(rng.uniform(-1, 1, size=s.ni))
+    lam = np.asfortranarray(rng.uniform(0, 0.1, size=s.ni))
+    lamv = [np.asfortranarray(rng.uniform(0, 0.1, size=s.arrays[k].shape)) for k in ("tyz", "txz", "txy")]
+    ref = {k: v.copy(order="F") for k, v in s.arrays.items()}
+    lam_r, lamv_r = lam.copy(order="F"), [x.copy(order="F") for x in lamv]
+    oracle.vep3d_stress(ref, theta, lam_r, lamv_r, oracle.rheology_struct(phases), _params(oracle, s))
+    assert (lam_r != lam).any() and (lam_r == lam).any() and (ref["eplxz"] != 0).any() and (ref["eplxz"] == 0).any()      # yielding and elastic nodes
+    ref.update(lam=lam_r, lamv0=lamv_r[0], lamv1=lamv_r[1], lamv2=lamv_r[2])
+    return dict(s=s, phases=phases, theta=theta, lam=lam, lamv=lamv, ref=ref)
+
+
+def _stress_run(jr, pb, **switches):
+    """jrx_vep3d_update_stresses on a fresh upload of the problem with the given switches; returns (every downloaded array + λ, λv; the deltas of VEP3_COUNTERS by name)"""
+    from justrelax_jl_amd import _lib, stokes as st_mod
+    from justrelax_jl_amd.arrays import from_numpy
+    s = pb["s"]
+    stokes, pr, ρg = _upload(jr, s)
+    dev = stokes.P.device
+    th_d, lam_d = from_numpy(pb["theta"], dev), from_numpy(pb["lam"], dev)
+    lamv_d = [from_numpy(x, dev) for x in pb["lamv"]]
+    h = _lib.default_handle()
+    fd = st_mod.vep_fields3d(stokes, ρg, pr)
+    pd = st_mod.vep_params3d(stokes, s.pt, s.grid, s.flow_bcs, s.dt)
+    lv = (C.c_void_p * 3)(*[x.data_ptr() for x in lamv_d])
+    try:
+        for k, v in switches.items():
+            h.set_option(k, v)
+        c0 = [h.get_option(k) for k in VEP3_COUNTERS]
+        h.call("jrx_vep3d_update_stresses", C.byref(fd), C.c_void_p(th_d.data_ptr()), C.c_void_p(lam_d.data_ptr()), lv, C.byref(st_mod.rheology_table(pb["phases"])), C.byref(pd))
+        d = {k: h.get_option(k) - c for k, c in zip(VEP3_COUNTERS, c0)}
+    finally:
+        for k, v in VEP3_DEFAULTS.items():
+            h.set_option(k, v)
+    out = _download(jr, stokes)
+    out.update(lam=jr.to_numpy(lam_d), lamv0=jr.to_numpy(lamv_d[0]), lamv1=jr.to_numpy(lamv_d[1]), lamv2=jr.to_numpy(lamv_d[2]))
+    return out, d
+
+
+def _stress_anchor(jr, pb):
+    """the node kernel (vep3_edges = 0, default thread map), within 1e-12 of the oracle"""
+    from justrelax_jl_amd.checks import max_rel_diff
+    out, d = _stress_run(jr, pb, vep3_edges=0)
+    assert d["stat_vep3_edges_node"] == 1 and d["stat_vep3_edges_node_nomap"] == d["stat_vep3_edges_node_noxcd"] == 0, d
+    assert d["stat_vep3_edges_kz16"] == d["stat_vep3_edges_kz8"] == d["stat_vep3_edges_kz4"] == d["stat_vep3_edges_peel"] == 0, d
+    for k in STRESS_OUT:
+        assert max_rel_diff(out[k], pb["ref"][k]) <= 1e-12, k
+    return out
+
+
+def _assert_stress_form(jr, pb, anchor, want, **switches):
+    """one form: within the file's bound of the oracle, equal to the anchor in every array, and the counters say that it ran"""
+    from justrelax_jl_amd.checks import max_rel_diff
+    out, d = _stress_run(jr, pb, **switches)
+    full = dict({k: 0 for k in VEP3_COUNTERS}, **want)
+    assert d == full, (switches, d, full)
+    for k in STRESS_OUT:
+        assert max_rel_diff(out[k], pb["ref"][k]) <= 1e-12, (switches, k)
+    for k in out:
+        assert np.array_equal(out[k], anchor[k]), (switches, k)
+
+
+@pytest.mark.parametrize("edges,cfg,ni", [(e, c, ni) for e, c in ((4, 162), (4, 82), (4, 42), (1, 163), (1, 82)) for ni in ((70, 5, 6), (125, 6, 18), (61, 7, 33), (62, 4, 16))])
+def test_update_stresses_3d_edge_kernel_configurations(jr, oracle, edges, cfg, ni):
+    """the table of test_update_stresses_3d_matches_oracle with a `cfg` column (vep3_cfg = chunk depth * 10 + min blocks per CU).  Left to itself the plan of that test's small
+    grids halves the depth of form 4 to 4 planes; production grids of about 100^3 to 150^3 run 8 planes (128^3: 2 x 129 x 9 = 2,322 < 3,000 blocks at depth 16, 4,386 at depth 8)
+    and larger ones 16.  Form 4 at 16, 8 and 4 planes and form 1 at 16 planes / three blocks per CU and 8 planes / two, on one, two and three lane segments (the last one
+    peeled at nx = 125) and nz + 1 = 7, 17, 19, 34 planes (a part of a chunk, one chunk of 16 and one plane, two chunks of 8 and three planes, ...).  Each is within 1e-12 of
+    the oracle and equals the node kernel (vep3_edges = 0) in every array, bit for bit; the stat_vep3_edges_* counters show the depth that ran."""
+    pb = _stress_problem(jr, oracle, ni)
+    anchor = _stress_anchor(jr, pb)
+    want = {"stat_vep3_edges_kz%d" % (cfg // 10): 1, "stat_vep3_edges_mb3": int(cfg % 10 == 3), "stat_vep3_edges_peel": int(ni[0] == 125)}
+    _assert_stress_form(jr, pb, anchor, want, vep3_edges=edges, vep3_cfg=cfg)
+
+
+@pytest.mark.parametrize("edges", [4, 1])
+@pytest.mark.parametrize("nphase", [1, 2, 3, 4])
+def test_update_stresses_3d_eight_plane_chunks_with_other_phase_counts(jr, oracle, nphase, edges):
+    """the 8-plane instantiations of the z-marching edge kernels exist per phase count (1..4): (66, 7, 19) is two lane segments and 20 planes = two chunks of 8 and four planes"""
+    pb = _stress_problem(jr, oracle, (66, 7, 19), nphase)
+    anchor = _stress_anchor(jr, pb)
+    _assert_stress_form(jr, pb, anchor, dict(stat_vep3_edges_kz8=1), vep3_edges=edges, vep3_cfg=82)
+
+
+@pytest.mark.parametrize("edges", [1, 3, 4, 6])
+def test_update_stresses_3d_without_the_peel_launch(jr, oracle, edges):
+    """vep3_peel = 0 at (125, 6, 18): 126 node columns are two full lane segments and two columns; by default those two go to the node kernel in a launch of their own, with the
+    switch off the z-marching kernel runs a third, nearly empty segment"""
+    pb = _stress_problem(jr, oracle, (125, 6, 18))
+    anchor = _stress_anchor(jr, pb)
+    kz = "stat_vep3_edges_kz4" if edges == 4 else "stat_vep3_edges_kz16"          # form 4 halves its depth on a launch this small; the others are built for 16 planes
+    _assert_stress_form(jr, pb, anchor, {kz: 1, "stat_vep3_edges_peel": 1}, vep3_edges=edges)      # the default, for the counter's sake
+    _assert_stress_form(jr, pb, anchor, {kz: 1}, vep3_edges=edges, vep3_peel=0)
+
+
+@pytest.mark.parametrize("ni", [(13, 9, 7), (70, 5, 6), (125, 6, 18)])
+def test_update_stresses_3d_thread_maps_of_the_node_kernel(jr, oracle, ni):
+    """vep3_map / vep3_xcd act on the one-node-per-thread edge kernel (vep3_edges = 0; the z-marching kernels have one map): 64 x 4 tiles of node columns dealt to the XCDs in
+    slabs with a constant phase count (default), the tiles alone (vep3_xcd = 0), consecutive nodes (vep3_map = 0, with either value of vep3_xcd)"""
+    pb = _stress_problem(jr, oracle, ni)
+    anchor = _stress_anchor(jr, pb)
+    _assert_stress_form(jr, pb, anchor, dict(stat_vep3_edges_node=1, stat_vep3_edges_node_noxcd=1), vep3_edges=0, vep3_xcd=0)
+    _assert_stress_form(jr, pb, anchor, dict(stat_vep3_edges_node=1, stat_vep3_edges_node_nomap=1), vep3_edges=0, vep3_map=0)
+    _assert_stress_form(jr, pb, anchor, dict(stat_vep3_edges_node=1, stat_vep3_edges_node_nomap=1), vep3_edges=0, vep3_map=0, vep3_xcd=0)
+
+
+SOLVE_OUT = ("P", "P0", "Vx", "Vy", "Vz", "Ux", "txx", "tyy", "tzz", "tyz", "txz", "txy", "tyz_c", "tII", "eta", "eta_vep", "exx", "exz", "eplxx", "eplyy", "eplzz",
+             "eplxy", "eplxz", "eplyz", "evol_pl", "divV", "EII_pl", "EVol_pl", "Rx", "Rz", "RP", "toxx", "toxz", "toxy_c", "omega_yz", "omega_xz", "omega_xy", "exz_c", "eplyz_c")
+
+
+def _solve_problem(jr, oracle, ni=(20, 12, 10), iterMax=39, nout=10):
+    """the short solve of test_vep3d_solve_matches_oracle_over_iterations (pre-stress close to yield) and the oracle's result"""
+    s = jr.miniapps.shearband3d(ni, iterMax=iterMax, nout=nout)
+    s.pt.ϵ_rel = s.pt.ϵ_abs = 1e-30
+    rng = np.random.default_rng(3)
+    for c in ("xx", "yy", "zz", "yz", "xz", "xy", "yz_c", "xz_c", "xy_c"):
+        s.arrays["to" + c][...] = rng.uniform(-1.5, 1.5, size=s.arrays["to" + c].shape)
+        s.arrays["t" + c][...] = s.arrays["to" + c]
+    s.arrays["EII_pl"][...] = rng.uniform(0, 0.1, size=s.ni)
+    ref = {k: v.copy(order="F") for k, v in s.arrays.items()}
+    r_ref = oracle.stokes3d_vep_solve(ref, oracle.rheology_struct(s.extra["phases"]), _params(oracle, s))
+    assert (ref["eplxx"] != 0).any()
+    return s, ref, r_ref
+
+
+def _solve_run(jr, s, ref, r_ref, **switches):
+    """the device solve with the given switches, compared with the oracle at the file's bound over iterations; returns (downloaded arrays, error history, counter deltas)"""
+    from justrelax_jl_amd import _lib
+    from justrelax_jl_amd.checks import interior_mask3d
+    h = _lib.default_handle()
+    stokes, pr, ρg = _upload(jr, s)
+    try:
+        for k, v in switches.items():
+            h.set_option(k, v)
+        c0 = [h.get_option(k) for k in VEP3_COUNTERS]
+        r = jr.solve_(stokes, s.pt, s.grid, s.flow_bcs, ρg, pr, s.extra["phases"], None, s.dt, None, kwargs=s.kwargs)
+        d = {k: h.get_option(k) - c for k, c in zip(VEP3_COUNTERS, c0)}
+    finally:
+        for k, v in VEP3_DEFAULTS.items():
+            h.set_option(k, v)
+    out = _download(jr, stokes)
+    assert r.iter == r_ref["iter"]
+    assert np.allclose(r.err_evo1, r_ref["err_evo1"], rtol=1e-9) and np.allclose(r.norm_Rz, r_ref["norm_Rz"], rtol=1e-9)
+    for k in SOLVE_OUT:
+        m = interior_mask3d(k, ref[k].shape)
+        assert np.abs(out[k] - ref[k])[m].max() <= 1e-9 * max(np.abs(ref[k]).max(), 1e-300), (switches, k)
+    return out, np.asarray(r.err_evo1), d
+
+
+@pytest.mark.parametrize("edges", [4, 1])
+@pytest.mark.parametrize("fuse", [0, 1])
+def test_vep3d_solve_with_non_temporal_stores_keeps_the_bits(jr, oracle, fuse, edges):
+    """vep3_nt = 1: the kernels of the solve loop store their outputs with non-temporal stores -- the pre, viscosity and centre kernels (vep3_fuse_pc = 0), the fused pre / centre
+    kernel (1), and the edge pass (the node kernel on a grid this small; vep3_edges = 1: the z-marching kernel).  (66, 9, 19), 12 iterations, checks at 5 and 10: both runs are
+    within 1e-9 of the oracle and equal each other in every array, bit for bit."""
+    s, ref, r_ref = _solve_problem(jr, oracle, (66, 9, 19), 11, 5)
+    runs = [_solve_run(jr, s, ref, r_ref, vep3_nt=nt, vep3_fuse_pc=fuse, vep3_edges=edges) for nt in (0, 1)]
+    for out, err, d in runs:
+        assert (d["stat_vep3_fused"] > 0) == bool(fuse), d                         # the fused pre / centre kernel ran, or the three kernels
+        assert (d["stat_vep3_edges_node"] > 0) == (edges == 4) and (d["stat_vep3_edges_kz16"] > 0) == (edges == 1), d
+    assert np.array_equal(runs[0][1], runs[1][1])
+    for k in runs[0][0]:
+        assert np.array_equal(runs[0][0][k], runs[1][0][k]), k
+
+
+def test_vep3d_solve_that_stores_every_iteration_keeps_the_bits(jr, oracle):
+    """vep_store_all = 1: every iteration stores ∇V, RP, ε_pl, ε_vol_pl, τII, η_vep; by default only the iterations whose results can be observed do (A.obs).  The last iteration
+    is observed, so at the end every array -- the output-only ones included -- equals the other run's bit for bit, and both runs are within 1e-9 of the oracle."""
+    s, ref, r_ref = _solve_problem(jr, oracle)
+    runs = [_solve_run(jr, s, ref, r_ref, vep_store_all=v) for v in (0, 1)]
+    assert all(d["stat_vep3_fused"] > 0 and d["stat_vep3_edges_node"] > 0 for _, _, d in runs)      # the default kernels of a grid this small, with and without their stores
+    assert runs[0][2]["stat_vep_store_all"] == 0 and runs[1][2]["stat_vep_store_all"] > 0               # unobserved iterations that stored because of the switch
+    assert np.array_equal(runs[0][1], runs[1][1])
+    for k in runs[0][0]:
+        assert np.array_equal(runs[0][0][k], runs[1][0][k]), k

@@ -76,7 +76,7 @@ def test_fused_form_is_bit_identical_to_the_per_kernel_form(jr, nx, ny, method):
     h = _handle(jr)
     u, vx, vy, dx, dy, dt = _inputs(nx, ny)
     ref = _run(jr, h, u, vx, vy, dx, dy, dt, method, fused=False)
-    for rows in (0, 64):
+    for rows in (0, 8, 16, 32, 64):          # the depth the grid picks (8 on grids this small) and every depth the size rule can pick
         h.set_option("weno_rows", rows)
         got = _run(jr, h, u, vx, vy, dx, dy, dt, method, fused=True)
         assert np.array_equal(got[0], ref[0]), rows

@@ -84,7 +84,7 @@ def test_fused_form_is_bit_identical_to_the_per_kernel_form(jr, shape, method):
     u, v, d, dt = _inputs(*shape)
     ref = _run(jr, h, u, v, d, dt, method, fused=False)
     assert np.abs(ref[0] - u).max() > 0.0 or shape == (1, 1, 1)
-    for rows in (0, 64):
+    for rows in (0, 8, 16, 32, 64):          # the depth the grid picks (8 on grids this small) and every depth the size rule can pick
         h.set_option("weno_rows", rows)
         got = _run(jr, h, u, v, d, dt, method, fused=True)
         assert np.array_equal(got[0], ref[0]), rows
